@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — sampled motions/sec of the ReGenNet diffusion-sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +11,13 @@ configs[1] = NTU120-AS shape [B=256, 56, 6, 60], online/concat/no_cond, 8 layers
 of the packed weight blob). Inputs (condition, weights) are resident in HBM before the timed region; noise
 comes from the on-device Philox stream. Prints ONE JSON line on rank 0.
 
-Extra objects: "roofline" for the dominant kernel class (the MFMA GEMMs; durations measured with HIP
-events on the engine's stream in a short profiled pass inside this script) and "cpu_baseline" (the oracle
-= CPU port of the reference path, timed on this host's cores on a bounded sample, rank 0 / N=1 only).
+A plain run sets up, warms up, times the K steps and prints the line. --dump-outputs DIR writes what the last
+timed call returned (rank 0's motions) as DIR/samples.npy (float32); the inputs depend on the arguments only.
+
+--full adds what takes runs of its own: "headline_row_check_max_abs" (motions of the last timed call against
+B = 1 re-runs), "roofline" for the dominant kernel class (the MFMA GEMMs; durations measured with HIP events
+on the engine's stream in a short profiled pass inside this script) and "cpu_baseline" (the oracle = CPU port
+of the reference path, timed on this host's cores on a bounded sample, rank 0 / N=1 only).
 """
 import argparse
 import importlib
@@ -321,6 +325,9 @@ def main(argv=None):
     ap.add_argument("--recogniser-f16", action="store_true",
                     help="--config stgcn / eval_pipeline: the recogniser on single fp16 operand planes (SG_F16: one MFMA per product instead of the split-bf16 three)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed call's samples (rank 0) as DIR/samples.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also the row check, the profiled roofline pass and the CPU baseline (each switched off again by its --no-* / --profile-evals 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-dist", action="store_true", default=bool(os.environ.get("REGENNET_FORCE_DIST")),
                     help="take every multi-rank code path with a ONE-rank process group (RCCL init, blob broadcast, barriers, reductions)")
@@ -330,6 +337,10 @@ def main(argv=None):
     ap.add_argument("--profile-evals", type=int, default=3)
     ap.add_argument("--engine-stub", default="", help=argparse.SUPPRESS)   # tests only: "module:Class" replaces _lib.Engine (CPU, gloo);
     a = ap.parse_args(argv)                                                 # the line is then marked "data": "STUB ENGINE ..." and measures nothing
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.config in ("stgcn", "eval_pipeline"):
+        ap.error("--dump-outputs: the sampling configs only")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus, argv))
     if a.config == "stgcn":
@@ -427,6 +438,9 @@ def main(argv=None):
     sync()
     dt = time.perf_counter() - t0
     assert torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "samples.npy"), out.float().cpu().numpy())
     devices = [str(dev)]
     if multi:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -436,18 +450,18 @@ def main(argv=None):
         dist.all_gather_object(devices, f"rank{rank}:{dev}" + (f" ({torch.cuda.get_device_name(dev)})" if dev.type == "cuda" else ""))
 
     # ---- the timed launch at its real shape: motions 0 and B-1 of the LAST timed call against single-motion runs of the same kernel form
-    plan = {} if a.engine_stub else eng.plan_query(B, a.guided, split_phase=False)
+    plan = {} if a.engine_stub or not a.full else eng.plan_query(B, a.guided, split_phase=False)
     # the precision plan the timed calls followed (rgn_precision_plan: the engine's own answer for this batch on this schedule)
     n16, tail = (0, 0) if a.engine_stub else eng.precision_plan(B, a.guided)
     row_dev = None
-    if rank == 0 and not a.engine_stub and not a.no_row_check and a.steps > 0:
+    if rank == 0 and a.full and not a.engine_stub and not a.no_row_check:
         row_dev = row_check(cfg, synth.make_state_dict(cfg, seed=0), a, dev, y, out, 100 + a.steps - 1, lo, plan,
                             "p_sample_loop" if a.sampler == "ddpm" else "ddim_sample_loop", sorted({0, B - 1}))
 
     # ---- roofline: HIP events around every launch of a short eager single-chain pass on the engine's stream -----------
     # (the first loop indices: the plain-bf16 phase under the precision schedule = where >= 97 % of the evaluations run)
     roof = None
-    if rank == 0 and a.profile_evals > 0 and not a.engine_stub:   # (--profile-evals 0: tools/collect_pmc.sh wants the sampling call only)
+    if rank == 0 and a.full and a.profile_evals > 0 and not a.engine_stub:
         eng.profile_enable(True)
         x = torch.empty(shape, device=dev)
         st = torch.cuda.current_stream().cuda_stream
@@ -585,7 +599,7 @@ def main(argv=None):
             line["e2e_algorithmic_tflops"] = round(e2e, 2)
             line["e2e_frac_of_peak"] = round(e2e / (PEAK_TFLOPS[a.precision] * world), 4)
         line["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline and not a.engine_stub:
+        if world == 1 and a.full and not a.no_cpu_baseline and not a.engine_stub:
             line["cpu_baseline"] = cpu_baseline(cfg, synth.make_state_dict(cfg, seed=0), evals)
             line["speedup_vs_cpu_baseline"] = round(value / line["cpu_baseline"]["value"], 1)
     # The JSON line must be the LAST thing on stdout: RCCL prints a version banner through C stdio, which is flushed when the process

@@ -357,6 +357,21 @@ def test_bench_rank_failure_is_a_nonzero_exit():
     del json
 
 
+def test_bench_dump_outputs_writes_the_last_timed_call(tmp_path):
+    """`--dump-outputs DIR`: the samples the last timed call returned, as DIR/samples.npy in float32; the same arguments give the same
+    inputs and so the same file, another --steps another last call. `--steps` below 1 is refused."""
+    dumps = {}
+    for tag, steps in (("a", "2"), ("b", "2"), ("c", "1")):
+        rc, line, log = _run_bench({}, "--steps", steps, "--dump-outputs", str(tmp_path / tag))
+        assert rc == 0 and line is not None and line["steps"] == int(steps) and line["ms_per_step"] > 0, log
+        assert line["roofline"] is None and "cpu_baseline" not in line and line["headline_row_check_max_abs"] is None, line
+        dumps[tag] = np.load(tmp_path / tag / "samples.npy")
+    assert dumps["a"].dtype == np.float32 and dumps["a"].shape == (2, 5, 6, 8)
+    assert np.array_equal(dumps["a"], dumps["b"]) and not np.array_equal(dumps["a"], dumps["c"])
+    rc, line, log = _run_bench({}, "--steps", "0")
+    assert rc != 0 and line is None and "--steps" in log, log
+
+
 def test_bench_refuses_a_rank_count_that_differs_from_gpus():
     rc, line, log = _run_bench({"WORLD_SIZE": "1", "RANK": "0"}, "--gpus", "2")
     assert rc != 0 and line is None and "refusing" in log, log

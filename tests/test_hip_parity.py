@@ -1331,7 +1331,7 @@ def test_rccl_one_rank_group_takes_the_multi_gpu_code_paths():
     assert p.returncode == 0 and "[rccl] ok" in p.stdout and "values unchanged: True" in p.stdout, p.stdout + p.stderr
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "1", "--warmup", "1", "--respacing", "50", "--batch", "64",
-                        "--no-cpu-baseline", "--profile-evals", "0"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--profile-evals", "0"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and lines, p.stdout + p.stderr
     line = json.loads(lines[-1])
