@@ -288,6 +288,7 @@ int rgn_denoise(rgn_handle h, const float* x, const int64_t* t, int32_t flags, f
         rc = pack_state(c, x, dm, guided, s);
         if (rc) return rc;
         c->phase_x3 = true;               // a single evaluation is always split-bf16 under the precision schedule
+        c->phase_f16 = false;
         rc = run_eval(c, c->B, guided, uncond, false, s);
         if (rc) return rc;
         return stream_exit(c, us);
@@ -373,9 +374,8 @@ int rgn_set_option(rgn_handle h, const char* key, int32_t value) {
             return RGN_OK;
         }
         if (h->finalized) return h->fail(RGN_ERR_STATE, "rgn_set_option: the switches select kernels when the weights are packed - set them before rgn_finalize_weights");
-        static const char* known[] = {"NO_FUSED_QKV", "BIG_TILE_ROWS", "NO_ROWGEMM", "NO_MLP", "MLP_X3", "NO_QKV_RS", "NO_STEP_FUSION", "LAYERS_MIN_TQ", "LAYERS", "LAYERS_STEPS",
-                                      "LAYERS_MIN_B", "LAYERS_GUIDED", "STEP_NO_QUADS", "NO_QKV_LONG", "SB_FUSED_ATTN", "SB_ROWS", "BULK_RESID_LO", "GRAPH_STEPS", "STREAMS", "SB_GRAPH",
-                                      "BULK_F16", "F16_STEPS", "QKV_X3_DMA"};
+        static const char* known[] = {"LAYERS", "LAYERS_STEPS", "LAYERS_MIN_B", "LAYERS_GUIDED", "MLP_X3", "NO_STEP_FUSION", "STEP_NO_QUADS", "NO_QKV_LONG",
+                                      "QKV_X3_DMA", "BIG_TILE_ROWS", "SB_ROWS", "SB_GRAPH", "STREAMS", "GRAPH_STEPS", "BULK_F16", "F16_STEPS"};
         bool ok = false;
         for (const char* k : known) ok = ok || strcmp(k, key) == 0;
         if (!ok) return h->fail(RGN_ERR_BAD_KEY, std::string("rgn_set_option: unknown switch '") + key + "'");

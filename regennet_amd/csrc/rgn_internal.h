@@ -121,7 +121,7 @@ struct QkvAttnArgs {
     int Bm, Kp, d, H, Tq;
     float qscale;
     int Bm_eval;                                        // samples of the WHOLE evaluation (all kernel chains; 0: = Bm): what else runs beside this launch
-    int f16;                                            // k_qkv_attn_long / k_qkv_attn_rs<1>: Ahi, Wfr and the output plane hold IEEE fp16 (OpFmt<true>), not bf16
+    int f16;                                            // k_qkv_attn_long / k_qkv_attn_rs: Ahi, Wfr and the output plane hold IEEE fp16 (OpFmt<true>), not bf16
 };
 bool qkv_attn_supported(int Tq, int dh, int d);
 hipError_t configure_qkv_attn();
@@ -171,7 +171,7 @@ struct MlpArgs {
     const float* pervec; int ldper;       // + pervec[(row / Tq) * ldper + n]     (nullable)
     const float* stepvec; int ldstep; const int* d_step;   // + stepvec[(*d_step) * ldstep + n] (nullable)
     int Tq;
-    int f16;                              // k_mlp2<2> only: att / h / out planes and the three weight planes hold IEEE fp16 (OpFmt<true>)
+    int f16;                              // k_mlp2 only: att / h / out planes and the three weight planes hold IEEE fp16 (OpFmt<true>)
 };
 bool mlp_supported(int d, int ff, int Tq);
 hipError_t configure_mlp();
@@ -187,10 +187,6 @@ struct MlpX3Args {
 bool mlp_x3_supported(int d, int ff, int Tq);
 hipError_t configure_mlp_x3();
 hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s);
-// second build of the layer tail (rgn_mlp2.hip): rows = 64 (8 waves, one workgroup per CU) or 32 (4 waves, two per CU)
-bool mlp2_supported(int rows, int d, int ff, int Tq);
-hipError_t configure_mlp2();
-hipError_t launch_mlp2(int rows, const MlpArgs& g, hipStream_t s);
 
 // The whole decoder stack of one evaluation as one kernel, one sample (Tq <= 64 tokens) per workgroup (rgn_layers.hip): plain-bf16 phase,
 // d = 512, ff = 1024, 4 heads of 128. Weight planes fragment-ordered as for k_mlp / k_qkv_attn_rs.
@@ -257,16 +253,10 @@ struct SbArgs {
     // POST 2: packed in_proj -> attention-ready q (pre-scaled) / k / v planes [Bm*H][Tqp][dh]
     __bf16 *Qhi, *Qlo, *Khi, *Klo, *Vhi, *Vlo;
     int d, H, dh, Tqp; float qscale;
-    // k_sb_qkv_attn (rgn_sb_attn.hip): the attention output, K32-blocked planes of the out_proj GEMM
-    Planes att;
 };
 bool sb_supported(int d, int ff, int dh);
 hipError_t configure_sb();
 hipError_t launch_sb_gemm(const SbArgs& g, int pre, int post, bool x3, hipStream_t s);
-// LayerNorm prologue + in_proj + causal self-attention of one (sample, head) per workgroup (rgn_sb_attn.hip): d = 512, dh = 128, <= 64 tokens
-bool sb_qkv_attn_supported(int d, int dh, int Tq);
-hipError_t configure_sb_qkv_attn();
-hipError_t launch_sb_qkv_attn(const SbArgs& g, int Bm, bool x3, hipStream_t s);
 
 // The 16-bit operand format of the plain phase's MFMAs (weights, activation images / planes, q / k / v / p): bf16 (8 mantissa bits) or IEEE fp16
 // (11). Both instructions are 8 passes of 4 cycles per 32 x 32 x 16 tile and take 16 bytes per lane and operand, so a kernel's structure - rings,

@@ -5,12 +5,9 @@
 //   y  = LN3( gelu( h' . W1^T + b1 ) . W2^T + b2 + h' )                                 linear1, GELU, linear2, norm3
 //
 // (nn.TransformerDecoderLayer post-norm blocks constructed at model/cmdm.py:75-81, called at :227) with every intermediate on chip.
-// Two instantiations of one template:
-//   MT = 2: R = 64 rows, 8 waves, wave w = output columns [64 w, 64 w + 64) (2 x 2 accumulator tiles of 32 x 32), one workgroup
-//           per CU - a weight fragment feeds two MFMAs; the shape for launches that fill the chip
-//   MT = 1: R = 32 rows, 4 waves, wave w = columns [128 w, 128 w + 128) (4 x 1 tiles), TWO independently scheduled workgroups
-//           per CU - a weight fragment feeds one MFMA, i.e. twice the L2 -> register weight stream per row: measured slower
-//           whenever the 64-row tiles fill the chip (the stream is what bounds the loops), faster for launches of few tiles
+// R = 64 rows, 8 waves, wave w = output columns [64 w, 64 w + 64) (MT x NT = 2 x 2 accumulator tiles of 32 x 32), one workgroup per
+// CU - a weight fragment feeds two MFMAs. (A 32-row form with two workgroups per CU streams twice the weights per row and lost
+// wherever the 64-row tiles fill the chip: DESIGN.md 4.0b2.)
 // What changed against round 2's k_mlp (all measured in the sampling loop):
 //   * the layer input tile h (residual of norm1) never touches LDS: every lane loads the 64 values it will add straight into
 //     registers BEHIND the att DMA and the first weight fragments, and the first MFMA waits for the att tile only
@@ -27,7 +24,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace rgn {
@@ -47,21 +43,20 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define RGN_AS1 __attribute__((address_space(1)))
 #define RGN_AS3 __attribute__((address_space(3)))
 
-template <int MT>
 struct M2 {
+    static constexpr int MT = 2;                      // row tiles of 32 per workgroup
     static constexpr int R = 32 * MT, NW = 4 * MT, NTH = 64 * NW, NT = 4 / MT, CW = 512 / NW;   // rows, waves, threads, column blocks and columns per wave
-    static constexpr int RD = 4 * MT;                 // weight ring depth in granules (half k-steps of NT fragments): 64 registers either way
+    static constexpr int RD = 4 * MT;                 // weight ring depth in granules (half k-steps of NT fragments): 64 registers
     static constexpr int KB = R * 64, IMG = 16 * KB;  // bytes of one k-block [R rows][64 B] and of an image
-    static constexpr int NSAMP = MT == 1 ? 2 : 4;     // samples a tile can touch (mlp2_supported)
+    static constexpr int NSAMP = 4;                   // samples a tile can touch (mlp_supported)
     // LDS map: X | Y | statistics exchange (2 buffers x [2 stats][NW waves][R tokens]) | NW wave-private vector regions
     static constexpr int X = 0, Y = IMG, RED = 2 * IMG, REDF = 2 * NW * R, VEC = RED + 2 * REDF * 4, VECW = (4 + NSAMP) * CW, LDS = VEC + NW * VECW * 4;
     // wave-private vector region (floats): phase A (stage 1) and phase B (stages 2, 3)
     static constexpr int A_BO = 0, A_G1 = CW, A_G2 = 2 * CW, A_B2 = 3 * CW, A_SPV = 4 * CW /* NSAMP x CW */;
     static constexpr int B_BF1 = 0 /* 2 x CW: hidden halves */, B_BF2 = 2 * CW, B_G3 = 3 * CW, B_B3 = 4 * CW;
     static_assert(32 % RD == 0, "ring slots continue across passes");
-    static_assert((2 / MT) * LDS <= 160 * 1024, "LDS map");
+    static_assert(LDS == 152 * 1024, "LDS map");
 };
-static_assert(M2<1>::LDS == 78 * 1024 && M2<2>::LDS == 152 * 1024, "LDS map");
 
 #ifdef RGN_M2_STAMPS
 // tools/mlp_bench -DRGN_M2_STAMPS: wave 0 of EVERY workgroup stamps s_memtime at the phase boundaries, plus where it runs
@@ -103,14 +98,14 @@ __device__ __forceinline__ f32x2 m2_gelu2(f32x2 x) {
     return x * __builtin_elementwise_fma(t, p, f32x2{0.5f, 0.5f});
 }
 
-template <int MT, bool F16 = false>
-__global__ __launch_bounds__(M2<MT>::NTH, 2) void k_mlp2(MlpArgs g) {
-    using C = M2<MT>;
+template <bool F16 = false>
+__global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
+    using C = M2;
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): planes in, planes out, weight planes
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;
-    constexpr int NT = C::NT, NW = C::NW, R = C::R, CW = C::CW, RD = C::RD, KB = C::KB, NSAMP = C::NSAMP, VK = CW / 64;
+    constexpr int MT = C::MT, NT = C::NT, NW = C::NW, R = C::R, CW = C::CW, RD = C::RD, KB = C::KB, NSAMP = C::NSAMP, VK = CW / 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(M2<MT>::NTH, 2) void k_mlp2(MlpArgs g) {
     int red_base = C::RED + 4 * l31;
     asm volatile("" : "+v"(red_base));
     const float invn = 1.0f / 512.f;
-    int red_base2 = red_base + (MT == 2 ? 128 * kh : 0);        // MT = 2, post-barrier reads: lane (l31, kh) reduces token 32 kh + l31
+    int red_base2 = red_base + 128 * kh;                          // post-barrier reads: lane (l31, kh) reduces token 32 kh + l31
     asm volatile("" : "+v"(red_base2));
     auto layernorm = [&](f32x16 (&acc)[NT][MT], const float* gam, auto slot, auto shift /* (nt, i4, mt) -> f32x4 */) {
         const char* buf = smem + red_base + decltype(slot)::value * C::REDF * 4;   // two alternating buffers: a barrier separates each write from its reads
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(M2<MT>::NTH, 2) void k_mlp2(MlpArgs g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         f32x2 rs[MT], nm[MT];
-        {   // MT = 2: the halves share the work - lane (l31, kh) reduces the partials of token 32 kh + l31, two swaps hand the results over
+        {   // the halves share the work - lane (l31, kh) reduces the partials of token 32 kh + l31, two swaps hand the results over
             float p[2][NW];
 #pragma unroll
             for (int st = 0; st < 2; ++st)
@@ -245,14 +240,12 @@ __global__ __launch_bounds__(M2<MT>::NTH, 2) void k_mlp2(MlpArgs g) {
             const float mean = p[0][0] * invn;
             const float var = __builtin_fmaxf(p[1][0] * invn - mean * mean, 0.f);
             float r0 = __builtin_amdgcn_rsqf(var + 1e-5f), n0 = -mean * r0;
-            if constexpr (MT == 2) {
-                float r1 = r0, n1 = n0;
-                asm volatile("" : "+v"(r1), "+v"(n1));           // (copies in registers of their own)
-                half_swap(r0, r1);
-                half_swap(n0, n1);
-                rs[MT - 1] = f32x2{r1, r1};
-                nm[MT - 1] = f32x2{n1, n1};
-            }
+            float r1 = r0, n1 = n0;
+            asm volatile("" : "+v"(r1), "+v"(n1));               // (copies in registers of their own)
+            half_swap(r0, r1);
+            half_swap(n0, n1);
+            rs[1] = f32x2{r1, r1};
+            nm[1] = f32x2{n1, n1};
             rs[0] = f32x2{r0, r0};
             nm[0] = f32x2{n0, n0};
         }
@@ -485,34 +478,16 @@ __global__ __launch_bounds__(M2<MT>::NTH, 2) void k_mlp2(MlpArgs g) {
 void m2_stamps_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_m2_st), sizeof(long long) * 1024 * 12); }
 #endif
 
-// samples a tile of `rows` rows can touch
-bool mlp2_supported(int rows, int d, int ff, int Tq) {
-    if (d != 512 || ff != 1024) return false;
-    return rows == 32 ? 31 / Tq + 2 <= M2<1>::NSAMP : rows == 64 ? 63 / Tq + 2 <= M2<2>::NSAMP : false;
+// a 64-row tile must not touch more samples than it has per-sample vector slots for
+bool mlp_supported(int d, int ff, int Tq) { return d == 512 && ff == 1024 && 63 / Tq + 2 <= M2::NSAMP; }
+hipError_t configure_mlp() {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2::LDS);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, M2::LDS);
 }
-hipError_t configure_mlp2() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<1>), hipFuncAttributeMaxDynamicSharedMemorySize, M2<1>::LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2<2>::LDS);
-    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<2>), hipFuncAttributeMaxDynamicSharedMemorySize, M2<2>::LDS);
-}
-hipError_t launch_mlp2(int rows, const MlpArgs& g, hipStream_t s) {
-    if (g.f16 && rows != 64) return hipErrorInvalidValue;         // (fp16 operands: the 64-row form only)
-    if (rows == 32) hipLaunchKernelGGL(k_mlp2<1>, dim3((g.M + 31) / 32), dim3(M2<1>::NTH), M2<1>::LDS, s, g);
-    else if (g.f16) hipLaunchKernelGGL((k_mlp2<2, true>), dim3((g.M + 63) / 64), dim3(M2<2>::NTH), M2<2>::LDS, s, g);
-    else hipLaunchKernelGGL(k_mlp2<2>, dim3((g.M + 63) / 64), dim3(M2<2>::NTH), M2<2>::LDS, s, g);
-    return hipGetLastError();
-}
-
-// ---- the layer tail as the engine sees it: 64-row tiles by default; REGENNET_MLP_ROWS=32 selects the two-workgroups-per-CU form where the
-//      sequence allows it (tools, A/B: it loses wherever the 64-row tiles fill the chip)
-bool mlp_supported(int d, int ff, int Tq) { return mlp2_supported(64, d, ff, Tq); }
-hipError_t configure_mlp() { return configure_mlp2(); }
 hipError_t launch_mlp(const MlpArgs& g, hipStream_t s) {
-    static const int rows = [] {
-        const char* e = getenv("REGENNET_MLP_ROWS");
-        return e && atoi(e) == 32 ? 32 : 64;
-    }();
-    return launch_mlp2(rows == 32 && !g.f16 && mlp2_supported(32, 512, 1024, g.Tq) ? 32 : 64, g, s);
+    if (g.f16) hipLaunchKernelGGL((k_mlp2<true>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
+    else hipLaunchKernelGGL((k_mlp2<false>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
+    return hipGetLastError();
 }
 
 }  // namespace rgn

@@ -154,7 +154,7 @@ bool opt_get(const rgn_ctx* c, const char* key, int* value) {
     }
     return false;
 }
-// "flag" switches (REGENNET_NO_MLP ...): on when the variable exists at all / when the option was set to a non-zero value
+// "flag" switches (REGENNET_NO_STEP_FUSION ...): on when the variable exists at all / when the option was set to a non-zero value
 bool opt_flag(const rgn_ctx* c, const char* key) {
     auto it = c->opts.find(key);
     if (it != c->opts.end()) return it->second != 0;
@@ -336,13 +336,13 @@ int finalize_weights(rgn_ctx* c) {
             }
             RGN_HIP(c, configure_attn_x3(c->Tq, d / c->H));
         }
-        c->fuse_qkv = qkv_attn_supported(c->Tq, d / c->H, d) && !opt_flag(c, "NO_FUSED_QKV");
+        c->fuse_qkv = qkv_attn_supported(c->Tq, d / c->H, d);
         { int v; if (opt_get(c, "BIG_TILE_ROWS", &v)) c->big_tile_rows = v; }
-        c->rowgemm = c->cfg.precision == RGN_PREC_BF16_X3TAIL && !opt_flag(c, "NO_ROWGEMM") && c->Tq >= 8 &&   // (8 rows of a wave: <= 2 samples)
+        c->rowgemm = c->cfg.precision == RGN_PREC_BF16_X3TAIL && c->Tq >= 8 &&   // (8 rows of a wave: <= 2 samples)
                      rowgemm_supported(d, d, true) && rowgemm_supported(d, (int)align_up((size_t)ff, 32), true) &&
                      rowgemm_supported(ff, d, false);
         if (c->rowgemm) RGN_HIP(c, configure_rowgemm());
-        c->mlp = c->rowgemm && mlp_supported(d, ff, c->Tq) && !opt_flag(c, "NO_MLP");
+        c->mlp = c->rowgemm && mlp_supported(d, ff, c->Tq);
         if (c->mlp) RGN_HIP(c, configure_mlp());
         {   // the split-bf16 layer tail as one kernel (REGENNET_MLP_X3=0: k_gemm_x3 x 3 + k_layernorm x 2 per layer instead)
             int v = 1;
@@ -351,19 +351,17 @@ int finalize_weights(rgn_ctx* c) {
             if (c->mlp_x3) RGN_HIP(c, configure_mlp_x3());
         }
         if (c->fuse_qkv) RGN_HIP(c, configure_qkv_attn());
-        c->qkv_rs = !opt_flag(c, "NO_QKV_RS");
         c->qkv_x3_dma = opt_flag(c, "QKV_X3_DMA");
         c->step_fused = c->rowgemm && !c->etd && c->lin_x.fr && c->lin_out.fr && c->lin_out.has_bias && !c->lin_x.has_bias &&
                         step_fused_supported(d, F, c->lin_x.Kp) && !opt_flag(c, "NO_STEP_FUSION");
         if (c->step_fused) RGN_HIP(c, configure_step());
         // one workgroup per sample costs a full 64-row tile whatever the length, the kernel-per-stage chain costs the rows there are, and the
-        // fused form is worth ~20 % of a layer: it takes evaluations of at least 52 tokens per sample (REGENNET_LAYERS_MIN_TQ overrides: tests)
-        int ly_min_tq = 52, ly_on = 1, ly_steps = 1;
-        (void)opt_get(c, "LAYERS_MIN_TQ", &ly_min_tq);
+        // fused form is worth ~20 % of a layer: it takes evaluations of at least LY_MIN_TQ tokens per sample
+        constexpr int LY_MIN_TQ = 52;
+        int ly_on = 1, ly_steps = 1;
         (void)opt_get(c, "LAYERS", &ly_on);
         (void)opt_get(c, "LAYERS_STEPS", &ly_steps);
-        c->layers_fused = c->mlp && c->fuse_qkv && c->qkv_rs && layers_supported(d, ff, c->H, c->Tq, c->L) && c->Tq >= ly_min_tq &&
-                          ly_on != 0;
+        c->layers_fused = c->mlp && c->fuse_qkv && layers_supported(d, ff, c->H, c->Tq, c->L) && c->Tq >= LY_MIN_TQ && ly_on != 0;
         if (c->layers_fused) RGN_HIP(c, configure_layers());
         { int v; if (opt_get(c, "LAYERS_MIN_B", &v)) c->layers_min_b = c->layers_min_b_default = v < 1 ? 1 : v; }
         { int v; if (opt_get(c, "LAYERS_GUIDED", &v)) c->layers_guided = c->layers_guided_default = v < 0 ? 1 : (v > 2 ? 2 : v); }
@@ -374,12 +372,10 @@ int finalize_weights(rgn_ctx* c) {
         c->qkv_long = c->cfg.precision == RGN_PREC_BF16_X3TAIL && qkv_attn_long_supported(c->Tq, d / c->H, d) && !opt_flag(c, "NO_QKV_LONG");
         if (c->qkv_long) RGN_HIP(c, configure_qkv_attn_long());
         // the forms with fp16 instantiations: the multi-step one-kernel stack; k_qkv_attn_long + k_mlp2 + k_step (prec_plan decides per batch)
-        c->bulk_f16 = c->bulk_f16 && c->step_fused && (c->layers_steps || ((c->qkv_long || (c->fuse_qkv && c->qkv_rs && d == 512)) && c->mlp));
+        c->bulk_f16 = c->bulk_f16 && c->step_fused && (c->layers_steps || ((c->qkv_long || (c->fuse_qkv && d == 512)) && c->mlp));
         c->sb = c->attn_x3 && sb_supported(d, ff, d / c->H);
-        { int v; if (opt_get(c, "SB_FUSED_ATTN", &v)) c->sb_attn = v != 0; }
         { int v; if (opt_get(c, "SB_ROWS", &v)) c->sb_rows = c->sb_rows_default = v < 0 ? 0 : v; }
         if (c->sb) RGN_HIP(c, configure_sb());
-        if (c->sb) RGN_HIP(c, configure_sb_qkv_attn());
     }
     if ((rc = ws_alloc(c, &c->d_tab, (size_t)1024))) return rc;
     if ((rc = ws_alloc(c, &c->d_step, (size_t)4 + 1 + B))) return rc;   // [0] loop index, [3] scratch, [4 ..] k_update's ticket counters
@@ -393,7 +389,6 @@ int finalize_weights(rgn_ctx* c) {
         RGN_HIP(c, hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
     }
     RGN_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    { int v; if (opt_get(c, "BULK_RESID_LO", &v)) c->bulk_resid_lo = v != 0; }
     { int v; if (opt_get(c, "GRAPH_STEPS", &v)) c->graph_steps = v < 1 ? 1 : (v > 100 ? 100 : v); }
     int v_streams;
     if (opt_get(c, "STREAMS", &v_streams)) {

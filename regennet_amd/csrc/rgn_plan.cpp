@@ -114,7 +114,7 @@ inline bool eval_x3_phase(const rgn_ctx* c, bool phase_x3) {
 // throughput kernels with hi-only residual planes; guided and unguided (guided sampling runs one k_step over the conditional rows
 // after the chains have joined).
 bool step_fusable(const rgn_ctx* c, bool x3, int rows) {
-    return c->step_fused && !x3 && c->cfg.precision == RGN_PREC_BF16_X3TAIL && !use_sb(c, rows) && !c->bulk_resid_lo;
+    return c->step_fused && !x3 && c->cfg.precision == RGN_PREC_BF16_X3TAIL && !use_sb(c, rows);
 }
 // dm: the WHOLE evaluation (Bm = all rows of all chains); x3: split-bf16 arithmetic for it; sampling: inside a sampler loop
 EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool sampling) {
@@ -122,14 +122,13 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     const int prec = c->cfg.precision, rows = dm.Bm * dm.Tq;
     const bool fast = prec != RGN_PREC_F32;
     const bool lo_planes = prec == RGN_PREC_BF16X3 || prec == RGN_PREC_BF16_X3TAIL;     // has_lo()
-    const bool h_lo = x3 || (lo_planes && c->bulk_resid_lo);                              // residual stream carries a lo plane
     p.sb = use_sb(c, rows);
     if (p.sb) {
-        p.attn = (c->sb_attn && sb_qkv_attn_supported(c->d, dm.dh, dm.Tq)) ? AF_QKV : AF_GEMM_ATTN;
+        p.attn = AF_GEMM_ATTN;
         return p;
     }
     p.step_fused = sampling && step_fusable(c, x3, rows);
-    p.layers = fast && !x3 && c->layers_fused && dm.Bm >= c->layers_min_b && !h_lo && all_frag(c);
+    p.layers = fast && !x3 && c->layers_fused && dm.Bm >= c->layers_min_b && all_frag(c);
     const bool motion_per_wg = c->layers_guided == 2 || (c->layers_guided == 1 && dm.Bm > c->num_cus);   // (rgn_host.h: where a motion per workgroup pays)
     p.steps = p.layers && p.step_fused && c->layers_steps && (!guided || (motion_per_wg && c->ffn_hi &&
               // the guided form parks a motion's conditional x0 (6 x 4096 floats) in the idle hidden-tensor planes: 2 max_batch Tq ffp bf16
@@ -147,7 +146,7 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     else p.attn = AF_PLAIN;
     const bool frlo = c->L > 0 && c->layers[0].out.fr_lo && c->layers[0].ff1.fr_lo && c->layers[0].ff2.fr_lo;
     if (fast && x3 && c->mlp_x3 && lo_planes && frlo) p.tail = TF_MLP_X3;
-    else if (fast && !x3 && c->mlp && !h_lo) p.tail = TF_MLP;
+    else if (fast && !x3 && c->mlp) p.tail = TF_MLP;
     else if (fast && !x3 && c->rowgemm) p.tail = TF_ROWGEMM;
     else p.tail = TF_GEMM_LN;
     return p;
@@ -169,7 +168,7 @@ PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided) {
     //  k_qkv_attn_long + k_mlp2 + k_step - and the same chain at <= 64 tokens below the one-kernel stack's batch threshold: k_qkv_attn_rs + k_mlp2 +
     //  k_step - whose planes hand the residual stream from step to step)
     const bool f16_ok = c->bulk_f16 && ((plain.layers && plain.step_fused) || (plain.step_fused && !plain.layers && plain.tail == TF_MLP &&
-                                                       (plain.attn == AF_QKV_LONG || (plain.attn == AF_QKV && c->qkv_rs && c->d == 512 && c->L > 0 && c->layers[0].qkv.fr16))));
+                                                       (plain.attn == AF_QKV_LONG || (plain.attn == AF_QKV && c->d == 512 && c->L > 0 && c->layers[0].qkv.fr16))));
     pp.n16 = !f16_ok ? 0 : (c->f16_steps >= 0 ? c->f16_steps : F16_STEPS_DEFAULT);
     if (c->x3_tail >= 0) pp.tail = c->x3_tail;
     else if (pp.n16 > 0 && c->L >= 8 && !c->etd) pp.tail = F16_TAIL < c->S ? F16_TAIL : c->S;
@@ -203,7 +202,6 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
             RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(c->emb, nullptr, nullptr, c->dp<float>(c->off_pe), c->tmp, none, dm, c->cfg.wo_pos_emb, s));
     }
     const Planes att_p{c->att_hi, x3 ? c->att_lo : nullptr, M};
-    const bool fused_attn = plan_eval(c, dm, false, x3, sampling).attn == AF_QKV;
     for (int l = 0; l < c->L; ++l) {
         const LayerW& w = c->layers[l];
         {   // layer input = norm3 of the previous layer (layer 0: the embedding itself); in_proj -> q (pre-scaled), k, v
@@ -213,14 +211,9 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
             g.Qhi = c->q_hi; g.Khi = c->k_hi; g.Vhi = c->vt_hi;
             if (x3) { g.Qlo = c->q_lo; g.Klo = c->k_lo; g.Vlo = c->vt_lo; }
             g.d = d; g.H = c->H; g.dh = dm.dh; g.Tqp = c->Tqp; g.qscale = 1.0f / sqrtf((float)dm.dh);
-            if (fused_attn) {   // ... and the attention, a (sample, head) per workgroup: one launch, q / k / v stay in LDS
-                g.att = att_p;
-                RGN_LAUNCH(c, KC_QKV, s, launch_sb_qkv_attn(g, dm.Bm, x3, s));
-            } else {
-                RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 2, x3, s));
-            }
+            RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 2, x3, s));
         }
-        if (!fused_attn) {
+        {   // causal self-attention, a (sample, head) per workgroup -> att planes
             AttnX3Args a{};
             a.Qhi = c->q_hi; a.Qlo = c->q_lo; a.Khi = c->k_hi; a.Klo = c->k_lo; a.Vthi = c->vt_hi; a.Vtlo = c->vt_lo;
             a.out = att_p;
@@ -296,13 +289,12 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
     //      K32-blocked planes between kernels (k_gemm_x3, DMA-fed). Plane pointers are advanced by row0 rows
     //      (32 elements each) while Planes::rows stays the row count of the whole evaluation.
     // x3: this evaluation's GEMMs form three MFMAs per product and read hi + lo planes. In the bulk phase of the precision
-    // schedule every plane is written hi-only (the residual stream's lo plane is an option, bulk_resid_lo).
+    // schedule every plane is written hi-only.
     auto pln = [&](__bf16* hi, __bf16* lo, bool with_lo) {
         return Planes{fast ? hi + (size_t)row0 * 32 : nullptr, (fast && with_lo) ? lo + (size_t)row0 * 32 : nullptr, Mtot};
     };
     const Planes none{nullptr, nullptr, 0};
-    const bool h_lo = x3 || (has_lo(c) && c->bulk_resid_lo);
-    const Planes xin_p = pln(c->xin_hi, c->xin_lo, has_lo(c)), h_p = pln(c->h_hi, c->h_lo, h_lo), att_p = pln(c->att_hi, c->att_lo, x3),
+    const Planes xin_p = pln(c->xin_hi, c->xin_lo, has_lo(c)), h_p = pln(c->h_hi, c->h_lo, x3), att_p = pln(c->att_hi, c->att_lo, x3),
                  ffn_p = pln(c->ffn_hi, c->ffn_lo, x3);
     float* h = c->h + (size_t)row0 * d;
     float* tmp = c->tmp + (size_t)row0 * d;
@@ -372,12 +364,12 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
     for (int l = layers_done ? c->L : 0; l < c->L; ++l) {
         const LayerW& w = c->layers[l];
         if (pl.attn == AF_QKV) {
-            // in_proj + attention in one kernel (two samples x half the heads per workgroup): q, k, v only ever exist in LDS
+            // in_proj + attention in one kernel (a sample - the DMA-fed form: a pair - and a group of heads per workgroup): q, k, v never reach memory
             QkvAttnArgs g{};
             g.Ahi = h_p.hi; g.Alo = h_p.lo; g.a_rows = h_p.rows;
             g.Whi = c->dp<__bf16>(w.qkv.hi); g.Wlo = c->dp<__bf16>(w.qkv.lo);
-            g.Wfr = (w.qkv.fr && c->qkv_rs) ? c->dp<__bf16>(f16 ? w.qkv.fr16 : w.qkv.fr) : nullptr;   // plain phase: weights streamed to registers
-            g.Wfr_lo = (x3 && w.qkv.fr && w.qkv.fr_lo && c->qkv_rs && !c->qkv_x3_dma) ? c->dp<__bf16>(w.qkv.fr_lo) : nullptr;   // ... and the split phase's (k_qkv_attn_rs_x3)
+            g.Wfr = w.qkv.fr ? c->dp<__bf16>(f16 ? w.qkv.fr16 : w.qkv.fr) : nullptr;   // plain phase: weights streamed to registers
+            g.Wfr_lo = (x3 && w.qkv.fr && w.qkv.fr_lo && !c->qkv_x3_dma) ? c->dp<__bf16>(w.qkv.fr_lo) : nullptr;   // ... and the split phase's (k_qkv_attn_rs_x3)
             g.f16 = f16 ? 1 : 0;
             g.bias = c->dp<float>(w.qkv.b);
             g.out = att_p;
@@ -675,6 +667,11 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
         return c->fail(RGN_ERR_INVALID_ARG, "rgn_sample_range: guidance needs cond_mode text/action (cfg_sampler.py:26)");
     if (guided && !c->cond_has_scale) return c->fail(RGN_ERR_STATE, "rgn_sample_range: guided sampling needs y['scale']");
     hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = c->stream;
+    // every return, failed or not, leaves the phase flags at their default (split-bf16, no fp16)
+    struct PhaseReset {
+        rgn_ctx* c;
+        ~PhaseReset() { c->phase_x3 = true; c->phase_f16 = false; }
+    } phase_reset{c};
     RGN_HIP(c, hipSetDevice(c->cfg.device));
     int rc = build_step_table(c, eta);
     if (rc) return rc;
@@ -806,8 +803,6 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
             k += 1;
         }
     }
-    c->phase_x3 = true;
-    c->phase_f16 = false;
     return stream_exit(c, us);
 }
 
@@ -830,10 +825,8 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     for (int i = 0; i < KC_COUNT; ++i) kn[i] = "";
     const double Fp = (double)align_up((size_t)c->F, 32), wl = L * (4 * d * d + 2 * d * ff);
     if (pl.sb) {
-        const bool fa = pl.attn == AF_QKV;
-        mac[KC_SB] = embed + tail + (fa ? 0.0 : qkv); n[KC_SB] = 2 + L * (fa ? 3 : 4); kn[KC_SB] = "k_sb_gemm";
-        if (fa) { mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = "k_sb_qkv_attn"; }
-        else { mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3"; }
+        mac[KC_SB] = embed + tail + qkv; n[KC_SB] = 2 + L * 4; kn[KC_SB] = "k_sb_gemm";
+        mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3";
         n[KC_UPDATE] = 1; kn[KC_UPDATE] = "k_update";
     } else {
         const bool f32 = c->cfg.precision == RGN_PREC_F32;
@@ -854,7 +847,7 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
                 l2[KC_LAYERS] = (double)dm.Bm * wl * 2.0;
             } else {
                 switch (pl.attn) {
-                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = !c->qkv_rs ? "k_qkv_attn" : x3 ? (c->qkv_x3_dma || c->d != 512 ? "k_qkv_attn" : "k_qkv_attn_rs_x3") : "k_qkv_attn_rs"; break;
+                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = x3 ? (c->qkv_x3_dma || c->d != 512 ? "k_qkv_attn" : "k_qkv_attn_rs_x3") : "k_qkv_attn_rs"; break;
                 case AF_QKV_LONG: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = "k_qkv_attn_long"; break;
                 case AF_ROWGEMM_ATTN: mac[KC_ROWACT] += qkv; n[KC_ROWACT] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3"; break;
                 case AF_GEMM_ATTN: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3"; break;

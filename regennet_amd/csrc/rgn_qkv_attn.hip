@@ -23,8 +23,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 namespace rgn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -416,17 +414,19 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
 // vmcnt at loop back-edges and before the first LDS read behind a DMA).
 constexpr int QR_NK = 16, QR_WQ = 18;                          // weight fragment ring (6 fragments per k-step)
 constexpr int QR_DA = 4, QR_ARING = QR_DA + 1;                // activation pieces: QR_DA ahead (they must be in LDS one step early)
-// NS = samples per workgroup (4 waves each). LDS: [exchange buffer NS x 48 KiB | activation ring [2][NS x 64 rows][64 B] | biases].
-// NS = 1 is the build for full launches: two INDEPENDENT 4-wave workgroups per CU (one wave each per SIMD) instead of one
-// 8-wave workgroup whose two waves per SIMD move through the phases in lockstep - the attention phase and the ring fill of one
-// workgroup (no MFMA work, no weight requests) then run under the other's k-loop.
-template <int NS> constexpr int qr_abuf() { return NS * 48 * 1024; }
-template <int NS> constexpr int qr_lds() { return qr_abuf<NS>() + 2 * NS * QA_ROWS * 64 + 8 * QA_WROWS * 4; }
-template <int NS, bool F16 = false>
-__global__ __launch_bounds__(NS * 256, 2 / NS) void k_qkv_attn_rs(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
+// QR_NS = 1 sample per workgroup (4 waves). LDS: [exchange buffer 48 KiB | activation ring [2][64 rows][64 B] | biases].
+// Two INDEPENDENT 4-wave workgroups per CU (one wave each per SIMD) instead of one 8-wave workgroup of two samples whose two waves per
+// SIMD move through the phases in lockstep - the attention phase and the ring fill of one workgroup (no MFMA work, no weight requests)
+// then run under the other's k-loop: 36.4 -> 35.4 us alone at B = 256, 28 -> 21 us at B = 128, +3 - 4.5 % on
+// the whole step, same results bit for bit.
+constexpr int QR_NS = 1, QR_NT = QR_NS * 256;
+constexpr int QR_ABUF = QR_NS * 48 * 1024;
+constexpr int QR_LDS = QR_ABUF + 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
+template <bool F16 = false>
+__global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): input plane, weight plane, q / k / v / p, output plane
     using op8 = typename OP::v8;
-    constexpr int NT = NS * 256, STAGE = NS * QA_ROWS * 64;
+    constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(NS * 256, 2 / NS) void k_qkv_attn_rs(QkvAttnArgs g,
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
     }
-    char* abuf = smem + qr_abuf<NS>();
+    char* abuf = smem + QR_ABUF;
     float* bias_s = reinterpret_cast<float*>(abuf + 2 * STAGE);
     for (int i = tid; i < hpb * QA_WROWS; i += NT) {
         const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
@@ -540,18 +540,17 @@ __global__ __launch_bounds__(NS * 256, 2 / NS) void k_qkv_attn_rs(QkvAttnArgs g,
 // ---- split-bf16 phase, d = 512: the register-streamed form of the SPLIT arithmetic (round 6) ---------------------------------------
 // k_qkv_attn<true> above moves 64 KiB of operands per k-step through the ~20 B/clk direct-to-LDS path against 2304 cycles of MFMA (3400 measured):
 // the same weight stream through the vector-memory path into register rings, hi and lo fragment planes side by side, leaves only the activation tile
-// (hi | lo, 16 KiB per k-step pair of stages) in LDS. One sample (4 waves) per workgroup, two workgroups per CU like k_qkv_attn_rs<1>. Every accumulator
+// (hi | lo, 16 KiB per k-step pair of stages) in LDS. One sample (4 waves) per workgroup, two workgroups per CU like k_qkv_attn_rs. Every accumulator
 // sees the MFMAs of k_qkv_attn<true> in the same order (k-block, k half; lo x hi, hi x lo, hi x hi): the two forms agree bit for bit
 // (tests/test_hip_parity.py), "QKV_X3_DMA" = 1 keeps the direct-to-LDS form. The kernel itself runs 53 us where the direct-to-LDS form ran 73 (rocprofv3, the
 // evaluation schedule at B = 256) - and the CALL gains 1 - 3 %: the split steps run three kernel chains side by side and are short of L2 bandwidth chip-wide
 // (k_mlp_x3 streams 5.2 MB of weight fragments per 32-row tile), so time a chain's in_proj gives back is taken by its neighbours' layer tails.
+// One sample per workgroup: 5.71 ms per ddim5 call at B = 256 against 5.79 with two (whose sample halves request the same weight fragments at the same
+// time) and 5.78 with the direct-to-LDS form, 3.04 / 3.06 / 3.14 at B = 64 (profiles/r06_qkv_x3_forms.txt).
 constexpr int QX_WQ = 9, QX_DA = 2, QX_ARING = QX_DA + 1;        // ring depths: 1.5 k-steps of (hi, lo) weight fragment pairs, activation pieces 2 ahead
-template <int NS> constexpr int qx_lds() { return qr_abuf<NS>() + 2 * 2 * NS * QA_ROWS * 64 + 8 * QA_WROWS * 4; }
-// NS = samples per workgroup (4 waves each): 2 = one 8-wave workgroup per CU whose sample halves request the SAME weight fragments at the same time (one L2
-// read serves both: half the L2 weight traffic per sample, which is what a full chip of concurrent chains is short of); 1 = two independent workgroups per CU.
-template <int NS>
-__global__ __launch_bounds__(NS * 256, 2 / NS) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
-    constexpr int NT = NS * 256, STAGE = NS * QA_ROWS * 64;          // one plane of one stage; a stage = hi | lo
+constexpr int QX_LDS = QR_ABUF + 2 * 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
+__global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
+    constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;   // one plane of one stage; a stage = hi | lo
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -580,7 +579,7 @@ __global__ __launch_bounds__(NS * 256, 2 / NS) void k_qkv_attn_rs_x3(QkvAttnArgs
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
     }
-    char* abuf = smem + qr_abuf<NS>();                               // [stage 2][plane 2][NS x 64 rows][64 B]
+    char* abuf = smem + QR_ABUF;                                     // [stage 2][plane 2][64 rows][64 B]
     float* bias_s = reinterpret_cast<float*>(abuf + 4 * STAGE);
     for (int i = tid; i < hpb * QA_WROWS; i += NT) {
         const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
@@ -672,35 +671,23 @@ hipError_t configure_qkv_attn() {
     // (the plain-bf16 build is given the same allocation: its operand buffers, one plane each, alias its 64 KiB of stages)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<2>), hipFuncAttributeMaxDynamicSharedMemorySize, qr_lds<2>());
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, qr_lds<1>());
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<1>), hipFuncAttributeMaxDynamicSharedMemorySize, qx_lds<1>());
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<2>), hipFuncAttributeMaxDynamicSharedMemorySize, qx_lds<2>());
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<1>), hipFuncAttributeMaxDynamicSharedMemorySize, qr_lds<1>());
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
 }
 hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s) {
     if (!x3 && g.Wfr && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // plain-bf16 phase: weights streamed to registers (32-bit buffer offsets)
-        // One sample (4 waves) per workgroup, two workgroups per CU: same results bit for bit as the two-sample workgroup, 36.4 -> 35.4 us
-        // alone at B = 256, 28 -> 21 us at B = 128, and +3 - 4.5 % on the whole step (tools/qkv_attn_bench; REGENNET_QKV_NS=2 keeps the
-        // two-sample build for that comparison).
-        static const bool two = getenv("REGENNET_QKV_NS") && atoi(getenv("REGENNET_QKV_NS")) == 2;
-        static const int hs_env = getenv("REGENNET_QKV_HSPLIT") ? atoi(getenv("REGENNET_QKV_HSPLIT")) : 0;   // tools
-        const int pairs = (g.Bm + QA_NS - 1) / QA_NS;
         // Heads per workgroup: two (half the in_proj weight requests per sample) once the evaluation alone fills the chip with 4-wave
         // workgroups - >= 256 samples over all chains: 512 workgroups, two per CU - and ONE head per workgroup below that (B = 64 / 128 /
         // 192 at 60 frames: 116.9 / 131.0 / 154.1 vs 135.6 / 139.7 / 158.0 ms per 250-step call; B = 256: 360 vs 369 motions/s the other way)
         const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
-        const int hsplit = (hs_env > 0 && g.H % hs_env == 0) ? hs_env : (beval < 256 || g.H % 2) ? g.H : 2;
-        if (g.f16)     // fp16 operands (the schedule's fp16 sub-phase): the one-sample form
-            hipLaunchKernelGGL((k_qkv_attn_rs<1, true>), dim3(g.Bm, hsplit), dim3(256), qr_lds<1>(), s, g, g.Wfr);
-        else if (!two)
-            hipLaunchKernelGGL(k_qkv_attn_rs<1>, dim3(g.Bm, hsplit), dim3(256), qr_lds<1>(), s, g, g.Wfr);
+        const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;
+        if (g.f16)     // fp16 operands (the schedule's fp16 sub-phase)
+            hipLaunchKernelGGL((k_qkv_attn_rs<true>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
         else
-            hipLaunchKernelGGL(k_qkv_attn_rs<2>, dim3(pairs, hsplit), dim3(512), qr_lds<2>(), s, g, g.Wfr);
+            hipLaunchKernelGGL((k_qkv_attn_rs<false>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
         return hipGetLastError();
     }
     // heads per workgroup: half of them (the weight stream per sample is what bounds the kernel), but one head each while
@@ -709,11 +696,7 @@ hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s) {
     if (x3 && g.Wfr && g.Wfr_lo && g.Alo && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // split phase, weights streamed to registers
         const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
         const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;      // (the plain form's rule)
-        // one sample per workgroup: 5.71 ms per ddim5 call at B = 256 against 5.79 with two (and 5.78 with the direct-to-LDS form), 3.04 / 3.06 / 3.14 at B = 64
-        // (tools/ab_qkv_x3.sh, profiles/r06_qkv_x3_forms.txt; REGENNET_QKV_X3_NS=2 keeps the two-sample build for that comparison)
-        static const bool two = getenv("REGENNET_QKV_X3_NS") && atoi(getenv("REGENNET_QKV_X3_NS")) == 2;
-        if (!two) hipLaunchKernelGGL(k_qkv_attn_rs_x3<1>, dim3(g.Bm, hsplit), dim3(256), qx_lds<1>(), s, g);
-        else hipLaunchKernelGGL(k_qkv_attn_rs_x3<2>, dim3((g.Bm + 1) / 2, hsplit), dim3(512), qx_lds<2>(), s, g);
+        hipLaunchKernelGGL(k_qkv_attn_rs_x3, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
         return hipGetLastError();
     }
     const int pairs = (g.Bm + QA_NS - 1) / QA_NS;

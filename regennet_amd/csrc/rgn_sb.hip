@@ -32,14 +32,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 namespace rgn {
-
-namespace {
-static int g_sb_small_rows = 128;             // REGENNET_SB_SMALL_ROWS / REGENNET_SB_WIDE_ROWS override (tools; read once in configure_sb)
-static int g_sb_wide_rows = 512;
-}  // namespace
 
 // PRE: 0 = A fragments from K32-blocked planes, 1 = A = LayerNorm(s) of fp32 rows (through an LDS image)
 // POST: 0 = fp32 rows (+ bias + residual), 1 = GELU -> K32-blocked planes, 2 = attention-ready q / k / v planes
@@ -320,6 +313,7 @@ static hipError_t sb_launch(const SbArgs& g, hipStream_t s, bool cfg) {
 // 32-row x 32-column tiles while the evaluation has at most 128 rows (B <= 2 at 60 frames: the most workgroups, the shortest
 // LayerNorm phase each), 64 x 32 up to 512 rows, 64 x 64 beyond (half the workgroups re-normalising each row tile). Measured
 // at 60 frames, ms per 1000-step call, 64 x 32 vs 64 x 64: B = 4: 357 / 412, B = 8: 421 / 426, B = 12: 549 / 497.
+constexpr int SB_ROWS_SMALL = 128, SB_ROWS_WIDE = 512;
 template <int PRE, int POST>
 static hipError_t sb_go(const SbArgs& g, bool x3, hipStream_t s, bool cfg) {
     if (cfg) {
@@ -331,7 +325,7 @@ static hipError_t sb_go(const SbArgs& g, bool x3, hipStream_t s, bool cfg) {
         if (e == hipSuccess) e = sb_launch<PRE, POST, false, 2, 1>(g, s, true);
         return e;
     }
-    const bool small = g.M <= g_sb_small_rows, wide = g.M > g_sb_wide_rows;
+    const bool small = g.M <= SB_ROWS_SMALL, wide = g.M > SB_ROWS_WIDE;
     if (x3) return small ? sb_launch<PRE, POST, true, 1, 1>(g, s, false) : (wide ? sb_launch<PRE, POST, true, 2, 2>(g, s, false) : sb_launch<PRE, POST, true, 2, 1>(g, s, false));
     return small ? sb_launch<PRE, POST, false, 1, 1>(g, s, false) : (wide ? sb_launch<PRE, POST, false, 2, 2>(g, s, false) : sb_launch<PRE, POST, false, 2, 1>(g, s, false));
 }
@@ -343,8 +337,6 @@ static hipError_t sb_dispatch(const SbArgs& g, int pre, int post, bool x3, hipSt
     return hipErrorInvalidValue;
 }
 hipError_t configure_sb() {
-    if (const char* e = getenv("REGENNET_SB_SMALL_ROWS")) g_sb_small_rows = atoi(e);
-    if (const char* e = getenv("REGENNET_SB_WIDE_ROWS")) g_sb_wide_rows = atoi(e);
     SbArgs g{};
     const int combos[4][2] = {{0, 0}, {1, 0}, {1, 1}, {1, 2}};
     for (auto& c : combos) {

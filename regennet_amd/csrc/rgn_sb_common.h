@@ -1,5 +1,5 @@
-// Device helpers shared by the small-batch kernels (rgn_sb.hip, rgn_sb_attn.hip): DPP row sums, the 16-lane-per-row
-// LayerNorm of a 512-wide fp32 row, the erf GELU of the split-bf16 epilogues.
+// Device helpers of the small-batch kernels (rgn_sb.hip): DPP row sums, the 16-lane-per-row LayerNorm of a 512-wide fp32 row,
+// the erf GELU of the split-bf16 epilogues.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,16 +17,6 @@ constexpr int SB_D = 512;        // model width of the PRE_LN variants (row = 64
 template <int CTRL>
 __device__ __forceinline__ float sb_dpp(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// wave-wide sum on the VALU (DPP inside rows of 16 lanes, the four row totals through SGPRs), as in rgn_rowgemm.hip
-__device__ __forceinline__ float sb_wave_sum(float v) {
-    v += sb_dpp<0xB1>(v);
-    v += sb_dpp<0x4E>(v);
-    v += sb_dpp<0x141>(v);
-    v += sb_dpp<0x140>(v);
-    const int b = __builtin_bit_cast(int, v);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16)) +
-           __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
 }
 
 // erf: Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7), the split-bf16 GEMM epilogue's form

@@ -448,7 +448,7 @@ def test_two_shards_after_a_blob_transfer_reproduce_the_unsharded_batch():
     (pa, na), (pb, nb) = ea.weight_blob(), eb.weight_blob()
     dist_util.device_view(pb, nb, "cuda:0").copy_(dist_util.device_view(pa, na, "cuda:0"))
     torch.cuda.synchronize()
-    eb.schedule_id = None                                    # what dist_util.broadcast_engine_weights does after the collective
+    eb.schedule_id = None                                    # re-derive the schedule tables (dist_util.sync_model_weights marks engines stale instead)
     ya = {k: v[:half].contiguous() for k, v in y.items()}
     yb = {k: v[half:].contiguous() for k, v in y.items()}
     sa = da.p_sample_loop(ma, shape(half), clip_denoised=False, model_kwargs={"y": ya}, seed=21, sample_offset=0)
@@ -662,46 +662,6 @@ def test_small_batch_engine_is_bit_exact_under_batch_composition(config, B, T):
             yb = {k: v[b:b + 1].contiguous() for k, v in y.items()}
             one = diffusion.ddim_sample_loop(fm, (1, 56, 6, T), clip_denoised=False, model_kwargs={"y": yb}, seed=13, sample_offset=b)
             assert torch.equal(full[b:b + 1], one), (b, (full[b:b + 1] - one).abs().max().item())
-
-
-def test_small_batch_fused_in_proj_attention_kernel(golden, monkeypatch):
-    """k_sb_qkv_attn (rgn_sb_attn.hip; opt-in, REGENNET_SB_FUSED_ATTN=1 when the engine is created: it loses below B ~ 6,
-    profiles/r04_sb_fused_attn.txt): LayerNorm prologue + in_proj + attention of a (sample, head) per workgroup in place of
-    k_sb_gemm<1, 2> + k_attn_x3. Against the reference's outputs on identical noise (both phases of the precision schedule, the
-    guided golden, the 61-token emb_trans_dec one), and bit-exact under batch composition like the two-launch form."""
-    from regennet_amd import synth
-    from regennet_amd.model.cfg_sampler import ClassifierFreeSampleModel
-    monkeypatch.setenv("REGENNET_SB_FUSED_ATTN", "1")
-    for name in ("ntu_ddpm50", "ntu_action_ddim100_cfg", "ntu_add_etd_ddpm20"):
-        g = golden(name)
-        cfg, sd, y, tape = fixture_inputs(g, loop=True)
-        model, diffusion = build_hip(cfg, sd, resp=str(g["resp"]), precision="bf16_x3tail")
-        fm = ClassifierFreeSampleModel(model) if bool(g["guided"]) else model
-        B = int(g["B"])
-        fn = diffusion.p_sample_loop if str(g["mode"]) == "ddpm" else diffusion.ddim_sample_loop
-        out = fn(fm, (B, cfg["njoints"], cfg["nfeats"], cfg["num_frames"]), clip_denoised=False, model_kwargs={"y": y_to_device(y)},
-                 noise_tape=torch.from_numpy(tape))
-        err = np.abs(out.cpu().numpy() - g["final"]).max()
-        print(f"\n[k_sb_qkv_attn] {name}: {err:.2e}")
-        assert err < 1e-3, (name, err)
-        model._engine.close()
-    cfg = synth.get_config("ntu_action")
-    model, diffusion = build_hip(cfg, synth.make_state_dict(cfg, seed=0), resp="ddim5", precision="bf16_x3tail", x3_tail=2)
-    B = 5
-    y = {"cmotion": torch.from_numpy(synth.make_cmotion(cfg, B, seed=1)).cuda(),
-         "action": torch.from_numpy(synth.make_actions(cfg, B, seed=2)).cuda(), "scale": torch.full((B,), 2.5, device="cuda")}
-    fm = ClassifierFreeSampleModel(model)
-    full = diffusion.ddim_sample_loop(fm, (B, 56, 6, 60), clip_denoised=False, model_kwargs={"y": y}, seed=13)
-    for b in (0, B - 1):
-        yb = {k: v[b:b + 1].contiguous() for k, v in y.items()}
-        one = diffusion.ddim_sample_loop(fm, (1, 56, 6, 60), clip_denoised=False, model_kwargs={"y": yb}, seed=13, sample_offset=b)
-        assert torch.equal(full[b:b + 1], one), (b, (full[b:b + 1] - one).abs().max().item())
-    # and it IS another kernel: the default engine's result differs in the last bits
-    monkeypatch.delenv("REGENNET_SB_FUSED_ATTN")
-    model2, diffusion2 = build_hip(cfg, synth.make_state_dict(cfg, seed=0), resp="ddim5", precision="bf16_x3tail", x3_tail=2)
-    two = diffusion2.ddim_sample_loop(ClassifierFreeSampleModel(model2), (B, 56, 6, 60), clip_denoised=False, model_kwargs={"y": y}, seed=13)
-    dev = (full - two).abs().max().item()
-    assert 0.0 < dev < 5e-4, dev
 
 
 @pytest.mark.parametrize("precision,tail", [("bf16x3", None), ("bf16_x3tail", 2)])
@@ -1246,37 +1206,6 @@ def test_auto_regressive_grouping_invariance_with_device_rng():
         assert torch.equal(out, ref), (fpc, trunc)
     other = sample_auto_regressive(diffusion.p_sample_loop, model, shape, {"y": y}, frames_per_call=T, seed=12)
     assert not torch.equal(other, ref)
-
-
-def test_one_and_two_sample_attention_workgroups_agree_bit_for_bit():
-    """k_qkv_attn_rs<1> (one sample, four waves per workgroup, two workgroups per CU: the default) against k_qkv_attn_rs<2>
-    (REGENNET_QKV_NS=2, the round-2 two-sample workgroup): same arithmetic in the same order, so whole sampling runs must be
-    identical - odd batch (the two-sample build pads a dummy), guided, both precision phases. Fresh interpreters: the switch is
-    read once per process."""
-    import os
-    import subprocess
-    import sys
-    code = (
-        "import sys, hashlib, torch; sys.path.insert(0, '.')\n"
-        "from regennet_amd import synth\n"
-        "from regennet_amd.model.cfg_sampler import ClassifierFreeSampleModel\n"
-        "cfg = synth.get_config('ntu_action')\n"
-        "model, diffusion = synth.build_model(cfg, synth.make_state_dict(cfg, seed=0), resp='ddim6', precision='bf16_x3tail', device='cuda:0', x3_tail=2)\n"
-        "model.small_batch_rows = 0\n"
-        "B = 37\n"
-        "y = {'cmotion': torch.from_numpy(synth.make_cmotion(cfg, B, seed=4)).cuda(), 'action': torch.from_numpy(synth.make_actions(cfg, B, seed=5)).cuda(),\n"
-        "     'scale': torch.full((B,), 2.5, device='cuda')}\n"
-        "out = diffusion.ddim_sample_loop(ClassifierFreeSampleModel(model), (B, 56, 6, 60), clip_denoised=False, model_kwargs={'y': y}, seed=3)\n"
-        "assert torch.isfinite(out).all()\n"
-        "print('HASH', hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest())\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    digests = []
-    for ns in ("1", "2"):
-        env = dict(os.environ, REGENNET_QKV_NS=ns)
-        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        digests.append([ln for ln in r.stdout.splitlines() if ln.startswith("HASH")][0])
-    assert digests[0] == digests[1], digests
 
 
 @pytest.mark.parametrize("T", [65, 96, 97, 128, 129, 160])

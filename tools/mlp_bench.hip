@@ -1,6 +1,6 @@
 // Stand-alone micro-benchmark + reference check of the row-persistent layer-tail kernel (tools only; the parity tests proper are
 // tests/test_hip_parity.py).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DRGN_M2_STAMPS] -I regennet_amd/csrc tools/mlp_bench.hip regennet_amd/csrc/rgn_mlp2.hip -o tools/bin/mlp_bench      (REGENNET_MLP_ROWS=32: the two-workgroups-per-CU form)
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DRGN_M2_STAMPS] -I regennet_amd/csrc tools/mlp_bench.hip regennet_amd/csrc/rgn_mlp2.hip -o tools/bin/mlp_bench
 //   mlp_bench [M] [iters] [check]      check = 1: compare the first and the last 64-row tile with an fp64 host evaluation of the
 //                                      same bf16 inputs (the kernel rounds h', the GELU'd hidden tile and its output to bf16)
 #include "rgn_internal.h"
@@ -82,8 +82,7 @@ int main(int argc, char** argv) {
     {   // phase stamps of wave 0 of every workgroup, grouped by the CU it ran on (the last launch)
         std::vector<long long> st(1024 * 12);
         m2_stamps_read(st.data());
-        const int trows = (getenv("REGENNET_MLP_ROWS") && atoi(getenv("REGENNET_MLP_ROWS")) == 32) ? 32 : 64;
-        const int nwg = std::min(1024, (M + trows - 1) / trows);
+        const int nwg = std::min(1024, (M + 63) / 64);
         std::map<long long, std::vector<int>> by_cu;
         for (int b = 0; b < nwg; ++b) {
             const unsigned hw = (unsigned)st[b * 12 + 10];

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
 #endif
 #ifdef RGN_QA_LIFE
     {   // -DRGN_QA_LIFE (RS=1 BF16=1): start / first MFMA operands landed / end of every workgroup of the last launch, 10 ns units
-        const int nwg = (getenv("REGENNET_QKV_NS") && atoi(getenv("REGENNET_QKV_NS")) == 2) ? (Bm + 1) / 2 * 2 : Bm * (getenv("REGENNET_QKV_HSPLIT") ? atoi(getenv("REGENNET_QKV_HSPLIT")) : 2);   // grid = sample groups x 2 head halves
+        const int nwg = Bm * (Bm < 256 ? H : 2);   // grid = samples x head groups (launch_qkv_attn's rule)
         std::vector<long long> t(nwg * 3); qa_life_read(t.data(), nwg * 3);
         long long t0 = t[0], t1 = t[2];
         for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, t[3 * i]); t1 = std::max(t1, t[3 * i + 2]); }
