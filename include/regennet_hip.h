@@ -41,7 +41,7 @@ typedef enum {
     RGN_ERR_MISSING_KEY = -4,    /* finalize: a required key was never loaded (model_util.py:8) */
     RGN_ERR_STATE = -5,          /* call order violated (e.g. sample before set_schedule)       */
     RGN_ERR_HIP = -6,            /* HIP runtime error (text in rgn_last_error)                  */
-    RGN_ERR_UNSUPPORTED = -7,    /* configuration outside the hot path (e.g. arch != online)    */
+    RGN_ERR_UNSUPPORTED = -7,    /* configuration outside the hot path (e.g. latent_dim > 1024) */
     RGN_ERR_INTERNAL = -8        /* a host-side C++ exception (std::bad_alloc ...) caught at the boundary */
 } rgn_status;
 
@@ -54,13 +54,17 @@ enum { RGN_PREC_F32 = 0,      /* fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact
                                  still contracts errors (large t), split-bf16 for the last steps of a sampling
                                  loop (rgn_set_x3_tail) and for every rgn_denoise call; the residual stream and
                                  LayerNorm/softmax stay hi+lo / fp32 throughout. Inside the 1e-3 parity bound. */
+enum { RGN_ARCH_ONLINE = 0,   /* causal nn.TransformerDecoder (model/cmdm.py:205-227)                 */
+       RGN_ARCH_OFFLINE = 1 };/* non-causal nn.TransformerEncoder, embedding as token 0 (cmdm.py:228-238) */
 enum { RGN_SAMPLER_DDPM = 0,  /* GaussianDiffusion.p_sample   diffusion/gaussian_diffusion.py:508  */
        RGN_SAMPLER_DDIM = 1 };/* GaussianDiffusion.ddim_sample diffusion/gaussian_diffusion.py:744 */
 enum { RGN_FLAG_UNCOND = 1,   /* y['uncond']=True  (model/cmdm.py:181, mask_cond :129-137)         */
        RGN_FLAG_GUIDED = 2 }; /* ClassifierFreeSampleModel.forward (model/cfg_sampler.py:24-31)    */
 
-/* Mirrors the keyword arguments `CMDM(**get_model_args(args, data))` receives for arch='online'
- * (utils/model_util.py:20-72; model/cmdm.py:13-16). */
+/* Mirrors the keyword arguments `CMDM(**get_model_args(args, data))` receives for arch='online' or 'offline'
+ * (utils/model_util.py:20-72; model/cmdm.py:13-16). A zero-initialised tail means arch='online'. For arch='offline'
+ * emb_trans_dec and wo_pos_emb are ignored: the reference always prepends the embedding token and always adds the
+ * positional encoding (cmdm.py:228-238). */
 typedef struct {
     int32_t njoints;        /* 56 for SMPL-X (model_util.py:45-46)                     */
     int32_t nfeats;         /* 6 for rot6d (model_util.py:47-48)                       */
@@ -78,6 +82,7 @@ typedef struct {
     int32_t max_batch;      /* largest B any later call will use                       */
     int32_t precision;      /* RGN_PREC_*                                              */
     int32_t device;         /* HIP device ordinal                                      */
+    int32_t arch;           /* RGN_ARCH_* (--arch, parser_util.py:32)                  */
 } rgn_config;
 
 /* Per-timestep fp64 tables of the (re-spaced) diffusion, each of length S, exactly the attributes

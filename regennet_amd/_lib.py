@@ -15,6 +15,7 @@ RGN_OK = 0
 RGN_ERR_UNSUPPORTED = -7
 ERR_NAMES = {-1: "INVALID_ARG", -2: "BAD_KEY", -3: "BAD_SHAPE", -4: "MISSING_KEY", -5: "STATE", -6: "HIP", -7: "UNSUPPORTED", -8: "INTERNAL"}
 CM = {"add": 0, "concat": 1}
+ARCH = {"online": 0, "offline": 1}     # RGN_ARCH_* (include/regennet_hip.h)
 COND = {"no_cond": 0, "action": 1, "text": 2}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16_x3tail": 3}
 DEFAULT_PRECISION = "bf16_x3tail"
@@ -31,7 +32,7 @@ class RgnError(RuntimeError):
 class RgnConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "njoints", "nfeats", "num_frames", "latent_dim", "ff_size", "num_heads", "num_layers", "cm_mode",
-        "cond_mode", "num_actions", "clip_dim", "emb_trans_dec", "wo_pos_emb", "max_batch", "precision", "device")]
+        "cond_mode", "num_actions", "clip_dim", "emb_trans_dec", "wo_pos_emb", "max_batch", "precision", "device", "arch")]
 
 
 class RgnSchedule(C.Structure):
@@ -144,7 +145,7 @@ class Engine:
             ff_size=cfg["ff_size"], num_heads=cfg["num_heads"], num_layers=cfg["layers"], cm_mode=CM[cfg["cm_mode"]],
             cond_mode=COND[cfg["cond_mode"]], num_actions=int(cfg.get("num_actions", 1)), clip_dim=int(cfg.get("clip_dim", 512)),
             emb_trans_dec=int(bool(cfg.get("emb_trans_dec", False))), wo_pos_emb=int(bool(cfg.get("wo_pos_emb", False))),
-            max_batch=self.max_batch, precision=PREC[precision], device=int(device_index))
+            max_batch=self.max_batch, precision=PREC[precision], device=int(device_index), arch=ARCH[cfg.get("arch", "online")])
         h = C.c_void_p()
         code = self.lib.rgn_create(C.byref(rc), C.byref(h))
         if code != RGN_OK:

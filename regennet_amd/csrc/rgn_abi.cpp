@@ -80,6 +80,7 @@ int rgn_create(const rgn_config* cfg, rgn_handle* out) {
         if (cfg->precision < RGN_PREC_F32 || cfg->precision > RGN_PREC_BF16_X3TAIL) return bad(RGN_ERR_INVALID_ARG, "rgn_create: precision");
         if (cfg->cond_mode == RGN_COND_ACTION && cfg->num_actions <= 0) return bad(RGN_ERR_INVALID_ARG, "rgn_create: num_actions");
         if (cfg->cond_mode == RGN_COND_TEXT && cfg->clip_dim <= 0) return bad(RGN_ERR_INVALID_ARG, "rgn_create: clip_dim");
+        if (cfg->arch != RGN_ARCH_ONLINE && cfg->arch != RGN_ARCH_OFFLINE) return bad(RGN_ERR_INVALID_ARG, "rgn_create: arch");
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bad(RGN_ERR_HIP, "rgn_create: no HIP device visible");
         if (cfg->device < 0 || cfg->device >= ndev) return bad(RGN_ERR_INVALID_ARG, "rgn_create: device ordinal out of range");
@@ -89,7 +90,11 @@ int rgn_create(const rgn_config* cfg, rgn_handle* out) {
         c->cfg = *cfg;
         c->F = cfg->njoints * cfg->nfeats;
         c->d = cfg->latent_dim;
-        c->etd = cfg->emb_trans_dec ? 1 : 0;
+        // arch='offline' (cmdm.py:228-238): the embedding is always token 0 and the positional encoding always applies, so the
+        // handle is an emb_trans_dec one whose layers are encoder layers (enc: full attention, no cross-attention, two norms)
+        c->enc = cfg->arch == RGN_ARCH_OFFLINE ? 1 : 0;
+        if (c->enc) c->cfg.wo_pos_emb = 0;
+        c->etd = (cfg->emb_trans_dec || c->enc) ? 1 : 0;
         c->Tq = cfg->num_frames + c->etd;
         c->L = cfg->num_layers;
         c->H = cfg->num_heads;
@@ -211,8 +216,10 @@ int rgn_set_schedule(rgn_handle h, const rgn_schedule* s) {
         RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
         g = gemm_args(c, c->lin_t2, c->sched_tmp + (size_t)1024 * d, d, c->te_all, d, S);
         RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
-        g = gemm_args(c, c->lin_g, c->te_all, d, c->call_time, c->L * d, S);
-        RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
+        if (!c->enc) {   // (encoder layers have no cross-attention to fold)
+            g = gemm_args(c, c->lin_g, c->te_all, d, c->call_time, c->L * d, S);
+            RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
+        }
         RGN_HIP(c, hipStreamSynchronize(es));
         return RGN_OK;
     });
@@ -251,7 +258,7 @@ int rgn_set_condition(rgn_handle h, int32_t B, const float* cmotion, const int64
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(t, small_prec(c), s));
             RGN_LAUNCH(c, KC_EMBED, s, launch_fill_rows(c->condemb + (size_t)B * d, c->dp<float>(c->off_bt), B, d, s));  // embed_text(0) = bias
         }
-        if (c->cfg.cond_mode != RGN_COND_NONE) {   // folded cross-attention image of the condition rows (cond | uncond)
+        if (c->cfg.cond_mode != RGN_COND_NONE && !c->enc) {   // folded cross-attention image of the condition rows (cond | uncond)
             GemmArgs cg = gemm_args(c, c->lin_g, c->condemb, d, c->call_cond, c->L * d, 2 * B);
             cg.bias = nullptr;
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(cg, small_prec(c), s));

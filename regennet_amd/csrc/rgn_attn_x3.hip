@@ -1,4 +1,5 @@
-// Split-bf16 ("bf16x3") causal self-attention on attention-ready planes emitted by the in_proj GEMM epilogue.
+// Split-bf16 ("bf16x3") self-attention on attention-ready planes emitted by the in_proj GEMM epilogue: causal (decoder layers,
+// arch='online') or full (CAUSAL = false: encoder layers, arch='offline' - every wave visits every key tile, keys >= Tq stay masked).
 //
 // One workgroup per (sample, head), one wave per 32-query tile, v_mfma_f32_32x32x16_bf16 with fp32 accumulate;
 // every product of two fp32 quantities a.b is formed as ah.bh + ah.bl + al.bh (hi/lo bf16 planes), like the GEMMs.
@@ -26,7 +27,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <int NT, int DH, bool X3>
+template <int NT, int DH, bool X3, bool CAUSAL = true>
 __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     constexpr int DP = DH < 32 ? 32 : DH;          // dh padded to a multiple of 32 for the PV tiles
     constexpr int NS = DH / 16;                    // k16 steps of S^T (DH is 16, 32, 64 or 128)
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     for (int kj = 0; kj < NT; ++kj) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) st[kj][i] = 0.f;
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int o = (32 * kj + l31) * KLD + 16 * s + 8 * kh;
@@ -126,11 +127,11 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     float mx = -INFINITY;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj)
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * kh;
-                const bool ok = (key <= qrow) && (key < Tq);
+                const bool ok = (!CAUSAL || key <= qrow) && (key < Tq);
                 st[kj][i] = ok ? st[kj][i] : -INFINITY;
                 mx = fmaxf(mx, st[kj][i]);
             }
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     float sum = 0.f;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj)
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const float e = __expf(st[kj][i] - mx);
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
         for (int i = 0; i < 16; ++i) oa[dt][i] = 0.f;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj) {
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int step = 0; step < 2; ++step) {
                 bf16x8 ph, pl;     // B operand: this lane's 8 keys = registers 8*step .. 8*step+7
@@ -250,38 +251,39 @@ static size_t ax3_lds() {
     const size_t slab = 2 * plane * 2, patch = (size_t)NT * 32 * (DP + 4) * 4;
     return slab > patch ? slab : patch;
 }
-template <int NT, int DH>
+template <int NT, int DH, bool CAUSAL>
 static hipError_t ax3_go(const AttnX3Args& a, hipStream_t s, bool cfg) {
     const size_t lds = ax3_lds<NT, DH>();
     if (cfg) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_x3<NT, DH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_x3<NT, DH, true, CAUSAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_x3<NT, DH, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_x3<NT, DH, false, CAUSAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     if (a.x3)
-        hipLaunchKernelGGL((k_attn_x3<NT, DH, true>), dim3(a.Bm * a.H), dim3(64 * NT), lds, s, a);
+        hipLaunchKernelGGL((k_attn_x3<NT, DH, true, CAUSAL>), dim3(a.Bm * a.H), dim3(64 * NT), lds, s, a);
     else
-        hipLaunchKernelGGL((k_attn_x3<NT, DH, false>), dim3(a.Bm * a.H), dim3(64 * NT), lds, s, a);
+        hipLaunchKernelGGL((k_attn_x3<NT, DH, false, CAUSAL>), dim3(a.Bm * a.H), dim3(64 * NT), lds, s, a);
     return hipGetLastError();
 }
-template <int DH>
+template <int DH, bool CAUSAL>
 static hipError_t ax3_nt(int nt, const AttnX3Args& a, hipStream_t s, bool cfg) {
     switch (nt) {
-        case 1: return ax3_go<1, DH>(a, s, cfg);
-        case 2: return ax3_go<2, DH>(a, s, cfg);
-        case 3: return ax3_go<3, DH>(a, s, cfg);
-        case 4: return ax3_go<4, DH>(a, s, cfg);
-        case 5: return ax3_go<5, DH>(a, s, cfg);
+        case 1: return ax3_go<1, DH, CAUSAL>(a, s, cfg);
+        case 2: return ax3_go<2, DH, CAUSAL>(a, s, cfg);
+        case 3: return ax3_go<3, DH, CAUSAL>(a, s, cfg);
+        case 4: return ax3_go<4, DH, CAUSAL>(a, s, cfg);
+        case 5: return ax3_go<5, DH, CAUSAL>(a, s, cfg);
     }
     return hipErrorInvalidValue;
 }
+template <bool CAUSAL>
 static hipError_t ax3(const AttnX3Args& a, hipStream_t s, bool cfg) {
     const int nt = (a.Tq + 31) / 32;
     switch (a.dh) {
-        case 16: return ax3_nt<16>(nt, a, s, cfg);
-        case 32: return ax3_nt<32>(nt, a, s, cfg);
-        case 64: return ax3_nt<64>(nt, a, s, cfg);
-        case 128: return ax3_nt<128>(nt, a, s, cfg);
+        case 16: return ax3_nt<16, CAUSAL>(nt, a, s, cfg);
+        case 32: return ax3_nt<32, CAUSAL>(nt, a, s, cfg);
+        case 64: return ax3_nt<64, CAUSAL>(nt, a, s, cfg);
+        case 128: return ax3_nt<128, CAUSAL>(nt, a, s, cfg);
     }
     return hipErrorInvalidValue;
 }
@@ -290,8 +292,9 @@ hipError_t configure_attn_x3(int Tq, int dh) {
     AttnX3Args a{};
     a.Tq = Tq;
     a.dh = dh;
-    return ax3(a, nullptr, true);
+    hipError_t e = ax3<true>(a, nullptr, true);
+    return e != hipSuccess ? e : ax3<false>(a, nullptr, true);
 }
-hipError_t launch_attn_x3(const AttnX3Args& a, hipStream_t s) { return ax3(a, s, false); }
+hipError_t launch_attn_x3(const AttnX3Args& a, hipStream_t s, bool causal) { return causal ? ax3<true>(a, s, false) : ax3<false>(a, s, false); }
 
 }  // namespace rgn

@@ -40,7 +40,7 @@ struct Lin {  // one packed nn.Linear: offsets (bytes) into the weight blob
 
 struct LayerW {
     Lin qkv, out, ff1, ff2;
-    size_t ln[6];  // g1,b1,g2,b2,g3,b3
+    size_t ln[6];  // g1,b1,g2,b2,g3,b3 (encoder layers: norm1 in [0..1], norm2 in [4..5], [2..3] unused)
 };
 
 struct ProfEv {
@@ -93,6 +93,7 @@ struct rgn_ctx {
     std::map<std::string, int> opts;   // rgn_set_option: per-handle kernel-selection switches (they take precedence over REGENNET_<KEY> in the environment)
     bool finalized = false, have_sched = false, have_cond = false;
     int F = 0, d = 0, Tq = 0, etd = 0, L = 0, H = 0, ff = 0, pe_len = 0;
+    int enc = 0;                       // arch='offline': encoder layers (non-causal self-attention, norm1 / norm2, no cross-attention); implies etd
 
     // packed weights
     std::vector<char> hblob;

@@ -125,7 +125,8 @@ struct QkvAttnArgs {
 };
 bool qkv_attn_supported(int Tq, int dh, int d);
 hipError_t configure_qkv_attn();
-hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s);
+// causal = false: full self-attention (arch='offline' encoder layers; all four S^T tiles, keys >= Tq stay masked)
+hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s, bool causal = true);
 // long sequences (65 .. 160 tokens), plain-bf16 phase, d = 512: one workgroup per (sample, head) (rgn_qkv_attn_long.hip)
 bool qkv_attn_long_supported(int Tq, int dh, int d);
 hipError_t configure_qkv_attn_long();
@@ -175,7 +176,8 @@ struct MlpArgs {
 };
 bool mlp_supported(int d, int ff, int Tq);
 hipError_t configure_mlp();
-hipError_t launch_mlp(const MlpArgs& g, hipStream_t s);
+// enc: encoder layer tail h' = LN1(att . Wo^T + bo + h), y = LN(g3, b3)(...) - no cross-attention, no middle norm (g2 / b2 / pervec / stepvec unread)
+hipError_t launch_mlp(const MlpArgs& g, hipStream_t s, bool enc = false);
 // the layer tail of the SPLIT-bf16 phase as one row-persistent kernel (rgn_mlp_x3.hip): 32-row tiles, (hi, lo) plane pairs everywhere, three MFMAs
 // per product, two-pass LayerNorm, erf GELU - replaces k_gemm_x3 x 3 + k_layernorm x 2 per layer. Weight planes fragment-ordered, hi and lo.
 struct MlpX3Args {
@@ -186,7 +188,7 @@ struct MlpX3Args {
 };
 bool mlp_x3_supported(int d, int ff, int Tq);
 hipError_t configure_mlp_x3();
-hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s);
+hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s, bool enc = false);   // (enc: as launch_mlp)
 
 // The whole decoder stack of one evaluation as one kernel, one sample (Tq <= 64 tokens) per workgroup (rgn_layers.hip): plain-bf16 phase,
 // d = 512, ff = 1024, 4 heads of 128. Weight planes fragment-ordered as for k_mlp / k_qkv_attn_rs.
@@ -369,8 +371,8 @@ struct AttnX3Args {
 };
 bool attn_x3_supported(int Tq, int dh);
 hipError_t configure_attn_x3(int Tq, int dh);
-hipError_t launch_attn_x3(const AttnX3Args& a, hipStream_t s);
-hipError_t launch_attention(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s);
+hipError_t launch_attn_x3(const AttnX3Args& a, hipStream_t s, bool causal = true);   // (causal = false: every wave visits every key tile)
+hipError_t launch_attention(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool causal = true);
 // h_out = LN_b( LN_a(in) + addvec[row/Tq] ) when ln_b != nullptr, else LN_a(in)
 // addvec: per-sample vector (row/Tq)*ldadd, may be nullptr; stepvec: per-step vector at (*d_step)*ldstep, may be nullptr
 hipError_t launch_layernorm(const float* in, Planes resid, float* out, Planes op, int M, int d, const float* ga, const float* ba,

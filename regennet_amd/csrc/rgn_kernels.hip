@@ -331,7 +331,9 @@ hipError_t launch_gemm(const GemmArgs& g, int precision, hipStream_t s) {
 // Causal self-attention, one workgroup per (sample, head). v1: fp32 VALU, K/V slab in LDS.
 // Replaces nn.MultiheadAttention inside TransformerDecoderLayer._sa_block with the mask of
 // generate_square_subsequent_mask (cmdm.py:168-171,220-227): softmax(q k^T / sqrt(dh) + causal) v.
+// CAUSAL = false: TransformerEncoderLayer._sa_block without a mask (arch='offline', cmdm.py:237): every query sees all Tq keys.
 // =================================================================================================
+template <bool CAUSAL = true>
 __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv, float* __restrict__ out, Planes op, Dims dm) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x, hd = blockIdx.y;
@@ -359,9 +361,10 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
             for (int c = lane; c < dh; c += 64) q[c] = qkv[(row0 + i) * (size_t)(3 * d) + hd * dh + c] * scale;
         __syncthreads();
         float inv = 0.f;
+        const int jl = CAUSAL ? i : Tq - 1;   // last visible key
         if (on) {
             float mx = -INFINITY;
-            for (int j = lane; j <= i; j += 64) {
+            for (int j = lane; j <= jl; j += 64) {
                 float s = 0.f;
                 const float* kr = Ks + j * ldk;
                 for (int c = 0; c < dh; ++c) s = fmaf(q[c], kr[c], s);
@@ -370,7 +373,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
             }
             mx = wave_max(mx);
             float sum = 0.f;
-            for (int j = lane; j <= i; j += 64) {
+            for (int j = lane; j <= jl; j += 64) {
                 const float e = __expf(p[j] - mx);
                 p[j] = e;
                 sum += e;
@@ -381,7 +384,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
         if (on)
             for (int c = lane; c < dh; c += 64) {
                 float o = 0.f;
-                for (int j = 0; j <= i; ++j) o = fmaf(p[j], Vs[j * ldk + c], o);
+                for (int j = 0; j <= jl; ++j) o = fmaf(p[j], Vs[j * ldk + c], o);
                 if (out) out[(row0 + i) * (size_t)d + hd * dh + c] = o * inv;
                 if (op.hi) plane_put(op, (int)(row0 + i), hd * dh + c, o * inv);
             }
@@ -399,10 +402,11 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 //   O^T[dh, query]  = V^T . P^T   B = the S^T accumulator registers as they are (C/D layout == B layout up
 //                                 to a permutation of the contraction index, which A follows), A = V from LDS
 // K and V time-share one LDS slab [32*NT][DH+4] (pad 4 floats: the 16 lanes of a ds_read_b128 group land on
-// 16 different bank quads). Causality: wave w only visits key tiles 0..w; the diagonal tile is masked.
+// 16 different bank quads). Causality: wave w only visits key tiles 0..w; the diagonal tile is masked (CAUSAL = false, arch='offline':
+// every wave visits every key tile; keys >= Tq stay masked).
 // The result is transposed through the (by then dead) slab so global stores are row-contiguous.
 // -------------------------------------------------------------------------------------------------
-template <int NT, int DH>
+template <int NT, int DH, bool CAUSAL = true>
 __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__ qkv, float* __restrict__ out, Planes op, Dims dm) {
     constexpr int DP = (DH < 32 ? 32 : DH);       // padded head dim (PV works on 32-wide dh tiles)
     constexpr int LD = DP + 4;
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
     for (int kj = 0; kj < NT; ++kj) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) st[kj][i] = 0.f;
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const f32x4 kf = *reinterpret_cast<const f32x4*>(&slab[(32 * kj + l31) * LD + 8 * c + 4 * half]);
@@ -457,11 +461,11 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
     float mx = -INFINITY;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj) {
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * half;
-                const bool ok = (key <= qrow) && (key < Tq);
+                const bool ok = (!CAUSAL || key <= qrow) && (key < Tq);
                 st[kj][i] = ok ? st[kj][i] : -INFINITY;
                 mx = fmaxf(mx, st[kj][i]);
             }
@@ -471,7 +475,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
     float sum = 0.f;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj) {
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const float e = __expf(st[kj][i] - mx);
@@ -492,7 +496,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
         for (int i = 0; i < 16; ++i) oa[dt][i] = 0.f;
 #pragma unroll
     for (int kj = 0; kj < NT; ++kj) {
-        if (kj <= w) {
+        if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * half;   // the key this lane's P register belongs to
@@ -531,54 +535,58 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
     }
 }
 
-template <int NT, int DH>
+template <int NT, int DH, bool CAUSAL>
 static hipError_t attn_mfma_go(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool configure_only) {
     constexpr int DP = (DH < 32 ? 32 : DH);
     const size_t lds = (size_t)32 * NT * (DP + 4) * sizeof(float);
     if (configure_only)
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_mfma<NT, DH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_attn_mfma<NT, DH>), dim3(dm.Bm, dm.H), dim3(64 * NT), lds, s, qkv, out, op, dm);
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_mfma<NT, DH, CAUSAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_attn_mfma<NT, DH, CAUSAL>), dim3(dm.Bm, dm.H), dim3(64 * NT), lds, s, qkv, out, op, dm);
     return hipGetLastError();
 }
-template <int DH>
+template <int DH, bool CAUSAL>
 static hipError_t attn_mfma_nt(int nt, const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool cfg) {
     switch (nt) {
-        case 1: return attn_mfma_go<1, DH>(qkv, out, op, dm, s, cfg);
-        case 2: return attn_mfma_go<2, DH>(qkv, out, op, dm, s, cfg);
-        case 3: return attn_mfma_go<3, DH>(qkv, out, op, dm, s, cfg);
-        case 4: return attn_mfma_go<4, DH>(qkv, out, op, dm, s, cfg);
-        case 5: return attn_mfma_go<5, DH>(qkv, out, op, dm, s, cfg);
+        case 1: return attn_mfma_go<1, DH, CAUSAL>(qkv, out, op, dm, s, cfg);
+        case 2: return attn_mfma_go<2, DH, CAUSAL>(qkv, out, op, dm, s, cfg);
+        case 3: return attn_mfma_go<3, DH, CAUSAL>(qkv, out, op, dm, s, cfg);
+        case 4: return attn_mfma_go<4, DH, CAUSAL>(qkv, out, op, dm, s, cfg);
+        case 5: return attn_mfma_go<5, DH, CAUSAL>(qkv, out, op, dm, s, cfg);
     }
     return hipErrorInvalidValue;
 }
 static bool attn_mfma_ok(int Tq, int dh) { return Tq <= 160 && (dh == 16 || dh == 32 || dh == 64 || dh == 128); }
+template <bool CAUSAL>
 static hipError_t attn_mfma(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool cfg) {
     const int nt = (dm.Tq + 31) / 32;
     switch (dm.dh) {
-        case 16: return attn_mfma_nt<16>(nt, qkv, out, op, dm, s, cfg);
-        case 32: return attn_mfma_nt<32>(nt, qkv, out, op, dm, s, cfg);
-        case 64: return attn_mfma_nt<64>(nt, qkv, out, op, dm, s, cfg);
-        case 128: return attn_mfma_nt<128>(nt, qkv, out, op, dm, s, cfg);
+        case 16: return attn_mfma_nt<16, CAUSAL>(nt, qkv, out, op, dm, s, cfg);
+        case 32: return attn_mfma_nt<32, CAUSAL>(nt, qkv, out, op, dm, s, cfg);
+        case 64: return attn_mfma_nt<64, CAUSAL>(nt, qkv, out, op, dm, s, cfg);
+        case 128: return attn_mfma_nt<128, CAUSAL>(nt, qkv, out, op, dm, s, cfg);
     }
     return hipErrorInvalidValue;
 }
 
 static size_t attn_lds_bytes(int Tq, int dh) { return ((size_t)2 * Tq * (dh + 1) + 4 * dh + 4 * Tq) * sizeof(float); }
-// Called once at finalize (never during graph capture): allow > 64 KiB of dynamic LDS.
+// Called once at finalize (never during graph capture): allow > 64 KiB of dynamic LDS (both the causal and the full form).
 hipError_t configure_attention(int Tq, int dh) {
     if (attn_mfma_ok(Tq, dh)) {
         Dims dm{};
         dm.Tq = Tq;
         dm.dh = dh;
-        return attn_mfma(nullptr, nullptr, Planes{nullptr, nullptr, 0}, dm, nullptr, true);
+        hipError_t e = attn_mfma<true>(nullptr, nullptr, Planes{nullptr, nullptr, 0}, dm, nullptr, true);
+        return e != hipSuccess ? e : attn_mfma<false>(nullptr, nullptr, Planes{nullptr, nullptr, 0}, dm, nullptr, true);
     }
     const size_t lds = attn_lds_bytes(Tq, dh);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_attention), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_attention<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(k_attention<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
-hipError_t launch_attention(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s) {
-    if (attn_mfma_ok(dm.Tq, dm.dh)) return attn_mfma(qkv, out, op, dm, s, false);
-    hipLaunchKernelGGL(k_attention, dim3(dm.Bm, dm.H), dim3(256), attn_lds_bytes(dm.Tq, dm.dh), s, qkv, out, op, dm);
+hipError_t launch_attention(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool causal) {
+    if (attn_mfma_ok(dm.Tq, dm.dh)) return causal ? attn_mfma<true>(qkv, out, op, dm, s, false) : attn_mfma<false>(qkv, out, op, dm, s, false);
+    if (causal) hipLaunchKernelGGL(k_attention<true>, dim3(dm.Bm, dm.H), dim3(256), attn_lds_bytes(dm.Tq, dm.dh), s, qkv, out, op, dm);
+    else hipLaunchKernelGGL(k_attention<false>, dim3(dm.Bm, dm.H), dim3(256), attn_lds_bytes(dm.Tq, dm.dh), s, qkv, out, op, dm);
     return hipGetLastError();
 }
 

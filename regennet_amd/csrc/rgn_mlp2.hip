@@ -98,7 +98,9 @@ __device__ __forceinline__ f32x2 m2_gelu2(f32x2 x) {
     return x * __builtin_elementwise_fma(t, p, f32x2{0.5f, 0.5f});
 }
 
-template <bool F16 = false>
+// ENC = true: the encoder-layer tail of arch='offline' (as k_mlp_x3<true>): h' = LN1(att . Wo^T + bo + h), final norm from g3 / b3; g2, b2,
+// pervec and stepvec are not read.
+template <bool F16 = false, bool ENC = false>
 __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     using C = M2;
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): planes in, planes out, weight planes
@@ -306,8 +308,8 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
 #pragma unroll
         for (int v = 0; v < 4; ++v)
 #pragma unroll
-            for (int k = 0; k < VK; ++k) va[v][k] = srcA[v][cw + 64 * k];
-        if (g.stepvec) step = *g.d_step;
+            for (int k = 0; k < VK; ++k) va[v][k] = (ENC && v >= 2) ? 0.f : srcA[v][cw + 64 * k];
+        if (!ENC && g.stepvec) step = *g.d_step;
         const int s0 = m0 / g.Tq, slast = (g.M - 1) / g.Tq;
 #pragma unroll
         for (int k = 0; k < VK; ++k) {
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
 #pragma unroll
             for (int j = 0; j < NSAMP; ++j) {
                 const int sidx = s0 + j < slast ? s0 + j : slast;
-                pv[j][k] = g.pervec ? g.pervec[(size_t)sidx * g.ldper + cw + 64 * k] : 0.f;
+                pv[j][k] = (!ENC && g.pervec) ? g.pervec[(size_t)sidx * g.ldper + cw + 64 * k] : 0.f;
             }
         }
     }
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
 #endif
     float tv[VK];
 #pragma unroll
-    for (int k = 0; k < VK; ++k) tv[k] = g.stepvec ? g.stepvec[(size_t)step * g.ldstep + cw + 64 * k] : 0.f;   // (the loop index landed long ago)
+    for (int k = 0; k < VK; ++k) tv[k] = (!ENC && g.stepvec) ? g.stepvec[(size_t)step * g.ldstep + cw + 64 * k] : 0.f;   // (the loop index landed long ago)
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
@@ -397,7 +399,8 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
         }
         layernorm(acc, vec + C::A_G1, std::integral_constant<int, 0>{}, [&](int nt, int i4, int mt) { return *reinterpret_cast<const f32x4*>(spv[mt] + col4(nt, i4)); });
     }
-    layernorm(acc, vec + C::A_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4, int) { return *reinterpret_cast<const f32x4*>(vec + C::A_B2 + col4(nt, i4)); });
+    if constexpr (!ENC)
+        layernorm(acc, vec + C::A_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4, int) { return *reinterpret_cast<const f32x4*>(vec + C::A_B2 + col4(nt, i4)); });
     store_img(acc, smem + C::Y);
     // phase B vectors over phase A (wave-private: program order suffices)
 #pragma unroll
@@ -482,10 +485,14 @@ void m2_stamps_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(
 bool mlp_supported(int d, int ff, int Tq) { return d == 512 && ff == 1024 && 63 / Tq + 2 <= M2::NSAMP; }
 hipError_t configure_mlp() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2::LDS);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, M2::LDS);
     return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, M2::LDS);
 }
-hipError_t launch_mlp(const MlpArgs& g, hipStream_t s) {
-    if (g.f16) hipLaunchKernelGGL((k_mlp2<true>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
+hipError_t launch_mlp(const MlpArgs& g, hipStream_t s, bool enc) {
+    if (enc && g.f16) return hipErrorInvalidValue;                  // (encoder handles have no fp16 phase)
+    if (enc) hipLaunchKernelGGL((k_mlp2<false, true>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
+    else if (g.f16) hipLaunchKernelGGL((k_mlp2<true>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
     else hipLaunchKernelGGL((k_mlp2<false>), dim3((g.M + 63) / 64), dim3(M2::NTH), M2::LDS, s, g);
     return hipGetLastError();
 }

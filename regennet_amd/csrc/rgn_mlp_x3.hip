@@ -9,6 +9,8 @@
 // (a_hi w_lo + a_lo w_hi + a_hi w_hi, fp32 accumulate; the lo lo term, 2^-18, is dropped), LayerNorm is two-pass (mean, then the centred sum of
 // squares), GELU is the erf form with |erf error| <= 1.5e-7 - the same accuracy class as the kernels it replaces (k_gemm_x3 x 3 + k_layernorm x 2
 // per layer, five launches and four round trips of the activations through HBM).
+// ENC = true: the nn.TransformerEncoderLayer tail of arch='offline' (cmdm.py:228-238): h' = LN1(att . Wo^T + bo + h), no cross-attention and no
+// middle norm; the final norm takes g3 / b3 (the host passes norm2 there). g2, b2, pervec and stepvec are not read.
 //
 // Why 32 rows: the images are pairs. LDS: XH | XL (att tile -> GELU(hidden half) -> output), YH | YL (h': A operand of linear1, residual of
 // norm3), 32 KiB each = 128 KiB, + statistics exchange + wave-private vectors = 144 KiB: one workgroup of 8 waves per CU, wave w = output columns
@@ -66,6 +68,7 @@ __device__ __forceinline__ float mx_gelu(float v) { return v * 0.5f * (1.0f + mx
 
 }  // namespace
 
+template <bool ENC = false>
 __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     using C = MX;
     constexpr int NT = C::NT, NW = C::NW, R = C::R, CW = C::CW, RD = C::RD, KB = C::KB, NSAMP = C::NSAMP;
@@ -241,14 +244,14 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     float va[4], sv, pv[NSAMP], vb[5];
     int step = 0;
     {
-        va[0] = g.bo[cw]; va[1] = g.g1[cw]; va[2] = g.g2[cw]; va[3] = g.b2[cw];
-        if (g.stepvec) step = *g.d_step;
+        va[0] = g.bo[cw]; va[1] = g.g1[cw]; va[2] = ENC ? 0.f : g.g2[cw]; va[3] = ENC ? 0.f : g.b2[cw];
+        if (!ENC && g.stepvec) step = *g.d_step;
         const int s0 = m0 / g.Tq, slast = (g.M - 1) / g.Tq;
         sv = g.b1[cw];                                                 // norm1's beta, folded into the per-sample vector
 #pragma unroll
         for (int j = 0; j < NSAMP; ++j) {
             const int sidx = s0 + j < slast ? s0 + j : slast;
-            pv[j] = g.pervec ? g.pervec[(size_t)sidx * g.ldper + cw] : 0.f;
+            pv[j] = (!ENC && g.pervec) ? g.pervec[(size_t)sidx * g.ldper + cw] : 0.f;
         }
     }
     bf16x4 rh[NT][4], rl[NT][4];
@@ -265,10 +268,12 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             }
     }
     vb[0] = g.bf1[cw]; vb[1] = g.bf1[512 + cw]; vb[2] = g.bf2[cw]; vb[3] = g.g3[cw]; vb[4] = g.b3[cw];
-    const float tv = g.stepvec ? g.stepvec[(size_t)step * g.ldstep + cw] : 0.f;
+    const float tv = (!ENC && g.stepvec) ? g.stepvec[(size_t)step * g.ldstep + cw] : 0.f;
     // the att images are complete once EVERY wave's DMA pieces have landed: they are this wave's oldest vector-memory operations; at least
-    // 46 younger ones follow (ring 20, vectors 5 + 5, residual 16; the per-sample / step vectors may be absent), which may stay in flight
-    asm volatile("s_waitcnt vmcnt(46)" ::: "memory");
+    // 46 younger ones follow (ring 20, vectors 5 + 5, residual 16; the per-sample / step vectors may be absent), which may stay in flight -
+    // 44 in the encoder form (no g2 / b2 among the phase A vectors: 3 + 5)
+    if constexpr (ENC) asm volatile("s_waitcnt vmcnt(44)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(46)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     f32x16 acc[NT];
 #pragma unroll
@@ -294,7 +299,8 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
         const float* spv = vec + C::A_SPV + ((m < g.M ? m : g.M - 1) / g.Tq - m0 / g.Tq) * CW;
         layernorm(acc, vec + C::A_G1, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(spv + col4(nt, i4)); });
     }
-    layernorm(acc, vec + C::A_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + C::A_B2 + col4(nt, i4)); });
+    if constexpr (!ENC)
+        layernorm(acc, vec + C::A_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + C::A_B2 + col4(nt, i4)); });
     store_img(acc, C::YH, C::YL);
     // phase B vectors over phase A (wave-private)
 #pragma unroll
@@ -364,9 +370,13 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
 }
 
 bool mlp_x3_supported(int d, int ff, int Tq) { return d == 512 && ff == 1024 && 31 / Tq + 2 <= MX::NSAMP; }
-hipError_t configure_mlp_x3() { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_x3), hipFuncAttributeMaxDynamicSharedMemorySize, MX::LDS); }
-hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s) {
-    hipLaunchKernelGGL(k_mlp_x3, dim3((g.p.M + 31) / 32), dim3(MX::NTH), MX::LDS, s, g);
+hipError_t configure_mlp_x3() {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_x3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, MX::LDS);
+    return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_x3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, MX::LDS);
+}
+hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s, bool enc) {
+    if (enc) hipLaunchKernelGGL(k_mlp_x3<true>, dim3((g.p.M + 31) / 32), dim3(MX::NTH), MX::LDS, s, g);
+    else hipLaunchKernelGGL(k_mlp_x3<false>, dim3((g.p.M + 31) / 32), dim3(MX::NTH), MX::LDS, s, g);
     return hipGetLastError();
 }
 

@@ -24,8 +24,10 @@ void build_expected(rgn_ctx* c) {
     e["embed_timestep.time_embed.2.weight"] = {d, d};
     e["embed_timestep.time_embed.2.bias"] = {d};
     for (int l = 0; l < c->L; ++l) {
-        const std::string p = "seqTransDecoder.layers." + std::to_string(l) + ".";
+        // arch='offline': nn.TransformerEncoderLayer keys (self_attn, linear1/2, norm1/2); 'online': nn.TransformerDecoderLayer's
+        const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         for (const char* a : {"self_attn.", "multihead_attn."}) {
+            if (c->enc && a[0] == 'm') continue;
             e[p + a + "in_proj_weight"] = {3 * d, d};
             e[p + a + "in_proj_bias"] = {3 * d};
             e[p + a + "out_proj.weight"] = {d, d};
@@ -36,6 +38,7 @@ void build_expected(rgn_ctx* c) {
         e[p + "linear2.weight"] = {d, ff};
         e[p + "linear2.bias"] = {d};
         for (const char* n : {"norm1", "norm2", "norm3"}) {
+            if (c->enc && n[4] == '3') continue;
             e[p + n + ".weight"] = {d};
             e[p + n + ".bias"] = {d};
         }
@@ -235,7 +238,7 @@ int finalize_weights(rgn_ctx* c) {
     std::vector<float> gall((size_t)c->L * d * d), gb((size_t)c->L * d);
     c->layers.resize(c->L);
     for (int l = 0; l < c->L; ++l) {
-        const std::string p = "seqTransDecoder.layers." + std::to_string(l) + ".";
+        const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         LayerW& lw = c->layers[l];
         if (c->bulk_f16)
             for (const char* nm : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"})
@@ -250,6 +253,15 @@ int finalize_weights(rgn_ctx* c) {
         lw.out = pack_linear(c, W(p + "self_attn.out_proj.weight"), W(p + "self_attn.out_proj.bias"), d, d, true, fr || frx, frx, c->bulk_f16);
         lw.ff1 = pack_linear(c, W(p + "linear1.weight"), W(p + "linear1.bias"), ff, d, true, fr || frx, frx, c->bulk_f16);
         lw.ff2 = pack_linear(c, W(p + "linear2.weight"), W(p + "linear2.bias"), d, ff, true, fr || frx, frx, c->bulk_f16);
+        if (c->enc) {   // encoder layer: norm1 where the decoder's norm1 is, norm2 where its LAST norm is (the kernels' "final norm")
+            const char* names[4] = {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias"};
+            lw.ln[0] = blob_put(c, W(p + names[0]), (size_t)d * 4);
+            lw.ln[1] = blob_put(c, W(p + names[1]), (size_t)d * 4);
+            lw.ln[2] = lw.ln[3] = 0;
+            lw.ln[4] = blob_put(c, W(p + names[2]), (size_t)d * 4);
+            lw.ln[5] = blob_put(c, W(p + names[3]), (size_t)d * 4);
+            continue;
+        }
         const char* names[6] = {"norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "norm3.weight", "norm3.bias"};
         for (int i = 0; i < 6; ++i) lw.ln[i] = blob_put(c, W(p + names[i]), (size_t)d * 4);
         const float* wv = W(p + "multihead_attn.in_proj_weight") + (size_t)2 * d * d;
@@ -265,7 +277,7 @@ int finalize_weights(rgn_ctx* c) {
             gb[(size_t)l * d + n] = (float)b;
         }
     }
-    c->lin_g = pack_linear(c, gall.data(), gb.data(), c->L * d, d);
+    if (!c->enc) c->lin_g = pack_linear(c, gall.data(), gb.data(), c->L * d, d);
     if (c->bulk_f16 && !f16_range("output_process.poseFinal.weight", W("output_process.poseFinal.weight"), (size_t)F * d)) return RGN_ERR_UNSUPPORTED;
     c->lin_out = pack_linear(c, W("output_process.poseFinal.weight"), W("output_process.poseFinal.bias"), F, d, true,
                              c->cfg.precision == RGN_PREC_BF16_X3TAIL, false, c->bulk_f16);   // fragment order: k_step
@@ -361,7 +373,8 @@ int finalize_weights(rgn_ctx* c) {
         int ly_on = 1, ly_steps = 1;
         (void)opt_get(c, "LAYERS", &ly_on);
         (void)opt_get(c, "LAYERS_STEPS", &ly_steps);
-        c->layers_fused = c->mlp && c->fuse_qkv && layers_supported(d, ff, c->H, c->Tq, c->L) && c->Tq >= LY_MIN_TQ && ly_on != 0;
+        // (encoder handles: k_layers has decoder layers only - the LAYERS* switches do not apply)
+        c->layers_fused = c->mlp && c->fuse_qkv && layers_supported(d, ff, c->H, c->Tq, c->L) && c->Tq >= LY_MIN_TQ && ly_on != 0 && !c->enc;
         if (c->layers_fused) RGN_HIP(c, configure_layers());
         { int v; if (opt_get(c, "LAYERS_MIN_B", &v)) c->layers_min_b = c->layers_min_b_default = v < 1 ? 1 : v; }
         { int v; if (opt_get(c, "LAYERS_GUIDED", &v)) c->layers_guided = c->layers_guided_default = v < 0 ? 1 : (v > 2 ? 2 : v); }
@@ -369,7 +382,8 @@ int finalize_weights(rgn_ctx* c) {
         c->layers_steps = c->layers_fused && c->step_fused && layers_steps_supported(d, F, c->lin_x.Kp) &&
                           ly_steps != 0;
         c->step_no_quads = opt_flag(c, "STEP_NO_QUADS");
-        c->qkv_long = c->cfg.precision == RGN_PREC_BF16_X3TAIL && qkv_attn_long_supported(c->Tq, d / c->H, d) && !opt_flag(c, "NO_QKV_LONG");
+        // (encoder handles: k_qkv_attn_long is causal only - their plain phase at 65 .. 160 tokens is k_rowgemm + k_attn_x3)
+        c->qkv_long = c->cfg.precision == RGN_PREC_BF16_X3TAIL && qkv_attn_long_supported(c->Tq, d / c->H, d) && !opt_flag(c, "NO_QKV_LONG") && !c->enc;
         if (c->qkv_long) RGN_HIP(c, configure_qkv_attn_long());
         // the forms with fp16 instantiations: the multi-step one-kernel stack; k_qkv_attn_long + k_mlp2 + k_step (prec_plan decides per batch)
         c->bulk_f16 = c->bulk_f16 && c->step_fused && (c->layers_steps || ((c->qkv_long || (c->fuse_qkv && d == 512)) && c->mlp));

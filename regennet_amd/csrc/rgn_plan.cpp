@@ -128,7 +128,10 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
         return p;
     }
     p.step_fused = sampling && step_fusable(c, x3, rows);
-    p.layers = fast && !x3 && c->layers_fused && dm.Bm >= c->layers_min_b && all_frag(c);
+    // encoder handles (arch='offline'): never k_layers / k_layers<true> - their decoder layers only (layers_fused is off for them; the LAYERS*
+    // switches have no effect), never k_step - already off for every emb_trans_dec handle (rgn_pack.cpp), never k_qkv_attn_long - causal only
+    // (qkv_long is off for them): the plain phase at 65 .. 160 tokens takes AF_ROWGEMM_ATTN, k_rowgemm in_proj + the full k_attn_x3
+    p.layers = fast && !x3 && c->layers_fused && dm.Bm >= c->layers_min_b && all_frag(c) && !c->enc;
     const bool motion_per_wg = c->layers_guided == 2 || (c->layers_guided == 1 && dm.Bm > c->num_cus);   // (rgn_host.h: where a motion per workgroup pays)
     p.steps = p.layers && p.step_fused && c->layers_steps && (!guided || (motion_per_wg && c->ffn_hi &&
               // the guided form parks a motion's conditional x0 (6 x 4096 floats) in the idle hidden-tensor planes: 2 max_batch Tq ffp bf16
@@ -140,7 +143,7 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     }
     const bool fr0 = c->L > 0 && c->layers[0].qkv.fr != 0;
     if (fast && c->fuse_qkv) p.attn = AF_QKV;
-    else if (fast && c->qkv_long && !x3 && fr0 && (size_t)rows * c->layers[0].qkv.Kp * 2 < (1ull << 31)) p.attn = AF_QKV_LONG;
+    else if (fast && c->qkv_long && !c->enc && !x3 && fr0 && (size_t)rows * c->layers[0].qkv.Kp * 2 < (1ull << 31)) p.attn = AF_QKV_LONG;
     else if (fast && c->attn_x3 && !x3 && c->rowgemm && dm.dh % 32 == 0 && fr0) p.attn = AF_ROWGEMM_ATTN;
     else if (fast && c->attn_x3) p.attn = AF_GEMM_ATTN;
     else p.attn = AF_PLAIN;
@@ -213,12 +216,12 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
             g.d = d; g.H = c->H; g.dh = dm.dh; g.Tqp = c->Tqp; g.qscale = 1.0f / sqrtf((float)dm.dh);
             RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 2, x3, s));
         }
-        {   // causal self-attention, a (sample, head) per workgroup -> att planes
+        {   // causal (encoder handles: full) self-attention, a (sample, head) per workgroup -> att planes
             AttnX3Args a{};
             a.Qhi = c->q_hi; a.Qlo = c->q_lo; a.Khi = c->k_hi; a.Klo = c->k_lo; a.Vthi = c->vt_hi; a.Vtlo = c->vt_lo;
             a.out = att_p;
             a.Bm = dm.Bm; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = x3;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
         }
         {   // tmp = attention . Wo^T + bo + h
             SbArgs g = base(w.out);
@@ -226,13 +229,14 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
             g.resid = c->h; g.ldr = d; g.C = c->tmp; g.ldc = d;
             RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 0, 0, x3, s));
         }
-        {   // h = norm2(norm1(tmp) + folded cross-attention); ffn = gelu(h . W1^T + b1)
+        {   // h = norm2(norm1(tmp) + folded cross-attention) (encoder layers: h = norm1(tmp)); ffn = gelu(h . W1^T + b1)
             SbArgs g = base(w.ff1);
             g.src = c->tmp; g.xout = c->h;
-            g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]); g.gb = c->dp<float>(w.ln[2]); g.bb = c->dp<float>(w.ln[3]);
-            g.pervec = sampling ? (ccond_rows ? ccond_rows + (size_t)l * d : nullptr) : c->call + (size_t)l * d;
+            g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]);
+            if (!c->enc) { g.gb = c->dp<float>(w.ln[2]); g.bb = c->dp<float>(w.ln[3]); }
+            g.pervec = c->enc ? nullptr : sampling ? (ccond_rows ? ccond_rows + (size_t)l * d : nullptr) : c->call + (size_t)l * d;
             g.ldper = Ld;
-            g.stepvec = sampling ? c->call_time + (size_t)l * d : nullptr;
+            g.stepvec = (sampling && !c->enc) ? c->call_time + (size_t)l * d : nullptr;
             g.ldstep = Ld; g.d_step = c->d_step;
             g.Chi = c->ffn_hi; g.Clo = x3 ? c->ffn_lo : nullptr; g.c_rows = M;
             RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 1, x3, s));
@@ -376,7 +380,7 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             g.Bm = ns; g.Kp = w.qkv.Kp; g.d = d; g.H = c->H; g.Tq = dm.Tq;
             g.qscale = 1.0f / sqrtf((float)dm.dh);
             g.Bm_eval = dmf.Bm;   // samples of the WHOLE evaluation (all kernel chains), not of this chain
-            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn(g, x3, s));   // 93 % of its MFMA work is the in_proj GEMM
+            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn(g, x3, s, !c->enc));   // 93 % of its MFMA work is the in_proj GEMM
         } else if (pl.attn == AF_QKV_LONG) {
             // plain-bf16 phase, long sequence: in_proj + attention of one (sample, head) per workgroup, q / k / v stay in LDS
             QkvAttnArgs g{};
@@ -401,7 +405,7 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             a.Qhi = g.Qhi; a.Qlo = c->q_lo + slab0; a.Khi = g.Khi; a.Klo = c->k_lo + slab0; a.Vthi = g.Vhi; a.Vtlo = c->vt_lo + slab0;
             a.out = att_p;
             a.Bm = ns; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = false;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
         } else if (pl.attn == AF_GEMM_ATTN) {
             // in_proj GEMM scatters q (pre-scaled), k and v as attention-ready split planes; no fp32 qkv round trip
             GemmX3Args g{};
@@ -420,14 +424,17 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             a.Qhi = g.Qhi; a.Qlo = c->q_lo + slab0; a.Khi = g.Khi; a.Klo = c->k_lo + slab0; a.Vthi = g.Vthi; a.Vtlo = c->vt_lo + slab0;
             a.out = att_p;
             a.Bm = ns; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = x3;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
         } else {
             if ((rc = big(w.qkv, h, d, h_p, qkv, 3 * d, none, nullptr, 0, M))) return rc;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attention(qkv, fast ? nullptr : att, att_p, dm, s));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attention(qkv, fast ? nullptr : att, att_p, dm, s, !c->enc));
         }
-        const float* per_sample = sampling ? (ccond_rows ? ccond_rows + (size_t)s0 * Ld + (size_t)l * d : nullptr)
-                                           : c->call + (size_t)s0 * Ld + (size_t)l * d;
-        const float* step_vec = sampling ? c->call_time + (size_t)l * d : nullptr;
+        // (encoder layers: no cross-attention vectors, and no middle norm - g2 / b2 are null)
+        const float* per_sample = c->enc ? nullptr : sampling ? (ccond_rows ? ccond_rows + (size_t)s0 * Ld + (size_t)l * d : nullptr)
+                                                              : c->call + (size_t)s0 * Ld + (size_t)l * d;
+        const float* step_vec = (sampling && !c->enc) ? c->call_time + (size_t)l * d : nullptr;
+        const float* g2 = c->enc ? nullptr : c->dp<float>(w.ln[2]);
+        const float* b2 = c->enc ? nullptr : c->dp<float>(w.ln[3]);
         if (pl.tail == TF_MLP_X3) {
             // split-bf16 phase, d = 512 / ff = 1024: the same layer tail on (hi, lo) plane pairs, three MFMAs per product (rgn_mlp_x3.hip):
             // one launch where k_gemm_x3 x 3 + k_layernorm x 2 were five; residual stream updated in place (both planes)
@@ -438,10 +445,10 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             g.Wo = c->dp<__bf16>(w.out.fr); g.W1 = c->dp<__bf16>(w.ff1.fr); g.W2 = c->dp<__bf16>(w.ff2.fr);
             gx.Wo_lo = c->dp<__bf16>(w.out.fr_lo); gx.W1_lo = c->dp<__bf16>(w.ff1.fr_lo); gx.W2_lo = c->dp<__bf16>(w.ff2.fr_lo);
             g.bo = c->dp<float>(w.out.b); g.bf1 = c->dp<float>(w.ff1.b); g.bf2 = c->dp<float>(w.ff2.b);
-            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = c->dp<float>(w.ln[2]); g.b2 = c->dp<float>(w.ln[3]);
+            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = g2; g.b2 = b2;
             g.g3 = c->dp<float>(w.ln[4]); g.b3 = c->dp<float>(w.ln[5]);
             g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
-            RGN_LAUNCH(c, KC_MLP, s, launch_mlp_x3(gx, s));
+            RGN_LAUNCH(c, KC_MLP, s, launch_mlp_x3(gx, s, c->enc != 0));
             continue;
         }
         if (pl.tail == TF_MLP) {
@@ -452,10 +459,10 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             g.Wo = c->dp<__bf16>(f16 ? w.out.fr16 : w.out.fr); g.W1 = c->dp<__bf16>(f16 ? w.ff1.fr16 : w.ff1.fr); g.W2 = c->dp<__bf16>(f16 ? w.ff2.fr16 : w.ff2.fr);
             g.f16 = f16 ? 1 : 0;
             g.bo = c->dp<float>(w.out.b); g.bf1 = c->dp<float>(w.ff1.b); g.bf2 = c->dp<float>(w.ff2.b);
-            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = c->dp<float>(w.ln[2]); g.b2 = c->dp<float>(w.ln[3]);
+            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = g2; g.b2 = b2;
             g.g3 = c->dp<float>(w.ln[4]); g.b3 = c->dp<float>(w.ln[5]);
             g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
-            RGN_LAUNCH(c, KC_MLP, s, launch_mlp(g, s));
+            RGN_LAUNCH(c, KC_MLP, s, launch_mlp(g, s, c->enc != 0));
             continue;
         }
         if (pl.tail == TF_ROWGEMM) {
@@ -466,7 +473,7 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             g.W = c->dp<__bf16>(w.out.fr); g.bias = c->dp<float>(w.out.b);
             g.M = M; g.N = d; g.Kp = w.out.Kp;
             g.Rhi = h_p.hi; g.Rlo = h_p.lo; g.r_rows = h_p.rows; g.Ohi = h_p.hi; g.Olo = h_p.lo; g.o_rows = h_p.rows;
-            g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]); g.gb = c->dp<float>(w.ln[2]); g.bb = c->dp<float>(w.ln[3]);
+            g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]); g.gb = g2; g.bb = b2;
             g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
             RGN_LAUNCH(c, KC_ROWLN, s, launch_rowgemm(g, true, s));
             RowGemmArgs f{};
@@ -486,7 +493,7 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
         if ((rc = big(w.out, att, d, att_p, tmp, d, none, h32 ? h : nullptr, 0, M))) return rc;
         RGN_LAUNCH(c, KC_LN, s,
                    launch_layernorm(tmp, h32 ? none : h_p, h32 ? h : nullptr, h_p, M, d, c->dp<float>(w.ln[0]), c->dp<float>(w.ln[1]), per_sample, Ld, step_vec, Ld,
-                                    c->d_step, dm.Tq, c->dp<float>(w.ln[2]), c->dp<float>(w.ln[3]), s));
+                                    c->d_step, dm.Tq, g2, b2, s));
         if ((rc = big(w.ff1, h, d, h_p, fast ? nullptr : ffn, c->ff, ffn_p, nullptr, 1, M))) return rc;
         if ((rc = big(w.ff2, ffn, c->ff, ffn_p, tmp, d, none, h32 ? h : nullptr, 0, M))) return rc;
         RGN_LAUNCH(c, KC_LN, s,
@@ -536,9 +543,11 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
         g.add = cond_rows;
         g.ldadd = d;
         RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
-        // cross-attention onto the 1-token memory, all layers at once: call[b, l*d:(l+1)*d]
-        g = gemm_args(c, c->lin_g, c->emb, d, c->call, Ld, dm.Bm);
-        RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
+        // cross-attention onto the 1-token memory, all layers at once: call[b, l*d:(l+1)*d] (encoder layers have none)
+        if (!c->enc) {
+            g = gemm_args(c, c->lin_g, c->emb, d, c->call, Ld, dm.Bm);
+            RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
+        }
     }
     // ---- layers. In the bf16 modes the samples of the evaluation are split into contiguous groups that run as
     //      independent kernel chains on separate streams (fork/join with events, also inside graph capture): the
@@ -815,6 +824,7 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     const Dims dm = make_dims(c, B, guided != 0);
     const bool x3 = eval_x3_phase(c, split_phase != 0);
     const EvalPlan pl = plan_eval(c, dm, guided != 0, x3, true);
+    const bool enc = c->enc != 0;   // (encoder handles: the full-attention / encoder-tail instantiations)
     // SURVEY.md 8(d) accounting: MACs of ONE evaluation of the bound batch (2 B rows under guidance), full T x T attention scores; the
     // timestep MLP and the folded 1-token cross-attention are per-schedule / per-condition work, not per step
     const double T = dm.T, d = c->d, ff = c->ff, L = c->L, F = c->F, M = (double)dm.Bm * T;
@@ -826,7 +836,7 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     const double Fp = (double)align_up((size_t)c->F, 32), wl = L * (4 * d * d + 2 * d * ff);
     if (pl.sb) {
         mac[KC_SB] = embed + tail + qkv; n[KC_SB] = 2 + L * 4; kn[KC_SB] = "k_sb_gemm";
-        mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3";
+        mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3";
         n[KC_UPDATE] = 1; kn[KC_UPDATE] = "k_update";
     } else {
         const bool f32 = c->cfg.precision == RGN_PREC_F32;
@@ -847,15 +857,19 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
                 l2[KC_LAYERS] = (double)dm.Bm * wl * 2.0;
             } else {
                 switch (pl.attn) {
-                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = x3 ? (c->qkv_x3_dma || c->d != 512 ? "k_qkv_attn" : "k_qkv_attn_rs_x3") : "k_qkv_attn_rs"; break;
+                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L;
+                    kn[KC_QKV] = x3 ? (c->qkv_x3_dma || c->d != 512 ? (enc ? "k_qkv_attn<full>" : "k_qkv_attn") : (enc ? "k_qkv_attn_rs_x3<full>" : "k_qkv_attn_rs_x3"))
+                                    : (enc ? "k_qkv_attn_rs<full>" : "k_qkv_attn_rs");
+                    break;
                 case AF_QKV_LONG: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = "k_qkv_attn_long"; break;
-                case AF_ROWGEMM_ATTN: mac[KC_ROWACT] += qkv; n[KC_ROWACT] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3"; break;
-                case AF_GEMM_ATTN: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = "k_attn_x3"; break;
-                default: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = f32 ? "k_attn_mfma" : "k_attention"; break;
+                case AF_ROWGEMM_ATTN: mac[KC_ROWACT] += qkv; n[KC_ROWACT] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;
+                case AF_GEMM_ATTN: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;
+                default: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L;
+                    kn[KC_ATTN] = f32 ? (enc ? "k_attn_mfma<full>" : "k_attn_mfma") : (enc ? "k_attention<full>" : "k_attention"); break;
                 }
                 switch (pl.tail) {
-                case TF_MLP_X3: mac[KC_MLP] = tail; n[KC_MLP] = L; kn[KC_MLP] = "k_mlp_x3"; break;
-                case TF_MLP: mac[KC_MLP] = tail; n[KC_MLP] = L; kn[KC_MLP] = "k_mlp2"; break;
+                case TF_MLP_X3: mac[KC_MLP] = tail; n[KC_MLP] = L; kn[KC_MLP] = enc ? "k_mlp_x3<enc>" : "k_mlp_x3"; break;
+                case TF_MLP: mac[KC_MLP] = tail; n[KC_MLP] = L; kn[KC_MLP] = enc ? "k_mlp2<enc>" : "k_mlp2"; break;
                 case TF_ROWGEMM:
                     mac[KC_ROWLN] = M * (d * d + d * ff) * L; n[KC_ROWLN] = 2 * L; kn[KC_ROWLN] = "k_rowgemm<LN>";
                     mac[KC_ROWACT] += M * d * ff * L; n[KC_ROWACT] += L;

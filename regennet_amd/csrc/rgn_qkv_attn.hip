@@ -1,4 +1,5 @@
 // Fused in_proj GEMM + causal self-attention (Tq <= 64 tokens, head dim 128): q, k, v never leave the register file.
+// Every kernel here also has a full-attention instantiation (CAUSAL = false) for the encoder layers of arch='offline' (cmdm.py:228-238).
 //
 // Replaces, per decoder layer, the packed in_proj Linear of nn.MultiheadAttention and the attention itself
 // (model/cmdm.py:227 -> TransformerDecoderLayer._sa_block with generate_square_subsequent_mask :168-171).
@@ -55,7 +56,9 @@ __device__ long long g_qa_prof[64];   // tools only: phase cycle stamps of one w
 
 // Attention straight from the in_proj accumulators of one head (see the file header); shared by the DMA-fed and the
 // register-streamed GEMM phases. acc[token tile][q | k | v]; smem: the 96 KiB fp32 exchange buffer for the S^T partials.
-template <bool X3, bool F16 = false>
+// CAUSAL = false (encoder layers, arch='offline'): all four S^T tiles, keys >= Tq masked. The fourth tile (keys 32-63, queries 0-31)
+// is reduced in a second pass through the first tile's slot of the same exchange buffer, so the LDS budget is the causal one.
+template <bool X3, bool F16 = false, bool CAUSAL = true>
 __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnArgs& g, char* smem, const float* bias_h, int hd, int hslot,
                                              int wm, int wn, int nsamp, int b0, int lane, int tid) {
     static_assert(!(X3 && F16), "the split form is bf16 (hi, lo) pairs");
@@ -107,11 +110,13 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
                 }
             }
     }
-    // causal tiles of S^T: 0 = (keys 0-31, queries 0-31), 1 = (keys 0-31, queries 32-63), 2 = (keys 32-63, queries 32-63)
-    f32x16 st[3];
+    // causal tiles of S^T: 0 = (keys 0-31, queries 0-31), 1 = (keys 0-31, queries 32-63), 2 = (keys 32-63, queries 32-63);
+    // the full form adds 3 = (keys 32-63, queries 0-31)
+    constexpr int NTL = CAUSAL ? 3 : 4;
+    f32x16 st[NTL];
 #pragma unroll
-    for (int tl = 0; tl < 3; ++tl) {
-        const int kj = tl >> 1, qtile = tl ? 1 : 0;
+    for (int tl = 0; tl < NTL; ++tl) {
+        const int kj = tl >> 1, qtile = CAUSAL ? (tl ? 1 : 0) : ((tl == 1 || tl == 2) ? 1 : 0);
 #pragma unroll
         for (int i = 0; i < 16; ++i) st[tl][i] = 0.f;
 #pragma unroll
@@ -149,6 +154,29 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
 #pragma unroll
             for (int e = 0; e < 4; ++e) st[tl][4 * i4 + e] = v[e];
         }
+    if constexpr (!CAUSAL) {   // second pass: tile 3 through tile 0's slot, once every wave's reads of it have landed
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int i4 = 0; i4 < 4; ++i4) {
+            const f32x4 v = {st[3][4 * i4], st[3][4 * i4 + 1], st[3][4 * i4 + 2], st[3][4 * i4 + 3]};
+            sred[(((wm * 3) * 4 + wn) * 4 + i4) * 64 + lane] = v;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int i4 = 0; i4 < 4; ++i4) {
+            f32x4 v = sred[(((wm * 3) * 4 + 0) * 4 + i4) * 64 + lane];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const f32x4 u = sred[(((wm * 3) * 4 + w) * 4 + i4) * 64 + lane];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += u[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) st[3][4 * i4 + e] = v[e];
+        }
+    }
     RGN_QT(hslot * 8 + 4)
     // softmax over keys for the lane's two queries (l31 and 32 + l31); every wave of the sample does the same work
     float inv[2];
@@ -156,13 +184,16 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
     for (int qtile = 0; qtile < 2; ++qtile) {
         const int q = 32 * qtile + l31;
         float mx = -INFINITY;
+        // tiles {0} for query tile 0, {1, 2} for query tile 1 (the full form: {0, 3}, {1, 2}; the causal bounds fold to tl = qtile .. 2 qtile)
+#define RGN_QA_TILES(tl) for (int tl = qtile; tl <= (CAUSAL ? 2 * qtile : (qtile ? 2 : 3)); tl += (CAUSAL ? 1 : (qtile ? 1 : 3)))
 #pragma unroll
-        for (int tl = qtile; tl <= 2 * qtile; ++tl) {             // tiles {0} for query tile 0, {1, 2} for query tile 1
+        RGN_QA_TILES(tl) {
             const int kj = tl >> 1;
             // key of register i = 32 kj + 4 kh + c_i, c_i = (i & 3) + 8 (i >> 2); visible iff key <= min(q, Tq - 1) (tile 1 - keys 0-31,
-            // queries 32-63 - lies below the diagonal: only key < Tq). ONE per-lane limit, made opaque here: written as 48 compares of
-            // loop-invariant values they are hoisted out of the head loop and their lane masks live in ~70 SGPRs spilled to VGPR lanes
-            int lim = (tl == 1 ? Tq - 1 : (q < Tq - 1 ? q : Tq - 1)) - 32 * kj - 4 * kh;
+            // queries 32-63 - lies below the diagonal: only key < Tq; the full form: key < Tq everywhere). ONE per-lane limit, made opaque
+            // here: written as 48 compares of loop-invariant values they are hoisted out of the head loop and their lane masks live in
+            // ~70 SGPRs spilled to VGPR lanes
+            int lim = ((CAUSAL ? tl == 1 : true) ? Tq - 1 : (q < Tq - 1 ? q : Tq - 1)) - 32 * kj - 4 * kh;
             asm volatile("" : "+v"(lim));
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -173,7 +204,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
         mx = half_max(mx);
         float sum = 0.f;
 #pragma unroll
-        for (int tl = qtile; tl <= 2 * qtile; ++tl)
+        RGN_QA_TILES(tl)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const float e = __builtin_amdgcn_exp2f(st[tl][i] - mx);
@@ -191,7 +222,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
 #pragma unroll
         for (int i = 0; i < 16; ++i) oa[i] = 0.f;
 #pragma unroll
-        for (int tl = qtile; tl <= 2 * qtile; ++tl) {
+        RGN_QA_TILES(tl) {
             const int kj = tl >> 1;
 #pragma unroll
             for (int sl = 0; sl < 2; ++sl) {
@@ -256,7 +287,9 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
     }
 }
 
-template <bool X3>
+#undef RGN_QA_TILES
+
+template <bool X3, bool CAUSAL = true>
 __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     constexpr int NPL = X3 ? 2 : 1;
     constexpr int A_BYTES = QA_NS * QA_ROWS * 64, W_BYTES = QA_WROWS * 64;
@@ -395,7 +428,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                              // every wave is done reading the last stage
         RGN_QT((hd - hd0) * 8 + 1)
-        qa_attention<X3>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
+        qa_attention<X3, false, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         RGN_QT((hd - hd0) * 8 + 6)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();      // the next head's DMA overwrites the reduction buffer
@@ -422,7 +455,7 @@ constexpr int QR_DA = 4, QR_ARING = QR_DA + 1;                // activation piec
 constexpr int QR_NS = 1, QR_NT = QR_NS * 256;
 constexpr int QR_ABUF = QR_NS * 48 * 1024;
 constexpr int QR_LDS = QR_ABUF + 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
-template <bool F16 = false>
+template <bool F16 = false, bool CAUSAL = true>
 __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): input plane, weight plane, q / k / v / p, output plane
     using op8 = typename OP::v8;
@@ -528,7 +561,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
             }
         }
         RGN_QT((hd - hd0) * 8 + 1)
-        qa_attention<false, F16>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
+        qa_attention<false, F16, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         RGN_QT((hd - hd0) * 8 + 6)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -549,6 +582,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
 // time) and 5.78 with the direct-to-LDS form, 3.04 / 3.06 / 3.14 at B = 64 (profiles/r06_qkv_x3_forms.txt).
 constexpr int QX_WQ = 9, QX_DA = 2, QX_ARING = QX_DA + 1;        // ring depths: 1.5 k-steps of (hi, lo) weight fragment pairs, activation pieces 2 ahead
 constexpr int QX_LDS = QR_ABUF + 2 * 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
+template <bool CAUSAL = true>
 __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
     constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;   // one plane of one stage; a stage = hi | lo
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -657,7 +691,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                // (the exchange buffer does not alias the ring, but every wave must have left the k-loop's last stage reads)
-        qa_attention<true>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
+        qa_attention<true, false, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
@@ -673,19 +707,31 @@ hipError_t configure_qkv_attn() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
+    if (e != hipSuccess) return e;
+    // the full-attention forms (encoder layers): the same allocations - the fourth S^T tile passes through the causal exchange buffer
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
 }
-hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s) {
+hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s, bool causal) {
     if (!x3 && g.Wfr && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // plain-bf16 phase: weights streamed to registers (32-bit buffer offsets)
         // Heads per workgroup: two (half the in_proj weight requests per sample) once the evaluation alone fills the chip with 4-wave
         // workgroups - >= 256 samples over all chains: 512 workgroups, two per CU - and ONE head per workgroup below that (B = 64 / 128 /
         // 192 at 60 frames: 116.9 / 131.0 / 154.1 vs 135.6 / 139.7 / 158.0 ms per 250-step call; B = 256: 360 vs 369 motions/s the other way)
         const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
         const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;
+        if (g.f16 && !causal) return hipErrorInvalidValue;          // (encoder handles have no fp16 phase)
         if (g.f16)     // fp16 operands (the schedule's fp16 sub-phase)
             hipLaunchKernelGGL((k_qkv_attn_rs<true>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
+        else if (!causal)
+            hipLaunchKernelGGL((k_qkv_attn_rs<false, false>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
         else
             hipLaunchKernelGGL((k_qkv_attn_rs<false>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
         return hipGetLastError();
@@ -696,13 +742,17 @@ hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s) {
     if (x3 && g.Wfr && g.Wfr_lo && g.Alo && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // split phase, weights streamed to registers
         const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
         const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;      // (the plain form's rule)
-        hipLaunchKernelGGL(k_qkv_attn_rs_x3, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
+        if (causal) hipLaunchKernelGGL(k_qkv_attn_rs_x3<true>, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
+        else hipLaunchKernelGGL(k_qkv_attn_rs_x3<false>, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
         return hipGetLastError();
     }
     const int pairs = (g.Bm + QA_NS - 1) / QA_NS;
     const int hsplit = (pairs * g.H <= 64) ? g.H : (g.H % 2 == 0 ? 2 : 1);
     const dim3 grid(pairs, hsplit);
-    if (x3)
+    if (!causal) {
+        if (x3) hipLaunchKernelGGL((k_qkv_attn<true, false>), grid, dim3(QA_NT), qa_lds(true), s, g);
+        else hipLaunchKernelGGL((k_qkv_attn<false, false>), grid, dim3(QA_NT), qa_lds(true), s, g);
+    } else if (x3)
         hipLaunchKernelGGL((k_qkv_attn<true>), grid, dim3(QA_NT), qa_lds(true), s, g);
     else
         hipLaunchKernelGGL((k_qkv_attn<false>), grid, dim3(QA_NT), qa_lds(true), s, g);

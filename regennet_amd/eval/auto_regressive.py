@@ -16,6 +16,8 @@ tokens 0..f alone at every diffusion step. A call that covers the frames [f0, f1
 is keyed by (sample, step, feature, frame), independent of the sequence length, so truncation changes no noise value; the kept
 frames then agree with the untruncated run to within the precision mode's rounding (bit for bit on the small-batch engine with
 uniform split-bf16 arithmetic, which is what the tests pin; a different sequence length can select different kernels).
+An arch='offline' model is an encoder (cmdm.py:228-238): frame f sees every token, the masked (zero) future actor frames included,
+so its calls always run the full T frames, as the reference does.
 """
 import torch as th
 
@@ -80,7 +82,7 @@ def sample_auto_regressive(sample_fn, model, shape, model_kwargs, setting="cmdm"
         n = f1 - f0
         # lengths in steps of 16 (extra tokens are harmless under the causal mask): at most ceil(T / 16) distinct engines
         # however the frames are grouped, below the model's per-length engine cache (CMDM.MAX_ENGINES)
-        Tc = min(T, -(-f1 // 16) * 16) if truncate else T
+        Tc = min(T, -(-f1 // 16) * 16) if truncate and getattr(getattr(model, "model", model), "arch", "online") != "offline" else T
         yy = _expand_y(y, B, f0, f1, cm_full, Tc)
         kw = dict(sample_kw)
         if noise_tapes is not None:

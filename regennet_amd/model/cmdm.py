@@ -1,4 +1,4 @@
-"""CMDM denoiser object for arch='online' — host-side mirror of the reference's `model/cmdm.py`.
+"""CMDM denoiser object for arch='online' and arch='offline' — host-side mirror of the reference's `model/cmdm.py`.
 
 The class keeps the reference's constructor keywords, attribute names and state_dict key names
 (so `load_model_wo_clip`, `model.to(dev())`, `model.eval()`, `next(model.parameters()).device`,
@@ -47,6 +47,21 @@ class _Decoder(nn.Module):
         self.layers = nn.ModuleList([_DecoderLayer(d, ff) for _ in range(n)])
 
 
+class _EncoderLayer(nn.Module):  # nn.TransformerEncoderLayer's parameter names (arch='offline', cmdm.py:63-71)
+    def __init__(self, d, ff):
+        super().__init__()
+        self.self_attn = _MHA(d)
+        self.linear1 = nn.Linear(d, ff)
+        self.linear2 = nn.Linear(ff, d)
+        self.norm1, self.norm2 = nn.LayerNorm(d), nn.LayerNorm(d)
+
+
+class _Encoder(nn.Module):       # nn.TransformerEncoder without a final norm (the reference passes none)
+    def __init__(self, d, ff, n):
+        super().__init__()
+        self.layers = nn.ModuleList([_EncoderLayer(d, ff) for _ in range(n)])
+
+
 class PositionalEncoding(nn.Module):
     """Sinusoid table buffer `pe` [max_len,1,d] (cmdm.py:265-276)."""
 
@@ -89,10 +104,10 @@ class CMDM(nn.Module):
                  arch="trans_enc", cm_mode="add", body_model="smpl", wo_pos_emb=False, emb_trans_dec=False,
                  clip_version=None, **kargs):
         super().__init__()
-        if arch != "online":
+        if arch not in ("online", "offline"):
             raise NotImplementedError(
-                f"arch={arch!r}: only the shipped 'online' decoder (cmdm.py:205-227) is on the HIP hot path; "
-                "offline/trans_enc/mlp/gru are ablation architectures (SURVEY.md §2 row 3)")
+                f"arch={arch!r}: the HIP hot path runs the 'online' decoder (cmdm.py:205-227) and the 'offline' encoder "
+                "(cmdm.py:228-238); trans_enc has no forward branch in the reference, mlp/gru are ablations (SURVEY.md §2 row 3)")
         if activation != "gelu":
             raise NotImplementedError("activation is hard-coded to gelu by the reference factory (model_util.py:70)")
         if data_rep not in ("rot6d", "xyz", "hml_vec"):
@@ -122,7 +137,10 @@ class CMDM(nn.Module):
         self.sequence_pos_encoder = PositionalEncoding(d, dropout)
         if cm_mode == "concat":
             self.fuse_process = nn.Linear(2 * d, d)
-        self.seqTransDecoder = _Decoder(d, ff_size, num_layers)
+        if arch == "offline":   # (emb_trans_dec / wo_pos_emb do not apply: the embedding is always token 0, positions always encoded)
+            self.seqTransEncoder = _Encoder(d, ff_size, num_layers)
+        else:
+            self.seqTransDecoder = _Decoder(d, ff_size, num_layers)
         self.embed_timestep = TimestepEmbedder(d, self.sequence_pos_encoder)
         if self.cond_mode == "text":
             self.embed_text = nn.Linear(clip_dim, d)
@@ -193,7 +211,7 @@ class CMDM(nn.Module):
         return dict(njoints=self.njoints, nfeats=self.nfeats, num_frames=int(num_frames or self.num_frames),
                     latent_dim=self.latent_dim, ff_size=self.ff_size, num_heads=self.num_heads, layers=self.num_layers,
                     cm_mode=self.cm_mode, cond_mode=self.cond_mode, num_actions=self.num_actions, clip_dim=self.clip_dim,
-                    emb_trans_dec=self.emb_trans_dec, wo_pos_emb=self.wo_pos_emb)
+                    emb_trans_dec=self.emb_trans_dec, wo_pos_emb=self.wo_pos_emb, arch=self.arch)
 
     MAX_ENGINES = 16    # engines kept alive, one per sequence length (auto_regressive evaluation walks through many lengths)
 

@@ -37,6 +37,10 @@ CONFIGS = {
                       num_heads=2, layers=2, cm_mode="concat", cond_mode="text", cond_mask_prob=0.1,
                       num_actions=1),
 }
+# arch='offline' (model/cmdm.py:228-238): the same shapes with the non-causal encoder denoiser
+for _name in ("tiny", "tiny_add", "ntu", "ntu_action", "chi3d"):
+    CONFIGS[_name + "_offline"] = dict(CONFIGS[_name], arch="offline")
+del _name
 
 
 def get_config(name, **overrides):
@@ -63,6 +67,8 @@ def make_state_dict(cfg, seed=0):
 
     Linear weights ~ N(0, gain^2/fan_in); q/k projections get a larger gain so the causal softmax is
     far from uniform; LayerNorm gamma ~ 1+0.1N, beta ~ 0.1N; biases ~ 0.02..0.1 N.
+    cfg["arch"] == "offline": nn.TransformerEncoderLayer keys (seqTransEncoder.layers.<l>: self_attn, linear1/2, norm1/2) drawn
+    in the decoder's order without the cross-attention and norm3 draws, q/k at gain 1; every other config draws exactly what it always did.
     """
     rng = np.random.Generator(np.random.PCG64(seed))
     d, ff, L = cfg["latent_dim"], cfg["ff_size"], cfg["layers"]
@@ -82,19 +88,23 @@ def make_state_dict(cfg, seed=0):
     sd["embed_timestep.sequence_pos_encoder.pe"] = pe.copy()
     lin("embed_timestep.time_embed.0", d, d, gain=1.5)
     lin("embed_timestep.time_embed.2", d, d, gain=1.5)
+    enc = cfg.get("arch", "online") == "offline"
     for l in range(L):
-        p = f"seqTransDecoder.layers.{l}."
+        p = f"seqTransEncoder.layers.{l}." if enc else f"seqTransDecoder.layers.{l}."
         w = rng.standard_normal((3 * d, d)) / np.sqrt(d)
-        w[: 2 * d] *= 2.5  # q,k gain -> peaky attention
+        # q,k gain -> peaky attention (the encoder's milder: without the decoder's third LayerNorm per layer and its causal
+        # mask, 2.5 makes the synthetic offline model so sensitive that fp32 summation order alone moves guided loops by 1e-1)
+        w[: 2 * d] *= 1.0 if enc else 2.5
         sd[p + "self_attn.in_proj_weight"] = w.astype(np.float32)
         sd[p + "self_attn.in_proj_bias"] = (rng.standard_normal(3 * d) * 0.05).astype(np.float32)
         lin(p + "self_attn.out_proj", d, d)
-        sd[p + "multihead_attn.in_proj_weight"] = (rng.standard_normal((3 * d, d)) / np.sqrt(d)).astype(np.float32)
-        sd[p + "multihead_attn.in_proj_bias"] = (rng.standard_normal(3 * d) * 0.05).astype(np.float32)
-        lin(p + "multihead_attn.out_proj", d, d)
+        if not enc:
+            sd[p + "multihead_attn.in_proj_weight"] = (rng.standard_normal((3 * d, d)) / np.sqrt(d)).astype(np.float32)
+            sd[p + "multihead_attn.in_proj_bias"] = (rng.standard_normal(3 * d) * 0.05).astype(np.float32)
+            lin(p + "multihead_attn.out_proj", d, d)
         lin(p + "linear1", ff, d, gain=1.2)
         lin(p + "linear2", d, ff, gain=1.2)
-        for n in ("norm1", "norm2", "norm3"):
+        for n in (("norm1", "norm2") if enc else ("norm1", "norm2", "norm3")):
             sd[p + n + ".weight"] = (1.0 + 0.1 * rng.standard_normal(d)).astype(np.float32)
             sd[p + n + ".bias"] = (0.1 * rng.standard_normal(d)).astype(np.float32)
     if "text" in cfg["cond_mode"]:
@@ -274,7 +284,7 @@ def build_model(cfg, sd, resp="", precision=None, device="cuda:0", noise_schedul
     model = CMDM("", cfg["njoints"], cfg["nfeats"], cfg["num_actions"], True, "rot6d", True, True,
                  num_frames=cfg["num_frames"], latent_dim=cfg["latent_dim"], ff_size=cfg["ff_size"],
                  num_layers=cfg["layers"], num_heads=cfg["num_heads"], dropout=0.1, activation="gelu",
-                 data_rep="rot6d", dataset=cfg["dataset"], arch="online", cm_mode=cfg["cm_mode"], body_model="smplx",
+                 data_rep="rot6d", dataset=cfg["dataset"], arch=cfg.get("arch", "online"), cm_mode=cfg["cm_mode"], body_model="smplx",
                  cond_mode=cfg["cond_mode"], cond_mask_prob=cfg["cond_mask_prob"], action_emb="tensor",
                  emb_trans_dec=cfg.get("emb_trans_dec", False), wo_pos_emb=cfg.get("wo_pos_emb", False),
                  x3_tail=x3_tail, engine_options=engine_options, f16_steps=f16_steps, **kw)
