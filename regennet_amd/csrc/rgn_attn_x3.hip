@@ -15,17 +15,11 @@
 // K and V^T time-share the LDS slab. The result is transposed through the dead slab and written as split planes in
 // the K32-blocked layout the out_proj GEMM consumes.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <int NT, int DH, bool X3, bool CAUSAL = true>
 __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) patch[l31 * OLD + 32 * dt + (i & 3) + 8 * (i >> 2) + 4 * kh] = oa[dt][i] * inv;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_wave_barrier();
     constexpr int C4 = DH / 4;
     const size_t row0 = (size_t)b * Tq;

@@ -30,47 +30,17 @@
 #include <algorithm>
 #include <cstdlib>
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
-
-// erf via Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7) on fast exp/rcp: ~12 VALU instead of ~30 for erff();
-// far inside the fp32 noise of the surrounding GEMM and of the 1e-3 tolerance.
-__device__ __forceinline__ float fast_erf(float x) {
-    const float ax = fabsf(x);
-    const float t = __frcp_rn(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = 1.0f - p * t * __expf(-ax * ax);
-    return copysignf(e, x);
-}
 __device__ __forceinline__ float x3_act(float v, int act) {
-    if (act == 1) return v * 0.5f * (1.0f + fast_erf(v * 0.70710678118654752440f));
+    if (act == 1) return gelu_as(v);
     if (act == 2) return v / (1.0f + __expf(-v));
     if (act == 3) return fmaxf(v, 0.f);
     return v;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
 }
 
 // ---- epilogue ------------------------------------------------------------------------------------------
@@ -118,7 +88,6 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 r[i] = x3_act(v, g.act);
             }
             if constexpr (QKV) {   // attention-ready scatter of the packed in_proj output (see GemmX3Args)
-                typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                 const int which = n / g.d, cin = n - which * g.d, hd = cin / g.dh, c = cin - hd * g.dh;
                 __bf16* ph = which == 0 ? g.Qhi : (which == 1 ? g.Khi : g.Vthi);
                 __bf16* pl = which == 0 ? g.Qlo : (which == 1 ? g.Klo : g.Vtlo);
@@ -182,7 +151,6 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const int ii = odd ? i + 8 : i;
                         const int ro = (ii & 3) + 8 * (ii >> 2);
                         const __bf16 h0 = (__bf16)lo_col, h1 = (__bf16)hi_col;
-                        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                         bf16x2 hv = {h0, h1};
                         *reinterpret_cast<bf16x2*>(g.Chi + o + ro * 32) = hv;
                         if (g.Clo) {
@@ -404,7 +372,7 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
             __builtin_amdgcn_s_barrier();
             RGN_T(3)
             compute(smem + (kt & 1) * STAGE);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkmcnt<0>();
             RGN_T(4)
             __builtin_amdgcn_s_barrier();         // stage (kt&1) may now be overwritten by tile kt+2
             RGN_T(5)

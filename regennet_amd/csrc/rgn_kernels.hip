@@ -8,29 +8,13 @@
 //
 // Reference arithmetic replaced (file:line in the upstream repo) is cited per kernel.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 #include "rgn_philox.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 namespace rgn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // element (row, col) of a K32-blocked plane [cols/32][rows][32]
 __device__ __forceinline__ size_t plane_off(int rows, int row, int col) {
@@ -168,15 +152,6 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs g) {
 // Blocks are remapped so that the column tiles of one A row-block run on the same XCD (shared L2).
 // -------------------------------------------------------------------------------------------------
 constexpr int H_BM = 128, H_BN = 128, H_BK = 32, H_LD = H_BK + 8;   // bf16 elements per LDS row
-
-__device__ __forceinline__ void split_bf16(const f32x4 v, bf16x4& hi, bf16x4& lo) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        hi[j] = h;
-        lo[j] = (__bf16)(v[j] - (float)h);
-    }
-}
 
 template <bool X3, bool VEC_A>
 __global__ __launch_bounds__(256) void k_gemm_bf16(GemmArgs g, int nbx, int nby) {
@@ -371,14 +346,14 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
                 p[j] = s;
                 mx = fmaxf(mx, s);
             }
-            mx = wave_max(mx);
+            mx = wave_max_shfl(mx);
             float sum = 0.f;
             for (int j = lane; j <= jl; j += 64) {
                 const float e = __expf(p[j] - mx);
                 p[j] = e;
                 sum += e;
             }
-            inv = 1.0f / wave_sum(sum);
+            inv = 1.0f / wave_sum_shfl(sum);
         }
         __syncthreads();
         if (on)
@@ -629,7 +604,7 @@ __device__ __forceinline__ void st_f32(float* __restrict__ p, const float* v) {
 }
 template <int N>
 __device__ __forceinline__ void ld_bf16_add(const __bf16* __restrict__ p, float* v) {   // v += p[0..N)
-    typedef __bf16 bf16xN __attribute__((ext_vector_type(N)));
+    typedef vec_t<__bf16, N> bf16xN;
     if constexpr (N == 1) {
         v[0] += (float)p[0];
     } else if constexpr (N <= 8) {
@@ -643,7 +618,7 @@ __device__ __forceinline__ void ld_bf16_add(const __bf16* __restrict__ p, float*
 }
 template <int N>
 __device__ __forceinline__ void st_split(__bf16* __restrict__ hi, __bf16* __restrict__ lo, const float* v) {
-    typedef __bf16 bf16xN __attribute__((ext_vector_type(N)));
+    typedef vec_t<__bf16, N> bf16xN;
     if constexpr (N == 1) {
         const __bf16 h = (__bf16)v[0];
         hi[0] = h;
@@ -689,14 +664,14 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ in,
 #pragma unroll
     for (int i = 0; i < VPL; ++i) s += v[i];
     const float invd = 1.0f / (float)d;
-    float mean = wave_sum(s) * invd;
+    float mean = wave_sum_shfl(s) * invd;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const float c = v[i] - mean;
         q += c * c;
     }
-    float rstd = 1.0f / sqrtf(wave_sum(q) * invd + 1e-5f);
+    float rstd = 1.0f / sqrtf(wave_sum_shfl(q) * invd + 1e-5f);
     ld_f32<VPL>(ga + c0, w);
     ld_f32<VPL>(ba + c0, bsh);
 #pragma unroll
@@ -715,14 +690,14 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ in,
         s = 0.f;
 #pragma unroll
         for (int i = 0; i < VPL; ++i) s += v[i];
-        mean = wave_sum(s) * invd;
+        mean = wave_sum_shfl(s) * invd;
         q = 0.f;
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             const float c = v[i] - mean;
             q += c * c;
         }
-        rstd = 1.0f / sqrtf(wave_sum(q) * invd + 1e-5f);
+        rstd = 1.0f / sqrtf(wave_sum_shfl(q) * invd + 1e-5f);
         ld_f32<VPL>(gb + c0, w);
         ld_f32<VPL>(bb + c0, bsh);
 #pragma unroll
@@ -985,8 +960,6 @@ __global__ void k_fill_rows(float* __restrict__ out, const float* __restrict__ r
 __global__ void k_cvt_bf16(const float* __restrict__ in, __bf16* __restrict__ out, long long n8) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n8) return;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     const f32x4 a = reinterpret_cast<const f32x4*>(in)[2 * i], b = reinterpret_cast<const f32x4*>(in)[2 * i + 1];
     bf16x8 o;
 #pragma unroll
@@ -1004,8 +977,6 @@ hipError_t launch_cvt_bf16(const float* in, __bf16* out, size_t n, hipStream_t s
 __global__ void k_cvt_f16(const float* __restrict__ in, _Float16* __restrict__ out, long long n8) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n8) return;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     const f32x4 a = reinterpret_cast<const f32x4*>(in)[2 * i], b = reinterpret_cast<const f32x4*>(in)[2 * i + 1];
     f16x8 o;
 #pragma unroll
@@ -1015,8 +986,6 @@ __global__ void k_cvt_f16(const float* __restrict__ in, _Float16* __restrict__ o
 __global__ void k_bf16_to_f16(__bf16* __restrict__ io, long long n8) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n8) return;
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     const bf16x8 a = reinterpret_cast<const bf16x8*>(io)[i];
     f16x8 o;
 #pragma unroll

@@ -30,6 +30,7 @@
 // workgroup; k_layers<true, true> - the same under classifier-free guidance (model/cfg_sampler.py:22-31): a workgroup owns a MOTION and runs its
 // conditional and its unconditional evaluation back to back, the conditional x0 parked in global scratch meanwhile.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 #include "rgn_philox.h"
 
 #include <hip/hip_runtime.h>
@@ -40,14 +41,6 @@
 
 namespace rgn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 #ifndef RGN_LY_ST_AUX
 #define RGN_LY_ST_AUX 16   // output stores write-through (sc1)
 #endif
@@ -81,27 +74,9 @@ __device__ long long g_ly_st[1024][16];
 #define RGN_LYS(i)
 #endif
 
-// GELU (erf form), see rgn_mlp2.hip
-__device__ __forceinline__ f32x2 ly_gelu2(f32x2 x) {
-    const f32x2 t = {__builtin_amdgcn_fmed3f(x[0], -3.9f, 3.9f), __builtin_amdgcn_fmed3f(x[1], -3.9f, 3.9f)};
-    const f32x2 z = t * t;
-    f32x2 p = f32x2{3.214928057e-08f, 3.214928057e-08f};
-    p = __builtin_elementwise_fma(p, z, f32x2{-2.075321845e-06f, -2.075321845e-06f});
-    p = __builtin_elementwise_fma(p, z, f32x2{5.740237248e-05f, 5.740237248e-05f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-9.056383278e-04f, -9.056383278e-04f});
-    p = __builtin_elementwise_fma(p, z, f32x2{9.218782187e-03f, 9.218782187e-03f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-6.556465477e-02f, -6.556465477e-02f});
-    p = __builtin_elementwise_fma(p, z, f32x2{3.986084461e-01f, 3.986084461e-01f});
-    return x * __builtin_elementwise_fma(t, p, f32x2{0.5f, 0.5f});
-}
-
 // step boundary (STEPS build): fp32 x0 tile [64][356] over the dead images, x' image (A operand of the input embedding) behind it
 constexpr int LY_XLD = 356, LY_TILE = 0, LY_XIMG = 92160, LY_NKX = 11;
 static_assert(64 * LY_XLD * 4 <= LY_XIMG && LY_XIMG + LY_NKX * 4096 <= LY_LDS, "step boundary LDS map");
-template <int... Is, class F>
-__device__ __forceinline__ void ly_static_for_seq(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void ly_static_for(F&& f) { ly_static_for_seq(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
 
 template <bool STEPS, bool GUIDED = false, bool F16 = false>
 __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
@@ -184,8 +159,8 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             if (hs + AH < NG) load_g(cur, hs + AH, (hs + AH) % LY_RDM);
             else if (CH) load_g(nxt, hs + AH - NG, (hs + AH) % LY_RDM);
             if (hs + AH < NG || CH) {
-                if (hs < AH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * AH + EX) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * AH) : "memory");
+                if (hs < AH) wait_vmcnt<2 * AH + EX>();
+                else wait_vmcnt<2 * AH>();
             }
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
@@ -229,7 +204,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             half_swap(s, q);                                        // s = [s.lo | q.lo], q = [s.hi | q.hi]
             *reinterpret_cast<float*>(const_cast<char*>(buf) + (kh * 512 + wave * 64 + 32 * mt) * 4) = s + q;   // kh = 0: the sum, kh = 1: the sum of squares
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         // the halves share the work: lane (l31, kh) reduces the eight partials of token 32 kh + l31, then the two results change hands
         f32x2 rs[2], nm[2];
@@ -325,7 +300,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         vb1 = bq[1024 + l31];
     };
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     load_qbias(g.lw[0].bqkv, 0);
 
@@ -383,7 +358,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.h + src), (RGN_AS3 void*)(smem + LY_X + p * 1024), 16, 0, 16);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
     }
     for (int l = 0; l < g.L; ++l) {
@@ -445,8 +420,8 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         if (hs + AH < 32) load_ga(pa[r], hs + AH, (32 * r + hs + AH) % LY_RDA);
                         else if (r == 0) load_ga(pa[1], hs + AH - 32, (32 * r + hs + AH) % LY_RDA);
                         if (hs + AH < 32 || r == 0) {
-                            if (hs < AH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * AH + 5) : "memory");   // (+ the 5 bias loads: behind round 1's chained granules)
-                            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * AH) : "memory");
+                            if (hs < AH) wait_vmcnt<3 * AH + 5>();   // (+ the 5 bias loads: behind round 1's chained granules)
+                            else wait_vmcnt<3 * AH>();
                         }
                         const int slot = (32 * r + hs) % LY_RDA;
 #pragma unroll
@@ -497,7 +472,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         sred[(((hg * 3 + tl) * 4 + wn) * 4 + i4) * 64 + lane] = v;
                     }
                 if (r == 0) { RGN_LYT(12) }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 if (r == 0) { RGN_LYT(13) }
                 // ---- softmax, each score ONCE: wave wn takes the queries {8 wn .. 8 wn + 7} of both query tiles, lane = (query qi, key group
@@ -565,7 +540,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                     }
                 }
                 if (r == 0) { RGN_LYT(14) }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 if (r == 0) { RGN_LYT(15) }
                 // O^T[dh tile wn, queries] = V (A operand, registers = keys) x P^T (B operand: this lane's slot of the probabilities)
@@ -590,7 +565,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         for (int e = 0; e < 4; ++e) attk[r][qtile][i4][e] = (op_t)oa[4 * i4 + e];
                 }
                 RGN_LYT(2 + 3 * r)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                wait_lgkmcnt<0>();
                 __builtin_amdgcn_s_barrier();                    // every wave has read this round's sums: the exchange may be overwritten
                 RGN_LYT(3 + 3 * r)
             }
@@ -625,7 +600,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
 #pragma unroll
                 for (int i4 = 0; i4 < 4; ++i4)
                     *reinterpret_cast<op4*>(smem + LY_Y + ((2 * r + hg) * 4 + wn) * LY_KB + (32 * qtile + l31) * 64 + ((i4 ^ swz) << 4) + 8 * kh) = attk[r][qtile][i4];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         f32x16 acc[2][2];
         init_bias(acc, vec + V_BO);
@@ -639,7 +614,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         layernorm(acc, vec + V_G1, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_SPV + col4(nt, i4)); });
         layernorm(acc, vec + V_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_B2 + col4(nt, i4)); });
         store_img(acc, LY_X);                                    // h' replaces h in place (this wave's columns: it read them above)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYT(9)
         f32x16 acc2[2][2];
@@ -654,13 +629,13 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                     for (int i = 0; i < 16; i += 2) {
-                        const f32x2 gl = ly_gelu2(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
+                        const f32x2 gl = gelu2_p13(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
                         acc[nt][mt][i] = gl[0];
                         acc[nt][mt][i + 1] = gl[1];
                     }
             if (c == 1) __builtin_amdgcn_s_barrier();             // every wave is done reading the first half's image
             store_img(acc, LY_Y);                                 // (c == 0: Y holds the attention output, dead since out_proj)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkmcnt<0>();
             __builtin_amdgcn_s_barrier();
             if (c == 0) gemm32(acc2, a_offy, p_w2a, p_w1b, std::true_type{}, std::integral_constant<int, 0>{});
             else gemm32(acc2, a_offy, p_w2b, p_w2b, std::false_type{}, std::integral_constant<int, 0>{});
@@ -693,7 +668,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         add_resid(acc2);
         layernorm(acc2, vec + V_G3, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_B3 + col4(nt, i4)); });
         store_img(acc2, LY_X);                                   // the next layer's input, in place
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYT(11)
     }
@@ -770,7 +745,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         c0u[nt][mt][i4] = *reinterpret_cast<const op4*>(g.c0 + ((size_t)g.half + row0_s + rr) * 512 + 64 * wave_s + col4s(nt, i4));
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYS(13)
         // ---- C: sampler update. lane = frame, the waves stride the features; Philox per quad of lanes where the quad is a run of four
@@ -829,7 +804,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 // x' (0 in the K padding columns and the surplus rows) -> the K32-blocked image of the embedding's A operand
                 *reinterpret_cast<op4*>(ximg + i2 * 4096 + ximg_lane) = nvb;
             };
-            ly_static_for<LY_NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
+            static_for<LY_NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
                 constexpr int i2 = decltype(IT)::value;
                 const int fg = wave_s + 8 * i2;
                 float eps4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -860,7 +835,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 update4(i2, fg, eps4, xpre[i2]);
             });
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYS(14)
         // ---- D: h' = x' . Wx'^T + c0 -> image X (the fp32 tile is dead since the barrier above; the x' image lies behind X)
@@ -897,7 +872,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[nt][mt][4 * i4 + e] += (float)c0v[nt][mt][i4][e];
         store_img(acc, LY_X);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if constexpr (GUIDED) {
             const __amdgpu_buffer_rsrc_t u_rs = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (int)((size_t)g.rows * 512 * 2), 0x00020000);

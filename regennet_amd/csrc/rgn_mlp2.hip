@@ -21,6 +21,7 @@
 //   LDS X: att tile image (A operand of out_proj) -> GELU(hidden half) image (A operand of linear2) -> output image
 //   LDS Y: h' image (A operand of linear1, residual of norm3)
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -28,20 +29,12 @@
 
 namespace rgn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #ifndef RGN_M2_HRES
 #define RGN_M2_HRES 0      // where the residual tile is requested: 0 = in the prologue behind the att DMA, 1 = behind the att barrier
 #endif
 #ifndef RGN_M2_ST_AUX
 #define RGN_M2_ST_AUX 16   // output stores write-through (sc1): nothing left dirty in the XCD L2s for the end-of-kernel write-back
 #endif
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 
 struct M2 {
     static constexpr int MT = 2;                      // row tiles of 32 per workgroup
@@ -80,23 +73,6 @@ __device__ long long g_m2_st[1024][12];
 #else
 #define RGN_M2T(i)
 #endif
-
-// GELU (erf form): x (0.5 + t Q(t^2)) with t = clamp(x, +-3.9) and t Q(t^2) ~ Phi(t) - 0.5: an odd degree-13 minimax polynomial on
-// [0, 3.9] (max abs error 8.3e-5 in Phi with the clamp's 4.8e-5 beyond it; max abs error of the GELU 3.2e-4 over [-8, 8], evaluated in
-// fp32 like here - the degree-15 fit on [0, 4.53] this replaces had 8.1e-5 and 6.4e-4: the wider interval bought nothing the bf16
-// rounding of the result does not hide 10x over), the 1/sqrt 2 and the 0.5 folded into the coefficients: 11 instructions per pair
-__device__ __forceinline__ f32x2 m2_gelu2(f32x2 x) {
-    const f32x2 t = {__builtin_amdgcn_fmed3f(x[0], -3.9f, 3.9f), __builtin_amdgcn_fmed3f(x[1], -3.9f, 3.9f)};   // (no canonicalising v_max in front, unlike min(max()))
-    const f32x2 z = t * t;
-    f32x2 p = f32x2{3.214928057e-08f, 3.214928057e-08f};
-    p = __builtin_elementwise_fma(p, z, f32x2{-2.075321845e-06f, -2.075321845e-06f});
-    p = __builtin_elementwise_fma(p, z, f32x2{5.740237248e-05f, 5.740237248e-05f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-9.056383278e-04f, -9.056383278e-04f});
-    p = __builtin_elementwise_fma(p, z, f32x2{9.218782187e-03f, 9.218782187e-03f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-6.556465477e-02f, -6.556465477e-02f});
-    p = __builtin_elementwise_fma(p, z, f32x2{3.986084461e-01f, 3.986084461e-01f});
-    return x * __builtin_elementwise_fma(t, p, f32x2{0.5f, 0.5f});
-}
 
 // ENC = true: the encoder-layer tail of arch='offline' (as k_mlp_x3<true>): h' = LN1(att . Wo^T + bo + h), final norm from g3 / b3; g2, b2,
 // pervec and stepvec are not read.
@@ -168,8 +144,8 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             if (hs + AH < 32) load_g(cur, hs + AH, (hs + AH) % RD);
             else if (CH) load_g(nxt, hs + AH - 32, (hs + AH) % RD);
             if (hs + AH < 32 || CH) {
-                if (hs < AH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NT * AH + EX) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NT * AH) : "memory");   // this granule is in; the next RD - 1 stay in flight
+                if (hs < AH) wait_vmcnt<NT * AH + EX>();
+                else wait_vmcnt<NT * AH>();   // this granule is in; the next RD - 1 stay in flight
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -224,7 +200,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             half_swap(s, q);                                        // s = [s.lo | q.lo], q = [s.hi | q.hi]
             *reinterpret_cast<float*>(const_cast<char*>(buf) + (kh * (NW * R) + wave * R + 32 * mt) * 4) = s + q;   // kh = 0: the sum, kh = 1: the sum of squares
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         f32x2 rs[MT], nm[MT];
         {   // the halves share the work - lane (l31, kh) reduces the partials of token 32 kh + l31, two swaps hand the results over
@@ -352,7 +328,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     constexpr int EXTRA = 16 + 6 * VK;                               // residual + phase B + step vector loads
     // the att image is complete once EVERY wave's DMA pieces have landed: they are the oldest vector-memory operations of this
     // wave, so the count below leaves everything younger than the first weight fragments in flight
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RGN_M2_HRES == 0 ? 16 : 0) + 5 * VK) : "memory");
+    wait_vmcnt<(RGN_M2_HRES == 0 ? 16 : 0) + 5 * VK>();
     RGN_M2T(7)
     __builtin_amdgcn_s_barrier();
 #if RGN_M2_HRES == 1
@@ -407,7 +383,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     for (int v = 0; v < 5; ++v)
 #pragma unroll
         for (int k = 0; k < VK; ++k) vec[CW * v + 64 * k + lane] = vb[v][k];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();                                     // h' image complete
     RGN_M2T(3)
 
@@ -424,13 +400,13 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int i = 0; i < 16; i += 2) {
-                    const f32x2 gl = m2_gelu2(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
+                    const f32x2 gl = gelu2_p13(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
                     acc[nt][mt][i] = gl[0];
                     acc[nt][mt][i + 1] = gl[1];
                 }
         if (c == 1) __builtin_amdgcn_s_barrier();                     // every wave is done reading the first half's image
         store_img(acc, smem + C::X);                                  // (c == 0: X still holds the att tile, dead since stage 1)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (c == 0) gemm32(acc2, smem + C::X, p_w2a, p_w1b, std::true_type{}, std::integral_constant<int, 0>{});   // linear2 over hidden k-blocks [16 c, 16 c + 16)
         else gemm32(acc2, smem + C::X, p_w2b, p_w2b, std::false_type{}, std::integral_constant<int, 0>{});
@@ -457,10 +433,9 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     }
     layernorm(acc2, vec + C::B_G3, std::integral_constant<int, 0>{}, [&](int nt, int i4, int) { return *reinterpret_cast<const f32x4*>(vec + C::B_B3 + col4(nt, i4)); });   // (its barrier also fences the last reads of X)
     store_img(acc2, smem + C::X);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t o_rs = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (int)((size_t)g.rows * 512 * 2), 0x00020000);
         const int r16 = lane >> 2, c = lane & 3;
 #pragma unroll

@@ -19,6 +19,7 @@
 // Weights: fragment-ordered hi and lo planes [K/32][N/32][2][64][8] (rgn_pack.cpp pack_linear), streamed through a register ring of RD granules
 // (half k-steps: 2 column blocks x (hi, lo) = 4 buffer loads) that never drains between the five GEMM passes.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -26,15 +27,6 @@
 #include <type_traits>
 
 namespace rgn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 
 #ifndef RGN_MX_RD
 #define RGN_MX_RD 6        // weight ring depth in granules of 4 fragments (16 registers each)
@@ -52,20 +44,6 @@ struct MX {
     static constexpr int B_BF1 = 0 /* 2 x CW */, B_BF2 = 2 * CW, B_G3 = 3 * CW, B_B3 = 4 * CW;
 };
 static_assert(MX::LDS == 144 * 1024 && MX::LDS <= 160 * 1024, "LDS map");
-
-// erf via Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7) on fast exp / rcp: rgn_gemm_x3.hip's
-__device__ __forceinline__ float mx_erf(float x) {
-    const float ax = fabsf(x);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));   // (1 ulp: below the fit's own 1.5e-7)
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = 1.0f - p * t * __expf(-ax * ax);
-    return copysignf(e, x);
-}
-__device__ __forceinline__ float mx_gelu(float v) { return v * 0.5f * (1.0f + mx_erf(v * 0.70710678118654752440f)); }
-
 }  // namespace
 
 template <bool ENC = false>
@@ -129,7 +107,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             if (hs + AH < 32) load_g(cur, hs + AH, (BASE + hs + AH) % RD);
             else if (CH) load_g(nxt, hs + AH - 32, (BASE + hs + AH) % RD);
             // this granule is in, the next RD - 1 stay in flight (the statement also keeps the compiler from hoisting later granules' loads up here)
-            if (hs + AH < 32 || CH) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NT * AH) : "memory");
+            if (hs + AH < 32 || CH) wait_vmcnt<2 * NT * AH>();
             const int slot = (BASE + hs) % RD;
             // small terms first, then hi . hi (rgn_gemm_x3.hip); the two accumulators alternate so that no MFMA waits for its predecessor
 #pragma unroll
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             for (int i = 0; i < 16; ++i) s += acc[nt][i];
         s = half_sum(s);
         b0[wave * R + l31] = s;                                       // (both halves write the same value)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         float tot = 0.f;
 #pragma unroll
@@ -193,7 +171,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             }
         q = half_sum(q);
         b1[wave * R + l31] = q;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         float qt = 0.f;
 #pragma unroll
@@ -272,8 +250,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     // the att images are complete once EVERY wave's DMA pieces have landed: they are this wave's oldest vector-memory operations; at least
     // 46 younger ones follow (ring 20, vectors 5 + 5, residual 16; the per-sample / step vectors may be absent), which may stay in flight -
     // 44 in the encoder form (no g2 / b2 among the phase A vectors: 3 + 5)
-    if constexpr (ENC) asm volatile("s_waitcnt vmcnt(44)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(46)" ::: "memory");
+    wait_vmcnt<ENC ? 44 : 46>();
     __builtin_amdgcn_s_barrier();
     f32x16 acc[NT];
 #pragma unroll
@@ -305,7 +282,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     // phase B vectors over phase A (wave-private)
 #pragma unroll
     for (int v = 0; v < 5; ++v) vec[CW * v + lane] = vb[v];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();                                     // h' images complete
 
     // =============== stage 2: linear1 + GELU + linear2, the hidden 1024 columns in two halves ==============================
@@ -319,9 +296,9 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) acc[nt][i] = mx_gelu(acc[nt][i]);
+            for (int i = 0; i < 16; ++i) acc[nt][i] = gelu_as_rcpf(acc[nt][i]);
         store_img(acc, C::XH, C::XL);                                 // (X still holds the att tile, dead since stage 1's loop: every wave passed the h' barrier)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         gemm32(acc2, smem + C::XH, smem + C::XL, p_w2a, p_w1b, std::true_type{}, std::integral_constant<int, B2>{});   // linear2 over hidden k-blocks [0, 16)
     }
@@ -331,10 +308,10 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) acc[nt][i] = mx_gelu(acc[nt][i]);
+            for (int i = 0; i < 16; ++i) acc[nt][i] = gelu_as_rcpf(acc[nt][i]);
         __builtin_amdgcn_s_barrier();                                 // every wave is done reading the first half's images
         store_img(acc, C::XH, C::XL);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         gemm32(acc2, smem + C::XH, smem + C::XL, p_w2b, p_w2b, std::false_type{}, std::integral_constant<int, B4>{});  // hidden k-blocks [16, 32)
     }
@@ -350,7 +327,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
         }
     layernorm(acc2, vec + C::B_G3, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + C::B_B3 + col4(nt, i4)); });   // (its barriers also fence the last reads of X)
     store_img(acc2, C::XH, C::XL);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
         const int bytes = (int)((size_t)g.rows * 512 * 2);

@@ -21,20 +21,12 @@
 // two 64 KiB LDS stages [A 128x32 | W_h 384x32] x {hi, lo}; tile rows 0-63 / 64-127 are the tokens of sample 0 / 1
 // (padding rows replicate the last token and are masked).
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 #ifndef RGN_QA_ST_AUX
 #define RGN_QA_ST_AUX 16   // cache policy of the plain-bf16 build's output stores: 16 = sc1 (write-through)
 #endif
@@ -137,7 +129,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
             const f32x4 v = {st[tl][4 * i4], st[tl][4 * i4 + 1], st[tl][4 * i4 + 2], st[tl][4 * i4 + 3]};
             sred[(((wm * 3 + tl) * 4 + wn) * 4 + i4) * 64 + lane] = v;
         }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     RGN_QT(hslot * 8 + 2)
 #pragma unroll
@@ -155,14 +147,14 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
             for (int e = 0; e < 4; ++e) st[tl][4 * i4 + e] = v[e];
         }
     if constexpr (!CAUSAL) {   // second pass: tile 3 through tile 0's slot, once every wave's reads of it have landed
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int i4 = 0; i4 < 4; ++i4) {
             const f32x4 v = {st[3][4 * i4], st[3][4 * i4 + 1], st[3][4 * i4 + 2], st[3][4 * i4 + 3]};
             sred[(((wm * 3) * 4 + wn) * 4 + i4) * 64 + lane] = v;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int i4 = 0; i4 < 4; ++i4) {
@@ -377,9 +369,9 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
         // group (one W tile x both A tiles) ahead.
         for (int kt = 0; kt < nk; ++kt) {
             // my pieces of tile kt landed; tiles kt+1 .. kt+NSTG-2 stay in flight (fewer near the end of the loop)
-            if (NSTG == 2 || kt + 1 >= nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (kt + 2 >= nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // LPT = 4 in the plain-bf16 build
-            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            if (NSTG == 2 || kt + 1 >= nk) wait_vmcnt<0>();
+            else if (kt + 2 >= nk) wait_vmcnt<4>();     // LPT = 4 in the plain-bf16 build
+            else wait_vmcnt<8>();
             __builtin_amdgcn_s_barrier();                          // ... everyone's did, and everyone left step kt-1
             const char* sb = smem + (kt % NSTG) * STAGE;
             char* nb = smem + ((kt + NSTG - 1) % NSTG) * STAGE;
@@ -425,12 +417,12 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();                              // every wave is done reading the last stage
         RGN_QT((hd - hd0) * 8 + 1)
         qa_attention<X3, false, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         RGN_QT((hd - hd0) * 8 + 6)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();      // the next head's DMA overwrites the reduction buffer
         RGN_QT((hd - hd0) * 8 + 3)
     }
@@ -529,7 +521,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
         *reinterpret_cast<u32x4*>(abuf + tid * 16) = areg[0];        // stage 0 <- k-block 0
 #pragma unroll
         for (int kt = 0; kt < QR_NK; ++kt) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkmcnt<0>();
             __builtin_amdgcn_s_barrier();                            // k-block kt is in its stage; everyone left stage (kt + 1) % 2
             const char* sb = abuf + (kt & 1) * STAGE;
             op8 af[2][2];
@@ -563,7 +555,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
         RGN_QT((hd - hd0) * 8 + 1)
         qa_attention<false, F16, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         RGN_QT((hd - hd0) * 8 + 6)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_QT((hd - hd0) * 8 + 3)
     }
@@ -651,7 +643,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
         *reinterpret_cast<u32x4*>(abuf + STAGE + tid * 16) = arl[0];
 #pragma unroll
         for (int kt = 0; kt < QR_NK; ++kt) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkmcnt<0>();
             __builtin_amdgcn_s_barrier();                            // k-block kt is in its stage; everyone left stage (kt + 1) % 2
             const char* sb = abuf + (kt & 1) * 2 * STAGE;
             bf16x8 ah[2][2], al[2][2];
@@ -689,10 +681,10 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();                                // (the exchange buffer does not alias the ring, but every wave must have left the k-loop's last stage reads)
         qa_attention<true, false, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
     }
 }

@@ -17,17 +17,11 @@
 //          registers, O^T = V^T . P^T with P from the S^T accumulators, result transposed through the dead Q/K slabs and stored as
 //          the hi plane of the K32-blocked layout the out_proj GEMM consumes.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 constexpr int QL_NW = 12, QL_NT = 64 * QL_NW;                        // waves / threads
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
     *reinterpret_cast<u32x4*>(abuf + tid * 16) = areg[0];
 #pragma unroll
     for (int kt = 0; kt < QL_NK; ++kt) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();                                // k-block kt is in its stage; everyone left the other stage
         const char* sb = abuf + (kt & 1) * QL_ASTAGE;
         __builtin_amdgcn_sched_barrier(0);
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 for (int e = 0; e < 4; ++e) sV[(wn * 32 + 8 * i4 + 4 * kh + e) * QL_VLD + t * 32 + l31] = (op_t)(acc[t][4 * i4 + e] + bv[e]);
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     RGN_LT(2)
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
         l_run = half_sum(l_run);
     }
     RGN_LT(3)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();                                    // every wave is done with Q / K / V^T: patches over Q and K, dumps behind them
     if (w >= 5 && w < 9) {
         char* dump = smem + QL_V + (w - 5) * DUMP;
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 *reinterpret_cast<f32x4*>(dump + ((dt * 4 + i4) * 64 + lane) * 16) = f32x4{oa[dt][4 * i4], oa[dt][4 * i4 + 1], oa[dt][4 * i4 + 2], oa[dt][4 * i4 + 3]};
         *reinterpret_cast<float2*>(dump + ND * 16 * 64 * 4 + lane * 8) = float2{m_run, l_run};
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (w < QL_TT) {
         if (w >= 2) {                                                // tiles 2, 3: one secondary (dumps 0, 1); tile 4: two (dumps 2, 3)
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
         for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) patch[l31 * QL_OLD + 32 * dt + (i & 3) + 8 * (i >> 2) + 4 * kh] = oa[dt][i] * inv;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_wave_barrier();
         // 16-byte WRITE-THROUGH stores (sc1): the plane is not left dirty in the XCD L2s for the end-of-kernel write-back
         constexpr int C8 = QL_DH / 8;

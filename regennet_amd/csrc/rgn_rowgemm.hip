@@ -27,18 +27,11 @@
 // Used only when the evaluation runs the plain-bf16 phase (RGN_PREC_BF16_X3TAIL, loop indices >= tail) and d == 512;
 // the split-bf16 tail and other widths keep k_gemm_x3 + k_layernorm.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 
 #ifndef RGN_RG_D_LN
 #define RGN_RG_D_LN 3
@@ -46,55 +39,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int RG_BM = 64, RG_BN = 512, RG_NT = 512;
 // weight prefetch distance in k-steps (register ring of D + 1 slots of 16 VGPRs): per epilogue kind, the ACT build has to fit 128 VGPRs
 template <int EPI> struct RgDepth { static constexpr int D = EPI == 0 ? RGN_RG_D_LN : 3; };
-
-// GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) for the plain-bf16 phase: erf as an odd degree-15 polynomial in u = clamp(x / sqrt 2,
-// +-3.2) (weighted least-squares fit, max abs error 1.6e-4 -> relative GELU error <= 8e-5, 25x below the bf16 rounding of the
-// result), evaluated two elements at a time with packed fp32 FMAs: no transcendental instruction (v_exp / v_rcp issue at
-// quarter rate; the A&S form of k_gemm_x3 spends ~40 % of its VALU time in them).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 rg_gelu2(f32x2 x) {
-    f32x2 u = x * 0.70710678118654752440f;
-    u = __builtin_elementwise_min(__builtin_elementwise_max(u, f32x2{-3.2f, -3.2f}), f32x2{3.2f, 3.2f});
-    const f32x2 z = u * u;
-    f32x2 p = f32x2{-2.6911866e-07f, -2.6911866e-07f};
-    p = __builtin_elementwise_fma(p, z, f32x2{1.2661994e-05f, 1.2661994e-05f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-2.5566161e-04f, -2.5566161e-04f});
-    p = __builtin_elementwise_fma(p, z, f32x2{2.9286479e-03f, 2.9286479e-03f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-2.1317327e-02f, -2.1317327e-02f});
-    p = __builtin_elementwise_fma(p, z, f32x2{1.0528564e-01f, 1.0528564e-01f});
-    p = __builtin_elementwise_fma(p, z, f32x2{-3.7135834e-01f, -3.7135834e-01f});
-    p = __builtin_elementwise_fma(p, z, f32x2{1.1274883e+00f, 1.1274883e+00f});
-    const f32x2 hx = x * 0.5f;
-    return __builtin_elementwise_fma(hx, p * u, hx);                  // 0.5 x (1 + erf)
-}
-
-// wave-wide sum on the VALU (DPP within rows of 16 lanes, then the four row totals through SGPRs): ~15 instructions
-// with no LDS round trip; ds_bpermute butterflies (what __shfl_xor compiles to) cost ~1.4 k cycles per row here.
-template <int CTRL>
-__device__ __forceinline__ float rg_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float rg_wave_sum(float v) {
-    v += rg_dpp<0xB1>(v);                                             // quad_perm [1,0,3,2]: lane ^ 1
-    v += rg_dpp<0x4E>(v);                                             // quad_perm [2,3,0,1]: lane ^ 2
-    v += rg_dpp<0x141>(v);                                            // row_half_mirror: sums of 8
-    v += rg_dpp<0x140>(v);                                            // row_mirror: sums of 16
-    const int b = __builtin_bit_cast(int, v);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16)) +
-           __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-}
-
-template <int N>
-__device__ __forceinline__ void rg_wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (N == 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else static_assert(N == 0, "add the vmcnt literal");
-}
 
 #ifdef RGN_RG_PROF
 __device__ long long g_rg_prof[8 * 16];   // tools only: phase cycle stamps (s_memtime) of wave w of workgroup RGN_RG_PROF
@@ -176,7 +120,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
 #pragma unroll
     for (int s = 0; s < RG_D; ++s) load_w(s, s);                      // nk >= 4 (host-checked)
     RGN_RT(1)
-    rg_wait_vmcnt<4 * RG_D>();                                        // in order: the activation pieces landed, weights may still fly
+    wait_vmcnt<4 * RG_D>();                                           // in order: the activation pieces landed, weights may still fly
     RGN_RT(2)
     __builtin_amdgcn_s_barrier();
     RGN_RT(3)
@@ -222,7 +166,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
     };
     // fully unrolled (ring slots are compile-time: slot = k-step % 4)
 #pragma unroll
-    for (int kt = 0; kt < nk - RG_D; ++kt) step(kt, kt % RING, kt + RG_D, (kt + RG_D) % RING, [] { rg_wait_vmcnt<4 * RG_D>(); });
+    for (int kt = 0; kt < nk - RG_D; ++kt) step(kt, kt % RING, kt + RG_D, (kt + RG_D) % RING, [] { wait_vmcnt<4 * RG_D>(); });
     if constexpr (EPI == 0) load_resid();                             // behind the last weight prefetch; the drain steps cover its latency
 #pragma unroll
     for (int kt = nk - RG_D; kt < nk; ++kt) step(kt, kt % RING, -1, 0, [] {});   // drain: straight-line code, the compiler's own counts are exact
@@ -252,7 +196,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                     float v[4] = {acc[nt][mt][4 * i4] + b.x, acc[nt][mt][4 * i4 + 1] + b.y, acc[nt][mt][4 * i4 + 2] + b.z,
                                   acc[nt][mt][4 * i4 + 3] + b.w};
                     if (g.act == 1) {
-                        const f32x2 g0 = rg_gelu2(f32x2{v[0], v[1]}), g1 = rg_gelu2(f32x2{v[2], v[3]});
+                        const f32x2 g0 = gelu2_p15(f32x2{v[0], v[1]}), g1 = gelu2_p15(f32x2{v[2], v[3]});
                         v[0] = g0[0]; v[1] = g0[1]; v[2] = g1[0]; v[3] = g1[1];
                     } else if (g.act == 2 && blockIdx.y == 0) {       // packed in_proj: column chunk 0 = q, pre-scaled by 1/sqrt(dh)
 #pragma unroll
@@ -271,7 +215,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                 }
             }
         RGN_RT(5)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_RT(6)
         // (2) copy out: a column block of the tile is ONE contiguous 4 KiB run of the K32-blocked plane (64 rows x 64 B);
@@ -308,7 +252,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
             }
         }
         RGN_RT(7)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         RGN_RT(8)
     } else {
         // (1) acc + bias -> fp32 row buffer [64][RLD] (aliases the dead activation image): lane = row, 4 consecutive
@@ -347,13 +291,13 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
             for (int e = 0; e < 8; ++e) sv[e] = 0.f;
             if (g.stepvec) ld8(g.stepvec + (size_t)(*g.d_step) * g.ldstep, sv);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_RT(6)
         // (2) one wave per row, 8 rows per wave: + residual, LayerNorm a (two-pass, like k_layernorm), optional
         //     + per-step / per-sample vectors and LayerNorm b, result -> residual-stream planes (in place)
         const float invn = 1.0f / (float)RG_BN;
-        auto wsum = [](float v) { return rg_wave_sum(v); };
+        auto wsum = [](float v) { return wave_sum_dpp(v); };
         // the wave's 8 consecutive rows belong to at most two samples: per-step + per-sample vector of each, combined once
         float spa[8], spb[8];
         int samp_a = 0;
@@ -431,7 +375,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
             }
         }
         RGN_RT(7)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         RGN_RT(8)
     }
 }

@@ -28,11 +28,56 @@
 // (sharding, chains).
 // Precision follows the phase of the schedule: X3 = three MFMAs per product on hi/lo planes, else hi planes only.
 #include "rgn_internal.h"
-#include "rgn_sb_common.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace rgn {
+
+namespace {
+
+constexpr int SB_D = 512;        // model width of the PRE_LN variants (row = 64 lanes x 8 floats)
+
+__device__ __forceinline__ void sb_ld8(const float* p, float (&v)[8]) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
+// LayerNorm phase register layout: a 512-wide row lives in ONE 16-lane DPP row (lane c of it holds columns
+// 128 j + 8 c .. + 8 for j = 0..3), a wave normalises 4 rows at once, and a row's sum is row16_sum (rgn_device.h):
+// 4 DPP adds with the result in every lane of the row, no cross-row traffic, no SGPR round trips.
+// two-pass LayerNorm, eps = 1e-5, like k_layernorm; gamma / beta from the workgroup's LDS copy (pointers at this lane's columns)
+__device__ __forceinline__ void sb_ln_row(float (&v)[4][8], const float* gv, const float* bv) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += v[j][i];
+    const float mean = row16_sum(s) * (1.0f / SB_D);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float c = v[j][i] - mean;
+            q += c * c;
+        }
+    const float rstd = 1.0f / sqrtf(row16_sum(q) * (1.0f / SB_D) + 1e-5f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float ga[8], ba[8];
+        sb_ld8(gv + j * 128, ga);
+        sb_ld8(bv + j * 128, ba);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[j][i] = (v[j][i] - mean) * rstd * ga[i] + ba[i];
+    }
+}
+__device__ __forceinline__ void sb_ldvec(const float* p, int lc, float (&v)[4][8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sb_ld8(p + j * 128 + lc * 8, v[j]);
+}
+
+}  // namespace
 
 // PRE: 0 = A fragments from K32-blocked planes, 1 = A = LayerNorm(s) of fp32 rows (through an LDS image)
 // POST: 0 = fp32 rows (+ bias + residual), 1 = GELU -> K32-blocked planes, 2 = attention-ready q / k / v planes
@@ -276,7 +321,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
             size_t o;
             if constexpr (POST == 1) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = sb_gelu(v[i]);
+                for (int i = 0; i < 4; ++i) v[i] = gelu_as(v[i]);
                 ph = g.Chi; pl = g.Clo;
                 o = ((size_t)(n >> 5) * g.c_rows + m) * 32 + (n & 31);
             } else {

@@ -7,6 +7,7 @@
 // LDS images, DMA (global_load_lds_dwordx4, 16 rows x 64 B per wave-instruction) and the 16-byte chunk swizzle c ^ ((row >> 2) & 3) are those of
 // k_gemm_x3 (rgn_gemm_x3.hip's header). All three kernels are PERSISTENT over output tiles.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -15,10 +16,6 @@
 
 namespace rgn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // F16 (every kernel of this file): the SINGLE-PLANE fp16 form - the hi planes of activations, residual, weights and output hold IEEE fp16, the lo planes
 // are neither read nor written, one v_mfma_f32_32x32x16_f16 per product instead of three bf16 ones: 2^-12 per operand instead of ~2^-16 per product
 // (rgn_stgcn.hip: SG_F16). The LDS images, the DMA schedule and every hazard stay those of the split form: what was the lo plane of channel block cb
@@ -26,14 +23,6 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // there are half as many of them, and the per-step costs that bound these kernels (DMA wait, barrier, DMA issue) are paid half as often. Channel
 // block counts are even (64 / 128 / 256 channels).
 __device__ __forceinline__ float f16_bits_to_float(unsigned b) { return (float)__builtin_bit_cast(_Float16, (unsigned short)b); }
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {   // at most N vector-memory operations of this wave still outstanding (the six-bit counter saturates at 63)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory");
-}
 
 // ---- the ST-GCN kernels' epilogue: out = act(acc + bias + addend), as fp32 [M, ldc] or as split planes. MODE (compile time):
 //   SGE_VERTEX_BIAS  the bias is a per-vertex row add[(row % add_mod)][n] (the graph convolution's, rgn_stgcn.hip); else bias[n]
@@ -152,7 +141,6 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         *reinterpret_cast<f16x2*>(g.Chi + o) = hv;
                     } else {
                         const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
-                        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                         bf16x2 hv = {h0, h1}, lv = {(__bf16)(c0 - (float)h0), (__bf16)(c1 - (float)h1)};
                         *reinterpret_cast<bf16x2*>(g.Chi + o) = hv;
                         *reinterpret_cast<bf16x2*>(g.Clo + o) = lv;
@@ -173,7 +161,6 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                     *reinterpret_cast<f16x2*>(g.Chi + o + ro * 32) = hv;
                 } else {
                     const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
-                    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                     bf16x2 hv = {h0, h1}, lv = {(__bf16)(c0 - (float)h0), (__bf16)(c1 - (float)h1)};
                     *reinterpret_cast<bf16x2*>(g.Chi + o + ro * 32) = hv;
                     *reinterpret_cast<bf16x2*>(g.Clo + o + ro * 32) = lv;

@@ -24,6 +24,7 @@
 // rounding, C is unchanged, D embeds x' once and writes it to both halves with their own c0 rows.
 // The last workgroup to finish (over all launches of the step) moves the device-side loop index on, like k_update.
 #include "rgn_internal.h"
+#include "rgn_device.h"
 #include "rgn_philox.h"
 
 #include <hip/hip_runtime.h>
@@ -33,23 +34,9 @@
 
 namespace rgn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-#define RGN_AS1 __attribute__((address_space(1)))
-#define RGN_AS3 __attribute__((address_space(3)))
 #ifndef RGN_ST_ST_AUX
 #define RGN_ST_ST_AUX 16   // cache policy of the h-plane stores: 16 = sc1 (write-through)
 #endif
-
-// compile-time loop: f(std::integral_constant<int, 0>{}) ... (the update loop's body is too large for `#pragma unroll` to be honoured,
-// and its prefetched operands must live in registers, i.e. be indexed by constants)
-template <int... Is, class F>
-__device__ __forceinline__ void st_static_for_seq(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void st_static_for(F&& f) { st_static_for_seq(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
 
 namespace {
 constexpr int ST_BM = 64, ST_NT = 512, ST_PF = 3;
@@ -124,7 +111,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             asm volatile("" ::: "memory");
             if (kt + ST_PF < NK) {
                 load_w(W, nb_all, cb0, kt + ST_PF, (kt + ST_PF) & 3);
-                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");    // this step's fragments are in; the next three steps' stay in flight
+                wait_vmcnt<12>();    // this step's fragments are in; the next three steps' stay in flight
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 for (int i = 0; i < 16; ++i) accu[a][b][i] = 0.f;
     }
     prefetch(g.Wout, g.nb_out, 2 * wave);
-    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");                // in order: the tile(s) landed, the weight prefetch may still fly
+    wait_vmcnt<12>();                                                 // in order: the tile(s) landed, the weight prefetch may still fly
     __builtin_amdgcn_s_barrier();
     if constexpr (!GUIDED) {
         gemm(acc, smem, g.Wout, g.nb_out, 2 * wave, std::integral_constant<int, 16>{});
@@ -177,7 +164,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             asm volatile("" ::: "memory");
             if (kt + ST_PF < 16) {
                 load_w(g.Wout, g.nb_out, 2 * wave, kt + ST_PF, (kt + ST_PF) & 3);
-                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+                wait_vmcnt<12>();
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             }
         }
     prefetch(g.Wx, 16, 2 * wave);                                    // GEMM 2's first fragments fly under the update phase
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     // ---- C: sampler update. lane = row of the tile (consecutive frames of a sample), the waves stride the features.
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             const int r = lane, chunk = (f & 31) >> 3;
             *reinterpret_cast<op_t*>(ximg + (f >> 5) * 4096 + r * 64 + ((chunk ^ ((r >> 2) & 3)) << 4) + (f & 7) * 2) = (op_t)nv;
         };
-        st_static_for<NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
+        static_for<NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
             constexpr int it = decltype(IT)::value;
             const int fg = wave + 8 * it;
             float eps4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -314,7 +301,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             for (int j = 0; j < 4; ++j) update(4 * fg + j, eps4[j], xpre[it][j]);
         });
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     // ---- D: h' = x' . Wx'^T (+ c0 in the copy-out). The condition rows of the copy-out are requested NOW, ahead of the GEMM
@@ -351,11 +338,10 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 for (int e = 0; e < 4; ++e) hv[e] = (op_t)acc[nt][mt][4 * i4 + e];
                 *reinterpret_cast<op4*>(smem + (2 * wave + nt) * 4096 + r * 64 + ((i4 ^ ((r >> 2) & 3)) << 4) + 8 * kh) = hv;
             }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
         // (write-through stores, as k_mlp's: the 15 / 31 MB of h planes are not left dirty in L2 for the end-of-kernel write-back)
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t h_rs = __builtin_amdgcn_make_buffer_rsrc(g.hout, 0, (int)((size_t)g.rows * 512 * 2), 0x00020000);
         const int r16 = lane >> 2, c = lane & 3;
 #pragma unroll

@@ -24,6 +24,7 @@
 // measured the same parity at 173 ms per 256 two-person motions of 60 frames; profiles/r05).
 #include "../../include/regennet_hip.h"
 #include "rgn_internal.h"
+#include "rgn_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -114,17 +115,6 @@ int sg_opt(const rgn_stgcn_ctx* c, const char* key, int dflt) {
     return dflt;
 }
 
-typedef __bf16 sg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sg_f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void sg_split8(const float (&v)[8], sg_bf16x8& h, sg_bf16x8& l) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        h[j] = (__bf16)v[j];
-        l[j] = (__bf16)(v[j] - (float)h[j]);
-    }
-}
-
 // data_bn + layout: output [N, V, M*C, T] (batch['output'], stgcn.py:83-101) -> x planes, rows (n M + m, t, v) with t < T + SG_PAD, channels c < C (the
 // rest of the 32-channel block zero), BatchNorm1d channel index (m*V + v)*C + c; pad frames are written as zeros. One thread per row.
 __global__ void k_sg_in(const float* __restrict__ out, SgPl x, const float* __restrict__ s, const float* __restrict__ t, int N, int V, int M, int C, int T) {
@@ -150,10 +140,10 @@ __global__ void k_sg_in(const float* __restrict__ out, SgPl x, const float* __re
         float v8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v8[j] = val[8 * q + j];
-        sg_bf16x8 h, l;
-        sg_split8(v8, h, l);
-        *reinterpret_cast<sg_bf16x8*>(x.hi + row * 32 + 8 * q) = h;
-        *reinterpret_cast<sg_bf16x8*>(x.lo + row * 32 + 8 * q) = l;
+        bf16x8 h, l;
+        split_bf16(v8, h, l);
+        *reinterpret_cast<bf16x8*>(x.hi + row * 32 + 8 * q) = h;
+        *reinterpret_cast<bf16x8*>(x.lo + row * 32 + 8 * q) = l;
     }
 }
 
@@ -188,15 +178,15 @@ __global__ __launch_bounds__(256) void k_sg_agg(SgPl x, SgPl z, const int* __res
     for (int j = j0; j < j1; ++j) {
         const size_t src = in_off + (size_t)(frame * (unsigned)V + (unsigned)(staged ? s_v[j] : nz_v[j])) * 32;
         const float a = staged ? s_a[j] : nz_a[j];
-        const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(x.hi + src), l = *reinterpret_cast<const sg_bf16x8*>(x.lo + src);
+        const bf16x8 h = *reinterpret_cast<const bf16x8*>(x.hi + src), l = *reinterpret_cast<const bf16x8*>(x.lo + src);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(a, (float)h[e] + (float)l[e], acc[e]);
     }
-    sg_bf16x8 h, l;
-    sg_split8(acc, h, l);
+    bf16x8 h, l;
+    split_bf16(acc, h, l);
     const size_t dst = ((size_t)(k * (C / 32) + (c8 >> 2)) * z.R + row) * 32 + 8 * (c8 & 3);
-    *reinterpret_cast<sg_bf16x8*>(z.hi + dst) = h;
-    *reinterpret_cast<sg_bf16x8*>(z.lo + dst) = l;
+    *reinterpret_cast<bf16x8*>(z.hi + dst) = h;
+    *reinterpret_cast<bf16x8*>(z.lo + dst) = l;
 }
 // the first block (C = in_channels / persons = 6, K C <= 32): one thread per row writes the whole 32-channel output row
 __global__ void k_sg_agg_small(SgPl x, SgPl z, const int* __restrict__ nz_ptr, const int* __restrict__ nz_v, const float* __restrict__ nz_a, size_t rows, int V, int K, int C) {
@@ -218,10 +208,10 @@ __global__ void k_sg_agg_small(SgPl x, SgPl z, const int* __restrict__ nz_ptr, c
         float v8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v8[j] = val[8 * q + j];
-        sg_bf16x8 h, l;
-        sg_split8(v8, h, l);
-        *reinterpret_cast<sg_bf16x8*>(z.hi + row * 32 + 8 * q) = h;
-        *reinterpret_cast<sg_bf16x8*>(z.lo + row * 32 + 8 * q) = l;
+        bf16x8 h, l;
+        split_bf16(v8, h, l);
+        *reinterpret_cast<bf16x8*>(z.hi + row * 32 + 8 * q) = h;
+        *reinterpret_cast<bf16x8*>(z.lo + row * 32 + 8 * q) = l;
     }
 }
 
@@ -242,7 +232,7 @@ __global__ __launch_bounds__(256) void k_sg_agg_small_t(SgPl x, SgPl z, const in
         for (int j = nz_ptr[k * V + w]; j < nz_ptr[k * V + w + 1]; ++j) {
             const size_t src = (frame * V + nz_v[j]) * 32;
             const float a = nz_a[j];
-            const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(x.hi + src), l = *reinterpret_cast<const sg_bf16x8*>(x.lo + src);
+            const bf16x8 h = *reinterpret_cast<const bf16x8*>(x.hi + src), l = *reinterpret_cast<const bf16x8*>(x.lo + src);
 #pragma unroll
             for (int c = 0; c < C; ++c) val[k * C + c] = fmaf(a, (float)h[c] + (float)l[c], val[k * C + c]);
         }
@@ -251,10 +241,10 @@ __global__ __launch_bounds__(256) void k_sg_agg_small_t(SgPl x, SgPl z, const in
         float v8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v8[j] = val[8 * q + j];
-        sg_bf16x8 h, l;
-        sg_split8(v8, h, l);
-        *reinterpret_cast<sg_bf16x8*>(z.hi + row * 32 + 8 * q) = h;
-        *reinterpret_cast<sg_bf16x8*>(z.lo + row * 32 + 8 * q) = l;
+        bf16x8 h, l;
+        split_bf16(v8, h, l);
+        *reinterpret_cast<bf16x8*>(z.hi + row * 32 + 8 * q) = h;
+        *reinterpret_cast<bf16x8*>(z.lo + row * 32 + 8 * q) = l;
     }
 }
 
@@ -278,7 +268,7 @@ __global__ __launch_bounds__(256) void k_sg_block0(SgPl x, SgPl g, const int* __
         for (int j = nz_ptr[k * V + w]; j < nz_ptr[k * V + w + 1]; ++j) {
             const size_t src = (frame * V + nz_v[j]) * 32;
             const float a = nz_a[j];
-            const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(x.hi + src), l = *reinterpret_cast<const sg_bf16x8*>(x.lo + src);
+            const bf16x8 h = *reinterpret_cast<const bf16x8*>(x.hi + src), l = *reinterpret_cast<const bf16x8*>(x.lo + src);
 #pragma unroll
             for (int c = 0; c < C; ++c) z[k * C + c] = fmaf(a, (float)h[c] + (float)l[c], z[k * C + c]);
         }
@@ -295,15 +285,15 @@ __global__ __launch_bounds__(256) void k_sg_block0(SgPl x, SgPl g, const int* __
         for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
         const size_t o = ((size_t)(og >> 2) * g.R + row) * 32 + 8 * (og & 3);
         if constexpr (F16) {
-            sg_f16x8 f;
+            f16x8 f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = (_Float16)acc[j];
-            *reinterpret_cast<sg_f16x8*>(g.hi + o) = f;
+            *reinterpret_cast<f16x8*>(g.hi + o) = f;
         } else {
-            sg_bf16x8 h, l;
-            sg_split8(acc, h, l);
-            *reinterpret_cast<sg_bf16x8*>(g.hi + o) = h;
-            *reinterpret_cast<sg_bf16x8*>(g.lo + o) = l;
+            bf16x8 h, l;
+            split_bf16(acc, h, l);
+            *reinterpret_cast<bf16x8*>(g.hi + o) = h;
+            *reinterpret_cast<bf16x8*>(g.lo + o) = l;
         }
     }
 }
@@ -327,12 +317,12 @@ __global__ void k_sg_zero(SgPl g, long long base, int NM, int Tr, int Tp, int V,
         const long long j = (long long)(e - npad);
         row = j < lead ? j - lead : (long long)NM * Tp * V + (j - lead);
     }
-    sg_bf16x8 zero;
+    bf16x8 zero;
 #pragma unroll
     for (int j = 0; j < 8; ++j) zero[j] = (__bf16)0.f;
     const long long o = ((long long)b * g.R + base + row) * 32 + 8 * q;
-    *reinterpret_cast<sg_bf16x8*>(g.hi + o) = zero;
-    *reinterpret_cast<sg_bf16x8*>(g.lo + o) = zero;
+    *reinterpret_cast<bf16x8*>(g.hi + o) = zero;
+    *reinterpret_cast<bf16x8*>(g.lo + o) = zero;
 }
 
 // split-bf16 planes -> the single fp16 plane of SG_F16, in place in the hi plane (block 0's graph convolution stays on the split GEMM: K = 32, 2 % of the forward):
@@ -342,11 +332,11 @@ __global__ void k_sg_to_f16(SgPl g, size_t rows, int cb) {
     if (idx >= rows * cb * 4) return;
     const size_t row = (idx >> 2) % rows;
     const size_t o = ((idx >> 2) / rows * (size_t)g.R + row) * 32 + 8 * (idx & 3);
-    const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(g.hi + o), l = *reinterpret_cast<const sg_bf16x8*>(g.lo + o);
-    sg_f16x8 f;
+    const bf16x8 h = *reinterpret_cast<const bf16x8*>(g.hi + o), l = *reinterpret_cast<const bf16x8*>(g.lo + o);
+    f16x8 f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = (_Float16)((float)h[e] + (float)l[e]);
-    *reinterpret_cast<sg_f16x8*>(g.hi + o) = f;
+    *reinterpret_cast<f16x8*>(g.hi + o) = f;
 }
 
 // x'[nm][t'][v][co] = relu(conv[nm][t'][v][co] + b2[co] + res) as planes, pads of x' zero. conv / rfull rows run (nm, frame < Tpi, v): the block's own
@@ -384,18 +374,18 @@ __global__ void k_sg_post(const float* __restrict__ conv, const float* __restric
             val[4] += r1.x + q1.x; val[5] += r1.y + q1.y; val[6] += r1.z + q1.z; val[7] += r1.w + q1.w;
         } else if (res_id) {                       // identity residual: stride 1, same channel count, same geometry as conv
             const size_t o = ((size_t)(c8 >> 2) * xin.R + srow) * 32 + 8 * (c8 & 3);
-            const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(xin.hi + o), l = *reinterpret_cast<const sg_bf16x8*>(xin.lo + o);
+            const bf16x8 h = *reinterpret_cast<const bf16x8*>(xin.hi + o), l = *reinterpret_cast<const bf16x8*>(xin.lo + o);
 #pragma unroll
             for (int e = 0; e < 8; ++e) val[e] += (float)h[e] + (float)l[e];
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) val[e] = fmaxf(val[e], 0.f);
     }
-    sg_bf16x8 h, l;
-    sg_split8(val, h, l);
+    bf16x8 h, l;
+    split_bf16(val, h, l);
     const size_t o = ((size_t)(c8 >> 2) * xout.R + orow) * 32 + 8 * (c8 & 3);
-    *reinterpret_cast<sg_bf16x8*>(xout.hi + o) = h;
-    *reinterpret_cast<sg_bf16x8*>(xout.lo + o) = l;
+    *reinterpret_cast<bf16x8*>(xout.hi + o) = h;
+    *reinterpret_cast<bf16x8*>(xout.lo + o) = l;
 }
 
 // global average pool over (t, v) and mean over the M persons (stgcn.py:113-114): pooled[n][c]. One workgroup per motion: thread = (run of 8 channels,
@@ -411,11 +401,11 @@ __global__ __launch_bounds__(256) void k_sg_pool(SgPl x, float* __restrict__ poo
             const size_t o = ((size_t)(c8 >> 2) * x.R + ((size_t)(n * M + m) * Tp) * V) * 32 + 8 * (c8 & 3);
             for (int i = sl; i < T * V; i += 8) {
                 if constexpr (F16) {
-                    const sg_f16x8 h = *reinterpret_cast<const sg_f16x8*>(x.hi + o + (size_t)i * 32);
+                    const f16x8 h = *reinterpret_cast<const f16x8*>(x.hi + o + (size_t)i * 32);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] += (float)h[e];
                 } else {
-                    const sg_bf16x8 h = *reinterpret_cast<const sg_bf16x8*>(x.hi + o + (size_t)i * 32), l = *reinterpret_cast<const sg_bf16x8*>(x.lo + o + (size_t)i * 32);
+                    const bf16x8 h = *reinterpret_cast<const bf16x8*>(x.hi + o + (size_t)i * 32), l = *reinterpret_cast<const bf16x8*>(x.lo + o + (size_t)i * 32);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] += (float)h[e] + (float)l[e];
                 }
