@@ -175,6 +175,18 @@ RGN_API int rgn_precision_plan(rgn_handle h, int32_t B, int32_t guided, int32_t*
  * following rgn_sample_range calls until cleared. */
 RGN_API int rgn_set_const_noise(rgn_handle h, int32_t on);
 
+/* Motion in-painting (gaussian_diffusion.py:319-323: y['inpainting_mask'] / y['inpainted_motion']) for the following
+ * rgn_sample_range calls: pred = mask ? motion : model_output, before clip_denoised, after the guidance combination, so
+ * x0_out, the sampler update and the next evaluation's input all see the blended prediction.
+ * mask_dev: uint8 [B,njoints,nfeats,T] (0 / non-zero; the storage of a contiguous torch.bool tensor), motion_dev: fp32,
+ * same shape; device pointers. The engine copies both on `stream` into buffers of its own (allocated at the first bind,
+ * sized by max_batch; a handle that never binds allocates nothing), so the caller may release or rewrite its arrays when
+ * the call returns, and one captured graph serves every mask. Both NULL clears the binding. Exactly one NULL pointer,
+ * or B outside (0, max_batch]: RGN_ERR_INVALID_ARG. rgn_sample_range with a binding whose B differs from the bound
+ * condition's fails with RGN_ERR_STATE. rgn_denoise never applies the binding: in the reference the blend belongs to
+ * the sampler (p_mean_variance), not to CMDM.forward. */
+RGN_API int rgn_set_inpainting(rgn_handle h, int32_t B, const uint8_t* mask_dev, const float* motion_dev, void* stream);
+
 /* Evaluations of at most `rows` token rows (motions x tokens, doubled under guidance) run the small-batch engine:
  * column-split GEMMs that spread one row tile over 16-48 workgroups (rgn_sb.hip; d = 512 models, bf16 modes), the
  * latency-bound regime of the reference CLI's own default batch (sample/cgenerate.py:109-135, BASELINE configs[0]).

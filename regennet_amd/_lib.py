@@ -60,6 +60,7 @@ SYMBOLS = {
     "rgn_precision_plan": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "rgn_set_small_batch_rows": (C.c_int, [_vp, _i32]),
     "rgn_set_const_noise": (C.c_int, [_vp, _i32]),
+    "rgn_set_inpainting": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
     "rgn_set_option": (C.c_int, [_vp, C.c_char_p, _i32]),
     "rgn_set_layers_min_b": (C.c_int, [_vp, _i32]),
     "rgn_plan_query": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double),
@@ -236,6 +237,16 @@ class Engine:
     def set_const_noise(self, on):
         """p_sample's const_noise (gaussian_diffusion.py:544-547) for the following sample_range calls."""
         self._ck(self.lib.rgn_set_const_noise(self.h, int(bool(on))))
+
+    def set_inpainting(self, mask, motion, stream):
+        """In-painting (gaussian_diffusion.py:319-323) for the following sample_range calls: mask bool / uint8 [B,njoints,nfeats,T],
+        motion fp32 of the same shape, both contiguous on the engine's device. The engine copies them (on `stream`)."""
+        assert mask.is_contiguous() and motion.is_contiguous() and mask.element_size() == 1 and motion.dtype.is_floating_point and motion.element_size() == 4
+        assert tuple(mask.shape) == tuple(motion.shape)
+        self._ck(self.lib.rgn_set_inpainting(self.h, int(mask.shape[0]), _ptr(mask), _ptr(motion), C.c_void_p(stream)))
+
+    def clear_inpainting(self):
+        self._ck(self.lib.rgn_set_inpainting(self.h, 0, None, None, None))
 
     def set_small_batch_rows(self, rows):
         """Evaluations of at most `rows` token rows run the small-batch (column-split) kernels; -1: default, 0: off."""

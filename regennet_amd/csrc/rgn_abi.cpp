@@ -351,6 +351,41 @@ int rgn_set_const_noise(rgn_handle h, int32_t on) {
     });
 }
 
+int rgn_set_inpainting(rgn_handle h, int32_t B, const uint8_t* mask_dev, const float* motion_dev, void* stream) {
+    return rgn_guard(h, "rgn_set_inpainting", [&]() -> int {
+        if (!h) return RGN_ERR_INVALID_ARG;
+        rgn_ctx* c = h;
+        if (!mask_dev && !motion_dev) {   // clear: the buffers stay (captured graphs of the in-painting forms hold their addresses)
+            c->inpaint_B = 0;
+            return RGN_OK;
+        }
+        if (!mask_dev || !motion_dev) return c->fail(RGN_ERR_INVALID_ARG, "rgn_set_inpainting: mask and motion come together (both null clears the binding)");
+        if (B <= 0 || B > c->cfg.max_batch) return c->fail(RGN_ERR_INVALID_ARG, "rgn_set_inpainting: B outside (0, max_batch]");
+        if (!c->finalized) return c->fail(RGN_ERR_STATE, "rgn_set_inpainting: weights not finalized");
+        RGN_HIP(c, hipSetDevice(c->cfg.device));
+        const size_t FT = (size_t)c->F * c->cfg.num_frames;
+        if (!c->inp_mask) {   // first bind: the engine's own copies, sized for max_batch motions (ONE allocation: mask bytes behind the floats)
+            const size_t n = (size_t)c->cfg.max_batch * FT;
+            void* v = nullptr;
+            RGN_HIP(c, hipMalloc(&v, n * sizeof(float) + n));
+            c->allocs.push_back(v);
+            c->inp_motion = reinterpret_cast<float*>(v);
+            c->inp_mask = reinterpret_cast<uint8_t*>(v) + n * sizeof(float);
+        }
+        c->inpaint_B = 0;                 // (a failed copy leaves nothing bound)
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = c->stream;
+        int rc = stream_enter(c, us);     // (behind earlier sampling calls on the engine's stream, which may still read the buffers)
+        if (rc) return rc;
+        hipError_t e = hipMemcpyAsync(c->inp_mask, mask_dev, (size_t)B * FT, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->inp_motion, motion_dev, (size_t)B * FT * sizeof(float), hipMemcpyDeviceToDevice, s);
+        rc = stream_exit(c, us);          // (the caller's stream is joined again whether the copies were enqueued or not)
+        RGN_HIP(c, e);
+        if (rc) return rc;
+        c->inpaint_B = B;
+        return RGN_OK;
+    });
+}
+
 int rgn_set_small_batch_rows(rgn_handle h, int32_t rows) {
     return rgn_guard(h, "rgn_set_small_batch_rows", [&]() -> int {
         if (!h) return RGN_ERR_INVALID_ARG;

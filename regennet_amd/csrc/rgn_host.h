@@ -159,6 +159,11 @@ struct rgn_ctx {
     int f16_steps_default = -1;        // (REGENNET_F16_STEPS / rgn_set_option "F16_STEPS")
     int f16_steps = -1;                // rgn_set_f16_steps: plain-phase steps right in front of the split-bf16 tail that run on fp16 operands (-1: default)
     int const_noise = 0;               // rgn_set_const_noise
+    // rgn_set_inpainting: the engine's own copies of mask and target (allocated at the first bind for max_batch motions: stable addresses
+    // under captured graphs, no lifetime rule for the caller); inpaint_B = 0: nothing bound
+    uint8_t* inp_mask = nullptr;
+    float* inp_motion = nullptr;
+    int inpaint_B = 0;
 
     // schedule (host copies)
     int S = 0;
@@ -172,7 +177,7 @@ struct rgn_ctx {
     int xin_rows = -1;                 // row count the xin planes are currently laid out for
     bool cond_has_scale = false;
 
-    // graphs: key = B | guided<<20 | sampler<<21 | phase_x3<<23 | steps<<24
+    // graphs: key = B | guided<<20 | sampler<<21 | phase_x3<<23 | steps<<24 | f16<<40 | inpainting<<41
     int graph_steps = 10;              // loop iterations per captured graph for long ranges (REGENNET_GRAPH_STEPS)
     std::map<uint64_t, hipGraphExec_t> graphs;
 

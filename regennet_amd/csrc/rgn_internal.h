@@ -54,6 +54,10 @@ struct SampleParams {
     int32_t guided;
     int32_t clip;             // clamp pred_xstart to [-1,1]
     int32_t const_noise;      // p_sample's const_noise: every motion takes motion 0's per-step draw
+    // in-painting (rgn_set_inpainting; gaussian_diffusion.py:319-323): pred = mask ? motion : pred, between the guidance combination and
+    // the clamp. Both in the boundary layout [B,F,T] of x, both null when nothing is bound; only the INPAINT kernel forms read them
+    const uint8_t* inpaint_mask;
+    const float* inpaint_motion;
 };
 
 struct GemmArgs {
@@ -231,7 +235,7 @@ struct LayersArgs {
 bool layers_supported(int d, int ff, int H, int Tq, int L);
 bool layers_steps_supported(int d, int F, int Kpx);
 hipError_t configure_layers();
-hipError_t launch_layers(const LayersArgs& g, hipStream_t s);
+hipError_t launch_layers(const LayersArgs& g, hipStream_t s, bool inpaint = false);   // inpaint: the step boundary applies sp->inpaint_* (steps > 0 only)
 
 // Small-batch column-split GEMM (rgn_sb.hip): 64 rows x 32 output columns per workgroup; LayerNorm applied by the consumer.
 struct SbArgs {
@@ -329,7 +333,7 @@ struct StepArgs {
 };
 bool step_fused_supported(int d, int F, int Kpx);
 hipError_t configure_step();
-hipError_t launch_step(const StepArgs& g, hipStream_t s);
+hipError_t launch_step(const StepArgs& g, hipStream_t s, bool inpaint = false);       // inpaint: the update phase applies sp->inpaint_*
 
 struct Dims {
     int B;        // motions in the bound condition
@@ -386,7 +390,7 @@ hipError_t launch_emb_rows(const float* emb, const float* stepemb, const int* d_
 hipError_t launch_add_pe(float* c0, const float* pe, const Dims& dm, hipStream_t s);
 hipError_t launch_pack_x(const float* x, float* xin, Planes xp, int copies, const Dims& dm, hipStream_t s);
 hipError_t launch_update(const float* x0tok, const float* scale, const StepCoef* tab, int* d_step,
-                         const SampleParams* sp, float* xin, Planes xp, const Dims& dm, int b0, int nb, hipStream_t s);
+                         const SampleParams* sp, float* xin, Planes xp, const Dims& dm, int b0, int nb, hipStream_t s, bool inpaint = false);
 hipError_t launch_advance(int* d_step, hipStream_t s);
 hipError_t launch_cond_rows(const float* table, const int64_t* action, float* out, int B, int d, int num_actions, hipStream_t s);
 hipError_t launch_fill_rows(float* out, const float* row, int rows, int d, hipStream_t s);

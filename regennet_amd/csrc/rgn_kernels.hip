@@ -843,6 +843,8 @@ hipError_t launch_randn(float* x, int B, int FT, int T, unsigned long long seed,
 // In sampling mode the LAST block to finish (of all k_update launches of the step: the chains' launches together cover the
 // B samples once) also moves the device-side loop index on: *d_step -= 1 (ticket counters behind d_step[4]). Every block read *d_step before it took its
 // ticket, and every other reader of *d_step (the layer kernels of a chain) precedes that chain's k_update in stream order.
+// INPAINT (rgn_set_inpainting; gaussian_diffusion.py:319-323): x0 = mask ? motion : x0 between the guidance combination and the clamp.
+template <bool INPAINT>
 __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok, const float* __restrict__ scale,
                                                  const StepCoef* __restrict__ tab, int* d_step,
                                                  const SampleParams* __restrict__ spp, float* __restrict__ xin, Planes xp,
@@ -878,6 +880,10 @@ __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok,
             if (sp.guided) {
                 const float u = tu[tx][i];
                 x0 = __fadd_rn(u, __fmul_rn(sc, __fsub_rn(x0, u)));
+            }
+            if constexpr (INPAINT) {
+                const size_t oi = (size_t)b * FT + (size_t)f * dm.T + t;
+                if (sp.inpaint_mask && sp.inpaint_mask[oi]) x0 = sp.inpaint_motion[oi];
             }
             if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
             const size_t o = (size_t)b * FT + (size_t)f * dm.T + t;
@@ -928,9 +934,10 @@ __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok,
     }
 }
 hipError_t launch_update(const float* x0tok, const float* scale, const StepCoef* tab, int* d_step,
-                         const SampleParams* sp, float* xin, Planes xp, const Dims& dm, int b0, int nb, hipStream_t s) {
+                         const SampleParams* sp, float* xin, Planes xp, const Dims& dm, int b0, int nb, hipStream_t s, bool inpaint) {
     dim3 grid((dm.T + 31) / 32, (dm.F + 31) / 32, nb);
-    hipLaunchKernelGGL(k_update, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
+    if (inpaint) hipLaunchKernelGGL(k_update<true>, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
+    else hipLaunchKernelGGL(k_update<false>, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
     return hipGetLastError();
 }
 

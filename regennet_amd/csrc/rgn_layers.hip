@@ -78,9 +78,10 @@ __device__ long long g_ly_st[1024][16];
 constexpr int LY_XLD = 356, LY_TILE = 0, LY_XIMG = 92160, LY_NKX = 11;
 static_assert(64 * LY_XLD * 4 <= LY_XIMG && LY_XIMG + LY_NKX * 4096 <= LY_LDS, "step boundary LDS map");
 
-template <bool STEPS, bool GUIDED = false, bool F16 = false>
+template <bool STEPS, bool GUIDED = false, bool F16 = false, bool INPAINT = false>
 __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
     static_assert(STEPS || !GUIDED, "guidance inside the launch needs the step boundary");
+    static_assert(STEPS || !INPAINT, "in-painting (rgn_set_inpainting) belongs to the step boundary");
     using OP = OpFmt<F16>;
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
@@ -770,6 +771,31 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             // the four features 4 fg + {0 .. 3} of this lane's frame: one 16-byte read of the x0 tile, four x updates, ONE 8-byte store of
             // the bf16 x' run (feature 32 i2 + 4 wave + j sits in k-block i2, 16-byte chunk wave >> 1, bytes 8 (wave & 1) + 2 j of its row)
             const int ximg_lane = lane_s * 64 + ((((wave_s >> 1) ^ ((lane_s >> 2) & 3)) << 4) + 8 * (wave_s & 1));
+            // in-painting (rgn_set_inpainting; gaussian_diffusion.py:319-323): x0 = mask ? motion : x0 ahead of the clamp. Buffer loads over THIS
+            // motion's [F, T] slice: one descriptor per array, the frame as the vector offset, the feature row as a scalar offset. The descriptor is
+            // sized by the pointer (wave-uniform: nothing bound, zero records, every load returns 0) and bounds what a surplus frame or a padding
+            // feature may touch; those values are never used (update4 tests valid && 4 fg < F). This kernel sits at its 256 VGPRs, so mask and
+            // target are NOT requested in one batch like xpre (88 more live registers: 54 - 96 spilled) but LY_IPD feature groups ahead of their
+            // use, under the Philox draw of the groups in between
+            constexpr int LY_IPD = GUIDED ? 1 : 2;                    // (guided: 255 VGPRs before in-painting)
+            unsigned char mpre[INPAINT ? LY_NKX : 1][4];
+            float ipre[INPAINT ? LY_NKX : 1][4];
+            const unsigned nrec = (INPAINT && sp.inpaint_mask) ? (unsigned)FT : 0u;
+            const __amdgpu_buffer_rsrc_t m_rs = __builtin_amdgcn_make_buffer_rsrc(INPAINT ? const_cast<uint8_t*>(sp.inpaint_mask) + (size_t)gb * FT : nullptr, 0, (int)nrec, 0x00020000);
+            const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc(INPAINT ? const_cast<float*>(sp.inpaint_motion) + (size_t)gb * FT : nullptr, 0, (int)(nrec * 4u), 0x00020000);
+            auto inp_request = [&](auto IG) __attribute__((always_inline)) {
+                constexpr int ig = decltype(IG)::value;
+                if constexpr (INPAINT && ig < LY_NKX) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int so = (4 * (wave_s + 8 * ig) + j) * T;         // wave-uniform
+                        mpre[ig][j] = __builtin_amdgcn_raw_buffer_load_b8(m_rs, t, so, 0);
+                        ipre[ig][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(v_rs, t * 4, so * 4, 0));
+                    }
+                    asm volatile("" ::: "memory");                              // (keeps the request where it is written)
+                }
+            };
+            static_for<LY_IPD>([&](auto IG) __attribute__((always_inline)) { inp_request(IG); });
             auto update4 = [&](int i2, int fg, const float (&eps_in)[4], const float (&xv)[4]) {
                 op4 nvb;
 #pragma unroll
@@ -780,6 +806,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                     for (int j = 0; j < 4; ++j) {
                         const int f = 4 * fg + j;
                         float x0 = x04[j];
+                        if constexpr (INPAINT) x0 = mpre[i2][j] ? ipre[i2][j] : x0;
                         if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
                         const size_t o = (size_t)gb * FT + (size_t)f * T + t;
                         if (sp.x0_out) sp.x0_out[o] = x0;
@@ -807,6 +834,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             static_for<LY_NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
                 constexpr int i2 = decltype(IT)::value;
                 const int fg = wave_s + 8 * i2;
+                inp_request(std::integral_constant<int, i2 + LY_IPD>{});
                 float eps4[4] = {0.f, 0.f, 0.f, 0.f};
                 if (quads) {                                               // wave-uniform
                     const uint32_t elem = (uint32_t)((4 * fg + q) * 4096 + tq);
@@ -930,10 +958,21 @@ hipError_t configure_layers() {
     if (e == hipSuccess) e = ly_lds(k_layers<true, false, true>);
     if (e == hipSuccess) e = ly_lds(k_layers<true, true, true>);
     if (e == hipSuccess) e = ly_lds(k_layers<false, false, true>);
+    if (e == hipSuccess) e = ly_lds(k_layers<true, false, false, true>);
+    if (e == hipSuccess) e = ly_lds(k_layers<true, true, false, true>);
+    if (e == hipSuccess) e = ly_lds(k_layers<true, false, true, true>);
+    if (e == hipSuccess) e = ly_lds(k_layers<true, true, true, true>);
     return e;
 }
-hipError_t launch_layers(const LayersArgs& g, hipStream_t s) {
-    if (g.steps > 0 && g.scale) {
+hipError_t launch_layers(const LayersArgs& g, hipStream_t s, bool inpaint) {
+    if (inpaint && g.steps <= 0) return hipErrorInvalidValue;
+    if (inpaint && g.scale) {   // the in-painting forms of the step boundary (a binding exists: rgn_set_inpainting)
+        if (g.f16) hipLaunchKernelGGL((k_layers<true, true, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
+        else hipLaunchKernelGGL((k_layers<true, true, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
+    } else if (inpaint) {
+        if (g.f16) hipLaunchKernelGGL((k_layers<true, false, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
+        else hipLaunchKernelGGL((k_layers<true, false, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
+    } else if (g.steps > 0 && g.scale) {
         if (g.f16) hipLaunchKernelGGL((k_layers<true, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
         else hipLaunchKernelGGL((k_layers<true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
     } else if (g.steps > 0) {

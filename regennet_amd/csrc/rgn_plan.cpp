@@ -581,6 +581,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     const Planes xin_p{fast ? c->xin_hi : nullptr, (fast && has_lo(c)) ? c->xin_lo : nullptr, M};
     c->skip_embed_out = false;
     const bool fused = pl.step_fused;                       // k_step instead of out GEMM + k_update + next in GEMM
+    const bool inp = sampling && c->inpaint_B > 0;          // rgn_set_inpainting: the boundary's in-painting form (rgn_denoise never applies it)
     const bool own_update = !guided && (nch > 1 || fused);
     int total_tiles = 0;
     if (fused) {
@@ -601,9 +602,9 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
             g.tab = c->d_tab; g.d_step = c->d_step; g.sp = c->d_sp;
             g.T = dm.T; g.B = dm.B; g.s0 = s_first; g.total_tiles = total_tiles; g.no_quads = c->step_no_quads;
             if (guided) { g.scale = c->scale; g.half = Mb; }  // x0 = x0_u + scale (x0_c - x0_u); rows [Mb, 2 Mb) are the unconditional half
-            RGN_LAUNCH(c, KC_STEP, st, launch_step(g, st));
+            RGN_LAUNCH(c, KC_STEP, st, launch_step(g, st, inp));
         } else {
-            RGN_LAUNCH(c, KC_UPDATE, st, launch_update(c->x0tok, c->scale, c->d_tab, c->d_step, c->d_sp, nullptr, xin_p, dm, s_first, n, st));
+            RGN_LAUNCH(c, KC_UPDATE, st, launch_update(c->x0tok, c->scale, c->d_tab, c->d_step, c->d_sp, nullptr, xin_p, dm, s_first, n, st, inp));
         }
         return RGN_OK;
     };
@@ -623,7 +624,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
         if ((rc = step_or_update(0, dm.B, s))) return rc;
     } else if (!own_update)
         RGN_LAUNCH(c, KC_UPDATE, s,
-                   launch_update(c->x0tok, c->scale, c->d_tab, c->d_step, c->d_sp, fast ? nullptr : c->xin, xin_p, dm, 0, dm.B, s));
+                   launch_update(c->x0tok, c->scale, c->d_tab, c->d_step, c->d_sp, fast ? nullptr : c->xin, xin_p, dm, 0, dm.B, s, inp));
     return RGN_OK;
 }
 
@@ -675,6 +676,10 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
     if (guided && c->cfg.cond_mode == RGN_COND_NONE)
         return c->fail(RGN_ERR_INVALID_ARG, "rgn_sample_range: guidance needs cond_mode text/action (cfg_sampler.py:26)");
     if (guided && !c->cond_has_scale) return c->fail(RGN_ERR_STATE, "rgn_sample_range: guided sampling needs y['scale']");
+    if (c->inpaint_B > 0 && c->inpaint_B != c->B)
+        return c->fail(RGN_ERR_STATE, "rgn_sample_range: the in-painting binding holds " + std::to_string(c->inpaint_B) + " motions, the bound condition " +
+                                          std::to_string(c->B) + " (rgn_set_inpainting / rgn_set_condition)");
+    const bool inp = c->inpaint_B > 0;
     hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = c->stream;
     // every return, failed or not, leaves the phase flags at their default (split-bf16, no fp16)
     struct PhaseReset {
@@ -699,6 +704,8 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
     sp.guided = guided != 0;
     sp.clip = clip_denoised != 0;
     sp.const_noise = c->const_noise;
+    sp.inpaint_mask = inp ? c->inp_mask : nullptr;
+    sp.inpaint_motion = inp ? c->inp_motion : nullptr;
     RGN_HIP(c, hipMemcpyAsync(c->d_sp, &sp, sizeof(sp), hipMemcpyHostToDevice, s));
     RGN_HIP(c, hipMemcpyAsync(c->d_step, &first_index, sizeof(int), hipMemcpyHostToDevice, s));
     RGN_HIP(c, hipMemsetAsync(c->d_step + 4, 0, (size_t)(1 + c->cfg.max_batch) * sizeof(int), s));   // k_update's ticket counters (clean even after an aborted call)
@@ -715,7 +722,7 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
     // a step at B = 256), the remainder single-step graphs.
     auto graph_for = [&](bool x3, bool f16g, int steps, hipGraphExec_t* out) -> int {
         const uint64_t key = (uint64_t)c->B | ((uint64_t)(guided != 0) << 20) | ((uint64_t)sampler << 21) | ((uint64_t)x3 << 23) |
-                             ((uint64_t)steps << 24) | ((uint64_t)f16g << 40);
+                             ((uint64_t)steps << 24) | ((uint64_t)f16g << 40) | ((uint64_t)inp << 41);   // (inp: the boundary kernels' in-painting forms)
         auto it = c->graphs.find(key);
         if (it != c->graphs.end()) {
             *out = it->second;
@@ -793,7 +800,7 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
                 g.c0 = f16 ? reinterpret_cast<const __bf16*>(c->c0h16) : c->c0h;
                 g.tab = c->d_tab; g.d_stepw = c->d_step; g.sp = c->d_sp;
                 g.B = dm.B; g.s0 = 0; g.no_quads = c->step_no_quads;
-                RGN_LAUNCH(c, KC_STEPS, s, launch_layers(g, s));
+                RGN_LAUNCH(c, KC_STEPS, s, launch_layers(g, s, inp));
                 k += phase_left;
                 continue;
             }

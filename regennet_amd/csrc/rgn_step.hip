@@ -22,6 +22,8 @@
 // launch over the conditional rows after the chains joined: A stages BOTH tiles (2 x 64 KiB) and runs the two output projections
 // in one pass over Wout (every weight fragment feeds both accumulator sets), B forms x0 = u + scale_b (c - u) with k_update's
 // rounding, C is unchanged, D embeds x' once and writes it to both halves with their own c0 rows.
+// INPAINT (rgn_set_inpainting; gaussian_diffusion.py:319-323): C replaces x0 by the bound motion where the bound mask is set, ahead of the clamp;
+// mask and motion are requested in one batch beside the sampler state. The launcher picks these forms only while a binding exists.
 // The last workgroup to finish (over all launches of the step) moves the device-side loop index on, like k_update.
 #include "rgn_internal.h"
 #include "rgn_device.h"
@@ -46,7 +48,7 @@ constexpr int ST_LDS = ST_XIMG + 11 * 4096;
 static_assert(ST_BM * ST_XLD * 4 <= ST_XIMG && 16 * 4096 <= ST_XIMG && 2 * 65536 <= ST_LDS, "tile / images (guided: two 64 KiB input images)");
 }  // namespace
 
-template <int NKX, bool GUIDED, bool F16 = false>
+template <int NKX, bool GUIDED, bool F16 = false, bool INPAINT = false>
 __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): h planes in and out, Wout / Wx, the x' image, c0
     using op_t = typename OP::t;
@@ -242,10 +244,31 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 const int f = 4 * (wave + 8 * it) + j;
                 xpre[it][j] = (valid && f < g.F) ? sp.x[(size_t)b * FT + (size_t)f * g.T + t] : 0.f;
             }
-        auto update = [&](int f, float eps_in, float xv) {
+        // in-painting: mask and target of the same elements ride in the same batch. Buffer loads: ONE descriptor per array, the lane's element
+        // (sample, frame) as the vector offset, the feature row as a scalar offset - 88 flat addresses cost ~330 spilled SGPRs. The descriptor is
+        // sized by the pointer (wave-uniform: nothing bound, zero records, every load returns 0 untouched by memory) and bounds what a surplus
+        // row or a padding feature may touch; those values are never used (update() tests valid && f < F)
+        unsigned char mpre[INPAINT ? NKX : 1][4];
+        float ipre[INPAINT ? NKX : 1][4];
+        if constexpr (INPAINT) {
+            const unsigned nrec = sp.inpaint_mask ? (unsigned)((size_t)g.B * FT) : 0u;
+            const __amdgpu_buffer_rsrc_t m_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(sp.inpaint_mask), 0, (int)nrec, 0x00020000);
+            const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sp.inpaint_motion), 0, (int)(nrec * 4u), 0x00020000);
+            const int vo = b * (int)FT + t;
+#pragma unroll
+            for (int it = 0; it < NKX; ++it)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int so = (4 * (wave + 8 * it) + j) * g.T;             // wave-uniform
+                    mpre[it][j] = __builtin_amdgcn_raw_buffer_load_b8(m_rs, vo, so, 0);
+                    ipre[it][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(v_rs, vo * 4, so * 4, 0));
+                }
+        }
+        auto update = [&](int f, float eps_in, float xv, unsigned char im, float iv) {
             float nv = 0.f;
             if (valid && f < g.F) {
                 float x0 = tile[lane * ST_XLD + f];
+                if constexpr (INPAINT) x0 = im ? iv : x0;
                 if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
                 const size_t o = (size_t)b * FT + (size_t)f * g.T + t;
                 if (sp.x0_out) sp.x0_out[o] = x0;
@@ -298,7 +321,12 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 eps4[3] = pick(std::integral_constant<int, 3>{});
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) update(4 * fg + j, eps4[j], xpre[it][j]);
+            for (int j = 0; j < 4; ++j) {
+                unsigned char im = 0;
+                float iv = 0.f;
+                if constexpr (INPAINT) { im = mpre[it][j]; iv = ipre[it][j]; }
+                update(4 * fg + j, eps4[j], xpre[it][j], im, iv);
+            }
         });
     }
     wait_lgkmcnt<0>();
@@ -379,13 +407,25 @@ hipError_t configure_step() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
 }
-hipError_t launch_step(const StepArgs& g, hipStream_t s) {
+hipError_t launch_step(const StepArgs& g, hipStream_t s, bool inpaint) {
     if (g.nkx != 11 || g.M <= 0) return hipErrorInvalidValue;
     const dim3 grid((g.M + ST_BM - 1) / ST_BM);
-    if (g.scale) {   // guided: M = token rows of the conditional half; half = row distance to the unconditional half
+    if (inpaint) {   // the in-painting forms (a binding exists: rgn_set_inpainting)
+        if (g.scale) {
+            if (g.f16) hipLaunchKernelGGL((k_step<11, true, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
+            else hipLaunchKernelGGL((k_step<11, true, false, true>), grid, dim3(ST_NT), ST_LDS, s, g);
+        } else {
+            if (g.f16) hipLaunchKernelGGL((k_step<11, false, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
+            else hipLaunchKernelGGL((k_step<11, false, false, true>), grid, dim3(ST_NT), ST_LDS, s, g);
+        }
+    } else if (g.scale) {   // guided: M = token rows of the conditional half; half = row distance to the unconditional half
         if (g.f16) hipLaunchKernelGGL((k_step<11, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
         else hipLaunchKernelGGL((k_step<11, true>), grid, dim3(ST_NT), ST_LDS, s, g);
     } else {

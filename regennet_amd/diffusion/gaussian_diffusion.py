@@ -194,7 +194,7 @@ class GaussianDiffusion:
     # ---- the hot loop --------------------------------------------------------------------------------
     def _loop(self, sampler, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
               skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, eta, noise_tape, seed,
-              use_graph, progressive, sample_offset):
+              use_graph, progressive, sample_offset, _per_step=False):
         if self.model_mean_type != ModelMeanType.START_X:
             raise NotImplementedError("CMDM predicts x_start (model_util.py:77)")
         for name, val in (("denoised_fn", denoised_fn), ("cond_fn", cond_fn)):
@@ -214,14 +214,23 @@ class GaussianDiffusion:
         y = (model_kwargs or {}).get("y", None)
         if y is None:
             raise KeyError("model_kwargs['y'] with 'cmotion' is required (gaussian_diffusion.py:317, cmdm.py:189)")
-        if "inpainting_mask" in y or "inpainted_motion" in y or y.get("uncond", False):
+        inpaint = "inpainting_mask" in y and "inpainted_motion" in y and not y.get("uncond", False) and not _per_step
+        if not inpaint and ("inpainting_mask" in y or "inpainted_motion" in y or y.get("uncond", False)):
             # keys the reference honours inside p_mean_variance on every step (gaussian_diffusion.py:319-323) / inside the
-            # denoiser (cmdm.py:181): the fused engine loop does not read them, so these calls take the per-step API
-            # (one HIP denoiser evaluation per step + torch elementwise glue) instead of being silently ignored
+            # denoiser (cmdm.py:181). Mask and motion TOGETHER are bound to the engine below (rgn_set_inpainting) and blended inside
+            # the fused loop; y['uncond'] and a lone key (which the reference ignores, :319) take the per-step API (one HIP
+            # denoiser evaluation per step + torch elementwise glue) instead of being silently ignored
             yield from self._loop_per_step(sampler, model, shape, noise, clip_denoised, model_kwargs, progress, skip_timesteps,
                                            init_image, eta, noise_tape, const_noise, seed, sample_offset)
             return
         assert len(shape) == 4, "shape must be (B, njoints, nfeats, T)"
+        if inpaint:   # the reference's assertion (gaussian_diffusion.py:322), made before anything runs
+            im, iv = y["inpainting_mask"], y["inpainted_motion"]
+            if not (th.is_tensor(im) and im.dtype == th.bool):
+                raise TypeError("y['inpainting_mask'] must be a torch.bool tensor (the reference applies ~mask, gaussian_diffusion.py:323)")
+            if not (tuple(im.shape) == tuple(iv.shape) == tuple(shape)):
+                raise AssertionError(f"inpainting_mask {tuple(im.shape)} / inpainted_motion {tuple(iv.shape)} must have the sample's shape {tuple(shape)} "
+                                     "(gaussian_diffusion.py:322)")
         self._maybe_calibrate_tail(sampler, model, shape, y, eta)
         eng, guided, dev = bind(B, y, device, T=int(shape[3]))
         if tuple(shape[1:]) != (eng.cfg["njoints"], eng.cfg["nfeats"], eng.cfg["num_frames"]):
@@ -260,6 +269,9 @@ class GaussianDiffusion:
         if progress:
             from tqdm.auto import tqdm
             bar = tqdm(total=first + 1)
+        if inpaint:   # device copies made once; the engine binding itself lives only around each sample_range below
+            inp_mask = y["inpainting_mask"].to(dev).contiguous()
+            inp_motion = y["inpainted_motion"].to(device=dev, dtype=th.float32).contiguous()
         i = first
         while i >= 0:
             n = min(chunk, i + 1)
@@ -268,10 +280,17 @@ class GaussianDiffusion:
                 eng.set_x3_tail(S)                      # (re-asserted per call: another bind may have reset the engine's knob)
             eng.set_const_noise(bool(const_noise))
             try:
+                # bound and cleared around every range, like const_noise: nothing stays on the engine between the yields of a progressive
+                # generator or behind an abandoned one, so another call on the same engine is never in-painted by this one's mask
+                # (a rebind is two device copies: one per call, or per step of a progressive / progress-bar run)
+                if inpaint:
+                    eng.set_inpainting(inp_mask, inp_motion, stream)
                 eng.sample_range(sampler, guided, eta, img, tp, seed, sample_offset, i, n, x0, use_graph, clip_denoised, stream)
             finally:
                 if const_noise:
                     eng.set_const_noise(False)
+                if inpaint:
+                    eng.clear_inpainting()
             i -= n
             if bar is not None:
                 if dev.type == "cuda":
@@ -495,14 +514,16 @@ class GaussianDiffusion:
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                       device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
                       cond_fn_with_grad=False, dump_steps=None, const_noise=False, *, noise_tape=None, seed=None,
-                      use_graph=True, sample_offset=0):
+                      use_graph=True, sample_offset=0, _per_step=False):
         """gaussian_diffusion.py:610-673. Extra keyword-only arguments (not in the reference):
         noise_tape [S+1,B,J,F,T] (entry 0 = x_T, entry k = k-th per-step draw) for bit-identical noise,
-        seed / sample_offset for the on-device Philox stream, use_graph to replay a captured hipGraph."""
+        seed / sample_offset for the on-device Philox stream, use_graph to replay a captured hipGraph.
+        y['inpainting_mask'] (bool) + y['inpainted_motion'] (:319-323) are blended inside the fused loop (rgn_set_inpainting);
+        _per_step (private: tools/inpaint_ab.py) sends such a call through _loop_per_step instead."""
         final, dump = None, []
         gen = self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
                          skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0, noise_tape, seed,
-                         use_graph, dump_steps is not None, sample_offset)
+                         use_graph, dump_steps is not None, sample_offset, _per_step)
         for i, out in enumerate(gen):
             if dump_steps is not None and i in dump_steps:
                 dump.append(deepcopy(out["sample"]))
@@ -522,8 +543,8 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None, randomize_class=False,
                          cond_fn_with_grad=False, dump_steps=None, const_noise=False, *, noise_tape=None, seed=None,
-                         use_graph=True, sample_offset=0):
-        """gaussian_diffusion.py:891-938."""
+                         use_graph=True, sample_offset=0, _per_step=False):
+        """gaussian_diffusion.py:891-938 (_per_step: as p_sample_loop)."""
         if dump_steps is not None:
             raise NotImplementedError()
         if const_noise == True:  # noqa: E712  (mirrors gaussian_diffusion.py:917)
@@ -531,7 +552,7 @@ class GaussianDiffusion:
         final = None
         for out in self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
                               skip_timesteps, init_image, randomize_class, cond_fn_with_grad, False, eta, noise_tape, seed,
-                              use_graph, False, sample_offset):
+                              use_graph, False, sample_offset, _per_step):
             final = out
         return final["sample"]
 

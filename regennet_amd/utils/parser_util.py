@@ -71,6 +71,18 @@ def add_generate_options(p):
     g.add_argument("--precision", default="bf16_x3tail", choices=["f32", "bf16x3", "bf16", "bf16_x3tail"], type=str)
 
 
+def add_edit_options(p):
+    """parser_util.py:223-237 (names and defaults), with 'rows' / --keep_rows in place of the HumanML3D-only 'upper_body' and the
+    inputs this CLI takes instead of a dataset."""
+    g = p.add_argument_group("edit")
+    g.add_argument("--edit_mode", default="in_between", choices=["in_between", "upper_body", "rows"], type=str,
+                   help="in_between: keep the frames outside [prefix_end, suffix_start); rows: keep the pose rows of --keep_rows in every frame")
+    g.add_argument("--prefix_end", default=0.25, type=float, help="in_between: end of the kept prefix, as a fraction of the length")
+    g.add_argument("--suffix_start", default=0.75, type=float, help="in_between: start of the kept suffix, as a fraction of the length")
+    g.add_argument("--keep_rows", default="", type=str, help="rows: pose rows to keep, e.g. 0-21,55")
+    g.add_argument("--input_motions", default="", type=str, help=".npy [N, njoints, nfeats, T]: the motions to edit (--synthetic: synthetic ones)")
+
+
 def _group_keys(parser, args, title):
     for grp in parser._action_groups:
         if grp.title == title:
@@ -78,7 +90,7 @@ def _group_keys(parser, args, title):
     raise ValueError("group_name was not found.")
 
 
-def cgenerate_args(argv=None):
+def cgenerate_args(argv=None, edit=False):
     p = argparse.ArgumentParser()
     add_base_options(p)
     add_data_options(p)
@@ -86,6 +98,8 @@ def cgenerate_args(argv=None):
     add_generate_options(p)
     add_model_options(p)
     add_diffusion_options(p)
+    if edit:
+        add_edit_options(p)
     args = p.parse_args(argv)
     if args.model_path:
         args_path = os.path.join(os.path.dirname(args.model_path), "args.json")
@@ -102,3 +116,8 @@ def cgenerate_args(argv=None):
     if args.cond_mask_prob == 0:
         args.guidance_param = 1
     return args
+
+
+def edit_args(argv=None):
+    """The reference's edit_args (parser_util.py:259-264) on this CLI's flag set: cgenerate's groups + the edit group."""
+    return cgenerate_args(argv, edit=True)
