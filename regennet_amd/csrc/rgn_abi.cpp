@@ -294,9 +294,7 @@ int rgn_denoise(rgn_handle h, const float* x, const int64_t* t, int32_t flags, f
         RGN_HIP(c, hipMemcpyAsync(c->d_sp, &sp, sizeof(sp), hipMemcpyHostToDevice, s));
         rc = pack_state(c, x, dm, guided, s);
         if (rc) return rc;
-        c->phase_x3 = true;               // a single evaluation is always split-bf16 under the precision schedule
-        c->phase_f16 = false;
-        rc = run_eval(c, c->B, guided, uncond, false, s);
+        rc = run_eval(c, c->B, guided, uncond, false, Phase{true, false}, s);   // a single evaluation is always split-bf16 under the precision schedule
         if (rc) return rc;
         return stream_exit(c, us);
     });

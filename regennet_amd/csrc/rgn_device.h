@@ -1,5 +1,6 @@
 // Device primitives shared by the kernel sources (every .hip under csrc/): vector types, address spaces, counted waits, DPP and shuffle
-// reductions, the compile-time loop, the split-bf16 conversion and the GELU / erf forms. Device code only; every helper has internal linkage.
+// reductions, the compile-time loop, the split-bf16 conversion, the GELU / erf forms, the 16-bit operand format of the plain phase (OpFmt), the
+// XCD-affine workgroup order and the half-wave exchange. Device code only; every helper has internal linkage.
 // Forms whose arithmetic differs (the GELU / erf variants, the DPP and the shuffle wave sums) are kept apart and named for what they compute.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -154,6 +155,54 @@ __device__ __forceinline__ f32x2 gelu2_p15(f32x2 x) {
     p = __builtin_elementwise_fma(p, z, f32x2{1.1274883e+00f, 1.1274883e+00f});
     const f32x2 hx = x * 0.5f;
     return __builtin_elementwise_fma(hx, p * u, hx);   // 0.5 x (1 + erf)
+}
+
+// ---- the 16-bit operand format of the plain phase's MFMAs (weights, activation images / planes, q / k / v / p): bf16 (8 mantissa bits) or IEEE fp16
+// (11). Both instructions are 8 passes of 4 cycles per 32 x 32 x 16 tile and take 16 bytes per lane and operand, so a kernel's structure - rings,
+// images, waits - does not depend on the format; what changes is every operand's rounding (2^-9 -> 2^-12 relative) and its range (fp16: 6.1e-5 ..
+// 65504 normal; LayerNorm outputs, GELU values, softmax probabilities and the weights of a transformer sit well inside, and rgn_finalize_weights
+// refuses a checkpoint that does not). Accumulation, LayerNorm statistics, softmax and the sampler update are fp32 either way. Nominally the same
+// rate - but the chip is power-managed under a matrix load and a pure f16 MFMA loop sustains 7.5 - 8 % less than the bf16 one
+// (tools/experiments/mfma_sustained.hip), which is why fp16 is a PHASE of the precision schedule (rgn_set_f16_steps), not its plain format.
+template <bool F16> struct OpFmt;
+template <> struct OpFmt<false> {
+    typedef __bf16 t;
+    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
+    typedef __bf16 v4 __attribute__((ext_vector_type(4)));
+    typedef float acc16 __attribute__((ext_vector_type(16)));
+    static __device__ __forceinline__ acc16 mfma(v8 a, v8 b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct OpFmt<true> {
+    typedef _Float16 t;
+    typedef _Float16 v8 __attribute__((ext_vector_type(8)));
+    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
+    typedef float acc16 __attribute__((ext_vector_type(16)));
+    static __device__ __forceinline__ acc16 mfma(v8 a, v8 b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+// ---- XCD-affine workgroup order: the hardware places workgroup id b on XCD b % 8. Remapping the id so that every XCD gets one
+// CONTIGUOUS range of tiles / samples makes the rows a kernel reads the rows the previous kernel of the chain wrote on the
+// same XCD (k_qkv_attn -> k_mlp -> k_qkv_attn ...): they are still in that XCD's L2 instead of behind the fabric.
+__device__ __forceinline__ int xcd_affine(int bid, int nwg) {
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+// ---- the other half-wave's value (lane ^ 32): v_permlane32_swap_b32 a, b gives a' = [a.lo | b.lo], b' = [a.hi | b.hi], so with b a copy of a in a
+// register of its own b' and a' are the two halves' values in every lane - one VALU instruction where __shfl_xor(v, 32) is a ds_bpermute round trip.
+// (inline asm: the builtin's second result is miscompiled by ROCm 7.2's clang, it adds a' to itself; tools/permlane_check.hip)
+__device__ __forceinline__ void half_swap(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ float half_max(float v) {
+    float o = v;
+    asm volatile("" : "+v"(o));
+    half_swap(v, o);
+    return fmaxf(v, o);
+}
+__device__ __forceinline__ float half_sum(float v) {
+    float o = v;
+    asm volatile("" : "+v"(o));
+    half_swap(v, o);
+    return v + o;
 }
 
 }  // namespace

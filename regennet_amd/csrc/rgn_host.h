@@ -131,7 +131,6 @@ struct rgn_ctx {
     // LAYERS_GUIDED: 0 never a motion per workgroup | 1 (default) when 2 B > #CUs | 2 always; rgn_set_option accepts it after finalize too (-1: the default again)
     int layers_guided = 1, layers_guided_default = 1;
     int num_cus = 256;
-    bool skip_embed_out = false;       // (set by run_eval around run_layers while it enqueues a fused step)
     int step_no_quads = 0;             // REGENNET_STEP_NO_QUADS=1 (tests)
     bool qkv_x3_dma = false;           // split-bf16 phase: keep the direct-to-LDS k_qkv_attn<true> (REGENNET_QKV_X3_DMA=1) instead of k_qkv_attn_rs_x3
     bool qkv_long = false;             // plain-bf16 phase, 65 .. 160 tokens: fused in_proj + attention per (sample, head) (REGENNET_NO_QKV_LONG=1: in_proj GEMM + k_attn_x3)
@@ -152,9 +151,7 @@ struct rgn_ctx {
     bool nchains_user = false;         // REGENNET_STREAMS was given: no size rule
     // Precision schedule (RGN_PREC_BF16_X3TAIL): the loop indices i >= x3_tail run plain-bf16 GEMMs (one MFMA per
     // product, hi planes only as GEMM operands), the last x3_tail indices and every rgn_denoise call the split-bf16 ones.
-    // phase_x3 is the phase of the evaluation being enqueued / captured.
-    bool phase_x3 = true;
-    bool phase_f16 = false;            // ... and, for a plain evaluation: fp16 operands (the fp16 sub-phase of the schedule, rgn_set_f16_steps)
+    // The phase of an evaluation is an argument of run_eval (rgnh::Phase), not state of the handle.
     int x3_tail = -1;                  // -1: default_tail(S)
     int f16_steps_default = -1;        // (REGENNET_F16_STEPS / rgn_set_option "F16_STEPS")
     int f16_steps = -1;                // rgn_set_f16_steps: plain-phase steps right in front of the split-bf16 tail that run on fp16 operands (-1: default)
@@ -177,7 +174,7 @@ struct rgn_ctx {
     int xin_rows = -1;                 // row count the xin planes are currently laid out for
     bool cond_has_scale = false;
 
-    // graphs: key = B | guided<<20 | sampler<<21 | phase_x3<<23 | steps<<24 | f16<<40 | inpainting<<41
+    // graphs: key = B | guided<<20 | sampler<<21 | Phase::x3<<23 | steps<<24 | Phase::f16<<40 | inpainting<<41 (the phase as run_eval runs it: eval_phase)
     int graph_steps = 10;              // loop iterations per captured graph for long ranges (REGENNET_GRAPH_STEPS)
     std::map<uint64_t, hipGraphExec_t> graphs;
 
@@ -209,7 +206,6 @@ extern const char* const kclass_names[KC_COUNT];
             return (h)->fail(RGN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
 
-// Launch wrapper: optional HIP-event bracketing per kernel class (eager mode only).
 // Launch wrapper: optional HIP-event bracketing per kernel class. Events come from a pool created by
 // rgn_profile_enable (no creation cost between launches); launches beyond the pool are simply not timed.
 #define RGN_LAUNCH(h, KCLS, stream, call)                                        \
@@ -238,7 +234,23 @@ bool opt_flag(const rgn_ctx* c, const char* key);
 Dims make_dims(const rgn_ctx* c, int B, bool guided);
 GemmArgs gemm_args(const rgn_ctx* c, const Lin& L, const float* A, int lda, float* C, int ldc, int M);
 int pack_state(rgn_ctx* c, const float* x, const Dims& dm, bool guided, hipStream_t s);
-int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStream_t s);
+// The arithmetic of one evaluation as the schedule asks for it (eval_phase: what the handle's precision mode makes of it): x3 - split-bf16 GEMMs,
+// three MFMAs per product | plain ones; f16 - a plain SAMPLING evaluation on fp16 operands (the schedule's fp16 sub-phase, rgn_set_f16_steps)
+struct Phase { bool x3 = true; bool f16 = false; };
+Phase eval_phase(const rgn_ctx* c, Phase ph, bool sampling);
+// The plan of one denoiser evaluation: WHICH kernels run it (plan_eval decides, run_eval / sample_range dispatch on it, plan_query reports it)
+enum AttnForm { AF_LAYERS = 0, AF_QKV, AF_QKV_LONG, AF_ROWGEMM_ATTN, AF_GEMM_ATTN, AF_PLAIN };
+enum TailForm { TF_LAYERS = 0, TF_MLP_X3, TF_MLP, TF_ROWGEMM, TF_GEMM_LN };
+struct EvalPlan {
+    bool sb = false;          // small-batch engine (k_sb_gemm chain) for the whole evaluation
+    bool layers = false;      // k_layers: the whole decoder stack in one kernel, one sample per workgroup
+    bool steps = false;       // k_layers<true>: whole runs of sampler steps in one launch (sampling only)
+    bool step_fused = false;  // k_step: output projection + sampler update + next input embedding (sampling only)
+    AttnForm attn = AF_PLAIN;
+    TailForm tail = TF_GEMM_LN;
+};
+// pl: the evaluation's plan where the caller has made it already (sample_range), for eval_phase(c, ph, sampling); nullptr: made here
+int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase ph, hipStream_t s, const EvalPlan* pl = nullptr);
 int build_step_table(rgn_ctx* c, float eta);
 int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* x, const float* noise, uint64_t seed, uint64_t sample_offset,
                  int32_t first_index, int32_t count, float* x0_out, int32_t use_graph, int32_t clip_denoised, void* stream);   // the body of rgn_sample_range
@@ -250,10 +262,9 @@ PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided);
 // precision of the per-schedule / per-condition / rgn_denoise-only GEMMs (k_gemm_f32 / k_gemm_bf16): the schedule mode
 // runs them split-bf16 (they are once-per-call work)
 inline int small_prec(const rgn_ctx* c) { return c->cfg.precision == RGN_PREC_BF16_X3TAIL ? RGN_PREC_BF16X3 : c->cfg.precision; }
-// split-bf16 (three MFMAs per product) for the evaluation being enqueued?
-inline bool eval_x3(const rgn_ctx* c) {
-    return c->cfg.precision == RGN_PREC_BF16X3 || (c->cfg.precision == RGN_PREC_BF16_X3TAIL && c->phase_x3);
-}
+// split-bf16 (three MFMAs per product) for an evaluation in the schedule's split phase (or not)? RGN_PREC_BF16X3 runs every evaluation split,
+// whatever the schedule says; the modes without lo planes none
+inline bool eval_x3(bool split_phase, int precision) { return precision == RGN_PREC_BF16X3 || (precision == RGN_PREC_BF16_X3TAIL && split_phase); }
 // do activation planes carry a lo part at all (allocation, sampler state, residual stream)?
 inline bool has_lo(const rgn_ctx* c) { return c->cfg.precision == RGN_PREC_BF16X3 || c->cfg.precision == RGN_PREC_BF16_X3TAIL; }
 inline bool use_sb(const rgn_ctx* c, int rows) { return c->sb && c->cfg.precision != RGN_PREC_F32 && rows <= c->sb_rows; }

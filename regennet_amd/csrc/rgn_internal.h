@@ -1,5 +1,5 @@
-// Internal declarations shared by the host translation units (rgn_pack.cpp, rgn_plan.cpp, rgn_abi.cpp: rgn_host.h) and rgn_kernels.hip (device code).
-// Not part of the C-ABI (that is include/regennet_hip.h).
+// Internal declarations shared by the host translation units (rgn_pack.cpp, rgn_plan.cpp, rgn_abi.cpp: rgn_host.h) and the kernel sources (.hip):
+// argument structs and launcher declarations only - device code lives in rgn_device.h. Not part of the C-ABI (that is include/regennet_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -162,6 +162,14 @@ bool rowgemm_supported(int N, int Kp, bool ln);
 hipError_t configure_rowgemm();
 hipError_t launch_rowgemm(const RowGemmArgs& g, bool ln, hipStream_t s);
 
+// One decoder layer's fragment-ordered weight planes, biases and LayerNorm vectors (encoder layers: g2 / b2 null). k_layers takes a table of them
+// in its kernel arguments (scalar loads), k_mlp2 / k_mlp_x3 one.
+struct LayerWts {
+    const __bf16 *Wqkv, *Wo, *W1, *W2;
+    const float *bqkv, *bo, *bf1, *bf2;
+    const float *g1, *b1, *g2, *b2, *g3, *b3;
+};
+
 // Row-persistent decoder-layer tail (rgn_mlp2.hip): out_proj + norm1 + folded cross-attention + norm2 + linear1 + GELU + linear2 + norm3
 // for 64-row tiles, plain-bf16 phase, d = 512, ff = 1024. All planes are hi-only K32-blocked [16][rows][32]; weights fragment-ordered.
 struct MlpArgs {
@@ -170,9 +178,7 @@ struct MlpArgs {
     __bf16* out;                          // layer output planes (may alias h)
     int rows;                             // plane row count (stride), M rows processed
     int M;
-    const __bf16 *Wo, *W1, *W2;           // out_proj [512x512], linear1 [1024x512], linear2 [512x1024]
-    const float *bo, *bf1, *bf2;
-    const float *g1, *b1, *g2, *b2, *g3, *b3;
+    LayerWts w;                           // Wo: out_proj [512x512], W1: linear1 [1024x512], W2: linear2 [512x1024], their biases, the three norms (Wqkv / bqkv are unread here)
     const float* pervec; int ldper;       // + pervec[(row / Tq) * ldper + n]     (nullable)
     const float* stepvec; int ldstep; const int* d_step;   // + stepvec[(*d_step) * ldstep + n] (nullable)
     int Tq;
@@ -197,13 +203,6 @@ hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s, bool enc = false);  
 // The whole decoder stack of one evaluation as one kernel, one sample (Tq <= 64 tokens) per workgroup (rgn_layers.hip): plain-bf16 phase,
 // d = 512, ff = 1024, 4 heads of 128. Weight planes fragment-ordered as for k_mlp / k_qkv_attn_rs.
 constexpr int LY_MAXL = 8;
-struct StepCoef;
-struct SampleParams;
-struct LayerWts {                          // one entry per decoder layer; the table travels in the kernel arguments (scalar loads)
-    const __bf16 *Wqkv, *Wo, *W1, *W2;
-    const float *bqkv, *bo, *bf1, *bf2;
-    const float *g1, *b1, *g2, *b2, *g3, *b3;
-};
 struct LayersArgs {
     const __bf16* h;                      // residual-stream planes (hi) [16][rows][32], advanced to the first sample's row
     __bf16* out;                          // (may alias h)
@@ -264,58 +263,8 @@ bool sb_supported(int d, int ff, int dh);
 hipError_t configure_sb();
 hipError_t launch_sb_gemm(const SbArgs& g, int pre, int post, bool x3, hipStream_t s);
 
-// The 16-bit operand format of the plain phase's MFMAs (weights, activation images / planes, q / k / v / p): bf16 (8 mantissa bits) or IEEE fp16
-// (11). Both instructions are 8 passes of 4 cycles per 32 x 32 x 16 tile and take 16 bytes per lane and operand, so a kernel's structure - rings,
-// images, waits - does not depend on the format; what changes is every operand's rounding (2^-9 -> 2^-12 relative) and its range (fp16: 6.1e-5 ..
-// 65504 normal; LayerNorm outputs, GELU values, softmax probabilities and the weights of a transformer sit well inside, and rgn_finalize_weights
-// refuses a checkpoint that does not). Accumulation, LayerNorm statistics, softmax and the sampler update are fp32 either way. Nominally the same
-// rate - but the chip is power-managed under a matrix load and a pure f16 MFMA loop sustains 7.5 - 8 % less than the bf16 one
-// (tools/experiments/mfma_sustained.hip), which is why fp16 is a PHASE of the precision schedule (rgn_set_f16_steps), not its plain format.
-template <bool F16> struct OpFmt;
-template <> struct OpFmt<false> {
-    typedef __bf16 t;
-    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-    typedef __bf16 v4 __attribute__((ext_vector_type(4)));
-    typedef float acc16 __attribute__((ext_vector_type(16)));
-    static __device__ __forceinline__ acc16 mfma(v8 a, v8 b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct OpFmt<true> {
-    typedef _Float16 t;
-    typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
-    typedef float acc16 __attribute__((ext_vector_type(16)));
-    static __device__ __forceinline__ acc16 mfma(v8 a, v8 b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// XCD-affine workgroup order: the hardware places workgroup id b on XCD b % 8. Remapping the id so that every XCD gets one
-// CONTIGUOUS range of tiles / samples makes the rows a kernel reads the rows the previous kernel of the chain wrote on the
-// same XCD (k_qkv_attn -> k_mlp -> k_qkv_attn ...): they are still in that XCD's L2 instead of behind the fabric.
-__device__ __forceinline__ int xcd_affine(int bid, int nwg) {
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-}
-
-// The other half-wave's value (lane ^ 32): v_permlane32_swap_b32 a, b gives a' = [a.lo | b.lo], b' = [a.hi | b.hi], so with b a copy of a in a
-// register of its own b' and a' are the two halves' values in every lane - one VALU instruction where __shfl_xor(v, 32) is a ds_bpermute round trip.
-// (inline asm: the builtin's second result is miscompiled by ROCm 7.2's clang, it adds a' to itself; tools/permlane_check.hip)
-__device__ __forceinline__ void half_swap(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ float half_max(float v) {
-    float o = v;
-    asm volatile("" : "+v"(o));
-    half_swap(v, o);
-    return fmaxf(v, o);
-}
-__device__ __forceinline__ float half_sum(float v) {
-    float o = v;
-    asm volatile("" : "+v"(o));
-    half_swap(v, o);
-    return v + o;
-}
-
 // Step boundary of the plain-bf16 phase as one kernel (rgn_step.hip): output projection + sampler update + the next
 // evaluation's input embedding for 64-row tiles; d = 512, no emb_trans_dec token; with or without guidance.
-struct StepCoef;
-struct SampleParams;
 struct StepArgs {
     const __bf16* h;            // last layer's output planes (hi) [16][rows][32], advanced to the first row of this launch
     __bf16* hout;               // residual-stream planes the next evaluation's layer 0 reads (normally the same buffer)

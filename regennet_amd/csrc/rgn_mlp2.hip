@@ -79,7 +79,7 @@ __device__ long long g_m2_st[1024][12];
 template <bool F16 = false, bool ENC = false>
 __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     using C = M2;
-    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): planes in, planes out, weight planes
+    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): planes in, planes out, weight planes
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;
@@ -267,8 +267,8 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     auto wrs = [&](const __bf16* W, int cb0, int bytes) {
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(W) + (size_t)cb0 * 1024, 0, bytes - cb0 * 2048, 0x00020000);
     };
-    const Pass p_wo{wrs(g.Wo, NT * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{wrs(g.W1, NT * wave, 1024 * 512 * 2), 32 * 2048, 0},
-        p_w1b{wrs(g.W1, 16 + NT * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{wrs(g.W2, NT * wave, 512 * 1024 * 2), 16 * 2048, 0},
+    const Pass p_wo{wrs(g.w.Wo, NT * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{wrs(g.w.W1, NT * wave, 1024 * 512 * 2), 32 * 2048, 0},
+        p_w1b{wrs(g.w.W1, 16 + NT * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{wrs(g.w.W2, NT * wave, 512 * 1024 * 2), 16 * 2048, 0},
         p_w2b{p_w2a.rs, 16 * 2048, 32};
     f32x16 acc[NT][MT];
 #pragma unroll
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     float va[4][VK], sv[VK], pv[NSAMP][VK];
     int step = 0;
     {
-        const float* srcA[4] = {g.bo, g.g1, g.g2, g.b2};
+        const float* srcA[4] = {g.w.bo, g.w.g1, g.w.g2, g.w.b2};
 #pragma unroll
         for (int v = 0; v < 4; ++v)
 #pragma unroll
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
         const int s0 = m0 / g.Tq, slast = (g.M - 1) / g.Tq;
 #pragma unroll
         for (int k = 0; k < VK; ++k) {
-            sv[k] = g.b1[cw + 64 * k];                               // norm1's beta, folded into the per-sample vector
+            sv[k] = g.w.b1[cw + 64 * k];                             // norm1's beta, folded into the per-sample vector
 #pragma unroll
             for (int j = 0; j < NSAMP; ++j) {
                 const int sidx = s0 + j < slast ? s0 + j : slast;
@@ -318,11 +318,11 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     float vb[5][VK];                                                 // phase B, held in registers until the wave is past norm2
 #pragma unroll
     for (int k = 0; k < VK; ++k) {
-        vb[0][k] = g.bf1[cw + 64 * k];
-        vb[1][k] = g.bf1[512 + cw + 64 * k];
-        vb[2][k] = g.bf2[cw + 64 * k];
-        vb[3][k] = g.g3[cw + 64 * k];
-        vb[4][k] = g.b3[cw + 64 * k];
+        vb[0][k] = g.w.bf1[cw + 64 * k];
+        vb[1][k] = g.w.bf1[512 + cw + 64 * k];
+        vb[2][k] = g.w.bf2[cw + 64 * k];
+        vb[3][k] = g.w.g3[cw + 64 * k];
+        vb[4][k] = g.w.b3[cw + 64 * k];
     }
     asm volatile("" ::: "memory");
     constexpr int EXTRA = 16 + 6 * VK;                               // residual + phase B + step vector loads

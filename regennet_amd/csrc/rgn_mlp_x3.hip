@@ -210,10 +210,10 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(W) + (size_t)cb0 * 1024, 0, bytes - cb0 * 2048, 0x00020000);
     };
     const int cb = NT * wave;
-    const Pass p_wo{wrs(g.Wo, cb, 512 * 512 * 2), wrs(gx.Wo_lo, cb, 512 * 512 * 2), 16 * 2048, 0},
-        p_w1a{wrs(g.W1, cb, 1024 * 512 * 2), wrs(gx.W1_lo, cb, 1024 * 512 * 2), 32 * 2048, 0},
-        p_w1b{wrs(g.W1, 16 + cb, 1024 * 512 * 2), wrs(gx.W1_lo, 16 + cb, 1024 * 512 * 2), 32 * 2048, 0},
-        p_w2a{wrs(g.W2, cb, 512 * 1024 * 2), wrs(gx.W2_lo, cb, 512 * 1024 * 2), 16 * 2048, 0}, p_w2b{p_w2a.hi, p_w2a.lo, 16 * 2048, 32};
+    const Pass p_wo{wrs(g.w.Wo, cb, 512 * 512 * 2), wrs(gx.Wo_lo, cb, 512 * 512 * 2), 16 * 2048, 0},
+        p_w1a{wrs(g.w.W1, cb, 1024 * 512 * 2), wrs(gx.W1_lo, cb, 1024 * 512 * 2), 32 * 2048, 0},
+        p_w1b{wrs(g.w.W1, 16 + cb, 1024 * 512 * 2), wrs(gx.W1_lo, 16 + cb, 1024 * 512 * 2), 32 * 2048, 0},
+        p_w2a{wrs(g.w.W2, cb, 512 * 1024 * 2), wrs(gx.W2_lo, cb, 512 * 1024 * 2), 16 * 2048, 0}, p_w2b{p_w2a.hi, p_w2a.lo, 16 * 2048, 32};
 #pragma unroll
     for (int s = 0; s < RD - 1; ++s) load_g(p_wo, s, s);             // right behind the att DMA
     const int cw = CW * wave + lane;                                   // this lane's column of every vector slice
@@ -222,10 +222,10 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     float va[4], sv, pv[NSAMP], vb[5];
     int step = 0;
     {
-        va[0] = g.bo[cw]; va[1] = g.g1[cw]; va[2] = ENC ? 0.f : g.g2[cw]; va[3] = ENC ? 0.f : g.b2[cw];
+        va[0] = g.w.bo[cw]; va[1] = g.w.g1[cw]; va[2] = ENC ? 0.f : g.w.g2[cw]; va[3] = ENC ? 0.f : g.w.b2[cw];
         if (!ENC && g.stepvec) step = *g.d_step;
         const int s0 = m0 / g.Tq, slast = (g.M - 1) / g.Tq;
-        sv = g.b1[cw];                                                 // norm1's beta, folded into the per-sample vector
+        sv = g.w.b1[cw];                                               // norm1's beta, folded into the per-sample vector
 #pragma unroll
         for (int j = 0; j < NSAMP; ++j) {
             const int sidx = s0 + j < slast ? s0 + j : slast;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
                 rl[nt][i4] = *reinterpret_cast<const bf16x4*>(gx.h_lo + o);
             }
     }
-    vb[0] = g.bf1[cw]; vb[1] = g.bf1[512 + cw]; vb[2] = g.bf2[cw]; vb[3] = g.g3[cw]; vb[4] = g.b3[cw];
+    vb[0] = g.w.bf1[cw]; vb[1] = g.w.bf1[512 + cw]; vb[2] = g.w.bf2[cw]; vb[3] = g.w.g3[cw]; vb[4] = g.w.b3[cw];
     const float tv = (!ENC && g.stepvec) ? g.stepvec[(size_t)step * g.ldstep + cw] : 0.f;
     // the att images are complete once EVERY wave's DMA pieces have landed: they are this wave's oldest vector-memory operations; at least
     // 46 younger ones follow (ring 20, vectors 5 + 5, residual 16; the per-sample / step vectors may be absent), which may stay in flight -

@@ -58,17 +58,13 @@ GemmArgs gemm_args(const rgn_ctx* c, const Lin& L, const float* A, int lda, floa
     g.W = c->dp<float>(L.w);
     g.Whi = c->dp<uint16_t>(L.hi);
     g.Wlo = c->dp<uint16_t>(L.lo);
-    g.bias = L.has_bias ? c->dp<float>(L.b) : nullptr;
-    g.add = nullptr;
-    g.ldadd = 0;
-    g.add_mod = 0;
+    g.bias = L.has_bias ? c->dp<float>(L.b) : nullptr;   // (no addend, no activation: the caller's)
     g.C = C;
     g.ldc = ldc;
     g.M = M;
     g.N = L.N;
     g.K = L.K;
     g.Kp = L.Kp;
-    g.act = 0;
     return g;
 }
 
@@ -91,24 +87,18 @@ int pack_state(rgn_ctx* c, const float* x, const Dims& dm, bool guided, hipStrea
 
 // ---- the plan of one denoiser evaluation: WHICH kernels run it. The one place that decides - run_layers / run_eval /
 //      rgn_sample_range dispatch on it and rgn_plan_query reports it (launches, algorithmic FLOPs and L2 weight-stream bytes per
-//      kernel class), so that what bench.py prices is by construction what the engine launches.
-enum AttnForm { AF_LAYERS = 0, AF_QKV, AF_QKV_LONG, AF_ROWGEMM_ATTN, AF_GEMM_ATTN, AF_PLAIN };
-enum TailForm { TF_LAYERS = 0, TF_MLP_X3, TF_MLP, TF_ROWGEMM, TF_GEMM_LN };
-struct EvalPlan {
-    bool sb = false;          // small-batch engine (k_sb_gemm chain) for the whole evaluation
-    bool layers = false;      // k_layers: the whole decoder stack in one kernel, one sample per workgroup
-    bool steps = false;       // k_layers<true>: whole runs of sampler steps in one launch (sampling only)
-    bool step_fused = false;  // k_step: output projection + sampler update + next input embedding (sampling only)
-    AttnForm attn = AF_PLAIN;
-    TailForm tail = TF_GEMM_LN;
-};
+//      kernel class), so that what bench.py prices is by construction what the engine launches. (EvalPlan: rgn_host.h)
 bool all_frag(const rgn_ctx* c) {
     bool ok = true;
     for (int l = 0; l < c->L; ++l) ok = ok && c->layers[l].qkv.fr && c->layers[l].out.fr && c->layers[l].ff1.fr && c->layers[l].ff2.fr;
     return ok;
 }
-inline bool eval_x3_phase(const rgn_ctx* c, bool phase_x3) {
-    return c->cfg.precision == RGN_PREC_BF16X3 || (c->cfg.precision == RGN_PREC_BF16_X3TAIL && phase_x3);
+// The phase an evaluation RUNS in, from the one the schedule asks for - the one place where the handle's precision mode overrides the schedule
+// (eval_x3) and where f16 is confined to what has an fp16 form: a plain sampling evaluation (sample_range asks for it only where prec_plan allows)
+Phase eval_phase(const rgn_ctx* c, Phase ph, bool sampling) {
+    ph.x3 = eval_x3(ph.x3, c->cfg.precision);
+    ph.f16 = ph.f16 && !ph.x3 && sampling;
+    return ph;
 }
 // Can this evaluation end in the fused step boundary (rgn_step.hip)? Sampling step of the plain-bf16 phase on the
 // throughput kernels with hi-only residual planes; guided and unguided (guided sampling runs one k_step over the conditional rows
@@ -181,9 +171,114 @@ PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided) {
     return pp;
 }
 
-int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_rows, const float* ccond_rows, hipStream_t s) {
-    const int d = c->d, Ld = c->L * c->d, M = dm.Bm * dm.Tq;
-    const bool x3 = eval_x3(c);
+// ---- argument builders: each family of kernel arguments is filled in ONE place, whichever kernel form consumes it
+inline float qscale(const Dims& dm) { return 1.0f / sqrtf((float)dm.dh); }
+
+// Layer l's fragment-ordered weight planes, biases and LayerNorm vectors. The only place that picks an operand format: the bf16 planes, or the
+// fp16 ones of the schedule's fp16 sub-phase. (encoder layers: no middle norm - g2 / b2 are null)
+LayerWts layer_wts(const rgn_ctx* c, int l, bool f16) {
+    const LayerW& w = c->layers[l];
+    auto frag = [&](const Lin& L) { return c->dp<__bf16>(f16 ? L.fr16 : L.fr); };
+    LayerWts t{};
+    t.Wqkv = frag(w.qkv); t.Wo = frag(w.out); t.W1 = frag(w.ff1); t.W2 = frag(w.ff2);
+    t.bqkv = c->dp<float>(w.qkv.b); t.bo = c->dp<float>(w.out.b); t.bf1 = c->dp<float>(w.ff1.b); t.bf2 = c->dp<float>(w.ff2.b);
+    t.g1 = c->dp<float>(w.ln[0]); t.b1 = c->dp<float>(w.ln[1]);
+    if (!c->enc) { t.g2 = c->dp<float>(w.ln[2]); t.b2 = c->dp<float>(w.ln[3]); }
+    t.g3 = c->dp<float>(w.ln[4]); t.b3 = c->dp<float>(w.ln[5]);
+    return t;
+}
+
+// The vectors layer l adds between norm1 and norm2, for the samples from s0 on: the folded cross-attention per sample (rgn_denoise: c->call, made
+// by run_eval; sampling: the bound condition's rows, null without a condition) and, when sampling, per step (read at *d_step). Encoder layers
+// have no cross-attention: both null.
+struct LayerVecs { const float* pervec; int ldper; const float* stepvec; int ldstep; const int* d_step; };
+LayerVecs layer_vecs(const rgn_ctx* c, int l, int s0, bool sampling, const float* ccond_rows) {
+    const size_t d = c->d, Ld = (size_t)c->L * d, off = (size_t)s0 * Ld + (size_t)l * d;
+    LayerVecs v{};
+    if (!c->enc) {
+        v.pervec = sampling ? (ccond_rows ? ccond_rows + off : nullptr) : c->call + off;
+        v.stepvec = sampling ? c->call_time + (size_t)l * d : nullptr;
+    }
+    v.ldper = v.ldstep = (int)Ld;
+    v.d_step = c->d_step;
+    return v;
+}
+template <class Args>   // MlpArgs, RowGemmArgs, SbArgs, LayersArgs: the same five fields
+void put_vecs(Args& g, const LayerVecs& v) { g.pervec = v.pervec; g.ldper = v.ldper; g.stepvec = v.stepvec; g.ldstep = v.ldstep; g.d_step = v.d_step; }
+
+// k_attn_x3 over ns samples whose attention-ready q / k / v slabs start at slab0 (causal; encoder handles: full - the launcher's flag)
+AttnX3Args attn_x3_args(const rgn_ctx* c, const Dims& dm, int ns, size_t slab0, const Planes& out, bool x3) {
+    AttnX3Args a{};
+    a.Qhi = c->q_hi + slab0; a.Qlo = c->q_lo + slab0; a.Khi = c->k_hi + slab0; a.Klo = c->k_lo + slab0; a.Vthi = c->vt_hi + slab0; a.Vtlo = c->vt_lo + slab0;
+    a.out = out;
+    a.Bm = ns; a.H = c->H; a.dh = dm.dh; a.d = c->d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = x3;
+    return a;
+}
+
+// Fused in_proj + attention of layer l (w: its layer_wts in the phase's format) over the ns samples of a chain: k_qkv_attn* (AF_QKV), or k_qkv_attn_long (long_form: it reads the hi /
+// fragment plane only, the other operands stay null). Bm_eval: samples of the WHOLE evaluation (all kernel chains), not of this chain.
+QkvAttnArgs qkv_args(const rgn_ctx* c, const Dims& dm, int l, const LayerWts& w, int ns, const Planes& in, const Planes& out, Phase ph, bool long_form, int Bm_eval) {
+    const Lin& L = c->layers[l].qkv;
+    QkvAttnArgs g{};
+    g.Ahi = in.hi; g.a_rows = in.rows;
+    g.Wfr = L.fr ? w.Wqkv : nullptr;   // plain phase: weights streamed to registers
+    g.bias = w.bqkv;
+    g.out = out;
+    g.Bm = ns; g.Kp = L.Kp; g.d = c->d; g.H = c->H; g.Tq = dm.Tq;
+    g.qscale = qscale(dm);
+    g.f16 = ph.f16 ? 1 : 0;
+    if (!long_form) {
+        g.Alo = in.lo;
+        g.Whi = c->dp<__bf16>(L.hi); g.Wlo = c->dp<__bf16>(L.lo);
+        g.Wfr_lo = (ph.x3 && L.fr && L.fr_lo && !c->qkv_x3_dma) ? c->dp<__bf16>(L.fr_lo) : nullptr;   // ... and the split phase's (k_qkv_attn_rs_x3)
+        g.Bm_eval = Bm_eval;
+    }
+    return g;
+}
+
+// The step boundary's weights (k_step and the multi-step k_layers): output projection, folded input embedding and the hoisted condition part
+// c0, all in the phase's 16-bit format
+struct BoundaryWts { const __bf16* Wout; const float* bout; int F, nb_out; const __bf16 *Wx, *c0; };
+BoundaryWts boundary_wts(const rgn_ctx* c, bool f16) {
+    BoundaryWts b{};
+    b.Wout = c->dp<__bf16>(f16 ? c->lin_out.fr16 : c->lin_out.fr); b.bout = c->dp<float>(c->lin_out.b); b.F = c->F; b.nb_out = (c->F + 31) / 32;
+    b.Wx = c->dp<__bf16>(f16 ? c->lin_x.fr16 : c->lin_x.fr);
+    b.c0 = f16 ? reinterpret_cast<const __bf16*>(c->c0h16) : c->c0h;
+    return b;
+}
+template <class Args>   // StepArgs, LayersArgs; row0: first token row of the launch
+void put_boundary(Args& g, const BoundaryWts& b, size_t row0, int d) { g.Wout = b.Wout; g.bout = b.bout; g.F = b.F; g.nb_out = b.nb_out; g.Wx = b.Wx; g.c0 = b.c0 + row0 * d; }
+
+// Arguments of k_layers that do not depend on the launch's sample range but for the per-sample vector base (rgn_layers.hip)
+void fill_layers_args(const rgn_ctx* c, LayersArgs& g, const Dims& dm, bool sampling, const float* ccond_rows, int s0, bool f16) {
+    g.Tq = dm.Tq; g.L = c->L;
+    for (int l = 0; l < c->L; ++l) g.lw[l] = layer_wts(c, l, f16);
+    put_vecs(g, layer_vecs(c, 0, s0, sampling, ccond_rows));
+    g.qscale = qscale(dm);
+    g.f16 = f16 ? 1 : 0;
+}
+
+// What run_eval hands its kernel chains: one evaluation's shape (dm: the WHOLE evaluation, Bm = all rows of all chains), plan, phase (as
+// eval_phase returns it) and condition rows (embedding [Bm, d] / folded cross-attention vectors [Bm, L d]; null without a condition)
+struct Eval {
+    Dims dm; EvalPlan pl; Phase ph;
+    bool guided, sampling;
+    const float *cond_rows, *ccond_rows;
+};
+
+// emb_trans_dec: the timestep + condition embedding as token 0 of the samples from s0 on (sampling: condition rows + TE[*d_step], both made once
+// per condition / schedule; rgn_denoise: c->emb, made by run_eval), + the positional encoding
+int embed_token(rgn_ctx* c, const Eval& ev, const Dims& dm, int s0, float* h, const Planes& hp, hipStream_t s) {
+    const float* rows = ev.sampling ? ev.cond_rows : c->emb;
+    RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(rows ? rows + (size_t)s0 * c->d : nullptr, ev.sampling ? c->te_all : nullptr, ev.sampling ? c->d_step : nullptr,
+                                              c->dp<float>(c->off_pe), h, hp, dm, c->cfg.wo_pos_emb, s));
+    return RGN_OK;
+}
+
+int run_layers_sb(rgn_ctx* c, const Eval& ev, hipStream_t s) {
+    const Dims& dm = ev.dm;
+    const int d = c->d, M = dm.Bm * dm.Tq;
+    const bool x3 = ev.ph.x3, sampling = ev.sampling;
     auto base = [&](const Lin& L) {
         SbArgs g{};
         g.Whi = c->dp<__bf16>(L.hi); g.Wlo = c->dp<__bf16>(L.lo); g.w_rows = L.N;
@@ -191,19 +286,16 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
         g.M = M; g.N = L.N; g.Kp = L.Kp; g.Tq = dm.Tq;
         return g;
     };
-    {   // input embedding + hoisted condition part: tmp = xin . Wx'^T + c0
-        SbArgs g = base(c->lin_x);
-        g.Ahi = c->xin_hi; g.Alo = c->xin_lo; g.a_rows = M;
-        g.resid = c->c0; g.ldr = d; g.C = c->tmp; g.ldc = d;
+    auto to_tmp = [&](const Lin& L, const __bf16* Ahi, const __bf16* Alo, const float* resid) -> int {   // tmp = A . W^T + bias + resid
+        SbArgs g = base(L);
+        g.Ahi = Ahi; g.Alo = Alo; g.a_rows = M;
+        g.resid = resid; g.ldr = d; g.C = c->tmp; g.ldc = d;
         RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 0, 0, x3, s));
-    }
-    if (c->etd) {
-        const Planes none{nullptr, nullptr, 0};
-        if (sampling)
-            RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(cond_rows, c->te_all, c->d_step, c->dp<float>(c->off_pe), c->tmp, none, dm, c->cfg.wo_pos_emb, s));
-        else
-            RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(c->emb, nullptr, nullptr, c->dp<float>(c->off_pe), c->tmp, none, dm, c->cfg.wo_pos_emb, s));
-    }
+        return RGN_OK;
+    };
+    int rc;
+    if ((rc = to_tmp(c->lin_x, c->xin_hi, c->xin_lo, c->c0))) return rc;   // input embedding + hoisted condition part: tmp = xin . Wx'^T + c0
+    if (c->etd && (rc = embed_token(c, ev, dm, 0, c->tmp, Planes{nullptr, nullptr, 0}, s))) return rc;
     const Planes att_p{c->att_hi, x3 ? c->att_lo : nullptr, M};
     for (int l = 0; l < c->L; ++l) {
         const LayerW& w = c->layers[l];
@@ -213,40 +305,22 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
             if (l) { g.ga = c->dp<float>(c->layers[l - 1].ln[4]); g.ba = c->dp<float>(c->layers[l - 1].ln[5]); }
             g.Qhi = c->q_hi; g.Khi = c->k_hi; g.Vhi = c->vt_hi;
             if (x3) { g.Qlo = c->q_lo; g.Klo = c->k_lo; g.Vlo = c->vt_lo; }
-            g.d = d; g.H = c->H; g.dh = dm.dh; g.Tqp = c->Tqp; g.qscale = 1.0f / sqrtf((float)dm.dh);
+            g.d = d; g.H = c->H; g.dh = dm.dh; g.Tqp = c->Tqp; g.qscale = qscale(dm);
             RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 2, x3, s));
         }
-        {   // causal (encoder handles: full) self-attention, a (sample, head) per workgroup -> att planes
-            AttnX3Args a{};
-            a.Qhi = c->q_hi; a.Qlo = c->q_lo; a.Khi = c->k_hi; a.Klo = c->k_lo; a.Vthi = c->vt_hi; a.Vtlo = c->vt_lo;
-            a.out = att_p;
-            a.Bm = dm.Bm; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = x3;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
-        }
-        {   // tmp = attention . Wo^T + bo + h
-            SbArgs g = base(w.out);
-            g.Ahi = c->att_hi; g.Alo = c->att_lo; g.a_rows = M;
-            g.resid = c->h; g.ldr = d; g.C = c->tmp; g.ldc = d;
-            RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 0, 0, x3, s));
-        }
+        // causal (encoder handles: full) self-attention, a (sample, head) per workgroup -> att planes
+        RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(attn_x3_args(c, dm, dm.Bm, 0, att_p, x3), s, !c->enc));
+        if ((rc = to_tmp(w.out, c->att_hi, c->att_lo, c->h))) return rc;   // tmp = attention . Wo^T + bo + h
         {   // h = norm2(norm1(tmp) + folded cross-attention) (encoder layers: h = norm1(tmp)); ffn = gelu(h . W1^T + b1)
             SbArgs g = base(w.ff1);
             g.src = c->tmp; g.xout = c->h;
             g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]);
             if (!c->enc) { g.gb = c->dp<float>(w.ln[2]); g.bb = c->dp<float>(w.ln[3]); }
-            g.pervec = c->enc ? nullptr : sampling ? (ccond_rows ? ccond_rows + (size_t)l * d : nullptr) : c->call + (size_t)l * d;
-            g.ldper = Ld;
-            g.stepvec = (sampling && !c->enc) ? c->call_time + (size_t)l * d : nullptr;
-            g.ldstep = Ld; g.d_step = c->d_step;
+            put_vecs(g, layer_vecs(c, l, 0, sampling, ev.ccond_rows));
             g.Chi = c->ffn_hi; g.Clo = x3 ? c->ffn_lo : nullptr; g.c_rows = M;
             RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 1, 1, x3, s));
         }
-        {   // tmp = ffn . W2^T + b2 + h
-            SbArgs g = base(w.ff2);
-            g.Ahi = c->ffn_hi; g.Alo = c->ffn_lo; g.a_rows = M;
-            g.resid = c->h; g.ldr = d; g.C = c->tmp; g.ldc = d;
-            RGN_LAUNCH(c, KC_SB, s, launch_sb_gemm(g, 0, 0, x3, s));
-        }
+        if ((rc = to_tmp(w.ff2, c->ffn_hi, c->ffn_lo, c->h))) return rc;   // tmp = ffn . W2^T + b2 + h
     }
     SbArgs g = base(c->lin_out);   // x0tok = norm3(tmp) . Wout^T + bout
     g.src = c->tmp;
@@ -257,36 +331,16 @@ int run_layers_sb(rgn_ctx* c, const Dims& dm, bool sampling, const float* cond_r
 }
 
 // Embedding GEMM + the L decoder layers + output projection for samples [s0, s0+ns) of the evaluation's sample list
-// (row range [s0*Tq, (s0+ns)*Tq)), enqueued on stream s. F32 mode is always called with the full range.
-// Arguments of k_layers that do not depend on the launch's sample range but for the per-sample vector base (rgn_layers.hip)
-void fill_layers_args(rgn_ctx* c, LayersArgs& g, const Dims& dm, bool sampling, const float* ccond_rows, int s0, bool f16 = false) {
-    const int Ld = c->L * c->d;
-    g.Tq = dm.Tq; g.L = c->L;
-    for (int l = 0; l < c->L; ++l) {
-        const LayerW& w = c->layers[l];
-        LayerWts& t = g.lw[l];
-        t.Wqkv = c->dp<__bf16>(f16 ? w.qkv.fr16 : w.qkv.fr); t.Wo = c->dp<__bf16>(f16 ? w.out.fr16 : w.out.fr);
-        t.W1 = c->dp<__bf16>(f16 ? w.ff1.fr16 : w.ff1.fr); t.W2 = c->dp<__bf16>(f16 ? w.ff2.fr16 : w.ff2.fr);
-        t.bqkv = c->dp<float>(w.qkv.b); t.bo = c->dp<float>(w.out.b); t.bf1 = c->dp<float>(w.ff1.b); t.bf2 = c->dp<float>(w.ff2.b);
-        t.g1 = c->dp<float>(w.ln[0]); t.b1 = c->dp<float>(w.ln[1]); t.g2 = c->dp<float>(w.ln[2]); t.b2 = c->dp<float>(w.ln[3]);
-        t.g3 = c->dp<float>(w.ln[4]); t.b3 = c->dp<float>(w.ln[5]);
-    }
-    g.pervec = sampling ? (ccond_rows ? ccond_rows + (size_t)s0 * Ld : nullptr) : c->call + (size_t)s0 * Ld;
-    g.ldper = Ld;
-    g.stepvec = sampling ? c->call_time : nullptr;
-    g.ldstep = Ld; g.d_step = c->d_step;
-    g.qscale = 1.0f / sqrtf((float)dm.dh);
-}
-
-int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const float* cond_rows, const float* ccond_rows,
-               int s0, int ns, hipStream_t s) {
-    const int prec = c->cfg.precision;
-    const int d = c->d, Ld = c->L * c->d, Mtot = dmf.Bm * dmf.Tq, Mb = dmf.B * dmf.Tq;
+// (row range [s0*Tq, (s0+ns)*Tq)), enqueued on stream s. F32 mode is always called with the full range. An evaluation that ends in the
+// fused step boundary (ev.pl.step_fused) has neither GEMM: k_step leaves the next input embedding in the residual-stream planes and applies
+// the output projection itself.
+int run_layers(rgn_ctx* c, const Eval& ev, int s0, int ns, hipStream_t s) {
+    const Dims& dmf = ev.dm;
+    const EvalPlan& pl = ev.pl;
+    if (pl.sb) return run_layers_sb(c, ev, s);   // (called with the full range)
+    const int d = c->d, Mtot = dmf.Bm * dmf.Tq, Mb = dmf.B * dmf.Tq;
     const int row0 = s0 * dmf.Tq, M = ns * dmf.Tq;
-    const bool fast = prec != RGN_PREC_F32, x3 = eval_x3(c);
-    const EvalPlan pl = plan_eval(c, dmf, guided, x3, sampling);
-    if (pl.sb) return run_layers_sb(c, dmf, sampling, cond_rows, ccond_rows, s);   // (called with the full range)
-    const bool f16 = !x3 && sampling && c->phase_f16;      // the schedule's fp16 sub-phase (rgn_sample_range sets it only where prec_plan allows)
+    const bool fast = c->cfg.precision != RGN_PREC_F32, x3 = ev.ph.x3, f16 = ev.ph.f16, sampling = ev.sampling;
     Dims dm = dmf;
     dm.Bm = ns;
     // ---- the big GEMMs: F32 mode keeps fp32 activations (k_gemm_f32); the bf16 modes chain pre-split
@@ -336,133 +390,83 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
     };
     int rc;
     // input embedding + hoisted condition part (InputProcess/fuse/pos-enc, cmdm.py:201-218)
-    if (c->skip_embed_out) {
+    if (pl.step_fused) {
         // fused step boundary (k_step): the residual-stream planes already hold this evaluation's input embedding
     } else if (fast) {   // xin planes and c0 already hold both guidance halves
         if ((rc = big(c->lin_x, nullptr, 0, xin_p, h32 ? h : nullptr, d, h_p, c->c0 + (size_t)row0 * d, 0, M))) return rc;
     } else {
         if ((rc = big(c->lin_x, c->xin, c->F, none, c->h, d, none, c->c0, 0, Mb))) return rc;
-        if (guided)
+        if (ev.guided)
             RGN_HIP(c, hipMemcpyAsync(c->h + (size_t)Mb * d, c->h, (size_t)Mb * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    if (c->etd) {
-        if (sampling)
-            RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(cond_rows ? cond_rows + (size_t)s0 * d : nullptr, c->te_all, c->d_step,
-                                                      c->dp<float>(c->off_pe), h, h_p, dm, c->cfg.wo_pos_emb, s));
-        else
-            RGN_LAUNCH(c, KC_EMBED, s, launch_emb_rows(c->emb + (size_t)s0 * d, nullptr, nullptr, c->dp<float>(c->off_pe), h, h_p, dm,
-                                                      c->cfg.wo_pos_emb, s));
-    }
+    if (c->etd && (rc = embed_token(c, ev, dm, s0, h, h_p, s))) return rc;
     const size_t slab0 = (size_t)s0 * c->H * c->Tqp * dm.dh;      // attention-ready planes: first slab of this range
-    bool layers_done = false;
     if (pl.layers) {
         // plain-bf16 phase, <= 64 tokens, d = 512 / ff = 1024 / 4 heads: ALL layers in one kernel, one sample per workgroup - the residual
         // stream stays in LDS from the input embedding to the last norm3, only the weights stream (rgn_layers.hip)
         LayersArgs g{};
         g.h = h_p.hi; g.out = h_p.hi; g.rows = h_p.rows; g.Bm = ns;
-        fill_layers_args(c, g, dm, sampling, ccond_rows, s0, f16);
-        g.f16 = f16 ? 1 : 0;
+        fill_layers_args(c, g, dm, sampling, ev.ccond_rows, s0, f16);
         RGN_LAUNCH(c, KC_LAYERS, s, launch_layers(g, s));
-        layers_done = true;
     }
-    for (int l = layers_done ? c->L : 0; l < c->L; ++l) {
+    for (int l = pl.layers ? c->L : 0; l < c->L; ++l) {
         const LayerW& w = c->layers[l];
+        const LayerWts lw = layer_wts(c, l, f16);
+        const LayerVecs lv = layer_vecs(c, l, s0, sampling, ev.ccond_rows);
         if (pl.attn == AF_QKV) {
             // in_proj + attention in one kernel (a sample - the DMA-fed form: a pair - and a group of heads per workgroup): q, k, v never reach memory
-            QkvAttnArgs g{};
-            g.Ahi = h_p.hi; g.Alo = h_p.lo; g.a_rows = h_p.rows;
-            g.Whi = c->dp<__bf16>(w.qkv.hi); g.Wlo = c->dp<__bf16>(w.qkv.lo);
-            g.Wfr = w.qkv.fr ? c->dp<__bf16>(f16 ? w.qkv.fr16 : w.qkv.fr) : nullptr;   // plain phase: weights streamed to registers
-            g.Wfr_lo = (x3 && w.qkv.fr && w.qkv.fr_lo && !c->qkv_x3_dma) ? c->dp<__bf16>(w.qkv.fr_lo) : nullptr;   // ... and the split phase's (k_qkv_attn_rs_x3)
-            g.f16 = f16 ? 1 : 0;
-            g.bias = c->dp<float>(w.qkv.b);
-            g.out = att_p;
-            g.Bm = ns; g.Kp = w.qkv.Kp; g.d = d; g.H = c->H; g.Tq = dm.Tq;
-            g.qscale = 1.0f / sqrtf((float)dm.dh);
-            g.Bm_eval = dmf.Bm;   // samples of the WHOLE evaluation (all kernel chains), not of this chain
-            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn(g, x3, s, !c->enc));   // 93 % of its MFMA work is the in_proj GEMM
+            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn(qkv_args(c, dm, l, lw, ns, h_p, att_p, ev.ph, false, dmf.Bm), x3, s, !c->enc));   // 93 % of its MFMA work is the in_proj GEMM
         } else if (pl.attn == AF_QKV_LONG) {
             // plain-bf16 phase, long sequence: in_proj + attention of one (sample, head) per workgroup, q / k / v stay in LDS
-            QkvAttnArgs g{};
-            g.Ahi = h_p.hi; g.a_rows = h_p.rows;
-            g.Wfr = c->dp<__bf16>(f16 ? w.qkv.fr16 : w.qkv.fr); g.bias = c->dp<float>(w.qkv.b);
-            g.out = att_p;
-            g.Bm = ns; g.Kp = w.qkv.Kp; g.d = d; g.H = c->H; g.Tq = dm.Tq;
-            g.qscale = 1.0f / sqrtf((float)dm.dh);
-            g.f16 = f16 ? 1 : 0;
-            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn_long(g, s));
+            RGN_LAUNCH(c, KC_QKV, s, launch_qkv_attn_long(qkv_args(c, dm, l, lw, ns, h_p, att_p, ev.ph, true, 0), s));
         } else if (pl.attn == AF_ROWGEMM_ATTN) {
             // plain-bf16 phase, long sequence: packed in_proj as a row-complete GEMM that scatters q (pre-scaled), k, v as
             // attention-ready planes (weights streamed to registers, output through an LDS image), then k_attn_x3
             RowGemmArgs g{};
             g.A = h_p.hi; g.a_rows = h_p.rows;
-            g.W = c->dp<__bf16>(w.qkv.fr); g.bias = c->dp<float>(w.qkv.b);
+            g.W = lw.Wqkv; g.bias = lw.bqkv;
             g.M = M; g.N = 3 * d; g.Kp = w.qkv.Kp; g.act = 2;
             g.Qhi = c->q_hi + slab0; g.Khi = c->k_hi + slab0; g.Vhi = c->vt_hi + slab0;
-            g.H = c->H; g.dh = dm.dh; g.Tq = dm.Tq; g.Tqp = c->Tqp; g.qscale = 1.0f / sqrtf((float)dm.dh);
+            g.H = c->H; g.dh = dm.dh; g.Tq = dm.Tq; g.Tqp = c->Tqp; g.qscale = qscale(dm);
             RGN_LAUNCH(c, KC_ROWACT, s, launch_rowgemm(g, false, s));
-            AttnX3Args a{};
-            a.Qhi = g.Qhi; a.Qlo = c->q_lo + slab0; a.Khi = g.Khi; a.Klo = c->k_lo + slab0; a.Vthi = g.Vhi; a.Vtlo = c->vt_lo + slab0;
-            a.out = att_p;
-            a.Bm = ns; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = false;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(attn_x3_args(c, dm, ns, slab0, att_p, false), s, !c->enc));
         } else if (pl.attn == AF_GEMM_ATTN) {
             // in_proj GEMM scatters q (pre-scaled), k and v as attention-ready split planes; no fp32 qkv round trip
             GemmX3Args g{};
             g.Ahi = h_p.hi; g.Alo = h_p.lo; g.a_rows = h_p.rows;
             g.Whi = c->dp<__bf16>(w.qkv.hi); g.Wlo = c->dp<__bf16>(w.qkv.lo);
-            g.bias = c->dp<float>(w.qkv.b);
+            g.bias = lw.bqkv;
             g.M = M; g.N = 3 * d; g.Kp = w.qkv.Kp;
             g.Qhi = c->q_hi + slab0; g.Qlo = x3 ? c->q_lo + slab0 : nullptr;
             g.Khi = c->k_hi + slab0; g.Klo = x3 ? c->k_lo + slab0 : nullptr;
             g.Vthi = c->vt_hi + slab0; g.Vtlo = x3 ? c->vt_lo + slab0 : nullptr;
             g.d = d; g.H = c->H; g.dh = dm.dh; g.Tq = dm.Tq; g.Tqp = c->Tqp;
-            g.qscale = 1.0f / sqrtf((float)dm.dh);
+            g.qscale = qscale(dm);
             g.tq_magic = (unsigned)((1ull << 32) / (unsigned)dm.Tq) + 1u;
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm_x3(g, x3, 0, s));
-            AttnX3Args a{};
-            a.Qhi = g.Qhi; a.Qlo = c->q_lo + slab0; a.Khi = g.Khi; a.Klo = c->k_lo + slab0; a.Vthi = g.Vthi; a.Vtlo = c->vt_lo + slab0;
-            a.out = att_p;
-            a.Bm = ns; a.H = c->H; a.dh = dm.dh; a.d = d; a.Tq = dm.Tq; a.Tqp = c->Tqp; a.x3 = x3;
-            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(a, s, !c->enc));
+            RGN_LAUNCH(c, KC_ATTN, s, launch_attn_x3(attn_x3_args(c, dm, ns, slab0, att_p, x3), s, !c->enc));
         } else {
             if ((rc = big(w.qkv, h, d, h_p, qkv, 3 * d, none, nullptr, 0, M))) return rc;
             RGN_LAUNCH(c, KC_ATTN, s, launch_attention(qkv, fast ? nullptr : att, att_p, dm, s, !c->enc));
         }
-        // (encoder layers: no cross-attention vectors, and no middle norm - g2 / b2 are null)
-        const float* per_sample = c->enc ? nullptr : sampling ? (ccond_rows ? ccond_rows + (size_t)s0 * Ld + (size_t)l * d : nullptr)
-                                                              : c->call + (size_t)s0 * Ld + (size_t)l * d;
-        const float* step_vec = (sampling && !c->enc) ? c->call_time + (size_t)l * d : nullptr;
-        const float* g2 = c->enc ? nullptr : c->dp<float>(w.ln[2]);
-        const float* b2 = c->enc ? nullptr : c->dp<float>(w.ln[3]);
-        if (pl.tail == TF_MLP_X3) {
-            // split-bf16 phase, d = 512 / ff = 1024: the same layer tail on (hi, lo) plane pairs, three MFMAs per product (rgn_mlp_x3.hip):
-            // one launch where k_gemm_x3 x 3 + k_layernorm x 2 were five; residual stream updated in place (both planes)
+        if (pl.tail == TF_MLP_X3 || pl.tail == TF_MLP) {
+            // plain-bf16 phase, d = 512 / ff = 1024: the whole layer tail (out_proj + norm1 + folded cross-attention + norm2 +
+            // linear1 + GELU + linear2 + norm3) as ONE row-persistent kernel; residual stream updated in place (hi plane)
             MlpX3Args gx{};
             MlpArgs& g = gx.p;
             g.att = att_p.hi; g.h = h_p.hi; g.out = h_p.hi; g.rows = h_p.rows; g.M = M;
-            gx.att_lo = att_p.lo; gx.h_lo = h_p.lo; gx.out_lo = h_p.lo;
-            g.Wo = c->dp<__bf16>(w.out.fr); g.W1 = c->dp<__bf16>(w.ff1.fr); g.W2 = c->dp<__bf16>(w.ff2.fr);
-            gx.Wo_lo = c->dp<__bf16>(w.out.fr_lo); gx.W1_lo = c->dp<__bf16>(w.ff1.fr_lo); gx.W2_lo = c->dp<__bf16>(w.ff2.fr_lo);
-            g.bo = c->dp<float>(w.out.b); g.bf1 = c->dp<float>(w.ff1.b); g.bf2 = c->dp<float>(w.ff2.b);
-            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = g2; g.b2 = b2;
-            g.g3 = c->dp<float>(w.ln[4]); g.b3 = c->dp<float>(w.ln[5]);
-            g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
-            RGN_LAUNCH(c, KC_MLP, s, launch_mlp_x3(gx, s, c->enc != 0));
-            continue;
-        }
-        if (pl.tail == TF_MLP) {
-            // plain-bf16 phase, d = 512 / ff = 1024: the whole layer tail (out_proj + norm1 + folded cross-attention + norm2 +
-            // linear1 + GELU + linear2 + norm3) as ONE row-persistent kernel; residual stream updated in place (hi plane)
-            MlpArgs g{};
-            g.att = att_p.hi; g.h = h_p.hi; g.out = h_p.hi; g.rows = h_p.rows; g.M = M;
-            g.Wo = c->dp<__bf16>(f16 ? w.out.fr16 : w.out.fr); g.W1 = c->dp<__bf16>(f16 ? w.ff1.fr16 : w.ff1.fr); g.W2 = c->dp<__bf16>(f16 ? w.ff2.fr16 : w.ff2.fr);
+            g.w = lw;
+            put_vecs(g, lv); g.Tq = dm.Tq;
             g.f16 = f16 ? 1 : 0;
-            g.bo = c->dp<float>(w.out.b); g.bf1 = c->dp<float>(w.ff1.b); g.bf2 = c->dp<float>(w.ff2.b);
-            g.g1 = c->dp<float>(w.ln[0]); g.b1 = c->dp<float>(w.ln[1]); g.g2 = g2; g.b2 = b2;
-            g.g3 = c->dp<float>(w.ln[4]); g.b3 = c->dp<float>(w.ln[5]);
-            g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
-            RGN_LAUNCH(c, KC_MLP, s, launch_mlp(g, s, c->enc != 0));
+            if (pl.tail == TF_MLP) {
+                RGN_LAUNCH(c, KC_MLP, s, launch_mlp(g, s, c->enc != 0));
+                continue;
+            }
+            // split-bf16 phase, d = 512 / ff = 1024: the same layer tail on (hi, lo) plane pairs, three MFMAs per product (rgn_mlp_x3.hip):
+            // one launch where k_gemm_x3 x 3 + k_layernorm x 2 were five; residual stream updated in place (both planes)
+            gx.att_lo = att_p.lo; gx.h_lo = h_p.lo; gx.out_lo = h_p.lo;
+            gx.Wo_lo = c->dp<__bf16>(w.out.fr_lo); gx.W1_lo = c->dp<__bf16>(w.ff1.fr_lo); gx.W2_lo = c->dp<__bf16>(w.ff2.fr_lo);
+            RGN_LAUNCH(c, KC_MLP, s, launch_mlp_x3(gx, s, c->enc != 0));
             continue;
         }
         if (pl.tail == TF_ROWGEMM) {
@@ -470,37 +474,37 @@ int run_layers(rgn_ctx* c, const Dims& dmf, bool guided, bool sampling, const fl
             // linear2 + residual + norm3, three row-complete kernels; the residual stream is updated in place as planes
             RowGemmArgs g{};
             g.A = att_p.hi; g.a_rows = att_p.rows;
-            g.W = c->dp<__bf16>(w.out.fr); g.bias = c->dp<float>(w.out.b);
+            g.W = lw.Wo; g.bias = lw.bo;
             g.M = M; g.N = d; g.Kp = w.out.Kp;
             g.Rhi = h_p.hi; g.Rlo = h_p.lo; g.r_rows = h_p.rows; g.Ohi = h_p.hi; g.Olo = h_p.lo; g.o_rows = h_p.rows;
-            g.ga = c->dp<float>(w.ln[0]); g.ba = c->dp<float>(w.ln[1]); g.gb = g2; g.bb = b2;
-            g.pervec = per_sample; g.ldper = Ld; g.stepvec = step_vec; g.ldstep = Ld; g.d_step = c->d_step; g.Tq = dm.Tq;
+            g.ga = lw.g1; g.ba = lw.b1; g.gb = lw.g2; g.bb = lw.b2;
+            put_vecs(g, lv); g.Tq = dm.Tq;
             RGN_LAUNCH(c, KC_ROWLN, s, launch_rowgemm(g, true, s));
             RowGemmArgs f{};
             f.A = h_p.hi; f.a_rows = h_p.rows;
-            f.W = c->dp<__bf16>(w.ff1.fr); f.bias = c->dp<float>(w.ff1.b);
+            f.W = lw.W1; f.bias = lw.bf1;
             f.M = M; f.N = c->ff; f.Kp = w.ff1.Kp; f.act = 1;
             f.Chi = ffn_p.hi; f.Clo = ffn_p.lo; f.c_rows = ffn_p.rows;
             RGN_LAUNCH(c, KC_ROWACT, s, launch_rowgemm(f, false, s));
             g.A = ffn_p.hi; g.a_rows = ffn_p.rows;
-            g.W = c->dp<__bf16>(w.ff2.fr); g.bias = c->dp<float>(w.ff2.b);
+            g.W = lw.W2; g.bias = lw.bf2;
             g.Kp = w.ff2.Kp;
-            g.ga = c->dp<float>(w.ln[4]); g.ba = c->dp<float>(w.ln[5]); g.gb = nullptr; g.bb = nullptr;
+            g.ga = lw.g3; g.ba = lw.b3; g.gb = nullptr; g.bb = nullptr;
             g.pervec = nullptr; g.stepvec = nullptr;
             RGN_LAUNCH(c, KC_ROWLN, s, launch_rowgemm(g, true, s));
             continue;
         }
         if ((rc = big(w.out, att, d, att_p, tmp, d, none, h32 ? h : nullptr, 0, M))) return rc;
         RGN_LAUNCH(c, KC_LN, s,
-                   launch_layernorm(tmp, h32 ? none : h_p, h32 ? h : nullptr, h_p, M, d, c->dp<float>(w.ln[0]), c->dp<float>(w.ln[1]), per_sample, Ld, step_vec, Ld,
-                                    c->d_step, dm.Tq, g2, b2, s));
+                   launch_layernorm(tmp, h32 ? none : h_p, h32 ? h : nullptr, h_p, M, d, lw.g1, lw.b1, lv.pervec, lv.ldper, lv.stepvec, lv.ldstep,
+                                    lv.d_step, dm.Tq, lw.g2, lw.b2, s));
         if ((rc = big(w.ff1, h, d, h_p, fast ? nullptr : ffn, c->ff, ffn_p, nullptr, 1, M))) return rc;
         if ((rc = big(w.ff2, ffn, c->ff, ffn_p, tmp, d, none, h32 ? h : nullptr, 0, M))) return rc;
         RGN_LAUNCH(c, KC_LN, s,
-                   launch_layernorm(tmp, h32 ? none : h_p, h32 ? h : nullptr, h_p, M, d, c->dp<float>(w.ln[4]), c->dp<float>(w.ln[5]), nullptr, 0, nullptr, 0,
+                   launch_layernorm(tmp, h32 ? none : h_p, h32 ? h : nullptr, h_p, M, d, lw.g3, lw.b3, nullptr, 0, nullptr, 0,
                                     nullptr, dm.Tq, nullptr, nullptr, s));
     }
-    if (c->skip_embed_out) return RGN_OK;   // (k_step applies the output projection)
+    if (pl.step_fused) return RGN_OK;   // (k_step applies the output projection)
     return big(c->lin_out, h, d, h_p, c->x0tok + (size_t)row0 * c->F, c->F, none, nullptr, 0, M);
 }
 
@@ -521,11 +525,11 @@ int embed_all(rgn_ctx* c, const Dims& dm, hipStream_t s) {
 
 // One denoiser evaluation on the bound condition, ending in k_update (sampler step or plain output).
 // Everything t-dependent is read on the device (d_step / d_sp) so the sequence is graph-capturable.
-int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStream_t s) {
+int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase phase, hipStream_t s, const EvalPlan* plan) {
     const Dims dm = make_dims(c, B, guided);
-    const int prec = c->cfg.precision;
+    const Phase ph = eval_phase(c, phase, sampling);
+    const EvalPlan pl = plan ? *plan : plan_eval(c, dm, guided, ph.x3, sampling);
     const int d = c->d, Ld = c->L * c->d, M = dm.Bm * dm.Tq, Mb = B * dm.Tq;
-    const EvalPlan pl = plan_eval(c, dm, guided, eval_x3(c), sampling);
 
     // timestep embedding (TimestepEmbedder cmdm.py:284-298) + condition embedding (cmdm.py:181-187).
     // Inside a sampling loop every sample shares t, so TE[s] and the folded cross-attention vectors were computed
@@ -534,6 +538,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     const bool has_cond = c->cfg.cond_mode != RGN_COND_NONE;
     const float* cond_rows = !has_cond ? nullptr : ((uncond && !guided) ? c->condemb + (size_t)B * d : c->condemb);
     const float* ccond_rows = !has_cond ? nullptr : ((uncond && !guided) ? c->call_cond + (size_t)B * Ld : c->call_cond);
+    const Eval ev{dm, pl, ph, guided, sampling, cond_rows, ccond_rows};
     if (!sampling) {
         RGN_LAUNCH(c, KC_EMBED, s, launch_gather_pe(c->dp<float>(c->off_pe), c->d_tab, c->d_step, c->d_sp, c->pe_rows, dm.Bm, B, d, c->pe_len, s));
         GemmArgs g = gemm_args(c, c->lin_t0, c->pe_rows, d, c->emb1, d, dm.Bm);
@@ -553,7 +558,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     //      independent kernel chains on separate streams (fork/join with events, also inside graph capture): the
     //      MFMA-bound GEMM main loops of one chain overlap the HBM-bound phases (GEMM epilogues, LayerNorm, attention)
     //      of the others. Samples are independent, so no kernel ever looks across a split.
-    const bool fast = prec != RGN_PREC_F32;
+    const bool fast = c->cfg.precision != RGN_PREC_F32;
     int rc;
     int nch = (fast && !c->prof) ? c->nchains : 1;       // per-kernel event timing wants un-overlapped kernels
     // Two chains instead of four when the whole evaluation is 129 .. 256 row tiles of 64 (B=256 at 60 frames: 240): each of the
@@ -564,7 +569,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     // now also prefer two - 1899 vs 1869 motions/s, three 1842, six 1581; cfg4's 300 tiles keep four (969 / 928 / 913 with 2 / 3 / 4),
     // cfg5's 1200 measure the same with two, three and four.
     const int tiles64 = (M + 63) / 64;
-    if (nch == 4 && !c->nchains_user && !eval_x3(c) && ((tiles64 > 128 && tiles64 <= 256) || (tiles64 > 384 && tiles64 <= 512))) nch = 2;
+    if (nch == 4 && !c->nchains_user && !ph.x3 && ((tiles64 > 128 && tiles64 <= 256) || (tiles64 > 384 && tiles64 <= 512))) nch = 2;
     // up to 48 tiles: ONE chain, in both phases (B = 32 at 60 frames, 250-step calls: plain-bf16 phase 108.3 vs 114.1 ms with four chains,
     // split-bf16 phase 246 vs 277; one chain in the bulk phase and four in the tail measured 120 - 137 ms against 111 with one throughout)
     // (B = 40 / 48: 114.3 / 113.8 vs 120.0 / 118.8 with four; B = 64, 60 tiles: the same with one, two and four)
@@ -579,7 +584,6 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     // chain (overlapping the other chains' layers); with guidance the cond / uncond halves of a sample sit in different
     // chains and the update waits for the join.
     const Planes xin_p{fast ? c->xin_hi : nullptr, (fast && has_lo(c)) ? c->xin_lo : nullptr, M};
-    c->skip_embed_out = false;
     const bool fused = pl.step_fused;                       // k_step instead of out GEMM + k_update + next in GEMM
     const bool inp = sampling && c->inpaint_B > 0;          // rgn_set_inpainting: the boundary's in-painting form (rgn_denoise never applies it)
     const bool own_update = !guided && (nch > 1 || fused);
@@ -587,18 +591,15 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     if (fused) {
         if (guided) total_tiles = (Mb + 63) / 64;            // one launch over the conditional rows, after the join
         else for (int k2 = 0; k2 < nch; ++k2) total_tiles += ((per + (k2 < extra ? 1 : 0)) * dm.Tq + 63) / 64;
-        c->skip_embed_out = true;
     }
     auto step_or_update = [&](int s_first, int n, hipStream_t st) -> int {
         if (fused) {
             StepArgs g{};
             const size_t row0 = (size_t)s_first * dm.Tq;
             g.h = c->h_hi + row0 * 32; g.hout = c->h_hi + row0 * 32; g.rows = M; g.M = n * dm.Tq;
-            const bool f16 = c->phase_f16 && !eval_x3(c);
-            g.Wout = c->dp<__bf16>(f16 ? c->lin_out.fr16 : c->lin_out.fr); g.bout = c->dp<float>(c->lin_out.b); g.F = c->F; g.nb_out = (c->F + 31) / 32;
-            g.Wx = c->dp<__bf16>(f16 ? c->lin_x.fr16 : c->lin_x.fr); g.nkx = c->lin_x.Kp / 32;
-            g.c0 = (f16 ? reinterpret_cast<const __bf16*>(c->c0h16) : c->c0h) + row0 * c->d;
-            g.f16 = f16 ? 1 : 0;
+            put_boundary(g, boundary_wts(c, ph.f16), row0, c->d);
+            g.nkx = c->lin_x.Kp / 32;
+            g.f16 = ph.f16 ? 1 : 0;
             g.tab = c->d_tab; g.d_step = c->d_step; g.sp = c->d_sp;
             g.T = dm.T; g.B = dm.B; g.s0 = s_first; g.total_tiles = total_tiles; g.no_quads = c->step_no_quads;
             if (guided) { g.scale = c->scale; g.half = Mb; }  // x0 = x0_u + scale (x0_c - x0_u); rows [Mb, 2 Mb) are the unconditional half
@@ -611,14 +612,13 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, hipStre
     for (int k = 1; k < nch; ++k) {
         const int n = per + (k < extra ? 1 : 0);
         RGN_HIP(c, hipStreamWaitEvent(c->side[k - 1], c->ev_fork, 0));
-        if ((rc = run_layers(c, dm, guided, sampling, cond_rows, ccond_rows, s0, n, c->side[k - 1]))) return rc;
+        if ((rc = run_layers(c, ev, s0, n, c->side[k - 1]))) return rc;
         if (own_update && (rc = step_or_update(s0, n, c->side[k - 1]))) return rc;
         RGN_HIP(c, hipEventRecord(c->ev_join[k - 1], c->side[k - 1]));
         s0 += n;
     }
-    if ((rc = run_layers(c, dm, guided, sampling, cond_rows, ccond_rows, 0, first_n, s))) return rc;
+    if ((rc = run_layers(c, ev, 0, first_n, s))) return rc;
     if (own_update && (rc = step_or_update(0, first_n, s))) return rc;
-    c->skip_embed_out = false;
     for (int k = 1; k < nch; ++k) RGN_HIP(c, hipStreamWaitEvent(s, c->ev_join[k - 1], 0));
     if (fused && guided) {
         if ((rc = step_or_update(0, dm.B, s))) return rc;
@@ -681,11 +681,6 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
                                           std::to_string(c->B) + " (rgn_set_inpainting / rgn_set_condition)");
     const bool inp = c->inpaint_B > 0;
     hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = c->stream;
-    // every return, failed or not, leaves the phase flags at their default (split-bf16, no fp16)
-    struct PhaseReset {
-        rgn_ctx* c;
-        ~PhaseReset() { c->phase_x3 = true; c->phase_f16 = false; }
-    } phase_reset{c};
     RGN_HIP(c, hipSetDevice(c->cfg.device));
     int rc = build_step_table(c, eta);
     if (rc) return rc;
@@ -720,9 +715,9 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
     // index lives on the device, so one instantiated graph serves any starting index. Long ranges replay the multi-step
     // graph (graph_steps iterations per host launch; a 4-branch launch costs the host ~1 ms, as much as the GPU needs for
     // a step at B = 256), the remainder single-step graphs.
-    auto graph_for = [&](bool x3, bool f16g, int steps, hipGraphExec_t* out) -> int {
-        const uint64_t key = (uint64_t)c->B | ((uint64_t)(guided != 0) << 20) | ((uint64_t)sampler << 21) | ((uint64_t)x3 << 23) |
-                             ((uint64_t)steps << 24) | ((uint64_t)f16g << 40) | ((uint64_t)inp << 41);   // (inp: the boundary kernels' in-painting forms)
+    auto graph_for = [&](Phase ph, const EvalPlan& pl, int steps, hipGraphExec_t* out) -> int {
+        const uint64_t key = (uint64_t)c->B | ((uint64_t)(guided != 0) << 20) | ((uint64_t)sampler << 21) | ((uint64_t)ph.x3 << 23) |
+                             ((uint64_t)steps << 24) | ((uint64_t)ph.f16 << 40) | ((uint64_t)inp << 41);   // (inp: the boundary kernels' in-painting forms)
         auto it = c->graphs.find(key);
         if (it != c->graphs.end()) {
             *out = it->second;
@@ -730,12 +725,10 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
         }
         hipGraph_t graph = nullptr;
         hipGraphExec_t ge = nullptr;
-        c->phase_x3 = x3;
-        c->phase_f16 = f16g;
         RGN_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         int r = RGN_OK;
         for (int k = 0; k < steps && r == RGN_OK; ++k) {
-            r = run_eval(c, c->B, guided != 0, false, true, s);   // (its k_update also moves the device-side loop index on)
+            r = run_eval(c, c->B, guided != 0, false, true, ph, s, &pl);   // (its k_update also moves the device-side loop index on)
         }
         hipError_t e = hipStreamEndCapture(s, &graph);
         if (r) {
@@ -767,13 +760,14 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
         const bool f16 = !x3 && i < tail + n16;              // (n16 > 0 only where the plain phase is k_layers<true>)
         const int phase_end = x3 ? 0 : (f16 ? tail : tail + n16);            // first loop index behind this phase
         const int phase_left = (i - phase_end + 1) < (count - k) ? (i - phase_end + 1) : (count - k);              // steps left in this phase
-        const EvalPlan pl = plan_eval(c, dm, guided != 0, x3, true);
+        const Phase ph = eval_phase(c, Phase{x3, f16}, true);                 // (the phase as the handle's precision mode runs it)
+        const EvalPlan pl = plan_eval(c, dm, guided != 0, ph.x3, true);
         const bool fused_now = pl.step_fused;
         if (fused_now && !prev_fused) {
             if ((rc = embed_all(c, dm, s))) return rc;
             planes_f16 = false;
         }
-        if (f16 && !planes_f16) {   // the fp16-operand forms read (and rewrite) the residual-stream planes as fp16: what the embedding or the bf16 steps left there is re-encoded
+        if (ph.f16 && !planes_f16) {   // the fp16-operand forms read (and rewrite) the residual-stream planes as fp16: what the embedding or the bf16 steps left there is re-encoded
             RGN_LAUNCH(c, KC_EMBED, s, launch_bf16_to_f16(c->h_hi, (size_t)dm.Bm * dm.Tq * c->d, s));
             planes_f16 = true;
         }
@@ -783,39 +777,30 @@ int sample_range(rgn_ctx* c, int32_t sampler, int32_t guided, float eta, float* 
             // plain-bf16 phase, <= 64 tokens: ALL remaining steps of the phase in one launch - a workgroup carries its sample (guided: its
             // motion's two evaluations) through decoder stack and step boundary step after step; nothing but x, the condition rows and the
             // weights is read
-            {
-                const int M = dm.Bm * dm.Tq;
-                const bool has_cond = c->cfg.cond_mode != RGN_COND_NONE;
-                LayersArgs g{};
-                g.h = c->h_hi; g.out = c->h_hi; g.rows = M; g.Bm = dm.B;   // one workgroup per MOTION (guided: its two evaluations back to back)
-                fill_layers_args(c, g, dm, true, has_cond ? c->call_cond : nullptr, 0, f16);
-                g.steps = phase_left;
-                g.f16 = f16 ? 1 : 0;
-                if (guided) {
-                    g.scale = c->scale; g.half = dm.B * dm.Tq;
-                    g.park = reinterpret_cast<float*>(c->ffn_hi);           // (the hidden-tensor planes are idle on this path: 2B * T * ff * 2 bytes >= B * 96 KiB)
-                }
-                g.Wout = c->dp<__bf16>(f16 ? c->lin_out.fr16 : c->lin_out.fr); g.bout = c->dp<float>(c->lin_out.b); g.F = c->F; g.nb_out = (c->F + 31) / 32;
-                g.Wx = c->dp<__bf16>(f16 ? c->lin_x.fr16 : c->lin_x.fr);
-                g.c0 = f16 ? reinterpret_cast<const __bf16*>(c->c0h16) : c->c0h;
-                g.tab = c->d_tab; g.d_stepw = c->d_step; g.sp = c->d_sp;
-                g.B = dm.B; g.s0 = 0; g.no_quads = c->step_no_quads;
-                RGN_LAUNCH(c, KC_STEPS, s, launch_layers(g, s, inp));
-                k += phase_left;
-                continue;
+            const bool has_cond = c->cfg.cond_mode != RGN_COND_NONE;
+            LayersArgs g{};
+            g.h = c->h_hi; g.out = c->h_hi; g.rows = dm.Bm * dm.Tq; g.Bm = dm.B;   // one workgroup per MOTION (guided: its two evaluations back to back)
+            fill_layers_args(c, g, dm, true, has_cond ? c->call_cond : nullptr, 0, ph.f16);
+            g.steps = phase_left;
+            if (guided) {
+                g.scale = c->scale; g.half = dm.B * dm.Tq;
+                g.park = reinterpret_cast<float*>(c->ffn_hi);           // (the hidden-tensor planes are idle on this path: 2B * T * ff * 2 bytes >= B * 96 KiB)
             }
+            put_boundary(g, boundary_wts(c, ph.f16), 0, c->d);
+            g.tab = c->d_tab; g.d_stepw = c->d_step; g.sp = c->d_sp;
+            g.B = dm.B; g.s0 = 0; g.no_quads = c->step_no_quads;
+            RGN_LAUNCH(c, KC_STEPS, s, launch_layers(g, s, inp));
+            k += phase_left;
+            continue;
         }
         if (graphs) {
             const int steps = (multi > 1 && phase_left >= multi) ? multi : 1;
             hipGraphExec_t ge = nullptr;
-            if ((rc = graph_for(x3, f16, steps, &ge))) return rc;
+            if ((rc = graph_for(ph, pl, steps, &ge))) return rc;
             RGN_HIP(c, hipGraphLaunch(ge, s));
             k += steps;
         } else {
-            c->phase_x3 = x3;
-            c->phase_f16 = f16;
-            rc = run_eval(c, c->B, guided != 0, false, true, s);
-            if (rc) return rc;
+            if ((rc = run_eval(c, c->B, guided != 0, false, true, ph, s, &pl))) return rc;
             k += 1;
         }
     }
@@ -829,7 +814,7 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     if (!c->finalized) return c->fail(RGN_ERR_STATE, "rgn_plan_query: weights not finalized");
     if (B <= 0 || B > c->cfg.max_batch) return c->fail(RGN_ERR_INVALID_ARG, "rgn_plan_query: B outside (0, max_batch]");
     const Dims dm = make_dims(c, B, guided != 0);
-    const bool x3 = eval_x3_phase(c, split_phase != 0);
+    const bool x3 = eval_x3(split_phase != 0, c->cfg.precision);
     const EvalPlan pl = plan_eval(c, dm, guided != 0, x3, true);
     const bool enc = c->enc != 0;   // (encoder handles: the full-attention / encoder-tail instantiations)
     // SURVEY.md 8(d) accounting: MACs of ONE evaluation of the bound batch (2 B rows under guidance), full T x T attention scores; the

@@ -54,7 +54,7 @@ template <bool X3, bool F16 = false, bool CAUSAL = true>
 __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnArgs& g, char* smem, const float* bias_h, int hd, int hslot,
                                              int wm, int wn, int nsamp, int b0, int lane, int tid) {
     static_assert(!(X3 && F16), "the split form is bf16 (hi, lo) pairs");
-    using OP = OpFmt<F16>;                // plain form: bf16 or fp16 operands (rgn_internal.h)
+    using OP = OpFmt<F16>;                // plain form: bf16 or fp16 operands (rgn_device.h)
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;
@@ -449,7 +449,7 @@ constexpr int QR_ABUF = QR_NS * 48 * 1024;
 constexpr int QR_LDS = QR_ABUF + 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
 template <bool F16 = false, bool CAUSAL = true>
 __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
-    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): input plane, weight plane, q / k / v / p, output plane
+    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): input plane, weight plane, q / k / v / p, output plane
     using op8 = typename OP::v8;
     constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -48,7 +48,7 @@ void ql_prof_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_
 
 template <bool F16>
 __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
-    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): input plane, weight plane, q / k / v slabs, p, output plane
+    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): input plane, weight plane, q / k / v slabs, p, output plane
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                     st[i] = ok ? st[i] : -INFINITY;
                     mt = fmaxf(mt, st[i]);
                 }
-                mt = half_max(mt);                                    // (one v_permlane32_swap instead of a ds_bpermute round trip: rgn_internal.h)
+                mt = half_max(mt);                                    // (one v_permlane32_swap instead of a ds_bpermute round trip: rgn_device.h)
                 const float m_new = fmaxf(fmaxf(m_run, mt), -1e30f);   // (a unit with no valid key at all - rows beyond Tq only - stays finite)
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * qs2);   // (first tile: exp2(-inf) = 0)
                 const float nm = -m_new * qs2;

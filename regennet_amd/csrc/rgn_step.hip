@@ -50,7 +50,7 @@ static_assert(ST_BM * ST_XLD * 4 <= ST_XIMG && 16 * 4096 <= ST_XIMG && 2 * 65536
 
 template <int NKX, bool GUIDED, bool F16 = false, bool INPAINT = false>
 __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
-    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_internal.h): h planes in and out, Wout / Wx, the x' image, c0
+    using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): h planes in and out, Wout / Wx, the x' image, c0
     using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;

@@ -149,6 +149,33 @@ def test_graph_replay_equals_eager(golden, precision):
     assert torch.equal(a, b) and torch.equal(b, c)
 
 
+@pytest.mark.parametrize("engine", ["throughput", "small-batch"])
+def test_the_phase_of_an_evaluation_does_not_leak_between_calls(engine):
+    """The arithmetic of an evaluation (split-bf16 | plain, fp16 operands) is an argument of the dispatch, not state a call leaves behind on
+    the handle: rgn_denoise is always split-bf16 under the precision schedule, so after an eager sampling loop and after a graph-replayed one
+    (10-step DDPM, 8 plain + 2 split steps) it must return, bit for bit, what a fresh engine that never sampled returns; and the two loops
+    must agree bit for bit on the same noise tape."""
+    from regennet_amd import synth
+    cfg = synth.get_config("tiny")
+    sd = synth.make_state_dict(cfg, seed=0)
+    B = 2
+    shape = (B, cfg["njoints"], cfg["nfeats"], cfg["num_frames"])
+    y = y_to_device({"cmotion": synth.make_cmotion(cfg, B), "action": synth.make_actions(cfg, B)})
+    x = torch.from_numpy(synth.make_noise_tape(cfg, B, 1, seed=3)[0]).cuda()
+    t = torch.tensor([7, 2], dtype=torch.long, device="cuda")
+    kw = dict(clip_denoised=False, model_kwargs={"y": y}, noise_tape=torch.from_numpy(synth.make_noise_tape(cfg, B, 10, seed=10)))
+    build = lambda: build_hip(cfg, sd, resp="10", precision="bf16_x3tail/" + engine, x3_tail=2)
+    fresh, _ = build()
+    want = fresh(x, t, y=y).clone()
+    model, diffusion = build()
+    eager = diffusion.p_sample_loop(model, shape, use_graph=False, **kw).clone()
+    after_eager = model(x, t, y=y).clone()
+    replay = diffusion.p_sample_loop(model, shape, use_graph=True, **kw).clone()
+    after_replay = model(x, t, y=y).clone()
+    assert torch.equal(after_eager, want) and torch.equal(after_replay, want)
+    assert torch.equal(eager, replay)
+
+
 def test_precision_schedule_auto_calibration_and_conservative_defaults():
     """The schedule's validity depends on how strongly a checkpoint damps early-step rounding (depth, emb_trans_dec,
     guidance: DESIGN.md §6). (1) `x3_tail="auto"` measures it on the checkpoint itself: a shallow guided model gets a longer

@@ -69,8 +69,7 @@ int main(int argc, char** argv) {
             q.Bm = Bm; q.Kp = d; q.d = d; q.H = H; q.Tq = Tq; q.qscale = ga.qscale; q.Bm_eval = Bm;
             CK(launch_qkv_attn(q, false, nullptr));
             MlpArgs m{};
-            m.att = att; m.h = h; m.out = h; m.rows = M; m.M = M; m.Wo = t.Wo; m.W1 = t.W1; m.W2 = t.W2; m.bo = t.bo; m.bf1 = t.bf1; m.bf2 = t.bf2;
-            m.g1 = t.g1; m.b1 = t.b1; m.g2 = t.g2; m.b2 = t.b2; m.g3 = t.g3; m.b3 = t.b3;
+            m.att = att; m.h = h; m.out = h; m.rows = M; m.M = M; m.w = t;
             m.pervec = ga.pervec + (size_t)l * d; m.ldper = Ld; m.stepvec = ga.stepvec + (size_t)l * d; m.ldstep = Ld; m.d_step = ds; m.Tq = Tq;
             CK(launch_mlp(m, nullptr));
         }

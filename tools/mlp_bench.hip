@@ -62,10 +62,10 @@ int main(int argc, char** argv) {
     MlpArgs g{};
     g.att = act(att, 1.f); g.h = act(h, 1.f); g.rows = M; g.M = M;
     { void* p; CK(hipMalloc(&p, (size_t)M * d * 2)); CK(hipMemset(p, 0, (size_t)M * d * 2)); g.out = (__bf16*)p; }
-    g.Wo = wgt(Wo, d, d, 1.f); g.W1 = wgt(W1, ff, d, 1.2f); g.W2 = wgt(W2, d, ff, 1.2f);
-    g.bo = vecf(bo, d, 0.f, 0.05f); g.bf1 = vecf(bf1, ff, 0.f, 0.05f); g.bf2 = vecf(bf2, d, 0.f, 0.05f);
-    g.g1 = vecf(g1, d, 1.f, .1f); g.b1 = vecf(b1, d, 0.f, .1f); g.g2 = vecf(g2, d, 1.f, .1f); g.b2 = vecf(b2, d, 0.f, .1f);
-    g.g3 = vecf(g3, d, 1.f, .1f); g.b3 = vecf(b3, d, 0.f, .1f);
+    g.w.Wo = wgt(Wo, d, d, 1.f); g.w.W1 = wgt(W1, ff, d, 1.2f); g.w.W2 = wgt(W2, d, ff, 1.2f);
+    g.w.bo = vecf(bo, d, 0.f, 0.05f); g.w.bf1 = vecf(bf1, ff, 0.f, 0.05f); g.w.bf2 = vecf(bf2, d, 0.f, 0.05f);
+    g.w.g1 = vecf(g1, d, 1.f, .1f); g.w.b1 = vecf(b1, d, 0.f, .1f); g.w.g2 = vecf(g2, d, 1.f, .1f); g.w.b2 = vecf(b2, d, 0.f, .1f);
+    g.w.g3 = vecf(g3, d, 1.f, .1f); g.w.b3 = vecf(b3, d, 0.f, .1f);
     const int nsamp = (M + Tq - 1) / Tq;
     g.pervec = vecf(per, (size_t)nsamp * d, 0.f, 0.5f); g.ldper = d; g.stepvec = vecf(stepv, d, 0.f, 0.5f); g.ldstep = d; g.Tq = Tq;
     int* ds; CK(hipMalloc(&ds, 4)); CK(hipMemset(ds, 0, 4)); g.d_step = ds;
