@@ -188,7 +188,8 @@ RGN_API int rgn_set_const_noise(rgn_handle h, int32_t on);
 RGN_API int rgn_set_inpainting(rgn_handle h, int32_t B, const uint8_t* mask_dev, const float* motion_dev, void* stream);
 
 /* Evaluations of at most `rows` token rows (motions x tokens, doubled under guidance) run the small-batch engine:
- * column-split GEMMs that spread one row tile over 16-48 workgroups (rgn_sb.hip; d = 512 models, bf16 modes), the
+ * column-split GEMMs that spread one row tile over 16-48 workgroups (rgn_sb.hip; d = 512 models with ff_size a multiple of 32 and >= 512, heads of 16 ... 128, <= 160 tokens, bf16 modes - every
+ * other model runs the throughput kernels at every batch size), the
  * latency-bound regime of the reference CLI's own default batch (sample/cgenerate.py:109-135, BASELINE configs[0]).
  * Larger evaluations run the row-complete throughput kernels. -1 restores the default (640, or REGENNET_SB_ROWS);
  * 0 switches the small-batch engine off. Results of the two engines agree within the precision mode's error (both are

@@ -102,7 +102,8 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const float c0 = odd ? got : mine, c1 = odd ? mine : got;
                         const int ii = odd ? i + 8 : i;
                         const unsigned m = (unsigned)(mb + (ii & 3) + 8 * (ii >> 2));
-                        const unsigned bb = __umulhi(m, g.tq_magic), tt = m - bb * (unsigned)g.Tq;   // m / Tq, m % Tq (exact: m*Tq < 2^32)
+                        // m / Tq, m % Tq (exact: m*Tq < 2^32); Tq = 1 has no 32-bit magic (floor(2^32 / 1) + 1 wraps to 1): the quotient is m itself
+                        const unsigned bb = g.Tq == 1 ? m : __umulhi(m, g.tq_magic), tt = m - bb * (unsigned)g.Tq;
                         const size_t o = (((size_t)bb * g.H + hd) * g.Tqp + tt) * g.dh + (c & ~1);
                         const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
                         bf16x2 hv = {h0, h1};

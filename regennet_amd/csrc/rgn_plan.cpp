@@ -849,10 +849,15 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
                 l2[KC_LAYERS] = (double)dm.Bm * wl * 2.0;
             } else {
                 switch (pl.attn) {
-                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L;
-                    kn[KC_QKV] = x3 ? (c->qkv_x3_dma || c->d != 512 ? (enc ? "k_qkv_attn<full>" : "k_qkv_attn") : (enc ? "k_qkv_attn_rs_x3<full>" : "k_qkv_attn_rs_x3"))
-                                    : (enc ? "k_qkv_attn_rs<full>" : "k_qkv_attn_rs");
+                case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; {
+                    // (launch_qkv_attn's own rule: the register-streamed forms are d = 512 instantiations that read fragment-ordered weights; every
+                    //  other width - and a mode that packs no fragment planes - runs the direct-to-LDS k_qkv_attn in both arithmetics)
+                    const bool fr0 = c->L > 0 && c->layers[0].qkv.fr != 0;
+                    const bool rs = c->d == 512 && fr0 && (!x3 || (c->layers[0].qkv.fr_lo != 0 && !c->qkv_x3_dma));
+                    kn[KC_QKV] = !rs ? (enc ? "k_qkv_attn<full>" : "k_qkv_attn")
+                                     : x3 ? (enc ? "k_qkv_attn_rs_x3<full>" : "k_qkv_attn_rs_x3") : (enc ? "k_qkv_attn_rs<full>" : "k_qkv_attn_rs");
                     break;
+                }
                 case AF_QKV_LONG: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; kn[KC_QKV] = "k_qkv_attn_long"; break;
                 case AF_ROWGEMM_ATTN: mac[KC_ROWACT] += qkv; n[KC_ROWACT] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;
                 case AF_GEMM_ATTN: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;

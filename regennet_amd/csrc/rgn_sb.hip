@@ -345,7 +345,10 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
     }
 }
 
-bool sb_supported(int d, int ff, int dh) { return d == SB_D && ff % 32 == 0 && dh % 4 == 0; }
+// ff >= d: a PRE 1 launch leaves the normalised rows (the residual stream, g.xout) to the workgroups whose column block holds them, so its grid must span
+// all d = 512 columns - in_proj (N = 3 d) does, linear1 (N = ff) only from ff = 512 on; a narrower hidden layer left columns ff .. 511 of the
+// stream unwritten (errors of O(1): tests/test_geometry_gpu.py). Such models run the throughput kernels at every batch size.
+bool sb_supported(int d, int ff, int dh) { return d == SB_D && ff % 32 == 0 && ff >= SB_D && dh % 4 == 0; }
 
 template <int PRE, int POST, bool X3, int NP, int NC>
 static hipError_t sb_launch(const SbArgs& g, hipStream_t s, bool cfg) {
@@ -391,7 +394,7 @@ hipError_t configure_sb() {
     return hipSuccess;
 }
 hipError_t launch_sb_gemm(const SbArgs& g, int pre, int post, bool x3, hipStream_t s) {
-    if (g.M <= 0 || g.N <= 0 || (g.Kp & 31) || (pre == 1 && g.Kp != SB_D) || (post != 0 && (g.N & 31))) return hipErrorInvalidValue;
+    if (g.M <= 0 || g.N <= 0 || (g.Kp & 31) || (pre == 1 && g.Kp != SB_D) || (post != 0 && (g.N & 31)) || (pre == 1 && g.xout && g.N < SB_D)) return hipErrorInvalidValue;   // (xout: see sb_supported)
     return sb_dispatch(g, pre, post, x3, s, false);
 }
 

@@ -201,10 +201,12 @@ def _random_rot6d(rng, shape):
 
 
 def make_cmotion(cfg, batch, seed=1):
-    """Actor motion [B, njoints, 6, T] fp32: rot6d joints + last row = translation [tx,ty,tz,0,0,0]."""
+    """Actor motion [B, njoints, 6, T] fp32: rot6d joints + last row = translation [tx,ty,tz,0,0,0].
+    Other feature layouts (nfeats != 6, e.g. a 263 x 1 feature vector): [B, njoints, nfeats, T] ~ N(0, 1)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     J, T = cfg["njoints"], cfg["num_frames"]
-    assert cfg["nfeats"] == 6
+    if cfg["nfeats"] != 6:
+        return rng.standard_normal((batch, J, cfg["nfeats"], T)).astype(np.float32)
     rot = _random_rot6d(rng, (batch, T, J - 1))                   # [B,T,J-1,6]
     tr = np.zeros((batch, T, 1, 6))
     tr[..., 0, :3] = rng.uniform(-1, 1, (batch, T, 3))
@@ -286,7 +288,7 @@ def build_model(cfg, sd, resp="", precision=None, device="cuda:0", noise_schedul
                  num_layers=cfg["layers"], num_heads=cfg["num_heads"], dropout=0.1, activation="gelu",
                  data_rep="rot6d", dataset=cfg["dataset"], arch=cfg.get("arch", "online"), cm_mode=cfg["cm_mode"], body_model="smplx",
                  cond_mode=cfg["cond_mode"], cond_mask_prob=cfg["cond_mask_prob"], action_emb="tensor",
-                 emb_trans_dec=cfg.get("emb_trans_dec", False), wo_pos_emb=cfg.get("wo_pos_emb", False),
+                 emb_trans_dec=cfg.get("emb_trans_dec", False), wo_pos_emb=cfg.get("wo_pos_emb", False), clip_dim=cfg.get("clip_dim", 512),
                  x3_tail=x3_tail, engine_options=engine_options, f16_steps=f16_steps, **kw)
     load_model_wo_clip(model, {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     model.x3_tail = x3_tail

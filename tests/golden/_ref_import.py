@@ -73,7 +73,7 @@ def build_reference(cfg, state_dict, timestep_respacing=""):
             data_rep="rot6d", dataset=cfg["dataset"], arch="online", cm_mode=cfg["cm_mode"],
             body_model="smplx", cond_mode=cfg["cond_mode"], cond_mask_prob=cfg["cond_mask_prob"],
             action_emb="tensor", emb_trans_dec=cfg.get("emb_trans_dec", False),
-            wo_pos_emb=cfg.get("wo_pos_emb", False),
+            wo_pos_emb=cfg.get("wo_pos_emb", False), clip_dim=cfg.get("clip_dim", 512),
         )
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in state_dict.items()}
     missing, unexpected = model.load_state_dict(sd, strict=False)

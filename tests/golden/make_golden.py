@@ -308,6 +308,14 @@ JOBS = {
     "tiny_etd_fwd": lambda: gen_forward("tiny_etd_fwd", "tiny", 2, [10, 999], emb_trans_dec=True),
     "tiny_wope_fwd": lambda: gen_forward("tiny_wope_fwd", "tiny", 2, [7, 640], wo_pos_emb=True),
     "tiny_text_fwd_cfg": lambda: gen_forward("tiny_text_fwd_cfg", "tiny_text", 3, [0, 321], guided=True),
+    # model geometries off the presets (forward only, 1 layer, 12 frames): one head of 128, heads of 8, an ff width that is no multiple
+    # of 32, feature layouts other than joints x 6, a text embedding that is not 512 wide
+    "geo_d128_h1_fwd": lambda: gen_forward("geo_d128_h1_fwd", "tiny", 2, [0, 650], latent_dim=128, num_heads=1, layers=1, num_frames=12),
+    "geo_d64_h8_fwd": lambda: gen_forward("geo_d64_h8_fwd", "tiny", 2, [0, 650], num_heads=8, layers=1, num_frames=12),
+    "geo_d256_h2_ff100_fwd": lambda: gen_forward("geo_d256_h2_ff100_fwd", "tiny", 2, [0, 650], latent_dim=256, num_heads=2, ff_size=100, layers=1, num_frames=12),
+    "geo_f88x4_fwd": lambda: gen_forward("geo_f88x4_fwd", "tiny", 2, [0, 650], njoints=88, nfeats=4, layers=1, num_frames=12),
+    "geo_f263x1_fwd": lambda: gen_forward("geo_f263x1_fwd", "tiny", 2, [0, 650], njoints=263, nfeats=1, layers=1, num_frames=12),
+    "geo_text_clip100_fwd_cfg": lambda: gen_forward("geo_text_clip100_fwd_cfg", "tiny_text", 2, [0, 321], guided=True, clip_dim=100, layers=1),
     "tiny_ddpm10": lambda: gen_loop("tiny_ddpm10", "tiny", 2, "10", "ddpm", keep_trace=True),
     "tiny_ddim10_cfg": lambda: gen_loop("tiny_ddim10_cfg", "tiny", 2, "ddim10", "ddim", guided=True, keep_trace=True),
     "tiny_etd_ddim10_cfg": lambda: gen_loop("tiny_etd_ddim10_cfg", "tiny", 2, "ddim10", "ddim", guided=True, emb_trans_dec=True),

@@ -92,3 +92,46 @@ def test_no_gpu_means_loud_failure_not_fallback():
         model(torch.zeros(1, 5, 6, 8), torch.zeros(1, dtype=torch.long), y=y)
     with pytest.raises(TypeError):
         diffusion.p_sample_loop(lambda *a, **k: None, (1, 5, 6, 8), model_kwargs={"y": y})
+
+
+def _create(**over):
+    """rgn_create on an ntu_action config with overrides: (status, error text). A handle that was made (on a machine with a GPU) is destroyed."""
+    from regennet_amd import _lib, synth
+    lib = _lib.load()
+    c = synth.get_config("ntu_action", **over)
+    cfg = _lib.RgnConfig(njoints=c["njoints"], nfeats=c["nfeats"], num_frames=c["num_frames"], latent_dim=c["latent_dim"], ff_size=c["ff_size"],
+                         num_heads=c["num_heads"], num_layers=c["layers"], cm_mode=_lib.CM[c["cm_mode"]], cond_mode=_lib.COND[c["cond_mode"]],
+                         num_actions=c["num_actions"], clip_dim=c.get("clip_dim", 512), emb_trans_dec=int(c.get("emb_trans_dec", False)), wo_pos_emb=0,
+                         max_batch=3, precision=_lib.PREC["bf16_x3tail"], device=0, arch=0)
+    h = ctypes.c_void_p()
+    rc = lib.rgn_create(ctypes.byref(cfg), ctypes.byref(h))
+    err = (lib.rgn_last_error(None) or b"").decode()
+    if rc == 0:
+        assert lib.rgn_destroy(h) == 0
+    return rc, err
+
+
+def test_rgn_create_refuses_the_geometries_no_kernel_serves():
+    """The shape checks of rgn_create run before the device is touched, so they answer the same with and without a GPU."""
+    rc, err = _create(latent_dim=1024, num_heads=4)                       # heads of 256
+    assert rc == -7 and "head dim > 128" in err, (rc, err)
+    rc, err = _create(latent_dim=512, num_heads=3)
+    assert rc == -1 and "latent_dim % num_heads" in err, (rc, err)
+    rc, err = _create(latent_dim=64, num_heads=3)
+    assert rc == -1 and "latent_dim % num_heads" in err, (rc, err)
+    rc, err = _create(latent_dim=2048, num_heads=16)
+    assert rc == -7 and "latent_dim" in err, (rc, err)
+    rc, err = _create(num_frames=4097)
+    assert rc == -7 and "4096 frames" in err, (rc, err)
+    rc, err = _create(cond_mode="text", clip_dim=0)
+    assert rc == -1 and "clip_dim" in err, (rc, err)
+
+
+def test_rgn_create_accepts_every_geometry_of_the_gpu_case_list():
+    """... and none of the geometries tests/test_geometry_gpu.py runs is refused at that stage: without a GPU the call gets as far as the device
+    (RGN_ERR_HIP, "no HIP device visible"), with one it returns a handle."""
+    from tests.geometry_cases import ACCEPTED
+    assert len(ACCEPTED) > 40
+    for over in ACCEPTED:
+        rc, err = _create(**over)
+        assert rc == 0 or (rc == -6 and "no HIP device" in err), (over, rc, err)

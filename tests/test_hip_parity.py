@@ -282,7 +282,7 @@ def test_oracle_parity_across_kernel_dispatch_paths(over, engine):
     """The plain-bf16 phase picks its kernels by shape: d = 512 / ff = 1024 -> k_mlp; d = 512 with another ff -> k_rowgemm
     (ff = 512) or the generic tiles (ff = 2048: activation image too large); other widths -> generic tiles. Each path against
     the oracle under the default precision schedule (2 layers, 50 steps: 18 plain-bf16 + 32 split-bf16) and with guidance.
-    engine "small-batch": the same shapes through the column-split kernels (any ff % 32 == 0; d = 512 only)."""
+    engine "small-batch": the same shapes through the column-split kernels (ff % 32 == 0 from 512 on; d = 512 only)."""
     if engine == "small-batch" and over.get("latent_dim", 512) != 512:
         pytest.skip("small-batch engine: d = 512 only")
     from oracle import regennet_oracle as orc

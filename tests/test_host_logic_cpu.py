@@ -193,3 +193,18 @@ def test_frechet_distance_matches_reference(golden, case):
     got = float(calculate_fid(s1, s2))
     assert abs(got - ref) <= 1e-6 * max(1.0, abs(ref)), (got, ref)
     assert abs(float(calculate_fid(s1, s1))) < 1e-6 and abs(float(g[f"fid_same_{case}"])) < 1e-3
+
+
+def test_short_sequence_boundaries_follow_the_kernels_tile_constants():
+    """tests/geometry_cases.py derives the sequence lengths on each side of mlp_supported / mlp_x3_supported from M2::NSAMP / MX::NSAMP: the
+    constants it carries are the kernels', and the predicates still have the form they were derived from."""
+    import os
+    import re
+    from tests import geometry_cases as gc
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "regennet_amd", "csrc")
+    m2, mx = open(os.path.join(csrc, "rgn_mlp2.hip")).read(), open(os.path.join(csrc, "rgn_mlp_x3.hip")).read()
+    assert int(re.search(r"static constexpr int NSAMP = (\d+);", m2).group(1)) == gc.M2_NSAMP
+    assert int(re.search(r"static constexpr int NSAMP = (\d+);", mx).group(1)) == gc.MX_NSAMP
+    assert "63 / Tq + 2 <= M2::NSAMP" in m2 and "31 / Tq + 2 <= MX::NSAMP" in mx
+    assert (gc.TQ_MLP, gc.TQ_MLP_X3) == (22, 32)
+    assert gc.SHORT_T == [1, 2, 7, 8, 21, 22, 31, 32]

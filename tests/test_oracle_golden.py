@@ -8,8 +8,11 @@ from regennet_amd import synth
 from tests.helpers import autoreg_inputs, fixture_inputs, fixture_opts
 
 FWD = ["tiny_fwd", "tiny_fwd_cfg", "tiny_add_fwd", "tiny_etd_fwd", "tiny_wope_fwd", "tiny_text_fwd_cfg", "ntu_fwd",
-       "ntu_action_fwd_cfg", "chi3d_fwd"]
-LOOPS = ["tiny_ddpm10", "tiny_ddim10_cfg", "tiny_add_ddpm1000", "tiny_text_ddim20_cfg", "tiny_etd_ddim10_cfg",
+       "ntu_action_fwd_cfg", "chi3d_fwd",
+       # geometries off the presets (tests/test_geometry_gpu.py trusts the oracle there): one head of 128, heads of 8, ff = 100 at two heads,
+       # 88 x 4 and 263 x 1 features, a 100-wide text embedding - each recorded from the reference (make_golden.py "geo_*")
+       "geo_d128_h1_fwd", "geo_d64_h8_fwd", "geo_d256_h2_ff100_fwd", "geo_f88x4_fwd", "geo_f263x1_fwd", "geo_text_clip100_fwd_cfg"]
+LOOPS =["tiny_ddpm10", "tiny_ddim10_cfg", "tiny_add_ddpm1000", "tiny_text_ddim20_cfg", "tiny_etd_ddim10_cfg",
          "tiny_wope_ddpm10", "ntu_ddpm50", "ntu_add_etd_ddpm20", "chi3d_ddpm20", "chi3d_ddim20_cfg",
          "ntu_eval_ddim5", "ntu_eval_5", "ntu_action_eval_ddim5"]   # (the last three: the reference's shipped evaluation setting, README.md:134-137)
 
