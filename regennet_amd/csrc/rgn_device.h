@@ -1,6 +1,7 @@
-// Device primitives shared by the kernel sources (every .hip under csrc/): vector types, address spaces, counted waits, DPP and shuffle
+// Primitives shared by the kernel sources (every .hip under csrc/): vector types, address spaces, counted waits, DPP and shuffle
 // reductions, the compile-time loop, the split-bf16 conversion, the GELU / erf forms, the 16-bit operand format of the plain phase (OpFmt), the
-// XCD-affine workgroup order and the half-wave exchange. Device code only; every helper has internal linkage.
+// XCD-affine workgroup order and the half-wave exchange. All of that is device code. One host-only section closes the file: dispatch_bools, which
+// the launchers at the foot of the .hip sources use to pick a template form. Every helper has internal linkage.
 // Forms whose arithmetic differs (the GELU / erf variants, the DPP and the shuffle wave sums) are kept apart and named for what they compute.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -203,6 +204,17 @@ __device__ __forceinline__ float half_sum(float v) {
     asm volatile("" : "+v"(o));
     half_swap(v, o);
     return v + o;
+}
+
+// =================================================== HOST ONLY ===================================================
+// ---- run-time flags -> template arguments, for launch_* / configure_*. dispatch_bools(f, a, b, ...) returns f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...):
+// a launcher and its configure_* name a kernel's forms once, as k<decltype(A)::value, ...> inside f, instead of an if ladder each
+template <class F>
+auto dispatch_bools(F&& f) { return f(); }
+template <class F, class... Rest>
+auto dispatch_bools(F&& f, bool b, Rest... rest) {
+    auto bind = [&](auto B) { return dispatch_bools([&](auto... bs) { return f(B, bs...); }, rest...); };
+    return b ? bind(std::true_type{}) : bind(std::false_type{});
 }
 
 }  // namespace

@@ -9,7 +9,7 @@
 // Reference arithmetic replaced (file:line in the upstream repo) is cited per kernel.
 #include "rgn_internal.h"
 #include "rgn_device.h"
-#include "rgn_philox.h"
+#include "rgn_sampler.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -818,14 +818,11 @@ hipError_t launch_pack_x(const float* x, float* xin, Planes xp, int copies, cons
     return hipGetLastError();
 }
 
-// The element counter is (feature * 4096 + frame), not the flat index: the draw for (sample, step, feature, frame) does
-// not depend on the sequence length, so a run truncated to the first frames (auto_regressive evaluation: frame f only
-// needs tokens 0..f of a causal decoder) sees the same noise as the full-length run.
 __global__ void k_randn(float* __restrict__ x, int B, int FT, int T, unsigned long long seed, unsigned long long off, uint32_t stream) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * FT) return;
     const int b = (int)(idx / FT), e = (int)(idx - (size_t)b * FT);
-    x[idx] = philox_normal(seed, off + b, stream, (uint32_t)((e / T) * 4096 + e % T));   // stream 0xFFFFFFFF = x_T draw, k = loop index k's noise
+    x[idx] = philox_normal(seed, off + b, stream, noise_elem(e / T, e % T));   // stream 0xFFFFFFFF = x_T draw, k = loop index k's noise
 }
 hipError_t launch_randn(float* x, int B, int FT, int T, unsigned long long seed, unsigned long long off, uint32_t stream, hipStream_t s) {
     const size_t n = (size_t)B * FT;
@@ -833,17 +830,13 @@ hipError_t launch_randn(float* x, int B, int FT, int T, unsigned long long seed,
     return hipGetLastError();
 }
 
-// Sampler update, one 32(f) x 32(t) tile per block.
-//   x0 = x0_c                                   (plain)          OutputProcess permute cmdm.py:353-354
-//   x0 = x0_u + scale_b * (x0_c - x0_u)         (guided)         cfg_sampler.py:31
-//   DDPM  x' = (c1*x0 + c2*x) + sig*eps                          gaussian_diffusion.py:265-276,559
-//   DDIM  e = (sr*x - x0)/srm1 ; x' = (x0*ca + cb*e) + sig*eps   gaussian_diffusion.py:419-423,785-793
-// Products and sums are rounded separately (no FMA contraction) to follow the reference's op order.
+// Sampler update, one 32(f) x 32(t) tile per block: x0 = x0_c (OutputProcess permute cmdm.py:353-354) or the guided combination of x0_c and
+// x0_u, then the step of rgn_sampler.h (guidance, in-painting select, clamp, noise, DDPM / DDIM update).
 // Writes the new state in boundary layout [B,F,T] and token-major xin for the next step's GEMM.
 // In sampling mode the LAST block to finish (of all k_update launches of the step: the chains' launches together cover the
 // B samples once) also moves the device-side loop index on: *d_step -= 1 (ticket counters behind d_step[4]). Every block read *d_step before it took its
 // ticket, and every other reader of *d_step (the layer kernels of a chain) precedes that chain's k_update in stream order.
-// INPAINT (rgn_set_inpainting; gaussian_diffusion.py:319-323): x0 = mask ? motion : x0 between the guidance combination and the clamp.
+// INPAINT: the forms that read the bound mask and motion (rgn_set_inpainting).
 template <bool INPAINT>
 __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok, const float* __restrict__ scale,
                                                  const StepCoef* __restrict__ tab, int* d_step,
@@ -872,38 +865,24 @@ __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok,
     if (sp.mode == 0) k = tab[step];
     const size_t FT = (size_t)dm.F * dm.T;
     const float sc = sp.guided ? scale[b] : 0.f;
+    const int bn = noise_motion(sp, b);
     for (int i = ty; i < 32; i += 8) {   // boundary layout, coalesced along t
         const int f = f0 + i, t = t0 + tx;
         float nv = 0.f;
         if (f < dm.F && t < dm.T) {
-            float x0 = tc[tx][i];
-            if (sp.guided) {
-                const float u = tu[tx][i];
-                x0 = __fadd_rn(u, __fmul_rn(sc, __fsub_rn(x0, u)));
-            }
-            if constexpr (INPAINT) {
-                const size_t oi = (size_t)b * FT + (size_t)f * dm.T + t;
-                if (sp.inpaint_mask && sp.inpaint_mask[oi]) x0 = sp.inpaint_motion[oi];
-            }
-            if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
             const size_t o = (size_t)b * FT + (size_t)f * dm.T + t;
+            unsigned char im = 0;
+            float iv = 0.f;
+            if constexpr (INPAINT) {
+                im = sp.inpaint_mask && sp.inpaint_mask[o];
+                if (im) iv = sp.inpaint_motion[o];
+            }
+            float x0 = tc[tx][i];
+            if (sp.guided) x0 = guide(x0, tu[tx][i], sc);
+            x0 = pred_x0<INPAINT>(x0, im, iv, sp.clip);
             if (sp.x0_out) sp.x0_out[o] = x0;
             if (sp.mode == 0) {
-                const float xv = sp.x[o];
-                float eps;
-                const int bn = sp.const_noise ? 0 : b;              // const_noise: motion 0's draw for every motion (gaussian_diffusion.py:546-547)
-                if (sp.noise)
-                    eps = sp.noise[(size_t)(sp.first_index - step) * dm.B * FT + (size_t)bn * FT + (size_t)f * dm.T + t];
-                else
-                    eps = philox_normal(sp.seed, sp.sample_offset + bn, (uint32_t)step, (uint32_t)(f * 4096 + t));   // (feature, frame): independent of T
-                if (sp.sampler == 0) {
-                    const float mean = __fadd_rn(__fmul_rn(k.c1, x0), __fmul_rn(k.c2, xv));
-                    nv = __fadd_rn(mean, __fmul_rn(k.sig_ddpm, eps));
-                } else {
-                    const float e = __fdiv_rn(__fsub_rn(__fmul_rn(k.sr, xv), x0), k.srm1);
-                    const float mean = __fadd_rn(__fmul_rn(x0, k.ca), __fmul_rn(k.cb, e));
-                    nv = __fadd_rn(mean, __fmul_rn(k.sig_ddim, eps));
-                }
+                nv = sampler_next(k, sp.sampler, x0, sp.x[o], step_eps(sp, step, dm.B, FT, bn, f, dm.T, t));
                 sp.x[o] = nv;
             }
         }
@@ -922,23 +901,21 @@ __global__ __launch_bounds__(256) void k_update(const float* __restrict__ x0tok,
             }
         }
     }
-    if (threadIdx.x == 0) {   // two-level tickets (one address takes ~88 atomics per us: 5632 blocks on one counter cost 60 us)
-        int* tick = d_step + 4;                                       // [0]: samples done this step, [1 + b]: blocks of sample b done
+    if (threadIdx.x == 0) {   // two-level tickets: [1 + b] counts the blocks of sample b, the last of them arrives at [0] for its sample
+        int* tick = d_step + 4;
         if (atomicAdd(tick + 1 + b, 1) == (int)(gridDim.x * gridDim.y) - 1) {
             tick[1 + b] = 0;
-            if (atomicAdd(tick, 1) == dm.B - 1) {
-                tick[0] = 0;
-                d_step[0] = step - 1;
-            }
+            step_ticket(tick, dm.B, d_step, step - 1);
         }
     }
 }
 hipError_t launch_update(const float* x0tok, const float* scale, const StepCoef* tab, int* d_step,
                          const SampleParams* sp, float* xin, Planes xp, const Dims& dm, int b0, int nb, hipStream_t s, bool inpaint) {
     dim3 grid((dm.T + 31) / 32, (dm.F + 31) / 32, nb);
-    if (inpaint) hipLaunchKernelGGL(k_update<true>, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
-    else hipLaunchKernelGGL(k_update<false>, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
-    return hipGetLastError();
+    return dispatch_bools([&](auto INP) {
+        hipLaunchKernelGGL(k_update<decltype(INP)::value>, grid, dim3(256), 0, s, x0tok, scale, tab, d_step, sp, xin, xp, dm, b0);
+        return hipGetLastError();
+    }, inpaint);
 }
 
 __global__ void k_advance(int* d_step) { *d_step -= 1; }

@@ -25,13 +25,13 @@
 // Weights: fragment-ordered planes streamed into register rings through buffer loads (scalar resource, compile-time offsets).
 //
 // Three instantiations: k_layers<false> - the stack of ONE evaluation (planes in, planes out); k_layers<true> - whole runs of sampler steps: after the
-// stack the step boundary of rgn_step.hip in per-sample form (output projection, sampler update of x in place - diffusion/gaussian_diffusion.py:508-560,
-// 744-794 - and the next evaluation's input embedding straight into X), looped `steps` times, the device-side loop index moved on by the last
+// stack the step boundary of rgn_step.hip in per-sample form (output projection, sampler update of x in place - the step of rgn_sampler.h -
+// and the next evaluation's input embedding straight into X), looped `steps` times, the device-side loop index moved on by the last
 // workgroup; k_layers<true, true> - the same under classifier-free guidance (model/cfg_sampler.py:22-31): a workgroup owns a MOTION and runs its
 // conditional and its unconditional evaluation back to back, the conditional x0 parked in global scratch meanwhile.
 #include "rgn_internal.h"
 #include "rgn_device.h"
-#include "rgn_philox.h"
+#include "rgn_sampler.h"
 
 #include <hip/hip_runtime.h>
 
@@ -676,9 +676,9 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
     }
     if constexpr (STEPS) {
         // ========================= step boundary, per sample (rgn_step.hip k_step<11, false>) =====================================
-        //   x0 = h . Wout^T + bout (OutputProcess, cmdm.py:353); x' = sampler(x, x0, eps) in place (gaussian_diffusion.py:508-560,
-        //   744-794; same arithmetic and Philox stream as k_update); h' = x' . Wx'^T + c0 (InputProcess / fuse / positional part hoisted
-        //   into c0, cmdm.py:201-218) -> the resident image X: the next step's layer 0 reads it without leaving the CU
+        //   x0 = h . Wout^T + bout (OutputProcess, cmdm.py:353); x' = sampler(x, x0, eps) in place (rgn_sampler.h); h' = x' . Wx'^T + c0
+        //   (InputProcess / fuse / positional part hoisted into c0, cmdm.py:201-218) -> the resident image X: the next step's layer 0 reads
+        //   it without leaving the CU
         // (lane / wave / sample ids made opaque PER ITERATION: everything below is invariant across the step loop, and hoisted out of it
         //  the ~90 addresses of the update phase alone spill hundreds of registers)
         int lane_s = lane, wave_s = wave, b_s = b;
@@ -710,11 +710,11 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
                         f32x4 v = {acc[nt][mt][4 * i4] + bb[0], acc[nt][mt][4 * i4 + 1] + bb[1], acc[nt][mt][4 * i4 + 2] + bb[2], acc[nt][mt][4 * i4 + 3] + bb[3]};
-                        if constexpr (GUIDED) {   // x0 = x0_u + scale_b (x0_c - x0_u), cfg_sampler.py:31, rounded like k_update / k_step
+                        if constexpr (GUIDED) {   // v holds the unconditional x0, the parked conditional one comes back
                             // (sc1: served by L2, past this CU's L1 - the same addresses were read a step ago and rewritten since)
                             const f32x4 cc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(park_rs, (lane_s * 4 + ((nt * 2 + mt) * 4 + i4) * 256) * 4, 0, 16));
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(v[e], __fmul_rn(gscale, __fsub_rn(cc[e] + bb[e], v[e])));
+                            for (int e = 0; e < 4; ++e) v[e] = guide(cc[e] + bb[e], v[e], gscale);
                         }
                         *reinterpret_cast<f32x4*>(tile + (32 * mt + l31_s) * LY_XLD + n) = v;
                     }
@@ -750,12 +750,12 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         __builtin_amdgcn_s_barrier();
         RGN_LYS(13)
         // ---- C: sampler update. lane = frame, the waves stride the features; Philox per quad of lanes where the quad is a run of four
-        //      frames (see rgn_step.hip), per element otherwise (bit-identical values)
+        //      frames (quad_normals), per element otherwise (bit-identical values)
         {
             const int t = lane_s;
             const bool valid = t < T;
             const size_t FT = (size_t)g.F * T;
-            const int bn = sp.const_noise ? 0 : gb;
+            const int bn = noise_motion(sp, gb);
             char* ximg = smem + LY_XIMG;
             const int q = lane_s & 3, tq = t - q;
             const bool run4 = valid && (tq & 3) == 0 && tq + 3 < T;
@@ -771,27 +771,18 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             // the four features 4 fg + {0 .. 3} of this lane's frame: one 16-byte read of the x0 tile, four x updates, ONE 8-byte store of
             // the bf16 x' run (feature 32 i2 + 4 wave + j sits in k-block i2, 16-byte chunk wave >> 1, bytes 8 (wave & 1) + 2 j of its row)
             const int ximg_lane = lane_s * 64 + ((((wave_s >> 1) ^ ((lane_s >> 2) & 3)) << 4) + 8 * (wave_s & 1));
-            // in-painting (rgn_set_inpainting; gaussian_diffusion.py:319-323): x0 = mask ? motion : x0 ahead of the clamp. Buffer loads over THIS
-            // motion's [F, T] slice: one descriptor per array, the frame as the vector offset, the feature row as a scalar offset. The descriptor is
-            // sized by the pointer (wave-uniform: nothing bound, zero records, every load returns 0) and bounds what a surplus frame or a padding
-            // feature may touch; those values are never used (update4 tests valid && 4 fg < F). This kernel sits at its 256 VGPRs, so mask and
-            // target are NOT requested in one batch like xpre (88 more live registers: 54 - 96 spilled) but LY_IPD feature groups ahead of their
-            // use, under the Philox draw of the groups in between
+            // in-painting: buffer loads over THIS motion's [F, T] slice (values of a surplus frame or a padding feature are never used: update4
+            // tests valid && 4 fg < F). This kernel sits at its 256 VGPRs, so mask and target are NOT requested in one batch like xpre (88 more
+            // live registers: 54 - 96 spilled) but LY_IPD feature groups ahead of their use, under the Philox draw of the groups in between
             constexpr int LY_IPD = GUIDED ? 1 : 2;                    // (guided: 255 VGPRs before in-painting)
             unsigned char mpre[INPAINT ? LY_NKX : 1][4];
             float ipre[INPAINT ? LY_NKX : 1][4];
-            const unsigned nrec = (INPAINT && sp.inpaint_mask) ? (unsigned)FT : 0u;
-            const __amdgpu_buffer_rsrc_t m_rs = __builtin_amdgcn_make_buffer_rsrc(INPAINT ? const_cast<uint8_t*>(sp.inpaint_mask) + (size_t)gb * FT : nullptr, 0, (int)nrec, 0x00020000);
-            const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc(INPAINT ? const_cast<float*>(sp.inpaint_motion) + (size_t)gb * FT : nullptr, 0, (int)(nrec * 4u), 0x00020000);
+            const InpaintRsrc irs = inpaint_rsrc(sp, INPAINT ? (size_t)gb * FT : 0, INPAINT ? FT : 0);
             auto inp_request = [&](auto IG) __attribute__((always_inline)) {
                 constexpr int ig = decltype(IG)::value;
                 if constexpr (INPAINT && ig < LY_NKX) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int so = (4 * (wave_s + 8 * ig) + j) * T;         // wave-uniform
-                        mpre[ig][j] = __builtin_amdgcn_raw_buffer_load_b8(m_rs, t, so, 0);
-                        ipre[ig][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(v_rs, t * 4, so * 4, 0));
-                    }
+                    for (int j = 0; j < 4; ++j) inpaint_load(irs, t, (4 * (wave_s + 8 * ig) + j) * T, mpre[ig][j], ipre[ig][j]);   // (row offset: wave-uniform)
                     asm volatile("" ::: "memory");                              // (keeps the request where it is written)
                 }
             };
@@ -805,25 +796,13 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int f = 4 * fg + j;
-                        float x0 = x04[j];
-                        if constexpr (INPAINT) x0 = mpre[i2][j] ? ipre[i2][j] : x0;
-                        if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+                        unsigned char im = 0;
+                        float iv = 0.f;
+                        if constexpr (INPAINT) { im = mpre[i2][j]; iv = ipre[i2][j]; }
+                        const float x0 = pred_x0<INPAINT>(x04[j], im, iv, sp.clip);
                         const size_t o = (size_t)gb * FT + (size_t)f * T + t;
                         if (sp.x0_out) sp.x0_out[o] = x0;
-                        float eps = eps_in[j];
-                        if (sp.noise)
-                            eps = sp.noise[(size_t)(sp.first_index - step) * g.B * FT + (size_t)bn * FT + (size_t)f * T + t];
-                        else if (!quads)
-                            eps = philox_normal(sp.seed, sp.sample_offset + bn, (uint32_t)step, (uint32_t)(f * 4096 + t));
-                        float nv;
-                        if (sp.sampler == 0) {
-                            const float mean = __fadd_rn(__fmul_rn(k.c1, x0), __fmul_rn(k.c2, xv[j]));
-                            nv = __fadd_rn(mean, __fmul_rn(k.sig_ddpm, eps));
-                        } else {
-                            const float e = __fdiv_rn(__fsub_rn(__fmul_rn(k.sr, xv[j]), x0), k.srm1);
-                            const float mean = __fadd_rn(__fmul_rn(x0, k.ca), __fmul_rn(k.cb, e));
-                            nv = __fadd_rn(mean, __fmul_rn(k.sig_ddim, eps));
-                        }
+                        const float nv = sampler_next(k, sp.sampler, x0, xv[j], quad_or_step_eps(quads, eps_in[j], sp, step, g.B, FT, bn, f, T, t));
                         sp.x[o] = nv;
                         nvb[j] = (op_t)nv;
                     }
@@ -836,30 +815,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 const int fg = wave_s + 8 * i2;
                 inp_request(std::integral_constant<int, i2 + LY_IPD>{});
                 float eps4[4] = {0.f, 0.f, 0.f, 0.f};
-                if (quads) {                                               // wave-uniform
-                    const uint32_t elem = (uint32_t)((4 * fg + q) * 4096 + tq);
-                    const unsigned long long sample = sp.sample_offset + bn;
-                    uint32_t rr4[4];
-                    philox4x32_10(elem >> 2, (uint32_t)step, (uint32_t)sample, (uint32_t)(sample >> 32), (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32), rr4);
-                    float n4[4];
-#pragma unroll
-                    for (int pair = 0; pair < 2; ++pair) box_muller(rr4[2 * pair], rr4[2 * pair + 1], n4[2 * pair], n4[2 * pair + 1]);
-                    // 4 x 4 transpose inside the quad (this lane - frame tq + q - needs, for feature 4 fg + j, element q of lane j's n4): two
-                    // butterfly stages of a conditional swap with the lane q ^ 1, then q ^ 2 (DPP quad_perm): 16 operations instead of 32
-                    auto stage = [&](float& lo_r, float& hi_r, bool bit, auto ctrl) {
-                        const float send = bit ? lo_r : hi_r;
-                        const float recv = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), decltype(ctrl)::value, 0xf, 0xf, true));
-                        lo_r = bit ? recv : lo_r;
-                        hi_r = bit ? hi_r : recv;
-                    };
-                    const bool b0 = (q & 1) != 0, b1 = (q & 2) != 0;
-                    stage(n4[0], n4[1], b0, std::integral_constant<int, 0xB1>{});   // quad_perm [1, 0, 3, 2]
-                    stage(n4[2], n4[3], b0, std::integral_constant<int, 0xB1>{});
-                    stage(n4[0], n4[2], b1, std::integral_constant<int, 0x4E>{});   // quad_perm [2, 3, 0, 1]
-                    stage(n4[1], n4[3], b1, std::integral_constant<int, 0x4E>{});
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) eps4[j] = n4[j];
-                }
+                if (quads) quad_normals(sp, step, bn, fg, q, tq, eps4);      // wave-uniform
                 update4(i2, fg, eps4, xpre[i2]);
             });
         }
@@ -933,13 +889,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         }
     }
     if constexpr (STEPS) {
-        if (tid == 0) {   // ticket: the last workgroup of the launch moves the device-side loop index on by the steps it ran
-            int* tick = g.d_stepw + 4;
-            if (atomicAdd(tick, 1) == (int)gridDim.x - 1) {
-                tick[0] = 0;
-                g.d_stepw[0] = first_step - g.steps;
-            }
-        }
+        if (tid == 0) step_ticket(g.d_stepw + 4, (int)gridDim.x, g.d_stepw, first_step - g.steps);   // the last workgroup of the launch moves the loop index on by the steps it ran
     }
 }
 
@@ -949,38 +899,33 @@ void ly_stamps_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(
 
 bool layers_supported(int d, int ff, int H, int Tq, int L) { return d == 512 && ff == 1024 && H == 4 && Tq >= 1 && Tq <= 64 && L >= 1 && L <= LY_MAXL; }
 bool layers_steps_supported(int d, int F, int Kpx) { return d == 512 && F % 4 == 0 && F <= 352 && Kpx == 32 * LY_NKX; }
-template <class K>
-static hipError_t ly_lds(K kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LY_LDS); }
+// k_layers' forms, named once: fn(kernel) for the form the flags pick. Guidance and in-painting belong to the step boundary: no STEPS == false
+// form takes them
+constexpr bool layers_form_exists(bool steps, bool guided, bool inpaint) { return steps || !(guided || inpaint); }
+template <class Fn>
+static hipError_t layers_form(bool steps, bool guided, bool f16, bool inpaint, Fn fn) {
+    return dispatch_bools([&](auto S, auto G, auto H, auto I) {
+        if constexpr (layers_form_exists(decltype(S)::value, decltype(G)::value, decltype(I)::value))
+            return fn(k_layers<decltype(S)::value, decltype(G)::value, decltype(H)::value, decltype(I)::value>);
+        else
+            return hipErrorInvalidValue;
+    }, steps, guided, f16, inpaint);
+}
 hipError_t configure_layers() {
-    hipError_t e = ly_lds(k_layers<false>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, false, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, true, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<false, false, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, false, false, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, true, false, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, false, true, true>);
-    if (e == hipSuccess) e = ly_lds(k_layers<true, true, true, true>);
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < 16 && e == hipSuccess; ++m)
+        if (layers_form_exists(m & 1, m & 2, m & 8))
+            e = layers_form(m & 1, m & 2, m & 4, m & 8, [](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LY_LDS); });
     return e;
 }
+// g.steps > 0: runs of sampler steps; g.scale then asks for guidance inside the launch (a single evaluation ignores it). inpaint: a binding
+// exists (rgn_set_inpainting)
 hipError_t launch_layers(const LayersArgs& g, hipStream_t s, bool inpaint) {
-    if (inpaint && g.steps <= 0) return hipErrorInvalidValue;
-    if (inpaint && g.scale) {   // the in-painting forms of the step boundary (a binding exists: rgn_set_inpainting)
-        if (g.f16) hipLaunchKernelGGL((k_layers<true, true, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-        else hipLaunchKernelGGL((k_layers<true, true, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    } else if (inpaint) {
-        if (g.f16) hipLaunchKernelGGL((k_layers<true, false, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-        else hipLaunchKernelGGL((k_layers<true, false, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    } else if (g.steps > 0 && g.scale) {
-        if (g.f16) hipLaunchKernelGGL((k_layers<true, true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-        else hipLaunchKernelGGL((k_layers<true, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    } else if (g.steps > 0) {
-        if (g.f16) hipLaunchKernelGGL((k_layers<true, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-        else hipLaunchKernelGGL(k_layers<true>, dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    } else if (g.f16) hipLaunchKernelGGL((k_layers<false, false, true>), dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    else hipLaunchKernelGGL(k_layers<false>, dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
-    return hipGetLastError();
+    const bool steps = g.steps > 0;
+    return layers_form(steps, steps && g.scale, g.f16 != 0, inpaint, [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(g.Bm), dim3(LY_NTH), LY_LDS, s, g);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rgn

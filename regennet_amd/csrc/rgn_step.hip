@@ -1,8 +1,7 @@
 // Step boundary of the plain-bf16 phase as ONE kernel (d = 512; GUIDED = classifier-free guidance, see below):
 //
 //   x0   = h . Wout^T + bout                       output projection of the evaluation just finished (OutputProcess, cmdm.py:353)
-//   x'   = sampler(x, x0, eps)                     p_sample / ddim_sample update in place (gaussian_diffusion.py:265-276, 508-560,
-//                                                  419-423, 744-794), same device arithmetic and Philox stream as k_update
+//   x'   = sampler(x, x0, eps)                     p_sample / ddim_sample update in place: the step of rgn_sampler.h
 //   h'   = x' . Wx'^T + c0                         input embedding of the NEXT evaluation (InputProcess / fuse / positional part
 //                                                  hoisted into c0, cmdm.py:201-218) -> residual-stream planes
 //
@@ -20,14 +19,14 @@
 //                   (the sum is rounded to bf16 twice, c0 once: plain-bf16 phase only)
 // GUIDED (cfg_sampler.py:22-31): a token's conditional / unconditional evaluations are rows m / m + half of the planes. One
 // launch over the conditional rows after the chains joined: A stages BOTH tiles (2 x 64 KiB) and runs the two output projections
-// in one pass over Wout (every weight fragment feeds both accumulator sets), B forms x0 = u + scale_b (c - u) with k_update's
-// rounding, C is unchanged, D embeds x' once and writes it to both halves with their own c0 rows.
-// INPAINT (rgn_set_inpainting; gaussian_diffusion.py:319-323): C replaces x0 by the bound motion where the bound mask is set, ahead of the clamp;
-// mask and motion are requested in one batch beside the sampler state. The launcher picks these forms only while a binding exists.
-// The last workgroup to finish (over all launches of the step) moves the device-side loop index on, like k_update.
+// in one pass over Wout (every weight fragment feeds both accumulator sets), B forms x0 = guide(c, u, scale_b),
+// C is unchanged, D embeds x' once and writes it to both halves with their own c0 rows.
+// INPAINT (rgn_set_inpainting): C reads the bound mask and motion, requested in one batch beside the sampler state. The launcher picks these
+// forms only while a binding exists.
+// The last workgroup to finish (over all launches of the step) moves the device-side loop index on (step_ticket).
 #include "rgn_internal.h"
 #include "rgn_device.h"
-#include "rgn_philox.h"
+#include "rgn_sampler.h"
 
 #include <hip/hip_runtime.h>
 
@@ -203,13 +202,10 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     f32x4 v = {acc[nt][mt][4 * i4] + b[0], acc[nt][mt][4 * i4 + 1] + b[1], acc[nt][mt][4 * i4 + 2] + b[2], acc[nt][mt][4 * i4 + 3] + b[3]};
-                    if constexpr (GUIDED) {   // x0 = x0_u + scale_b (x0_c - x0_u), cfg_sampler.py:31, rounded like k_update
+                    if constexpr (GUIDED) {
                         const float sc = scl[mt];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float u = accu[nt][mt][4 * i4 + e] + b[e];
-                            v[e] = __fadd_rn(u, __fmul_rn(sc, __fsub_rn(v[e], u)));
-                        }
+                        for (int e = 0; e < 4; ++e) v[e] = guide(v[e], accu[nt][mt][4 * i4 + e] + b[e], sc);
                     }
                     *reinterpret_cast<f32x4*>(tile + (32 * mt + l31) * ST_XLD + n) = v;
                 }
@@ -220,16 +216,14 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
     __builtin_amdgcn_s_barrier();
 
     // ---- C: sampler update. lane = row of the tile (consecutive frames of a sample), the waves stride the features.
-    //      Noise: one Philox4x32-10 call yields the four normals of frames 4j .. 4j+3 of a (sample, step, feature). When the
-    //      rows of every quad of lanes are exactly such a run (60 frames: always, but for the surplus rows of the last tile),
-    //      lane q of a quad draws feature f + q for the quad's four frames and the quad transposes (DPP): a quarter of the
-    //      Philox rounds, half of the Box-Muller work; the per-element form (bit-identical values) covers everything else.
+    //      Noise: when the rows of every quad of lanes are a run of four frames of one sample (60 frames: always, but for the surplus rows of
+    //      the last tile) the quad draws together (quad_normals); the per-element form (bit-identical values) covers everything else.
     {
         const int m = m0 + lane;
         const bool valid = m < g.M;
         const int bl = (valid ? m : g.M - 1) / g.T, t = (valid ? m : g.M - 1) - bl * g.T, b = g.s0 + bl;
         const size_t FT = (size_t)g.F * g.T;
-        const int bn = sp.const_noise ? 0 : b;                          // const_noise: motion 0's draw for every motion
+        const int bn = noise_motion(sp, b);
         char* ximg = smem + ST_XIMG;
         const int q = lane & 3, tq = t - q;                            // frame of the quad's first lane, if the quad is a run
         const bool run4 = valid && (m0 + (lane | 3)) < g.M && tq >= 0 && (tq & 3) == 0 && tq + 3 < g.T;
@@ -244,47 +238,25 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 const int f = 4 * (wave + 8 * it) + j;
                 xpre[it][j] = (valid && f < g.F) ? sp.x[(size_t)b * FT + (size_t)f * g.T + t] : 0.f;
             }
-        // in-painting: mask and target of the same elements ride in the same batch. Buffer loads: ONE descriptor per array, the lane's element
-        // (sample, frame) as the vector offset, the feature row as a scalar offset - 88 flat addresses cost ~330 spilled SGPRs. The descriptor is
-        // sized by the pointer (wave-uniform: nothing bound, zero records, every load returns 0 untouched by memory) and bounds what a surplus
-        // row or a padding feature may touch; those values are never used (update() tests valid && f < F)
+        // in-painting: mask and target of the same elements ride in the same batch (values of a surplus row or a padding feature are never used:
+        // update() tests valid && f < F)
         unsigned char mpre[INPAINT ? NKX : 1][4];
         float ipre[INPAINT ? NKX : 1][4];
         if constexpr (INPAINT) {
-            const unsigned nrec = sp.inpaint_mask ? (unsigned)((size_t)g.B * FT) : 0u;
-            const __amdgpu_buffer_rsrc_t m_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(sp.inpaint_mask), 0, (int)nrec, 0x00020000);
-            const __amdgpu_buffer_rsrc_t v_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sp.inpaint_motion), 0, (int)(nrec * 4u), 0x00020000);
+            const InpaintRsrc irs = inpaint_rsrc(sp, 0, (size_t)g.B * FT);
             const int vo = b * (int)FT + t;
 #pragma unroll
             for (int it = 0; it < NKX; ++it)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int so = (4 * (wave + 8 * it) + j) * g.T;             // wave-uniform
-                    mpre[it][j] = __builtin_amdgcn_raw_buffer_load_b8(m_rs, vo, so, 0);
-                    ipre[it][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(v_rs, vo * 4, so * 4, 0));
-                }
+                for (int j = 0; j < 4; ++j) inpaint_load(irs, vo, (4 * (wave + 8 * it) + j) * g.T, mpre[it][j], ipre[it][j]);   // (row offset: wave-uniform)
         }
         auto update = [&](int f, float eps_in, float xv, unsigned char im, float iv) {
             float nv = 0.f;
             if (valid && f < g.F) {
-                float x0 = tile[lane * ST_XLD + f];
-                if constexpr (INPAINT) x0 = im ? iv : x0;
-                if (sp.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+                const float x0 = pred_x0<INPAINT>(tile[lane * ST_XLD + f], im, iv, sp.clip);
                 const size_t o = (size_t)b * FT + (size_t)f * g.T + t;
                 if (sp.x0_out) sp.x0_out[o] = x0;
-                float eps = eps_in;
-                if (sp.noise)
-                    eps = sp.noise[(size_t)(sp.first_index - step) * g.B * FT + (size_t)bn * FT + (size_t)f * g.T + t];
-                else if (!quads)
-                    eps = philox_normal(sp.seed, sp.sample_offset + bn, (uint32_t)step, (uint32_t)(f * 4096 + t));
-                if (sp.sampler == 0) {
-                    const float mean = __fadd_rn(__fmul_rn(k.c1, x0), __fmul_rn(k.c2, xv));
-                    nv = __fadd_rn(mean, __fmul_rn(k.sig_ddpm, eps));
-                } else {
-                    const float e = __fdiv_rn(__fsub_rn(__fmul_rn(k.sr, xv), x0), k.srm1);
-                    const float mean = __fadd_rn(__fmul_rn(x0, k.ca), __fmul_rn(k.cb, e));
-                    nv = __fadd_rn(mean, __fmul_rn(k.sig_ddim, eps));
-                }
+                nv = sampler_next(k, sp.sampler, x0, xv, quad_or_step_eps(quads, eps_in, sp, step, g.B, FT, bn, f, g.T, t));
                 sp.x[o] = nv;
             }
             // x' (0 in the K padding columns and the surplus rows) -> the K32-blocked image of GEMM 2's A operand
@@ -295,31 +267,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             constexpr int it = decltype(IT)::value;
             const int fg = wave + 8 * it;
             float eps4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (quads) {                                               // wave-uniform
-                // this lane: the four normals of (feature 4 fg + q, frames tq .. tq + 3), exactly philox_normal's arithmetic
-                const uint32_t elem = (uint32_t)((4 * fg + q) * 4096 + tq);
-                const unsigned long long sample = sp.sample_offset + bn;
-                uint32_t r[4];
-                philox4x32_10(elem >> 2, (uint32_t)step, (uint32_t)sample, (uint32_t)(sample >> 32), (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32), r);
-                float n4[4];
-#pragma unroll
-                for (int pair = 0; pair < 2; ++pair) box_muller(r[2 * pair], r[2 * pair + 1], n4[2 * pair], n4[2 * pair + 1]);
-                // transpose inside the quad: this lane (frame tq + q) needs, for feature 4 fg + j, element q of lane j's n4
-                auto pick = [&](auto jc) {                              // element q of lane jc's n4, broadcast inside the quad
-                    constexpr int J = decltype(jc)::value;
-                    float v = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float bc = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, n4[e]), J * 0x55, 0xf, 0xf, true));   // quad_perm [J, J, J, J]
-                        v = q == e ? bc : v;
-                    }
-                    return v;
-                };
-                eps4[0] = pick(std::integral_constant<int, 0>{});
-                eps4[1] = pick(std::integral_constant<int, 1>{});
-                eps4[2] = pick(std::integral_constant<int, 2>{});
-                eps4[3] = pick(std::integral_constant<int, 3>{});
-            }
+            if (quads) quad_normals(sp, step, bn, fg, q, tq, eps4);      // wave-uniform
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned char im = 0;
@@ -393,46 +341,29 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             }
         }
     }
-    if (tid == 0) {   // ticket: the last tile of the step moves the loop index on (see k_update)
-        int* tick = g.d_step + 4;
-        if (atomicAdd(tick, 1) == g.total_tiles - 1) {
-            tick[0] = 0;
-            g.d_step[0] = step - 1;
-        }
-    }
+    if (tid == 0) step_ticket(g.d_step + 4, g.total_tiles, g.d_step, step - 1);   // the last tile of the step moves the loop index on
 }
 
 bool step_fused_supported(int d, int F, int Kpx) { return d == 512 && F % 4 == 0 && F <= 352 && Kpx == 352; }
-hipError_t configure_step() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_step<11, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
+// k_step's forms, named once: fn(kernel) for the form the flags pick
+template <class Fn>
+static hipError_t step_form(bool guided, bool f16, bool inpaint, Fn fn) {
+    return dispatch_bools([&](auto G, auto H, auto I) { return fn(k_step<11, decltype(G)::value, decltype(H)::value, decltype(I)::value>); }, guided, f16, inpaint);
 }
+hipError_t configure_step() {
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < 8 && e == hipSuccess; ++m)
+        e = step_form(m & 1, m & 2, m & 4, [](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS); });
+    return e;
+}
+// g.scale: guided - M = token rows of the conditional half; half = row distance to the unconditional half. inpaint: a binding exists (rgn_set_inpainting)
 hipError_t launch_step(const StepArgs& g, hipStream_t s, bool inpaint) {
     if (g.nkx != 11 || g.M <= 0) return hipErrorInvalidValue;
     const dim3 grid((g.M + ST_BM - 1) / ST_BM);
-    if (inpaint) {   // the in-painting forms (a binding exists: rgn_set_inpainting)
-        if (g.scale) {
-            if (g.f16) hipLaunchKernelGGL((k_step<11, true, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-            else hipLaunchKernelGGL((k_step<11, true, false, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-        } else {
-            if (g.f16) hipLaunchKernelGGL((k_step<11, false, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-            else hipLaunchKernelGGL((k_step<11, false, false, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-        }
-    } else if (g.scale) {   // guided: M = token rows of the conditional half; half = row distance to the unconditional half
-        if (g.f16) hipLaunchKernelGGL((k_step<11, true, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-        else hipLaunchKernelGGL((k_step<11, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-    } else {
-        if (g.f16) hipLaunchKernelGGL((k_step<11, false, true>), grid, dim3(ST_NT), ST_LDS, s, g);
-        else hipLaunchKernelGGL((k_step<11, false>), grid, dim3(ST_NT), ST_LDS, s, g);
-    }
-    return hipGetLastError();
+    return step_form(g.scale != nullptr, g.f16 != 0, inpaint, [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(ST_NT), ST_LDS, s, g);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rgn

@@ -341,7 +341,7 @@ def test_philox_stream_properties():
     n = a.numel()
     assert abs(a.mean().item()) < 4 / n ** 0.5 and abs(a.var().item() - 1) < 0.02
     assert abs((a ** 3).mean().item()) < 0.05 and abs((a ** 4).mean().item() - 3) < 0.1
-    # Box-Muller on the hardware transcendentals (rgn_philox.h): tails and the independence of the (cos, sin) pair
+    # Box-Muller on the hardware transcendentals (rgn_sampler.h): tails and the independence of the (cos, sin) pair
     flat = a.reshape(-1, 60)
     assert abs((flat[:, 0::2] * flat[:, 1::2]).mean().item()) < 5e-3                       # adjacent frames = the two outputs of one pair
     assert abs((a.abs() > 3).float().mean().item() - 2.6998e-3) < 3e-4 and a.abs().max().item() < 6.5
