@@ -229,6 +229,27 @@ RGN_API int rgn_rot6d_to_matrix(rgn_handle h, const float* d6_dev, float* mat_de
 RGN_API int rgn_gaussian_filter1d(rgn_handle h, const float* x_dev, float* out_dev, int64_t rows, int32_t T,
                           float sigma, void* stream);
 
+/* Replaces Rotation2xyz_x.__call__ / Rotation2xyz.__call__ (model/rotation2xyz.py:158-324 / :11-155) for the posed skeleton joints
+ * (jointstype 'smplx' / 'smpl'): the rigid-transform chain of the body layer, G_0 = [R_0 | j_0], G_i = G_parent(i) . [R_i | j_i - j_parent(i)],
+ * joint i = translation of G_i; then frames with mask == 0 are set to 0, joint 0 is subtracted, and with TRANSLATION and VERTSTRANS the
+ * translation row is added (num_person == 1: relative to frame 0, :318; num_person > 1: as stored, :247-249).
+ *   x_dev   fp32 [B, R, C * num_person, T], C = 6 | 3 | 4 | 9 by pose_rep; R = J rotation rows (J - 1 without RGN_R2X_GLOB: joint 0 then takes
+ *           axis_angle_to_matrix(glob_rot_host)) plus, with RGN_R2X_TRANSLATION, one last row whose channels p C .. p C + 2 are person p's translation
+ *   mask_dev uint8 [B, T] (the storage of a contiguous torch.bool tensor), NULL = every frame
+ *   rest_joints_host [J, 3] and parents_host [J] (parents[0] = -1, parents[i] < i): the skeleton, read during the call and passed to the kernel
+ *           by value - the call keeps no state and can be captured into a graph
+ *   xyz_dev fp32 [B, J, 3 * num_person, T]; rotmat_dev (nullable) fp32 [B, num_person, T, J, 3, 3], the matrices the chain used: for rot6d the
+ *           very values rgn_rot6d_to_matrix gives.
+ * RGN_ERR_INVALID_ARG, with text: a null pointer, B or T < 1, J outside [1, 64], a parent table that is not a tree in index order, num_person < 1,
+ * an unknown pose_rep, RGN_R2X_GLOB unset without glob_rot_host. */
+enum { RGN_POSE_ROT6D = 0, RGN_POSE_ROTVEC = 1, RGN_POSE_ROTQUAT = 2, RGN_POSE_ROTMAT = 3 };
+enum { RGN_R2X_TRANSLATION = 1, RGN_R2X_GLOB = 2, RGN_R2X_VERTSTRANS = 4 };
+RGN_API int rgn_rot2xyz(rgn_handle h, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T,
+                        int32_t J, const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/,
+                        int32_t pose_rep, int32_t num_person, int32_t flags /*RGN_R2X_TRANSLATION | _GLOB | _VERTSTRANS*/,
+                        const float* glob_rot_host /*[3] or NULL*/, float* xyz_dev, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/,
+                        void* stream);
+
 /* Introspection for bench/profiling: name and accumulated HIP-event time (ms) + launch count of the
  * internal kernel classes since the last reset; timing is only collected when enabled. */
 RGN_API int rgn_profile_enable(rgn_handle h, int32_t on);

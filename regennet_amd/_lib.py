@@ -21,6 +21,9 @@ PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16_x3tail": 3}
 DEFAULT_PRECISION = "bf16_x3tail"
 SAMPLER = {"ddpm": 0, "ddim": 1}
 FLAG_UNCOND, FLAG_GUIDED = 1, 2
+POSE_REP = {"rot6d": 0, "rotvec": 1, "rotquat": 2, "rotmat": 3}     # RGN_POSE_*; channels per rotation below
+POSE_REP_CHANNELS = {"rot6d": 6, "rotvec": 3, "rotquat": 4, "rotmat": 9}
+R2X_TRANSLATION, R2X_GLOB, R2X_VERTSTRANS = 1, 2, 4
 
 
 class RgnError(RuntimeError):
@@ -69,6 +72,7 @@ SYMBOLS = {
     "rgn_randn_step": (C.c_int, [_vp, _vp, _i32, _u64, _u64, _i32, _vp]),
     "rgn_rot6d_to_matrix": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "rgn_gaussian_filter1d": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
+    "rgn_rot2xyz": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rgn_profile_enable": (C.c_int, [_vp, _i32]),
     "rgn_profile_query": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "rgn_profile_bracket_overhead": (C.c_int, [_vp, C.POINTER(C.c_double)]),
@@ -287,6 +291,17 @@ class Engine:
 
     def gaussian_filter1d(self, x, out, rows, T, sigma, stream):
         self._ck(self.lib.rgn_gaussian_filter1d(self.h, _ptr(x), _ptr(out), int(rows), int(T), float(sigma), C.c_void_p(stream)))
+
+    def rot2xyz(self, x, mask, rest_joints, parents, pose_rep, num_person, flags, glob_rot, xyz, rotmat, stream):
+        """rgn_rot2xyz: x fp32 [B, R, C * num_person, T] and mask (bool / uint8 [B, T] or None), contiguous on the engine's device -> xyz
+        [B, J, 3 * num_person, T] (and rotmat [B, num_person, T, J, 3, 3] when given); rest_joints [J, 3] / parents [J] are host arrays."""
+        rj = np.ascontiguousarray(rest_joints, dtype=np.float32)
+        pa = np.ascontiguousarray(parents, dtype=np.int32)
+        gr = None if glob_rot is None else np.ascontiguousarray(glob_rot, dtype=np.float32).reshape(3)
+        assert rj.shape == (len(pa), 3) and x.is_contiguous() and xyz.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        self._ck(self.lib.rgn_rot2xyz(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), len(pa), rj.ctypes.data_as(C.c_void_p),
+                                      pa.ctypes.data_as(C.c_void_p), int(pose_rep), int(num_person), int(flags),
+                                      None if gr is None else gr.ctypes.data_as(C.c_void_p), _ptr(xyz), _ptr(rotmat), C.c_void_p(stream)))
 
     def profile_enable(self, on):
         self._ck(self.lib.rgn_profile_enable(self.h, int(bool(on))))

@@ -206,6 +206,23 @@ __device__ __forceinline__ float half_sum(float v) {
     return v + o;
 }
 
+// ---- rotation_6d_to_matrix (utils/rotation_conversions.py:513-534): Gram-Schmidt of the two 3-vectors a1, a2, F.normalize semantics
+// (v / max(||v||, 1e-12)); m[0..8] = the matrix, row-major (global memory or a local array). The one definition k_rot6d (rgn_kernels.hip) and
+// k_fk (rgn_fk.hip) share, so the two agree bit for bit.
+__device__ __forceinline__ void rot6d_to_matrix(float a1x, float a1y, float a1z, float a2x, float a2y, float a2z, float* m) {
+    float n1 = fmaxf(sqrtf(a1x * a1x + a1y * a1y + a1z * a1z), 1e-12f);
+    const float b1x = a1x / n1, b1y = a1y / n1, b1z = a1z / n1;
+    const float dot = b1x * a2x + b1y * a2y + b1z * a2z;
+    float b2x = a2x - dot * b1x, b2y = a2y - dot * b1y, b2z = a2z - dot * b1z;
+    const float n2 = fmaxf(sqrtf(b2x * b2x + b2y * b2y + b2z * b2z), 1e-12f);
+    b2x /= n2; b2y /= n2; b2z /= n2;
+    m[0] = b1x; m[1] = b1y; m[2] = b1z;
+    m[3] = b2x; m[4] = b2y; m[5] = b2z;
+    m[6] = b1y * b2z - b1z * b2y;
+    m[7] = b1z * b2x - b1x * b2z;
+    m[8] = b1x * b2y - b1y * b2x;
+}
+
 // =================================================== HOST ONLY ===================================================
 // ---- run-time flags -> template arguments, for launch_* / configure_*. dispatch_bools(f, a, b, ...) returns f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...):
 // a launcher and its configure_* name a kernel's forms once, as k<decltype(A)::value, ...> inside f, instead of an if ladder each

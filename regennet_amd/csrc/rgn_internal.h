@@ -351,4 +351,18 @@ hipError_t launch_randn(float* x, int B, int FT, int T, unsigned long long seed,
 hipError_t launch_rot6d(const float* d6, float* mat, long long n, hipStream_t s);
 hipError_t launch_gauss1d(const float* x, float* out, long long rows, int T, float sigma, hipStream_t s);
 
+// ---- rgn_fk.hip: forward kinematics of a skeleton (rgn_rot2xyz). Passed to the kernel by value: the call keeps no state.
+constexpr int FK_MAX_JOINTS = 64;
+struct FkSkel {
+    float rel[FK_MAX_JOINTS][3];     // j_i - j_parent(i); rel[0] = j_0, which is also joint 0's posed position
+    float glob[9];                   // joint 0's matrix where the rows hold no global rotation (glob = False)
+    int8_t parent[FK_MAX_JOINTS];    // -1 for joint 0
+    uint8_t order[FK_MAX_JOINTS];    // the joints sorted by depth, index order within a depth
+    uint8_t level[FK_MAX_JOINTS + 1];// depth l = order[level[l] .. level[l + 1])
+    int32_t nlevels;
+};
+// x [B, R, C*P, T] -> xyz [B, J, 3*P, T] (+ rotmat [B,P,T,J,3,3] when not null); pose_rep / flags: RGN_POSE_* / RGN_R2X_* (regennet_hip.h)
+hipError_t launch_fk(const float* x, const uint8_t* mask, float* xyz, float* rotmat, int B, int T, int P, int J, int pose_rep, int flags,
+                     const FkSkel& sk, hipStream_t s);
+
 }  // namespace rgn

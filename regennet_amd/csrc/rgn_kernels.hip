@@ -1003,18 +1003,7 @@ __global__ void k_rot6d(const float* __restrict__ d6, float* __restrict__ mat, l
     if (i >= n) return;
     const float* p = d6 + i * 6;
     float a1x = p[0], a1y = p[1], a1z = p[2], a2x = p[3], a2y = p[4], a2z = p[5];
-    float n1 = fmaxf(sqrtf(a1x * a1x + a1y * a1y + a1z * a1z), 1e-12f);
-    const float b1x = a1x / n1, b1y = a1y / n1, b1z = a1z / n1;
-    const float dot = b1x * a2x + b1y * a2y + b1z * a2z;
-    float b2x = a2x - dot * b1x, b2y = a2y - dot * b1y, b2z = a2z - dot * b1z;
-    const float n2 = fmaxf(sqrtf(b2x * b2x + b2y * b2y + b2z * b2z), 1e-12f);
-    b2x /= n2; b2y /= n2; b2z /= n2;
-    float* m = mat + i * 9;
-    m[0] = b1x; m[1] = b1y; m[2] = b1z;
-    m[3] = b2x; m[4] = b2y; m[5] = b2z;
-    m[6] = b1y * b2z - b1z * b2y;
-    m[7] = b1z * b2x - b1x * b2z;
-    m[8] = b1x * b2y - b1y * b2x;
+    rot6d_to_matrix(a1x, a1y, a1z, a2x, a2y, a2z, mat + i * 9);       // (rgn_device.h: shared with the forward-kinematics kernel, rgn_fk.hip)
 }
 hipError_t launch_rot6d(const float* d6, float* mat, long long n, hipStream_t s) {
     if (n <= 0) return hipSuccess;

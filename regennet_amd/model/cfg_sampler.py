@@ -12,12 +12,16 @@ class ClassifierFreeSampleModel(nn.Module):
         self.model = model
         assert self.model.cond_mask_prob > 0, \
             "Cannot run a guided diffusion on a model that has not been trained with no conditions"
-        self.rot2xyz = self.model.rot2xyz
         self.translation = self.model.translation
         self.njoints = self.model.njoints
         self.nfeats = self.model.nfeats
         self.data_rep = self.model.data_rep
         self.cond_mode = self.model.cond_mode
+
+    @property
+    def rot2xyz(self):
+        """The wrapped model's rot2xyz, read at the time of use (cfg_sampler.py:15 copies it once): a later model.set_skeleton is followed."""
+        return self.model.rot2xyz
 
     def _rgn_bind(self, B, y, device=None, T=None, cache=False):
         assert self.model.cond_mode in ["text", "action"]

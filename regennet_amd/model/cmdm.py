@@ -89,8 +89,9 @@ class EmbedAction(nn.Module):
 
 
 class _Rot2xyzUnavailable:
-    """model.rot2xyz needs the `smplx` package and licensed SMPL-X assets (model/rotation2xyz.py:165);
-    post-processing is outside the hot path. Assign your own callable to use it."""
+    """model.rot2xyz needs a skeleton: pass CMDM(skeleton=...) or call model.set_skeleton(load_skeleton("skel.npz")) - the rest joints and
+    parent table that tools/make_skeleton.py extracts from a licensed body-model file (model/rotation2xyz.py here; the reference's
+    model/rotation2xyz.py:165 loads the whole SMPL-X layer instead). Or assign your own callable."""
     smpl_model = None
 
     def __call__(self, *a, **k):
@@ -150,6 +151,8 @@ class CMDM(nn.Module):
             self.embed_action = EmbedAction(num_actions, d)
         self.output_process = _Pose("poseFinal", d, self.input_feats)
         self.rot2xyz = _Rot2xyzUnavailable()
+        if kargs.get("skeleton", None) is not None:
+            self.set_skeleton(kargs["skeleton"])
 
         self.precision = os.environ.get("REGENNET_PRECISION", kargs.get("precision", _lib.DEFAULT_PRECISION))
         # precision schedule: split-bf16 for the last x3_tail loop indices of a sampling loop (None: engine default rule;
@@ -179,6 +182,16 @@ class CMDM(nn.Module):
         self._keep = None
         for p in self.parameters():
             p.requires_grad_(False)
+
+    def set_skeleton(self, skeleton):
+        """model.rot2xyz = the device forward kinematics over `skeleton` (a dict as model.rotation2xyz.load_skeleton returns it, or the path of
+        such an npz); None takes it away again. Wrappers (ClassifierFreeSampleModel) follow."""
+        from .rotation2xyz import Rotation2xyz, load_skeleton
+        if skeleton is None:
+            self.rot2xyz = _Rot2xyzUnavailable()
+        else:
+            self.rot2xyz = Rotation2xyz(load_skeleton(skeleton) if isinstance(skeleton, (str, os.PathLike)) else skeleton, model=self)
+        return self
 
     # ---- nn.Module plumbing ---------------------------------------------------------------------------
     def parameters_wo_clip(self):

@@ -5,7 +5,9 @@ temporal Gaussian (cgenerate.py:142) — here on the device — and save `result
 
 The reference pulls actor clips from its h5 datasets (licence-restricted, absent here) and finishes with SMPL-X
 `rot2xyz`; this CLI takes actor clips from an .npz (or synthetic ones) and stores the rot6d output ('output',
-'cmotion' keys as in the reference); 'motion' (xyz) is only produced when `model.rot2xyz` has been supplied."""
+'cmotion' keys as in the reference). With `--skeleton FILE.npz` (tools/make_skeleton.py; `synthetic`: synth.make_skeleton, NOT a body model's
+skeleton) it also stores 'motion', the joint positions `model.rot2xyz` gives for the smoothed sample (cgenerate.py:154-163) - forward
+kinematics on the device, no body model needed."""
 import os
 import time
 import types
@@ -29,6 +31,26 @@ def _load_clips(args, cfg, n):
         return cm, act
     reps = max(1, args.num_repetitions)
     return synth.make_cmotion(cfg, n * reps, seed=1), synth.make_actions(cfg, n * reps, seed=2)
+
+
+def set_skeleton(model, args):
+    """--skeleton FILE.npz | synthetic -> model.set_skeleton (the model inside a guidance wrapper). True when one was given."""
+    if not args.skeleton:
+        return False
+    from ..model.rotation2xyz import load_skeleton
+    sk = synth.make_skeleton(model.njoints - 1) if args.skeleton == "synthetic" else load_skeleton(args.skeleton)
+    if args.skeleton == "synthetic":
+        print(f"--skeleton synthetic: a synthetic {model.njoints - 1}-joint tree (synth.make_skeleton), not a body model's skeleton")
+    model.set_skeleton(sk)
+    return True
+
+
+def joint_positions(model, args, sample, y):
+    """The reference's closing call (cgenerate.py:154-158) on this model's rot2xyz: [B, njoints, nfeats, T] -> [B, J, 3, T]."""
+    pose_rep = "xyz" if model.data_rep in ("xyz", "hml_vec") else model.data_rep
+    mask = None if pose_rep == "xyz" else y["mask"].reshape(sample.shape[0], sample.shape[-1]).bool()
+    return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=args.body_model, vertstrans=True,
+                         num_person=1, betas=None, beta=0, glob_rot=None, get_rotations_back=False)
 
 
 def main(argv=None):
@@ -76,7 +98,8 @@ def main(argv=None):
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     eng, _ = inner._get_engine(max(Bl, 1), n_frames)
-    all_outputs, all_cmotions, time_all = [], [], 0.0
+    with_motion = set_skeleton(inner, args)
+    all_outputs, all_cmotions, all_motions, time_all = [], [], [], 0.0
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
 
     def make_y(rep_i):
@@ -115,6 +138,9 @@ def main(argv=None):
             print("Generating time consumption: %s ms" % ((t_end - t_start) * 1000))
         all_outputs.append(dist_util.all_gather_samples(smooth, B).cpu().numpy())
         all_cmotions.append(dist_util.all_gather_samples(y["cmotion"], B).cpu().numpy())
+        if with_motion:                            # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
+            motion = joint_positions(inner, args, smooth, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
+            all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if rank == 0:
             print(f"created {len(all_outputs) * B} samples")
     npy_path = None
@@ -125,7 +151,8 @@ def main(argv=None):
         os.makedirs(out_path, exist_ok=True)
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
-        np.save(npy_path, {"output": np.concatenate(all_outputs), "cmotion": np.concatenate(all_cmotions),
+        np.save(npy_path, {**({"motion": np.concatenate(all_motions)} if with_motion else {}),
+                           "output": np.concatenate(all_outputs), "cmotion": np.concatenate(all_cmotions),
                            "lengths": np.full((len(all_outputs) * B,), n_frames), "num_samples": args.num_samples,
                            "num_repetitions": args.num_repetitions, "world_size": world})
         print(f"[Done] Results are at [{os.path.abspath(out_path)}]")

@@ -12,7 +12,8 @@ loop (gaussian_diffusion.py:319-323, rgn_set_inpainting).
 
 Input motions: --input_motions FILE.npy [N, njoints, nfeats, T], or synthetic ones with --synthetic. Like the reference's edit.py (and
 unlike cgenerate) the result is stored unsmoothed, so its kept part equals the input bit for bit; 'mask' and 'input_motions' are stored
-beside 'output' and 'cmotion'."""
+beside 'output' and 'cmotion'. With --skeleton FILE.npz | synthetic (see cgenerate) 'motion' holds the joint positions model.rot2xyz gives
+for that output."""
 import os
 import time
 import types
@@ -74,6 +75,7 @@ def main(argv=None):
     from ..utils.fixseed import fixseed
     from ..utils.model_util import create_model_and_diffusion, load_model_wo_clip
     from ..utils.parser_util import edit_args
+    from .cgenerate import joint_positions, set_skeleton
 
     args = edit_args(argv)
     fixseed(args.seed)
@@ -123,6 +125,7 @@ def main(argv=None):
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
+    with_motion = set_skeleton(inner, args)
 
     def make_y(rep_i):
         idx = (np.arange(lo, hi) + rep_i * B) % len(clips)
@@ -139,7 +142,7 @@ def main(argv=None):
 
     if world > 1:
         diffusion.agree_x3_tail(model, shape, {"y": make_y(0)} if Bl > 0 else None, sampler="ddim" if args.use_ddim else "ddpm")
-    outs, cms, ins = [], [], []
+    outs, cms, ins, motions = [], [], [], []
     for rep_i in range(args.num_repetitions):
         if rank == 0:
             print(f"### Start sampling [repetitions #{rep_i}]")
@@ -158,13 +161,16 @@ def main(argv=None):
         outs.append(dist_util.all_gather_samples(sample, B).cpu().numpy())
         cms.append(dist_util.all_gather_samples(y["cmotion"], B).cpu().numpy())
         ins.append(dist_util.all_gather_samples(y["inpainted_motion"], B).cpu().numpy())
+        if with_motion:
+            motion = joint_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
+            motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
     npy_path = None
     if rank == 0:
         out_path = args.output_dir or os.path.join(os.path.dirname(args.model_path) or ".", f"edit_seed{args.seed}_{args.edit_mode}")
         os.makedirs(out_path, exist_ok=True)
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
-        np.save(npy_path, {"output": np.concatenate(outs), "cmotion": np.concatenate(cms), "input_motions": np.concatenate(ins),
+        np.save(npy_path, {**({"motion": np.concatenate(motions)} if with_motion else {}), "output": np.concatenate(outs), "cmotion": np.concatenate(cms), "input_motions": np.concatenate(ins),
                            "mask": np.concatenate([full_mask] * len(outs)), "edit_mode": args.edit_mode,
                            "lengths": np.full((len(outs) * B,), n_frames), "num_samples": args.num_samples,
                            "num_repetitions": args.num_repetitions, "world_size": world})

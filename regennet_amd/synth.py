@@ -300,3 +300,32 @@ def build_model(cfg, sd, resp="", precision=None, device="cuda:0", noise_schedul
                                 model_var_type=gd.ModelVarType.FIXED_SMALL if sigma_small else gd.ModelVarType.FIXED_LARGE,
                                 loss_type=gd.LossType.MSE, rescale_timesteps=False)
     return model, diffusion
+
+
+def make_skeleton(njoints=55, depth=10, nbetas=10, seed=0):
+    """A deterministic SYNTHETIC skeleton for tests, tools and `--skeleton synthetic`: a valid tree of `njoints` joints in index order
+    (parents[0] = -1, parents[i] < i) whose deepest joint is `depth` edges from the root, bones of 5 - 30 cm, and small shape directions.
+    Joints 22 - 24 are leaves, as the jaw and the eyes are in SMPL-X: the reference does not hand their rotations to the body layer
+    (model/rotation2xyz.py:294-301), which is only harmless because no position depends on them.
+    It has the joint count of a body model's skeleton (55 like SMPL-X, 24 like SMPL) and nothing else of it: the licensed models' rest
+    joints come from tools/make_skeleton.py. Keys as model/rotation2xyz.py load_skeleton returns them."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    J = int(njoints)
+    depth = min(int(depth), J - 1)
+    parents = np.full(J, -1, dtype=np.int32)
+    level = np.zeros(J, dtype=np.int64)
+    for i in range(1, J):
+        if i <= depth:
+            parents[i] = i - 1                                        # a spine of `depth` edges ...
+        else:
+            ok = level[:i] < depth                                    # ... and every other joint below a joint that is not at the deepest level
+            ok[22:25] = False
+            parents[i] = rng.choice(np.flatnonzero(ok))
+        level[i] = level[parents[i]] + 1
+    rest = np.zeros((J, 3))
+    rest[0] = rng.uniform(-0.05, 0.05, 3)
+    for i in range(1, J):
+        d = rng.standard_normal(3)
+        rest[i] = rest[parents[i]] + d / np.linalg.norm(d) * rng.uniform(0.05, 0.30)
+    return {"rest_joints": rest.astype(np.float32), "parents": parents,
+            "shape_joints": (0.01 * rng.standard_normal((J, 3, int(nbetas)))).astype(np.float32), "body_model": f"synthetic{J}"}

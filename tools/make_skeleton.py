@@ -1,0 +1,49 @@
+"""Skeleton file for model.rot2xyz from a body-model file you have licensed (numpy only):
+
+    python tools/make_skeleton.py SMPLX_NEUTRAL.npz --out skel.npz [--body_model smplx] [--num_betas 10]
+
+MODEL.npz holds the usual arrays of an SMPL-family model: J_regressor [J, V], v_template [V, 3], shapedirs [V, 3, >= nb], kintree_table [2, J].
+The skeleton file holds what the posed skeleton joints depend on, a few hundred numbers and no vertex data:
+
+    rest_joints  [J, 3]      = J_regressor @ v_template
+    shape_joints [J, 3, nb]  = J_regressor @ shapedirs[:, :, k]  for the first nb shape directions
+    parents      [J]         = kintree_table[0], root set to -1
+
+Read it with regennet_amd.model.rotation2xyz.load_skeleton, or pass its path to `--skeleton` of the sampling CLIs."""
+import argparse
+
+import numpy as np
+
+
+def make_skeleton(model, num_betas=10, body_model=""):
+    """dict of the arrays above from a mapping with J_regressor, v_template, kintree_table (and shapedirs)."""
+    reg = np.asarray(model["J_regressor"], dtype=np.float64)
+    vt = np.asarray(model["v_template"], dtype=np.float64)
+    parents = np.asarray(model["kintree_table"])[0].astype(np.int64)
+    parents[0] = -1                                     # (stored as 2^32 - 1 in the model files)
+    J = reg.shape[0]
+    assert reg.shape[1] == vt.shape[0] and vt.shape[1] == 3 and parents.shape == (J,), (reg.shape, vt.shape, parents.shape)
+    assert all(0 <= parents[i] < i for i in range(1, J)), "kintree_table is not a tree in index order"
+    out = {"rest_joints": (reg @ vt).astype(np.float32), "parents": parents.astype(np.int32), "body_model": np.array(str(body_model))}
+    if "shapedirs" in model and num_betas > 0:
+        sd = np.asarray(model["shapedirs"], dtype=np.float64)[:, :, :num_betas]
+        out["shape_joints"] = np.einsum("jv,vck->jck", reg, sd).astype(np.float32)
+    return out
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("model", help="body-model npz (J_regressor, v_template, shapedirs, kintree_table)")
+    p.add_argument("--out", required=True)
+    p.add_argument("--body_model", default="", help="label stored in the file, e.g. smplx")
+    p.add_argument("--num_betas", default=10, type=int)
+    args = p.parse_args(argv)
+    with np.load(args.model, allow_pickle=False) as z:
+        sk = make_skeleton({k: z[k] for k in z.files if k in ("J_regressor", "v_template", "shapedirs", "kintree_table")}, args.num_betas, args.body_model)
+    np.savez(args.out, **sk)
+    print(f"{args.out}: {len(sk['parents'])} joints, {sk.get('shape_joints', np.zeros((0, 0, 0))).shape[2]} shape directions")
+    return args.out
+
+
+if __name__ == "__main__":
+    main()
