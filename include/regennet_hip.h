@@ -250,6 +250,41 @@ RGN_API int rgn_rot2xyz(rgn_handle h, const float* x_dev, const uint8_t* mask_de
                         const float* glob_rot_host /*[3] or NULL*/, float* xyz_dev, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/,
                         void* stream);
 
+/* ---- Mesh vertices: jointstype='vertices' ----
+ * Replaces the body layer the reference keeps in Rotation2xyz.smpl_model / Rotation2xyz_x.smpl_model (model/rotation2xyz.py:14-15 / :161-162, a CPU
+ * smplx layer over a licensed model file): the mesh data of a BODY FILE (tools/make_skeleton.py --mesh), resident on `device`.
+ *   v_template_host [V, 3]; posedirs_host [9 (J - 1), 3 V] (NULL: no pose blend shapes); lbs_weights_host [V, J]; shapedirs_host [V, 3, nb]
+ *   (NULL with nb = 0); identity_joints_host: the joints whose rotation the wrapper does not hand to the layer (Rotation2xyz_x: jaw and eyes,
+ *   22-24, model/rotation2xyz.py:294-301) - they take the identity in the chain, the pose feature and the skinning alike.
+ * The arguments are checked before the device is touched: RGN_ERR_INVALID_ARG, with text in rgn_body_last_error(NULL), for V outside [1, 65536],
+ * J outside [1, 64], nb outside [0, 16], a null v_template / lbs_weights / out, nb > 0 without shapedirs, an identity joint outside [1, J). */
+typedef struct rgn_body_ctx* rgn_body_handle;
+RGN_API int rgn_body_create(int32_t device, int32_t V, int32_t J, int32_t nb, const float* v_template_host /*[V,3]*/,
+                            const float* posedirs_host /*[9(J-1),3V] or NULL*/, const float* lbs_weights_host /*[V,J]*/,
+                            const float* shapedirs_host /*[V,3,nb] or NULL*/, const int32_t* identity_joints_host, int32_t n_identity,
+                            rgn_body_handle* out);
+RGN_API int rgn_body_destroy(rgn_body_handle b);
+RGN_API const char* rgn_body_last_error(rgn_body_handle b);   /* NULL: the calling thread's last failed rgn_body_create */
+/* Bytes of device memory rgn_rot2verts needs for B motions of T frames and num_person persons (the shaped template, and per tile of 32 frames the
+ * skinning transforms and the pose feature). */
+RGN_API int rgn_rot2verts_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes);
+/* Replaces Rotation2xyz_x.__call__ / Rotation2xyz.__call__ with jointstype='vertices' (model/rotation2xyz.py:303-321 / :236-249) and, inside them,
+ * smplx.lbs.lbs: v_shaped = v_template + shapedirs . betas; v_posed = v_shaped + posedirs^T . (R_j - I)_{j >= 1}; the chain of rgn_rot2xyz with
+ * A_j = [Rg_j | tg_j - Rg_j . j_j]; vertex = (sum_j w[v, j] A_j) . [v_posed; 1]. Then frames with mask == 0 are set to 0 and - there is NO root
+ * subtraction for vertices - with TRANSLATION and VERTSTRANS the translation row is added (one person: relative to frame 0; several: as stored).
+ * x_dev, mask_dev, rest_joints_host (for the body's J joints; with betas: rest + shape_joints . betas, formed by the caller), parents_host, pose_rep,
+ * num_person, flags, glob_rot_host and rotmat_dev mean what they mean for rgn_rot2xyz and are checked the same way; betas_host [nb] or NULL (zeros).
+ *   verts_dev fp32 [B, V, 3 * num_person, T]
+ *   work_dev  rgn_rot2verts_workspace bytes; a smaller work_bytes is RGN_ERR_INVALID_ARG
+ * fp32 throughout: the two sums run on the fp32-input MFMA (exact products, k-ordered accumulation). Tiles of 32 consecutive frames that are
+ * masked throughout cost no arithmetic; a tile with live frames is computed whole and its masked frames are set to 0. The work is enqueued on `stream` itself; the
+ * call allocates nothing, keeps no state and can be captured into a graph. */
+RGN_API int rgn_rot2verts(rgn_body_handle b, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T,
+                          const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/, int32_t pose_rep, int32_t num_person,
+                          int32_t flags, const float* glob_rot_host /*[3] or NULL*/, const float* betas_host /*[nb] or NULL*/,
+                          float* verts_dev /*[B,V,3P,T]*/, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes,
+                          void* stream);
+
 /* Introspection for bench/profiling: name and accumulated HIP-event time (ms) + launch count of the
  * internal kernel classes since the last reset; timing is only collected when enabled. */
 RGN_API int rgn_profile_enable(rgn_handle h, int32_t on);

@@ -92,6 +92,14 @@ SYMBOLS.update({
     "rgn_stgcn_forward": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
 })
 
+SYMBOLS.update({
+    "rgn_body_create": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "rgn_body_destroy": (C.c_int, [_vp]),
+    "rgn_body_last_error": (C.c_char_p, [_vp]),
+    "rgn_rot2verts_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "rgn_rot2verts": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+})
+
 _lib = None
 
 
@@ -367,3 +375,65 @@ class StgcnEngine:
 
     def forward(self, N, output, features, yhat, stream):
         self._ck(self.lib.rgn_stgcn_forward(self.h, int(N), _ptr(output), _ptr(features), _ptr(yhat), C.c_void_p(stream)))
+
+
+def _host(a, dtype):
+    """(contiguous array or None, its pointer or None): the array must outlive the call."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+class BodyEngine:
+    """Owns one rgn_body_handle: the mesh data of a body file on one device (include/regennet_hip.h). `mesh`: the dict
+    model.rotation2xyz.check_body returns under 'mesh'; J: the skeleton's joint count."""
+
+    def __init__(self, mesh, J, device_index):
+        self.lib = load()
+        vt, pt = _host(mesh["v_template"], np.float32)
+        pd, pp = _host(mesh.get("posedirs"), np.float32)
+        w, pw = _host(mesh["lbs_weights"], np.float32)
+        sd, ps = _host(mesh.get("shapedirs"), np.float32)
+        ij = mesh.get("identity_joints", None)
+        idj, pi = _host(() if ij is None else ij, np.int32)
+        self.V, self.J, self.nb = int(vt.shape[0]), int(J), 0 if sd is None else int(sd.shape[2])
+        h = C.c_void_p()
+        code = self.lib.rgn_body_create(int(device_index), self.V, self.J, self.nb, pt, pp, pw, ps, pi if len(idj) else None, len(idj), C.byref(h))
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_body_last_error(None) or b"").decode())
+        self.h = h
+
+    def _ck(self, code):
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_body_last_error(self.h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rgn_body_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, B, T, num_person):
+        n = C.c_uint64()
+        self._ck(self.lib.rgn_rot2verts_workspace(self.h, int(B), int(T), int(num_person), C.byref(n)))
+        return n.value
+
+    def rot2verts(self, x, mask, rest_joints, parents, pose_rep, num_person, flags, glob_rot, betas, verts, rotmat, work, stream):
+        """rgn_rot2verts: x fp32 [B, R, C * num_person, T] and mask (bool / uint8 [B, T] or None), contiguous on the body's device -> verts
+        [B, V, 3 * num_person, T] (and rotmat [B, num_person, T, J, 3, 3] when given); rest_joints [J, 3], parents [J], betas [nb] | None are host
+        arrays; work: a uint8 tensor of at least workspace_bytes(B, T, num_person)."""
+        rj, prj = _host(rest_joints, np.float32)
+        pa, ppa = _host(parents, np.int32)
+        gr, pgr = _host(None if glob_rot is None else np.asarray(glob_rot).reshape(3), np.float32)
+        be, pbe = _host(betas, np.float32)
+        assert rj.shape == (self.J, 3) and pa.shape == (self.J,) and (be is None or be.shape == (self.nb,))
+        assert x.is_contiguous() and verts.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        self._ck(self.lib.rgn_rot2verts(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, int(pose_rep), int(num_person),
+                                        int(flags), pgr, pbe, _ptr(verts), _ptr(rotmat), _ptr(work), int(work.numel() * work.element_size()),
+                                        C.c_void_p(stream)))

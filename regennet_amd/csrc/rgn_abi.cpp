@@ -51,6 +51,20 @@ int rgn_guard(rgn_ctx* h, const char* fn, F&& body) noexcept {
 
 }  // namespace
 
+namespace rgn {
+// axis_angle_to_matrix (utils/rotation_conversions.py:418-479, through the quaternion) of ONE vector, in fp32 like the reference's torch.tensor(glob_rot)
+void axis_angle_to_matrix_f32(const float* v, float* m) {
+    const float angle = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), half = 0.5f * angle;
+    const float s = angle < 1e-6f ? 0.5f - (angle * angle) / 48.0f : std::sin(half) / angle;
+    const float r = std::cos(half), i = v[0] * s, j = v[1] * s, k = v[2] * s;
+    const float two_s = 2.0f / (r * r + i * i + j * j + k * k);
+    const float out[9] = {1.0f - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
+                          two_s * (i * j + k * r), 1.0f - two_s * (i * i + k * k), two_s * (j * k - i * r),
+                          two_s * (i * k - j * r), two_s * (j * k + i * r), 1.0f - two_s * (i * i + j * j)};
+    std::memcpy(m, out, sizeof(out));
+}
+}  // namespace rgn
+
 extern "C" {
 
 const char* rgn_last_error(rgn_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -498,18 +512,6 @@ int rgn_gaussian_filter1d(rgn_handle h, const float* x, float* out, int64_t rows
     });
 }
 
-// axis_angle_to_matrix (utils/rotation_conversions.py:418-479, through the quaternion) of ONE vector, in fp32 like the reference's torch.tensor(glob_rot)
-static void axis_angle_to_matrix_f32(const float* v, float* m) {
-    const float angle = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), half = 0.5f * angle;
-    const float s = angle < 1e-6f ? 0.5f - (angle * angle) / 48.0f : std::sin(half) / angle;
-    const float r = std::cos(half), i = v[0] * s, j = v[1] * s, k = v[2] * s;
-    const float two_s = 2.0f / (r * r + i * i + j * j + k * k);
-    const float out[9] = {1.0f - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                          two_s * (i * j + k * r), 1.0f - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                          two_s * (i * k - j * r), two_s * (j * k + i * r), 1.0f - two_s * (i * i + j * j)};
-    std::memcpy(m, out, sizeof(out));
-}
-
 int rgn_rot2xyz(rgn_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t T, int32_t J, const float* rest_joints, const int32_t* parents,
                 int32_t pose_rep, int32_t num_person, int32_t flags, const float* glob_rot, float* xyz, float* rotmat, void* stream) {
     return rgn_guard(h, "rgn_rot2xyz", [&]() -> int {
@@ -521,24 +523,11 @@ int rgn_rot2xyz(rgn_handle h, const float* x, const uint8_t* mask, int32_t B, in
         if (pose_rep < RGN_POSE_ROT6D || pose_rep > RGN_POSE_ROTMAT) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz: unknown pose_rep");
         if (flags & ~(RGN_R2X_TRANSLATION | RGN_R2X_GLOB | RGN_R2X_VERTSTRANS)) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz: unknown flag");
         if (!(flags & RGN_R2X_GLOB) && !glob_rot) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz: glob_rot is required when RGN_R2X_GLOB is not set");
-        if (parents[0] != -1) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz: parents[0] != -1");
-        for (int i = 1; i < J; ++i)
-            if (parents[i] < 0 || parents[i] >= i)
-                return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz: parents[" + std::to_string(i) + "] outside [0, " + std::to_string(i) + ")");
         FkSkel sk;
-        std::memset(&sk, 0, sizeof(sk));
-        int depth[FK_MAX_JOINTS], count[FK_MAX_JOINTS + 1] = {0};
-        for (int i = 0; i < J; ++i) {
-            const int p = parents[i];
-            sk.parent[i] = (int8_t)p;
-            depth[i] = p < 0 ? 0 : depth[p] + 1;
-            for (int c = 0; c < 3; ++c) sk.rel[i][c] = p < 0 ? rest_joints[3 * i + c] : rest_joints[3 * i + c] - rest_joints[3 * p + c];
-            count[depth[i] + 1]++;
-            sk.nlevels = std::max(sk.nlevels, depth[i] + 1);
-        }
-        for (int l = 0; l < sk.nlevels; ++l) count[l + 1] += count[l];         // count[l] = first slot of depth l
-        for (int l = 0; l <= sk.nlevels; ++l) sk.level[l] = (uint8_t)count[l];
-        for (int i = 0; i < J; ++i) sk.order[count[depth[i]]++] = (uint8_t)i;
+        int at = -1;
+        if (const char* why = fk_build_skel(J, rest_joints, parents, sk, at))
+            return h->fail(RGN_ERR_INVALID_ARG, at < 0 ? std::string("rgn_rot2xyz: ") + why
+                                                       : "rgn_rot2xyz: parents[" + std::to_string(at) + "] outside [0, " + std::to_string(at) + ")");
         if (!(flags & RGN_R2X_GLOB)) axis_angle_to_matrix_f32(glob_rot, sk.glob);
         RGN_HIP(h, hipSetDevice(h->cfg.device));
         if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_rot2xyz: weights not finalized");

@@ -364,5 +364,33 @@ struct FkSkel {
 // x [B, R, C*P, T] -> xyz [B, J, 3*P, T] (+ rotmat [B,P,T,J,3,3] when not null); pose_rep / flags: RGN_POSE_* / RGN_R2X_* (regennet_hip.h)
 hipError_t launch_fk(const float* x, const uint8_t* mask, float* xyz, float* rotmat, int B, int T, int P, int J, int pose_rep, int flags,
                      const FkSkel& sk, hipStream_t s);
+// The skeleton argument checks of rgn_rot2xyz / rgn_rot2verts and the table their kernels take by value. nullptr when `sk` was filled, else the text of
+// the complaint (without the entry point's name); `at` receives the offending joint for the parent-table complaint, else -1. Host only.
+inline const char* fk_build_skel(int J, const float* rest_joints, const int32_t* parents, FkSkel& sk, int& at) {
+    at = -1;
+    if (J < 1 || J > FK_MAX_JOINTS) return "J outside [1, 64]";
+    if (parents[0] != -1) return "parents[0] != -1";
+    for (int i = 1; i < J; ++i)
+        if (parents[i] < 0 || parents[i] >= i) {
+            at = i;
+            return "parents";
+        }
+    sk = FkSkel{};
+    int depth[FK_MAX_JOINTS], count[FK_MAX_JOINTS + 1] = {0};
+    for (int i = 0; i < J; ++i) {
+        const int p = parents[i];
+        sk.parent[i] = (int8_t)p;
+        depth[i] = p < 0 ? 0 : depth[p] + 1;
+        for (int c = 0; c < 3; ++c) sk.rel[i][c] = p < 0 ? rest_joints[3 * i + c] : rest_joints[3 * i + c] - rest_joints[3 * p + c];
+        count[depth[i] + 1]++;
+        sk.nlevels = sk.nlevels > depth[i] + 1 ? sk.nlevels : depth[i] + 1;
+    }
+    for (int l = 0; l < sk.nlevels; ++l) count[l + 1] += count[l];         // count[l] = first slot of depth l
+    for (int l = 0; l <= sk.nlevels; ++l) sk.level[l] = (uint8_t)count[l];
+    for (int i = 0; i < J; ++i) sk.order[count[depth[i]]++] = (uint8_t)i;
+    return nullptr;
+}
+// axis_angle_to_matrix (utils/rotation_conversions.py:418-479, through the quaternion) of ONE vector, in fp32 like the reference's torch.tensor(glob_rot)
+void axis_angle_to_matrix_f32(const float* v, float* m);
 
 }  // namespace rgn

@@ -186,11 +186,11 @@ class CMDM(nn.Module):
     def set_skeleton(self, skeleton):
         """model.rot2xyz = the device forward kinematics over `skeleton` (a dict as model.rotation2xyz.load_skeleton returns it, or the path of
         such an npz); None takes it away again. Wrappers (ClassifierFreeSampleModel) follow."""
-        from .rotation2xyz import Rotation2xyz, load_skeleton
+        from .rotation2xyz import Rotation2xyz, load_skeleton_or_body
         if skeleton is None:
             self.rot2xyz = _Rot2xyzUnavailable()
         else:
-            self.rot2xyz = Rotation2xyz(load_skeleton(skeleton) if isinstance(skeleton, (str, os.PathLike)) else skeleton, model=self)
+            self.rot2xyz = Rotation2xyz(load_skeleton_or_body(skeleton) if isinstance(skeleton, (str, os.PathLike)) else skeleton, model=self)
         return self
 
     # ---- nn.Module plumbing ---------------------------------------------------------------------------

@@ -10,7 +10,19 @@ table and the rotations, not on vertices, pose blend shapes or skinning weights.
     body_model    str         optional label
 
 which tools/make_skeleton.py writes from a model file the user has licensed (`synth.make_skeleton` gives a synthetic one). The chain itself runs
-on the device (rgn_rot2xyz, csrc/rgn_fk.hip) straight from the sampler's [B, rows, feats, T] layout; there is no CPU path."""
+on the device (rgn_rot2xyz, csrc/rgn_fk.hip) straight from the sampler's [B, rows, feats, T] layout; there is no CPU path.
+
+jointstype='vertices' needs the body model's surface: a BODY FILE is a skeleton file with the mesh arrays beside it (`make_skeleton.py --mesh`;
+`synth.make_body` gives a synthetic one),
+
+    v_template       [V, 3]
+    posedirs         [9 (J - 1), 3 V]   optional: pose blend shapes, the layout smplx.lbs.lbs multiplies with
+    lbs_weights      [V, J]
+    shapedirs        [V, 3, nb]         optional; shape_joints = J_regressor @ shapedirs keeps joints and surface consistent
+    faces            [F, 3] int32       optional, for writing meshes
+    identity_joints  [n]                joints whose rotation the reference's wrapper does not hand to the layer (SMPL-X: 22, 23, 24)
+
+and linear blend skinning runs on the device too (rgn_rot2verts, csrc/rgn_lbs.hip)."""
 import numpy as np
 import torch
 
@@ -48,12 +60,80 @@ def load_skeleton(path):
     return check_skeleton(sk)
 
 
+MESH_KEYS = ("v_template", "posedirs", "lbs_weights", "shapedirs", "faces", "identity_joints")
+
+
+def check_body(d):
+    """check_skeleton's dict plus 'mesh': dict(v_template fp32 [V,3], posedirs fp32 [9(J-1),3V] | None, lbs_weights fp32 [V,J], shapedirs fp32
+    [V,3,nb] | None, faces int32 [F,3] | None, identity_joints int32 [n]), validated (the checks rgn_body_create makes, and those only a file can fail)."""
+    out = check_skeleton(d)
+    J = len(out["parents"])
+    m = d["mesh"] if isinstance(d.get("mesh", None), dict) else d
+    if m.get("v_template", None) is None or m.get("lbs_weights", None) is None:
+        raise ValueError("body: v_template and lbs_weights are required (a skeleton file holds no mesh: write one with tools/make_skeleton.py --mesh)")
+    vt = np.ascontiguousarray(m["v_template"], dtype=np.float32)
+    if vt.ndim != 2 or vt.shape[1] != 3 or not 1 <= vt.shape[0] <= 65536:
+        raise ValueError(f"body: v_template {vt.shape}: need [V, 3] with 1 <= V <= 65536")
+    V = vt.shape[0]
+    w = np.ascontiguousarray(m["lbs_weights"], dtype=np.float32)
+    if w.shape != (V, J):
+        raise ValueError(f"body: lbs_weights {w.shape} is not [V, J] = [{V}, {J}]")
+    if (w < 0).any() or float(np.abs(w.astype(np.float64).sum(1) - 1).max()) > 1e-5:
+        raise ValueError("body: every row of lbs_weights must be non-negative and sum to 1 (within 1e-5)")
+    pd = m.get("posedirs", None)
+    if pd is not None:
+        pd = np.ascontiguousarray(pd, dtype=np.float32)
+        if pd.shape != (9 * (J - 1), 3 * V):
+            raise ValueError(f"body: posedirs {pd.shape} is not [9 (J - 1), 3 V] = [{9 * (J - 1)}, {3 * V}]")
+    sd = m.get("shapedirs", None)
+    if sd is not None:
+        sd = np.ascontiguousarray(sd, dtype=np.float32)
+        if sd.ndim != 3 or sd.shape[:2] != (V, 3) or sd.shape[2] > 16:
+            raise ValueError(f"body: shapedirs {sd.shape} is not [V, 3, nb] with nb <= 16")
+        if out["shape_joints"] is None or out["shape_joints"].shape[2] != sd.shape[2]:
+            raise ValueError("body: shapedirs need shape_joints with as many shape directions (joints and surface move together)")
+        if sd.shape[2] == 0:
+            sd = None
+    faces = m.get("faces", None)
+    if faces is not None:
+        faces = np.ascontiguousarray(faces, dtype=np.int32)
+        if faces.ndim != 2 or faces.shape[1] != 3 or (faces.size and (faces.min() < 0 or faces.max() >= V)):
+            raise ValueError(f"body: faces {faces.shape} is not [F, 3] with vertex indices in [0, V)")
+    ij = m.get("identity_joints", None)
+    idj = np.zeros(0, np.int32) if ij is None else np.ascontiguousarray(ij, dtype=np.int32).reshape(-1)
+    if len(idj) and (idj.min() < 1 or idj.max() >= J):
+        raise ValueError(f"body: identity_joints {idj.tolist()} outside [1, J) = [1, {J})")
+    out["mesh"] = {"v_template": vt, "posedirs": pd, "lbs_weights": w, "shapedirs": sd, "faces": faces, "identity_joints": idj}
+    return out
+
+
+def load_body(path):
+    """Read a body npz (module docstring) -> check_body's dict."""
+    with np.load(path, allow_pickle=False) as z:
+        d = {k: z[k] for k in ("rest_joints", "parents")}
+        d["shape_joints"] = z["shape_joints"] if "shape_joints" in z.files else None
+        d["body_model"] = str(z["body_model"]) if "body_model" in z.files else ""
+        for k in MESH_KEYS:
+            d[k] = z[k] if k in z.files else None
+    return check_body(d)
+
+
+def load_skeleton_or_body(path):
+    """A body file gives check_body's dict, a skeleton file check_skeleton's."""
+    with np.load(path, allow_pickle=False) as z:
+        mesh = "v_template" in z.files
+    return load_body(path) if mesh else load_skeleton(path)
+
+
 class Rotation2xyz:
     """`Rotation2xyz(skeleton, model)(x, mask, pose_rep, translation, glob, jointstype, vertstrans, ...)` with the keyword arguments of both
     reference classes; unknown extras are accepted and ignored as on `Rotation2xyz_x`. `model` is the CMDM whose engine runs the kernel."""
 
     def __init__(self, skeleton, model=None):
-        self.skeleton = check_skeleton(skeleton)
+        with_mesh = isinstance(skeleton.get("mesh", None), dict) or skeleton.get("v_template", None) is not None
+        self.skeleton = check_body(skeleton) if with_mesh else check_skeleton(skeleton)
+        self.mesh = self.skeleton.get("mesh", None)     # None: a skeleton file, joints only
+        self._body, self._work = None, None             # (BodyEngine, its device), workspace tensor: made at the first 'vertices' call
         self.model = model
         self.smpl_model = None          # (the reference keeps its body layer here; there is none)
         sj = self.skeleton["shape_joints"]
@@ -62,6 +142,17 @@ class Rotation2xyz:
     def rest_joints(self, betas=None, beta=0):
         """rest + sum_k betas[k] * shape_joints[:, :, k], formed per call on the host; betas None -> zeros with betas[1] = beta (:289-292)."""
         sk = self.skeleton
+        b = self.betas_vector(betas, beta)
+        if not b.any():
+            return sk["rest_joints"]
+        if sk["shape_joints"] is None:
+            raise ValueError("non-zero betas / beta need `shape_joints` in the skeleton file")
+        if len(b) > sk["shape_joints"].shape[2]:
+            raise ValueError(f"{len(b)} betas but the skeleton file holds {sk['shape_joints'].shape[2]} shape directions")
+        return sk["rest_joints"] + sk["shape_joints"][:, :, :len(b)] @ b
+
+    def betas_vector(self, betas=None, beta=0):
+        """The one shape vector of a call, fp64 [n]."""
         if betas is None:
             b = np.zeros(self.num_betas)
             if beta != 0:
@@ -74,13 +165,15 @@ class Rotation2xyz:
                 b = b[0]
             if b.ndim != 1:
                 raise ValueError(f"betas {b.shape}: expected [nb] or [N, nb]")
-        if not b.any():
-            return sk["rest_joints"]
-        if sk["shape_joints"] is None:
-            raise ValueError("non-zero betas / beta need `shape_joints` in the skeleton file")
-        if len(b) > sk["shape_joints"].shape[2]:
-            raise ValueError(f"{len(b)} betas but the skeleton file holds {sk['shape_joints'].shape[2]} shape directions")
-        return sk["rest_joints"] + sk["shape_joints"][:, :, :len(b)] @ b
+        return b
+
+    def body_engine(self, dev):
+        """The device-resident mesh data for `dev`: created at first use, rebuilt when the model has moved."""
+        if self._body is None or self._body[1] != dev:
+            if self._body is not None:
+                self._body[0].close()
+            self._body, self._work = (_lib.BodyEngine(self.mesh, len(self.skeleton["parents"]), dev.index or 0), dev), None
+        return self._body[0]
 
     def __call__(self, x, mask, pose_rep, translation, glob, jointstype, vertstrans, betas=None, beta=0, glob_rot=None, num_person=1,
                  get_rotations_back=False, **kwargs):
@@ -90,7 +183,8 @@ class Rotation2xyz:
             raise TypeError("You must specify global rotation if glob is False")
         if jointstype not in JOINTSTYPES:
             raise NotImplementedError("This jointstype is not implemented.")
-        if jointstype not in SKELETON_JOINTSTYPES:
+        vertices = jointstype == "vertices" and self.mesh is not None
+        if jointstype not in SKELETON_JOINTSTYPES and not vertices:
             raise NotImplementedError(
                 f"jointstype={jointstype!r} is computed from the body model's vertices, which a skeleton file does not hold: "
                 f"only {SKELETON_JOINTSTYPES} (the skeleton's own joints) are served")
@@ -106,6 +200,8 @@ class Rotation2xyz:
             raise ValueError(f"x {tuple(x.shape)}: a {J}-joint skeleton with pose_rep={pose_rep!r}, glob={bool(glob)}, translation={bool(translation)}, "
                              f"num_person={P} takes [B, {want}, {C * P}, T]")
         model = self.model
+        if vertices:
+            return self._vertices(x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back)
         eng = model._engine if (model._engine is not None and not model._engine_stale) else model._get_engine(B, T)[0]
         dev = next(model.parameters()).device
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
@@ -118,6 +214,40 @@ class Rotation2xyz:
                     dist_util.stream_handle(dev))
         out = out.to(x.device)
         if get_rotations_back:      # Rotation2xyz (:152-153): the last person's matrices of the unmasked frames, without and with joint 0
+            r = rot[:, -1] if mc is None else rot[:, -1][mc]
+            r = r.reshape(-1, J, 3, 3)
+            return out, r[:, 1:], r[:, 0]
+        return out
+
+    def _vertices(self, x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back):
+        """jointstype='vertices' (:236-249 / :303-321): [B, V, 3 P, T] by linear blend skinning on the device (rgn_rot2verts)."""
+        J, V = len(self.skeleton["parents"]), self.mesh["v_template"].shape[0]
+        B, T = x.shape[0], x.shape[-1]
+        dev = next(self.model.parameters()).device
+        body = self.body_engine(dev)
+        b = self.betas_vector(betas, beta)
+        bv = None
+        if b.any():
+            if body.nb == 0:
+                raise ValueError("non-zero betas / beta need `shapedirs` in the body file")
+            if len(b) > body.nb:
+                raise ValueError(f"{len(b)} betas but the body file holds {body.nb} shape directions")
+            bv = np.zeros(body.nb, np.float32)
+            bv[:len(b)] = b
+        xc = x.to(device=dev, dtype=torch.float32).contiguous()
+        mc = None if mask is None else mask.to(device=dev).reshape(B, T).bool().contiguous()
+        out = torch.empty((B, V, 3 * P, T), device=dev, dtype=torch.float32)
+        rot = torch.empty((B, P, T, J, 3, 3), device=dev, dtype=torch.float32) if get_rotations_back else None
+        need = body.workspace_bytes(B, T, P)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, device=dev, dtype=torch.uint8)
+        flags = (_lib.R2X_TRANSLATION if translation else 0) | (_lib.R2X_GLOB if glob else 0) | (_lib.R2X_VERTSTRANS if vertstrans else 0)
+        gr = None if glob else np.asarray(glob_rot, dtype=np.float32).reshape(3)
+        with torch.cuda.device(dev):
+            body.rot2verts(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, bv, out, rot,
+                           self._work, dist_util.stream_handle(dev))
+        out = out.to(x.device)
+        if get_rotations_back:
             r = rot[:, -1] if mc is None else rot[:, -1][mc]
             r = r.reshape(-1, J, 3, 3)
             return out, r[:, 1:], r[:, 0]

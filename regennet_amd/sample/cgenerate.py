@@ -7,7 +7,9 @@ The reference pulls actor clips from its h5 datasets (licence-restricted, absent
 `rot2xyz`; this CLI takes actor clips from an .npz (or synthetic ones) and stores the rot6d output ('output',
 'cmotion' keys as in the reference). With `--skeleton FILE.npz` (tools/make_skeleton.py; `synthetic`: synth.make_skeleton, NOT a body model's
 skeleton) it also stores 'motion', the joint positions `model.rot2xyz` gives for the smoothed sample (cgenerate.py:154-163) - forward
-kinematics on the device, no body model needed."""
+kinematics on the device, no body model needed. With `--vertices` and a `--skeleton` that carries a mesh (a body file of
+`tools/make_skeleton.py --mesh`; `synthetic`: synth.make_body) it also stores 'vertices' [N, V, 3, T] and 'faces', the meshes the reference
+renders from (visualize/vis_utils.py:35-41), and `--obj_dir DIR` writes them as DIR/sample{i:02d}/frame{t:03d}.obj."""
 import os
 import time
 import types
@@ -35,22 +37,47 @@ def _load_clips(args, cfg, n):
 
 def set_skeleton(model, args):
     """--skeleton FILE.npz | synthetic -> model.set_skeleton (the model inside a guidance wrapper). True when one was given."""
+    vertices = getattr(args, "vertices", False)
+    if getattr(args, "obj_dir", "") and not vertices:
+        raise SystemExit("--obj_dir writes the meshes of --vertices")
     if not args.skeleton:
+        if vertices:
+            raise SystemExit("--vertices needs --skeleton BODY.npz (tools/make_skeleton.py --mesh) or --skeleton synthetic")
         return False
-    from ..model.rotation2xyz import load_skeleton
-    sk = synth.make_skeleton(model.njoints - 1) if args.skeleton == "synthetic" else load_skeleton(args.skeleton)
+    from ..model.rotation2xyz import load_skeleton_or_body
     if args.skeleton == "synthetic":
-        print(f"--skeleton synthetic: a synthetic {model.njoints - 1}-joint tree (synth.make_skeleton), not a body model's skeleton")
+        sk = synth.make_body(model.njoints - 1) if vertices else synth.make_skeleton(model.njoints - 1)
+        print(f"--skeleton synthetic: a synthetic {model.njoints - 1}-joint tree (synth.make_skeleton), not a body model's skeleton"
+              + (f", under a synthetic {sk['mesh']['v_template'].shape[0]}-vertex surface (synth.make_body)" if vertices else ""))
+    else:
+        sk = load_skeleton_or_body(args.skeleton)
+    if vertices and sk.get("mesh", None) is None:
+        raise SystemExit(f"--vertices: {args.skeleton} is a skeleton file without mesh arrays (write a body file with tools/make_skeleton.py --mesh)")
     model.set_skeleton(sk)
     return True
 
 
-def joint_positions(model, args, sample, y):
+def joint_positions(model, args, sample, y, jointstype=None):
     """The reference's closing call (cgenerate.py:154-158) on this model's rot2xyz: [B, njoints, nfeats, T] -> [B, J, 3, T]."""
     pose_rep = "xyz" if model.data_rep in ("xyz", "hml_vec") else model.data_rep
     mask = None if pose_rep == "xyz" else y["mask"].reshape(sample.shape[0], sample.shape[-1]).bool()
-    return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=args.body_model, vertstrans=True,
+    return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=jointstype or args.body_model, vertstrans=True,
                          num_person=1, betas=None, beta=0, glob_rot=None, get_rotations_back=False)
+
+
+def vertex_positions(model, args, sample, y):
+    """... and the call the reference's mesh export makes (visualize/vis_utils.py:35-41): jointstype='vertices' -> [B, V, 3, T]."""
+    return joint_positions(model, args, sample, y, jointstype="vertices")
+
+
+def mesh_results(model, args, all_vertices, lengths):
+    """The 'vertices' / 'faces' entries of results.npy; --obj_dir: the OBJ sequences beside them."""
+    from ..utils.mesh_io import write_obj_sequences
+    verts, faces = np.concatenate(all_vertices), model.rot2xyz.mesh["faces"]
+    if args.obj_dir:
+        n = write_obj_sequences(args.obj_dir, verts, faces, lengths)
+        print(f"wrote {n} OBJ files under [{os.path.abspath(args.obj_dir)}]")
+    return {"vertices": verts, "faces": faces}
 
 
 def main(argv=None):
@@ -99,7 +126,9 @@ def main(argv=None):
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     eng, _ = inner._get_engine(max(Bl, 1), n_frames)
     with_motion = set_skeleton(inner, args)
-    all_outputs, all_cmotions, all_motions, time_all = [], [], [], 0.0
+    with_vertices = with_motion and args.vertices
+    nverts = inner.rot2xyz.mesh["v_template"].shape[0] if with_vertices else 0
+    all_outputs, all_cmotions, all_motions, all_vertices, time_all = [], [], [], [], 0.0
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
 
     def make_y(rep_i):
@@ -141,6 +170,9 @@ def main(argv=None):
         if with_motion:                            # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
             motion = joint_positions(inner, args, smooth, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
             all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
+        if with_vertices:
+            verts = vertex_positions(inner, args, smooth, y) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)
+            all_vertices.append(dist_util.all_gather_samples(verts, B).cpu().numpy())
         if rank == 0:
             print(f"created {len(all_outputs) * B} samples")
     npy_path = None
@@ -152,6 +184,7 @@ def main(argv=None):
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
         np.save(npy_path, {**({"motion": np.concatenate(all_motions)} if with_motion else {}),
+                           **(mesh_results(inner, args, all_vertices, np.full((len(all_outputs) * B,), n_frames)) if with_vertices else {}),
                            "output": np.concatenate(all_outputs), "cmotion": np.concatenate(all_cmotions),
                            "lengths": np.full((len(all_outputs) * B,), n_frames), "num_samples": args.num_samples,
                            "num_repetitions": args.num_repetitions, "world_size": world})

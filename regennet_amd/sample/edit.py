@@ -75,7 +75,7 @@ def main(argv=None):
     from ..utils.fixseed import fixseed
     from ..utils.model_util import create_model_and_diffusion, load_model_wo_clip
     from ..utils.parser_util import edit_args
-    from .cgenerate import joint_positions, set_skeleton
+    from .cgenerate import joint_positions, mesh_results, set_skeleton, vertex_positions
 
     args = edit_args(argv)
     fixseed(args.seed)
@@ -142,7 +142,9 @@ def main(argv=None):
 
     if world > 1:
         diffusion.agree_x3_tail(model, shape, {"y": make_y(0)} if Bl > 0 else None, sampler="ddim" if args.use_ddim else "ddpm")
-    outs, cms, ins, motions = [], [], [], []
+    with_vertices = with_motion and args.vertices
+    nverts = inner.rot2xyz.mesh["v_template"].shape[0] if with_vertices else 0
+    outs, cms, ins, motions, vertices = [], [], [], [], []
     for rep_i in range(args.num_repetitions):
         if rank == 0:
             print(f"### Start sampling [repetitions #{rep_i}]")
@@ -164,13 +166,17 @@ def main(argv=None):
         if with_motion:
             motion = joint_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
             motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
+        if with_vertices:
+            verts = vertex_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)
+            vertices.append(dist_util.all_gather_samples(verts, B).cpu().numpy())
     npy_path = None
     if rank == 0:
         out_path = args.output_dir or os.path.join(os.path.dirname(args.model_path) or ".", f"edit_seed{args.seed}_{args.edit_mode}")
         os.makedirs(out_path, exist_ok=True)
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
-        np.save(npy_path, {**({"motion": np.concatenate(motions)} if with_motion else {}), "output": np.concatenate(outs), "cmotion": np.concatenate(cms), "input_motions": np.concatenate(ins),
+        np.save(npy_path, {**({"motion": np.concatenate(motions)} if with_motion else {}),
+                           **(mesh_results(inner, args, vertices, np.full((len(outs) * B,), n_frames)) if with_vertices else {}), "output": np.concatenate(outs), "cmotion": np.concatenate(cms), "input_motions": np.concatenate(ins),
                            "mask": np.concatenate([full_mask] * len(outs)), "edit_mode": args.edit_mode,
                            "lengths": np.full((len(outs) * B,), n_frames), "num_samples": args.num_samples,
                            "num_repetitions": args.num_repetitions, "world_size": world})

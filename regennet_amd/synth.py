@@ -329,3 +329,63 @@ def make_skeleton(njoints=55, depth=10, nbetas=10, seed=0):
         rest[i] = rest[parents[i]] + d / np.linalg.norm(d) * rng.uniform(0.05, 0.30)
     return {"rest_joints": rest.astype(np.float32), "parents": parents,
             "shape_joints": (0.01 * rng.standard_normal((J, 3, int(nbetas)))).astype(np.float32), "body_model": f"synthetic{J}"}
+
+
+def make_body(njoints=55, nverts=130, nbetas=10, seed=0, identity_joints=None):
+    """A deterministic SYNTHETIC body for tests, tools and `--skeleton synthetic --vertices`: the skeleton of make_skeleton(njoints, nbetas=nbetas,
+    seed=seed), unchanged, under a surface of `nverts` vertices, as model/rotation2xyz.py check_body returns a body file (skeleton keys + 'mesh').
+      v_template       within 10 cm of a bone (the segment joint - parent; of the joint itself where there is one joint)
+      lbs_weights      four non-zero weights per vertex (fewer where the tree has fewer joints): the bone's joint, its parent and neighbours, normalised
+      posedirs         0.01 N(0, 1)
+      J_regressor      (mesh['J_regressor'], for tests; no file holds it) synthetic and row-stochastic: with V >= 2 J joint j is the midpoint of
+                       vertices 2 j and 2 j + 1, which lie opposite each other about it; with J <= V < 2 J vertex j sits on joint j
+      shapedirs        0.005 N(0, 1), then shifted on each joint's own vertices so that J_regressor @ shapedirs IS the skeleton's shape_joints:
+                       with J_regressor @ v_template = rest_joints, the rest joints of any betas are the regressor applied to v_shaped
+      faces            a triangle strip over the vertex order
+      identity_joints  default 22 - 24 for 55 joints (the jaw and eyes Rotation2xyz_x does not hand over), else none
+    With fewer vertices than joints there is no such regressor: shapedirs are then plain noise and mesh['J_regressor'] is None.
+    It has a body model's array shapes and nothing else of one."""
+    sk = make_skeleton(njoints, nbetas=nbetas, seed=seed)
+    rng = np.random.Generator(np.random.PCG64([seed, 0x6d657368]))
+    J, V, nb = int(njoints), int(nverts), int(nbetas)
+    rest, parents = sk["rest_joints"].astype(np.float64), sk["parents"]
+    per = 2 if V >= 2 * J else (1 if V >= J else 0)                                # regressor vertices per joint, in front of the others
+    bone = rng.integers(1, J, V) if J > 1 else np.zeros(V, np.int64)              # the joint at the far end of the vertex's bone
+    bone[:per * J] = np.repeat(np.arange(J), per)
+    near = np.maximum(parents[bone], 0)
+    s = rng.uniform(0, 1, (V, 1))
+    d = rng.standard_normal((V, 3))
+    d *= rng.uniform(0, 0.10, (V, 1)) / np.linalg.norm(d, axis=1, keepdims=True)
+    vt = rest[near] * (1 - s) + rest[bone] * s + d
+    if per == 2:
+        vt[0:2 * J:2], vt[1:2 * J:2] = rest + d[0:2 * J:2], rest - d[0:2 * J:2]
+    elif per == 1:
+        vt[:J] = rest
+    children = [[int(c) for c in np.flatnonzero(parents == j)] for j in range(J)]
+    w = np.zeros((V, J))
+    for v in range(V):
+        b, n = int(bone[v]), int(near[v])
+        group = list(dict.fromkeys([b, n, int(max(parents[n], 0))] + children[b] + children[n]))[:4]
+        for j in range(J):                                                         # (a small tree: fill up to four with the lowest free joints)
+            if len(group) >= min(4, J):
+                break
+            if j not in group:
+                group.append(j)
+        w[v, group] = rng.uniform(0.1, 1.0, len(group))
+    w = (w / w.sum(1, keepdims=True)).astype(np.float32)
+    posedirs = (0.01 * rng.standard_normal((9 * (J - 1), 3 * V))).astype(np.float32)
+    reg = None
+    if per:
+        reg = np.zeros((J, V))
+        for k in range(per):
+            reg[np.arange(J), per * np.arange(J) + k] = 1.0 / per
+    mesh = {"v_template": vt.astype(np.float32), "posedirs": posedirs, "lbs_weights": w, "shapedirs": None, "J_regressor": reg,
+            "faces": np.stack([np.arange(0, V - 2), np.arange(1, V - 1), np.arange(2, V)], 1).astype(np.int32) if V >= 3 else np.zeros((0, 3), np.int32),
+            "identity_joints": np.asarray(([22, 23, 24] if J == 55 else []) if identity_joints is None else identity_joints, dtype=np.int32).reshape(-1)}
+    if nb > 0:
+        sd = 0.005 * rng.standard_normal((V, 3, nb))
+        if per:                                                                    # every vertex of joint j takes the same shift: the row's weights sum to 1
+            sd[:per * J] += np.repeat(sk["shape_joints"].astype(np.float64) - np.einsum("jv,vck->jck", reg, sd), per, axis=0)
+        mesh["shapedirs"] = sd.astype(np.float32)
+    sk["mesh"] = mesh
+    return sk

@@ -70,6 +70,9 @@ def add_generate_options(p):
     g.add_argument("--synthetic", action="store_true", help="synthetic checkpoint + actor motions (no assets needed)")
     g.add_argument("--skeleton", default="", type=str,
                    help="skeleton npz (tools/make_skeleton.py) or 'synthetic': also store 'motion', the joint positions model.rot2xyz gives")
+    g.add_argument("--vertices", action="store_true",
+                   help="also store 'vertices' [N,V,3,T] and 'faces': needs a --skeleton with mesh arrays (tools/make_skeleton.py --mesh; 'synthetic': synth.make_body)")
+    g.add_argument("--obj_dir", default="", type=str, help="with --vertices: write DIR/sample{i:02d}/frame{t:03d}.obj")
     g.add_argument("--precision", default="bf16_x3tail", choices=["f32", "bf16x3", "bf16", "bf16_x3tail"], type=str)
 
 

@@ -9,7 +9,16 @@ The skeleton file holds what the posed skeleton joints depend on, a few hundred 
     shape_joints [J, 3, nb]  = J_regressor @ shapedirs[:, :, k]  for the first nb shape directions
     parents      [J]         = kintree_table[0], root set to -1
 
-Read it with regennet_amd.model.rotation2xyz.load_skeleton, or pass its path to `--skeleton` of the sampling CLIs."""
+Read it with regennet_amd.model.rotation2xyz.load_skeleton, or pass its path to `--skeleton` of the sampling CLIs.
+
+With `--mesh` the file becomes a BODY FILE, which also serves jointstype='vertices' (load_body; `--vertices` of the CLIs): the arrays above and
+
+    v_template      [V, 3]
+    posedirs        [9 (J - 1), 3 V]  the model file's [V, 3, 9 (J - 1)] as smplx.lbs.lbs multiplies with it
+    lbs_weights     [V, J]            `weights` of the model file
+    shapedirs       [V, 3, nb]
+    faces           [F, 3] int32      where the model file has `f`
+    identity_joints [22, 23, 24] for --body_model smplx (the jaw and eye rotations the reference's wrapper does not hand over), else empty"""
 import argparse
 
 import numpy as np
@@ -31,17 +40,37 @@ def make_skeleton(model, num_betas=10, body_model=""):
     return out
 
 
+def make_mesh(model, num_betas=10, body_model=""):
+    """dict of the --mesh arrays from a mapping with v_template, weights, posedirs (and shapedirs, f)."""
+    vt = np.asarray(model["v_template"], dtype=np.float32)
+    V = vt.shape[0]
+    w = np.asarray(model["weights"], dtype=np.float32)
+    pd = np.asarray(model["posedirs"], dtype=np.float32)
+    assert w.ndim == 2 and w.shape[0] == V and pd.shape[:2] == (V, 3) and pd.shape[2] == 9 * (w.shape[1] - 1), (vt.shape, w.shape, pd.shape)
+    out = {"v_template": vt, "posedirs": np.ascontiguousarray(pd.reshape(3 * V, -1).T), "lbs_weights": w,
+           "identity_joints": np.array([22, 23, 24] if body_model == "smplx" else [], dtype=np.int32)}
+    if "shapedirs" in model and num_betas > 0:
+        out["shapedirs"] = np.ascontiguousarray(np.asarray(model["shapedirs"], dtype=np.float32)[:, :, :num_betas])
+    if "f" in model:
+        out["faces"] = np.asarray(model["f"]).astype(np.int32)
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("model", help="body-model npz (J_regressor, v_template, shapedirs, kintree_table)")
     p.add_argument("--out", required=True)
     p.add_argument("--body_model", default="", help="label stored in the file, e.g. smplx")
     p.add_argument("--num_betas", default=10, type=int)
+    p.add_argument("--mesh", action="store_true", help="write a body file: also v_template, posedirs, lbs_weights, shapedirs, faces, identity_joints")
     args = p.parse_args(argv)
     with np.load(args.model, allow_pickle=False) as z:
         sk = make_skeleton({k: z[k] for k in z.files if k in ("J_regressor", "v_template", "shapedirs", "kintree_table")}, args.num_betas, args.body_model)
+        if args.mesh:
+            sk.update(make_mesh({k: z[k] for k in z.files if k in ("v_template", "weights", "posedirs", "shapedirs", "f")}, args.num_betas, args.body_model))
     np.savez(args.out, **sk)
-    print(f"{args.out}: {len(sk['parents'])} joints, {sk.get('shape_joints', np.zeros((0, 0, 0))).shape[2]} shape directions")
+    print(f"{args.out}: {len(sk['parents'])} joints, {sk.get('shape_joints', np.zeros((0, 0, 0))).shape[2]} shape directions"
+          + (f", {sk['v_template'].shape[0]} vertices" if args.mesh else ""))
     return args.out
 
 
