@@ -285,6 +285,59 @@ RGN_API int rgn_rot2verts(rgn_body_handle b, const float* x_dev, const uint8_t* 
                           float* verts_dev /*[B,V,3P,T]*/, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes,
                           void* stream);
 
+/* ---- Rendering: z-buffer rasteriser over the vertices rgn_rot2verts writes ----
+ * Replaces render/crendermotion.py:20-42 (render_video: centring, the frame loop, the colours) and render/renderer.py:51-150 (Renderer: pyrender on
+ * OSMesa, one scene rebuild per frame). The geometry is the reference's - camera, centring, colours, light positions, background; its PBR material
+ * is replaced by the Lambert model below, and its clip volume |Z| <= 1 is NOT reproduced: every Z is drawn.
+ *   Input      verts fp32 [B, V, 3 P, T] (person p: channels 3 p .. 3 p + 2), faces int32 [F, 3] shared by all persons, mask uint8 [B, T] or NULL.
+ *              The global index of person p's face f is p F + f.
+ *   Centring   (params.center != 0; crendermotion.py:24-26) per motion, c = fp32(the mean, summed in fp64, over the vertices of person 0 in the
+ *              motion's first unmasked frame); (X, Y, Z) = vertex - c in fp32 for every person and frame of the motion (c = 0 otherwise).
+ *   Camera     WeakPerspectiveCamera, cam = (sx, sy, tx, ty), with the reference's 180-degree turn about x (renderer.py:98-99) and the image's row
+ *              order folded in:  col = (1 + sx (X + tx)) (W / 2),  row = (1 + sy (Y + ty)) (H / 2)  in fp32 in this order, no contraction;
+ *              depth is Z, the smaller Z the nearer. Pixel (i, j) is sampled at its centre (j + 0.5, i + 0.5).
+ *   Coverage   exact integer arithmetic. x = clamp(rint(256 col), +-2^20), y likewise: pixel centres sit at (256 j + 128, 256 i + 128). With
+ *              E(a -> b; p) = (bx - ax)(py - ay) - (by - ay)(px - ax) in 64 bits, area = E(a -> b; c). area == 0 draws nothing; area < 0 swaps b
+ *              and c (two-sided, no culling). e0 = E(b -> c; p), e1 = E(c -> a; p), e2 = E(a -> b; p), e0 + e1 + e2 = area. The pixel is covered
+ *              iff for each edge e > 0, or e == 0 and the edge a -> b OWNS its points: dy < 0 (a left edge), or dy == 0 and dx > 0 (a top edge),
+ *              with (dx, dy) = b - a after the swap. A centre on an edge two triangles share from opposite sides belongs to exactly one of them.
+ *   Depth      z = (fp32(e0) za + fp32(e1) zb + fp32(e2) zc) / fp32(area) in fp32. The winner of a pixel is the smallest z, at equal fp32 z the
+ *              lower global face index: the unsigned minimum of (order-preserving bits of z) << 32 | face index, whatever order triangles come in.
+ *   Normals    per vertex, the sum over its faces, in ascending face order, of (v1 - v0) x (v2 - v0) of the centred positions, divided by its
+ *              length (0 stays 0); per pixel n = b0 na + b1 nb + b2 nc with b_k = fp32(e_k) / fp32(area), normalised the same way, negated if
+ *              n_Z > 0 (away from the camera).
+ *   Shading    I = 0.4 + 0.2 sum_l max(0, n . normalize(L_l - p)), p = (b-interpolated X, Y, and z), L = (0, 1, -1), (0, -1, -1), (1, -1, -2):
+ *              the reference's three point lights (renderer.py:72-82) in vertex coordinates, its ambient 0.4, and the weight at which three
+ *              fully lit lights give exactly 1. rgb = rint(255 base_p I), clamped to [0, 255]; person p takes colors[min(p, 7)].
+ *   Output     rgb uint8 [B, T, H, W, 3]; depth fp32 [B, T, H, W] (nullable; +inf on background); face int32 [B, T, H, W] (nullable; global face
+ *              index, -1 on background). Uncovered pixels, and every pixel of a masked frame, are rint(255 background). */
+#define RGN_RENDER_MAX_PERSONS 8
+typedef struct {
+    int32_t width, height;                          /* [1, 4096] each (crendermotion.py:109-110: 1024 x 1024) */
+    float cam[4];                                   /* sx, sy, tx, ty (crendermotion.py:20: 0.75, 0.75, 0, 0.10) */
+    int32_t center;                                 /* crendermotion.py:24-26 */
+    float colors[RGN_RENDER_MAX_PERSONS][3];        /* base colours in [0, 1] (crendermotion.py:20, renderer.py:86-89) */
+    float background[3];                            /* in [0, 1] (renderer.py:155: white) */
+} rgn_render_params;
+/* A renderer for one mesh topology on `device`: uploads faces and the vertex -> face adjacency built from them. Replaces Renderer.__init__
+ * (renderer.py:52-83) with its faces file. The arguments are checked before the device is touched: RGN_ERR_INVALID_ARG, with text in
+ * rgn_render_last_error(NULL), for V outside [1, 65536], F < 1, null faces / out, a face index outside [0, V). */
+typedef struct rgn_render_ctx* rgn_render_handle;
+RGN_API int rgn_render_create(int32_t device, int32_t V, int32_t F, const int32_t* faces_host /*[F,3]*/, rgn_render_handle* out);
+RGN_API int rgn_render_destroy(rgn_render_handle r);
+RGN_API const char* rgn_render_last_error(rgn_render_handle r);   /* NULL: the calling thread's last failed rgn_render_create */
+/* Bytes of device memory rgn_render needs for B motions of T frames and num_person persons (per frame and person: 40 bytes a vertex, about 8 a
+ * face; it does not depend on the image size, which is only checked). */
+RGN_API int rgn_render_workspace(rgn_render_handle r, int32_t B, int32_t T, int32_t num_person, int32_t width, int32_t height, uint64_t* nbytes);
+/* Replaces Renderer.render (renderer.py:85-150) for every frame of B motions at once. RGN_ERR_INVALID_ARG, with text: width or height outside
+ * [1, 4096], B, T or num_person < 1, num_person x F >= 2^31, null verts / rgb / work / params, a work_bytes below rgn_render_workspace's, a
+ * work_dev that is not 16-byte aligned, a batch larger than one launch covers (B x T x num_person x max(V, F) items or
+ * B x T x tiles of 64 x 64 pixels above 2^24 - 1 workgroups). The work is enqueued on `stream` itself; the call allocates nothing,
+ * keeps no state and can be captured into a graph. Non-finite vertices give unspecified pixels, never an access outside the buffers. */
+RGN_API int rgn_render(rgn_render_handle r, const float* verts_dev /*[B,V,3P,T]*/, const uint8_t* mask_dev /*nullable [B,T]*/, int32_t B, int32_t T,
+                       int32_t num_person, const rgn_render_params* params, uint8_t* rgb_dev /*[B,T,H,W,3]*/, float* depth_dev /*nullable [B,T,H,W]*/,
+                       int32_t* face_dev /*nullable [B,T,H,W]*/, void* work_dev, uint64_t work_bytes, void* stream);
+
 /* Introspection for bench/profiling: name and accumulated HIP-event time (ms) + launch count of the
  * internal kernel classes since the last reset; timing is only collected when enabled. */
 RGN_API int rgn_profile_enable(rgn_handle h, int32_t on);

@@ -100,6 +100,21 @@ SYMBOLS.update({
     "rgn_rot2verts": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
 })
 
+RENDER_MAX_PERSONS = 8                 # RGN_RENDER_MAX_PERSONS
+
+
+class RgnRenderParams(C.Structure):
+    _fields_ = [("width", _i32), ("height", _i32), ("cam", _f32 * 4), ("center", _i32), ("colors", (_f32 * 3) * RENDER_MAX_PERSONS), ("background", _f32 * 3)]
+
+
+SYMBOLS.update({
+    "rgn_render_create": (C.c_int, [_i32, _i32, _i32, _vp, C.POINTER(_vp)]),
+    "rgn_render_destroy": (C.c_int, [_vp]),
+    "rgn_render_last_error": (C.c_char_p, [_vp]),
+    "rgn_render_workspace": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "rgn_render": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(RgnRenderParams), _vp, _vp, _vp, _vp, _u64, _vp]),
+})
+
 _lib = None
 
 
@@ -437,3 +452,56 @@ class BodyEngine:
         self._ck(self.lib.rgn_rot2verts(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, int(pose_rep), int(num_person),
                                         int(flags), pgr, pbe, _ptr(verts), _ptr(rotmat), _ptr(work), int(work.numel() * work.element_size()),
                                         C.c_void_p(stream)))
+
+
+class RenderEngine:
+    """Owns one rgn_render_handle: the faces of one mesh topology (and the vertex -> face adjacency built from them) on one device."""
+
+    def __init__(self, faces, V, device_index):
+        self.lib = load()
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        self.V, self.F = int(V), int(f.shape[0])
+        h = C.c_void_p()
+        code = self.lib.rgn_render_create(int(device_index), self.V, self.F, f.ctypes.data_as(C.c_void_p), C.byref(h))
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_render_last_error(None) or b"").decode())
+        self.h = h
+
+    def _ck(self, code):
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_render_last_error(self.h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rgn_render_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, B, T, num_person, width, height):
+        n = C.c_uint64()
+        self._ck(self.lib.rgn_render_workspace(self.h, int(B), int(T), int(num_person), int(width), int(height), C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def params(width, height, cam, center, colors, background):
+        """rgn_render_params from plain sequences; `colors`: one (r, g, b) per person, the last repeated up to the struct's RENDER_MAX_PERSONS."""
+        p = RgnRenderParams(width=int(width), height=int(height), center=int(bool(center)))
+        p.cam[:] = [float(c) for c in cam]
+        colors = [tuple(float(x) for x in c) for c in colors]
+        for i in range(RENDER_MAX_PERSONS):
+            p.colors[i][:] = colors[min(i, len(colors) - 1)]
+        p.background[:] = [float(c) for c in background]
+        return p
+
+    def render(self, verts, mask, num_person, params, rgb, depth, face, work, stream):
+        """rgn_render: verts fp32 [B, V, 3 * num_person, T] and mask (bool / uint8 [B, T] or None), contiguous on the renderer's device -> rgb uint8
+        [B, T, H, W, 3] (and depth fp32 / face int32 [B, T, H, W] when given); work: a uint8 tensor of at least workspace_bytes(...)."""
+        assert verts.is_contiguous() and rgb.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        assert tuple(verts.shape[1:3]) == (self.V, 3 * int(num_person)), (tuple(verts.shape), self.V, num_person)
+        self._ck(self.lib.rgn_render(self.h, _ptr(verts), _ptr(mask), int(verts.shape[0]), int(verts.shape[-1]), int(num_person), C.byref(params),
+                                     _ptr(rgb), _ptr(depth), _ptr(face), _ptr(work), int(work.numel() * work.element_size()), C.c_void_p(stream)))

@@ -9,7 +9,8 @@ The reference pulls actor clips from its h5 datasets (licence-restricted, absent
 skeleton) it also stores 'motion', the joint positions `model.rot2xyz` gives for the smoothed sample (cgenerate.py:154-163) - forward
 kinematics on the device, no body model needed. With `--vertices` and a `--skeleton` that carries a mesh (a body file of
 `tools/make_skeleton.py --mesh`; `synthetic`: synth.make_body) it also stores 'vertices' [N, V, 3, T] and 'faces', the meshes the reference
-renders from (visualize/vis_utils.py:35-41), and `--obj_dir DIR` writes them as DIR/sample{i:02d}/frame{t:03d}.obj."""
+renders from (visualize/vis_utils.py:35-41), and `--obj_dir DIR` writes them as DIR/sample{i:02d}/frame{t:03d}.obj. `--render_dir DIR` draws them on the
+device (utils/render.py; `--render_size N`, default 1024 as render/crendermotion.py:109-110) and writes DIR/sample{i:02d}/frame{t:03d}.png."""
 import os
 import time
 import types
@@ -40,6 +41,8 @@ def set_skeleton(model, args):
     vertices = getattr(args, "vertices", False)
     if getattr(args, "obj_dir", "") and not vertices:
         raise SystemExit("--obj_dir writes the meshes of --vertices")
+    if getattr(args, "render_dir", "") and not vertices:
+        raise SystemExit("--render_dir renders the meshes of --vertices")
     if not args.skeleton:
         if vertices:
             raise SystemExit("--vertices needs --skeleton BODY.npz (tools/make_skeleton.py --mesh) or --skeleton synthetic")
@@ -71,12 +74,20 @@ def vertex_positions(model, args, sample, y):
 
 
 def mesh_results(model, args, all_vertices, lengths):
-    """The 'vertices' / 'faces' entries of results.npy; --obj_dir: the OBJ sequences beside them."""
-    from ..utils.mesh_io import write_obj_sequences
+    """The 'vertices' / 'faces' entries of results.npy; --obj_dir: the OBJ sequences beside them; --render_dir: the rendered frames."""
+    from ..utils.mesh_io import write_obj_sequences, write_png_sequences
     verts, faces = np.concatenate(all_vertices), model.rot2xyz.mesh["faces"]
     if args.obj_dir:
         n = write_obj_sequences(args.obj_dir, verts, faces, lengths)
         print(f"wrote {n} OBJ files under [{os.path.abspath(args.obj_dir)}]")
+    if getattr(args, "render_dir", ""):                 # one motion at a time: a motion's frames are 3 W H T bytes
+        from ..utils.render import MeshRenderer
+        renderer, n = MeshRenderer(faces, next(model.parameters()).device), 0
+        for i in range(len(verts)):
+            frames = renderer.render(torch.from_numpy(verts[i:i + 1]), width=args.render_size, height=args.render_size)
+            n += write_png_sequences(args.render_dir, frames.cpu().numpy(), lengths[i:i + 1], first=i)
+        renderer.close()
+        print(f"wrote {n} PNG files under [{os.path.abspath(args.render_dir)}]")
     return {"vertices": verts, "faces": faces}
 
 

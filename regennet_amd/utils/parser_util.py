@@ -73,6 +73,8 @@ def add_generate_options(p):
     g.add_argument("--vertices", action="store_true",
                    help="also store 'vertices' [N,V,3,T] and 'faces': needs a --skeleton with mesh arrays (tools/make_skeleton.py --mesh; 'synthetic': synth.make_body)")
     g.add_argument("--obj_dir", default="", type=str, help="with --vertices: write DIR/sample{i:02d}/frame{t:03d}.obj")
+    g.add_argument("--render_dir", default="", type=str, help="with --vertices: render the meshes on the device and write DIR/sample{i:02d}/frame{t:03d}.png")
+    g.add_argument("--render_size", default=1024, type=int, help="with --render_dir: width and height of the frames (render/crendermotion.py:109-110: 1024)")
     g.add_argument("--precision", default="bf16_x3tail", choices=["f32", "bf16x3", "bf16", "bf16_x3tail"], type=str)
 
 
