@@ -21,7 +21,7 @@
 // Attention: heads two at a time, waves 0-3 / 4-7 one head each, wave = 32 dh columns of q, k, v for all 64 tokens (96 x 64
 // accumulators); q, k, v, the scores and p never leave the register file (rgn_qkv_attn.hip: the C/D layouts of q^T, k^T, v and
 // of the softmaxed S^T agree as MFMA operands by construction); the activation operand comes from the RESIDENT image X, so the
-// k-loop has no barrier and no staging at all. Layer tail: the structure of rgn_mlp2.hip (MT = 2) on the resident images.
+// k-loop has no barrier and no staging at all. Layer tail: the shared functions of rgn_tail.h (the ones k_mlp2 runs) on the resident images.
 // Weights: fragment-ordered planes streamed into register rings through buffer loads (scalar resource, compile-time offsets).
 //
 // Three instantiations: k_layers<false> - the stack of ONE evaluation (planes in, planes out); k_layers<true> - whole runs of sampler steps: after the
@@ -31,6 +31,7 @@
 // conditional and its unconditional evaluation back to back, the conditional x0 parked in global scratch meanwhile.
 #include "rgn_internal.h"
 #include "rgn_device.h"
+#include "rgn_tail.h"
 #include "rgn_sampler.h"
 
 #include <hip/hip_runtime.h>
@@ -54,6 +55,9 @@ static_assert(LY_PF + 8 * 256 <= LY_LDS, "LDS map");
 enum { V_BO = 0, V_G1 = 64, V_G2 = 128, V_B2 = 192, V_SPV = 256, V_BF1 = 320 /* 2 x 64: hidden halves */, V_BF2 = 448, V_G3 = 512, V_B3 = 576 };
 constexpr int LY_RDA = 6;   // in_proj weight ring: granules (half k-steps) of 3 fragments (q | k | v): 72 registers
 constexpr int LY_RDM = 8;   // layer-tail weight ring: granules of 2 fragments: 64 registers
+struct LYT {                // the layer tail's constants (rgn_tail.h): 2 x 2 tiles per wave, 8 waves, 64 rows
+    static constexpr int MT = 2, NT = 2, NW = 8, R = 64, RD = LY_RDM, KB = LY_KB, RED = LY_RED, REDF = LY_REDF;
+};
 
 #ifdef RGN_LY_STAMPS
 __device__ long long g_ly_st[1024][16];
@@ -98,7 +102,6 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
 #endif
     float* vec = reinterpret_cast<float*>(smem + LY_VEC) + wave * LY_VECW;   // this wave's private region
     const int lane16 = lane * 16;
-    const int swz = (l31 >> 2) & 3;
     // ---- the sample's residual rows -> X by DMA: 16 k-blocks x 4 pieces of 1 KiB (16 rows x 64 B); padding rows replicate the
     //      last token (row-local everywhere, masked as keys)
     {
@@ -112,181 +115,16 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         }
     }
     const int first_step = (g.stepvec || STEPS) ? *g.d_step : 0;
-    // B-operand fragment of token l31 (+ 32 ta: an immediate offset of 2 KiB) inside a k-block image, per 16-wide k-half; reads of
-    // the second image want their own base registers (16-bit ds_read offsets)
+    // ---- the layer tail's shared machinery (rgn_tail.h): accumulator <-> image map, weight ring, GEMM pass, LayerNorm, epilogue sweeps, FFN stage.
+    //      tl: the lane's opaque LDS bases, made once here. a_off / a_offy: B-operand fragment offsets into the images X and Y
+    const TailLane tl = tail_lane<LYT>(smem, lane, wave);
+    static_assert(LY_X == 0, "a_off addresses the image at byte 0");
     int a_off[2], a_offy[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        a_off[ks] = l31 * 64 + (((2 * ks + kh) ^ swz) << 4);
-        a_offy[ks] = a_off[ks] + LY_Y;
-    }
-    // element (token 32 mt + l31, column 64 wave + 32 nt + 8 i4 + 4 kh + e) <-> register acc[nt][mt][4 i4 + e] of the layer tail;
-    // its 8-byte run inside an image
-    auto col4 = [&](int nt, int i4) { return 32 * nt + 8 * i4 + 4 * kh; };
-    int img_base = (2 * wave) * LY_KB + l31 * 64 + 8 * kh;
-    asm volatile("" : "+v"(img_base));
-    auto img_off = [&](int nt, int i4, int mt) { return img_base + nt * LY_KB + mt * 2048 + ((i4 ^ swz) << 4); };
-    int red_base = LY_RED + 4 * l31;
-    asm volatile("" : "+v"(red_base));
-    const float invn = 1.0f / 512.f;
+    tail_a_off(a_off, lane);
+    tail_a_off(a_offy, a_off, LY_Y);
+    using Pass = TailPass;
+    op8 wf[LY_RDM][2];                                           // the layer tail's weight ring
     const float qs2 = g.qscale * 1.44269504088896340736f;        // 1 / sqrt(dh) in log2 units, applied INSIDE the softmax's exponent: exp2(qs2 s - qs2 max), one FMA where the subtraction was
-
-    struct Pass { __amdgpu_buffer_rsrc_t rs; int kstride, hs0; };
-    op8 wf[LY_RDM][2];
-    auto load_g = [&](const Pass& ps, int hs_rel, int slot) {
-        const int hs = ps.hs0 + hs_rel;
-        int soff;
-        asm volatile("s_mov_b32 %0, %1" : "=s"(soff) : "i"((hs >> 1) * ps.kstride + (hs & 1) * 1024));
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-            wf[slot][nt] = __builtin_bit_cast(op8, __builtin_amdgcn_raw_buffer_load_b128(ps.rs, lane16, soff + nt * 2048, 0));
-    };
-    // one GEMM pass over K = 512 from the image at byte offsets aoff (see rgn_mlp2.hip): the ring never drains between passes
-    auto gemm_n = [&](f32x16 (&acc)[2][2], const int (&aoff)[2], const Pass& cur, const Pass& nxt, auto chain, auto extra, auto ngran) {
-        constexpr int EX = decltype(extra)::value, AH = LY_RDM - 1, NG = decltype(ngran)::value;   // NG granules = NG / 2 k-blocks
-        constexpr bool CH = decltype(chain)::value;
-        __builtin_amdgcn_sched_barrier(0);
-        op8 af[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) af[mt] = *reinterpret_cast<const op8*>(smem + aoff[0] + mt * 2048);
-#pragma unroll
-        for (int hs = 0; hs < NG; ++hs) {
-            op8 afn[2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                afn[mt] = af[mt];
-                if (hs + 1 < NG) afn[mt] = *reinterpret_cast<const op8*>(smem + ((hs + 1) >> 1) * LY_KB + aoff[(hs + 1) & 1] + mt * 2048);
-            }
-            if (hs + AH < NG) load_g(cur, hs + AH, (hs + AH) % LY_RDM);
-            else if (CH) load_g(nxt, hs + AH - NG, (hs + AH) % LY_RDM);
-            if (hs + AH < NG || CH) {
-                if (hs < AH) wait_vmcnt<2 * AH + EX>();
-                else wait_vmcnt<2 * AH>();
-            }
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) acc[nt][mt] = OP::mfma(wf[hs % LY_RDM][nt], af[mt], acc[nt][mt]);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) af[mt] = afn[mt];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto init_bias = [&](f32x16 (&acc)[2][2], const float* bias) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + col4(nt, i4));
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[nt][mt][4 * i4 + e] = bb[e];
-            }
-    };
-    // LayerNorm over the 512 columns of every token, in place: one exchange of (sum, sum of squares) - rgn_mlp2.hip
-    int red_base2 = red_base + 128 * kh;                         // post-barrier reads: lane (l31, kh) reduces token 32 kh + l31
-    asm volatile("" : "+v"(red_base2));
-    auto layernorm = [&](f32x16 (&acc)[2][2], const float* gam, auto slot, auto shift /* (nt, i4) -> f32x4 */) {
-        const char* buf = smem + red_base + decltype(slot)::value * LY_REDF * 4;
-        const char* buf2 = smem + red_base2 + decltype(slot)::value * LY_REDF * 4;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            f32x2 s2 = f32x2{0.f, 0.f}, q2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    const f32x2 v = f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]};
-                    s2 += v;
-                    q2 = __builtin_elementwise_fma(v, v, q2);
-                }
-            float s = s2[0] + s2[1], q = q2[0] + q2[1];
-            half_swap(s, q);                                        // s = [s.lo | q.lo], q = [s.hi | q.hi]
-            *reinterpret_cast<float*>(const_cast<char*>(buf) + (kh * 512 + wave * 64 + 32 * mt) * 4) = s + q;   // kh = 0: the sum, kh = 1: the sum of squares
-        }
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        // the halves share the work: lane (l31, kh) reduces the eight partials of token 32 kh + l31, then the two results change hands
-        f32x2 rs[2], nm[2];
-        {
-            float p[2][8];
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int ww = 0; ww < 8; ++ww) p[st][ww] = *reinterpret_cast<const float*>(buf2 + (st * 512 + ww * 64) * 4);
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int dd = 1; dd < 8; dd *= 2)
-#pragma unroll
-                    for (int ww = 0; ww < 8; ww += 2 * dd) p[st][ww] += p[st][ww + dd];
-            const float mean = p[0][0] * invn;
-            const float var = __builtin_fmaxf(p[1][0] * invn - mean * mean, 0.f);
-            float r0 = __builtin_amdgcn_rsqf(var + 1e-5f), n0 = -mean * r0;
-            float r1 = r0, n1 = n0;
-            asm volatile("" : "+v"(r1), "+v"(n1));               // (copies in registers of their own)
-            half_swap(r0, r1);                                      // r0 = token l31's (tile 0), r1 = token 32 + l31's (tile 1), in every lane
-            half_swap(n0, n1);
-            rs[0] = f32x2{r0, r0}; rs[1] = f32x2{r1, r1};
-            nm[0] = f32x2{n0, n0}; nm[1] = f32x2{n1, n1};
-        }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            f32x4 ga[4], sh[4];
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) {
-                ga[i4] = *reinterpret_cast<const f32x4*>(gam + col4(nt, i4));
-                sh[i4] = shift(nt, i4);
-            }
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int e = 0; e < 4; e += 2) {
-                        const f32x2 t = __builtin_elementwise_fma(f32x2{acc[nt][mt][4 * i4 + e], acc[nt][mt][4 * i4 + e + 1]}, rs[mt], nm[mt]);   // (v - mean) rstd
-                        const f32x2 o = __builtin_elementwise_fma(t, f32x2{ga[i4][e], ga[i4][e + 1]}, f32x2{sh[i4][e], sh[i4][e + 1]});
-                        acc[nt][mt][4 * i4 + e] = o[0];
-                        acc[nt][mt][4 * i4 + e + 1] = o[1];
-                    }
-        }
-    };
-    auto store_img = [&](const f32x16 (&acc)[2][2], int img) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    op4 hh;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) hh[e] = (op_t)acc[nt][mt][4 * i4 + e];
-                    *reinterpret_cast<op4*>(smem + img + img_off(nt, i4, mt)) = hh;
-                }
-    };
-    // acc += bf16 residual from the image X (this wave's own columns)
-    auto add_resid = [&](f32x16 (&acc)[2][2]) {
-        op4 rr[2][2][4];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int i4 = 0; i4 < 4; ++i4) rr[nt][mt][i4] = *reinterpret_cast<const op4*>(smem + LY_X + img_off(nt, i4, mt));
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[nt][mt][4 * i4 + e] += (float)rr[nt][mt][i4][e];
-    };
-
-    auto gemm32 = [&](f32x16 (&acc)[2][2], const int (&aoff)[2], const Pass& cur, const Pass& nxt, auto chain, auto extra) {
-        gemm_n(acc, aoff, cur, nxt, chain, extra, std::integral_constant<int, 32>{});
-    };
 
     // ---- in_proj bias of the NEXT round, requested a phase ahead (before the previous layer's norm3 / during the previous round's softmax), so the
     //      round's first MFMA does not wait an L2 round trip for its accumulators' start value. q: register i <-> dh 8 (i >> 2) + 4 kh + (i & 3);
@@ -319,8 +157,8 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             const int cb0 = 2 * wv;
             const Pass p_out{__builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Wout) + (size_t)cb0 * 1024, 0, (16 * g.nb_out - cb0) * 2048, 0x00020000), LY_NKX * 2048, 0};
 #pragma unroll
-            for (int s2 = 0; s2 < LY_RDM - 1; ++s2) load_g(p_out, s2, s2);
-            gemm_n(acc, a_off, p_out, p_out, std::false_type{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 32>{});
+            for (int s2 = 0; s2 < LY_RDM - 1; ++s2) tail_load_g<OP, LYT>(wf, tl, p_out, s2, s2);
+            tail_gemm<OP, LYT, 32, false, 0>(acc, wf, tl, a_off, p_out, p_out);
         }
     };
     for (int it = 0; it < nit; ++it) {
@@ -571,17 +409,14 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 RGN_LYT(3 + 3 * r)
             }
         }
-        // ========================= layer tail on the resident images (rgn_mlp2.hip, MT = 2) ==================================
-        auto wrs = [&](const __bf16* W, int cb0, int bytes) {
-            return __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(W) + (size_t)cb0 * 1024, 0, bytes - cb0 * 2048, 0x00020000);
-        };
-        const Pass p_wo{wrs(w.Wo, 2 * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{wrs(w.W1, 2 * wave, 1024 * 512 * 2), 32 * 2048, 0},
-            p_w1b{wrs(w.W1, 16 + 2 * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{wrs(w.W2, 2 * wave, 512 * 1024 * 2), 16 * 2048, 0},
+        // ========================= layer tail on the resident images, composed from rgn_tail.h ================================
+        const Pass p_wo{tail_wrs(w.Wo, 2 * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{tail_wrs(w.W1, 2 * wave, 1024 * 512 * 2), 32 * 2048, 0},
+            p_w1b{tail_wrs(w.W1, 16 + 2 * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{tail_wrs(w.W2, 2 * wave, 512 * 1024 * 2), 16 * 2048, 0},
             p_w2b{p_w2a.rs, 16 * 2048, 32};
         // ---- out_proj's first fragments and this layer's per-column vectors (this wave's 64 columns: lane = column)
         vec[V_BO + lane] = bo_r;                                 // (wave-private; the exchange it lies in is dead: every wave passed the barrier behind the last round)
 #pragma unroll
-        for (int s = 0; s < LY_RDM - 1; ++s) load_g(p_wo, s, s);
+        for (int s = 0; s < LY_RDM - 1; ++s) tail_load_g<OP, LYT>(wf, tl, p_wo, s, s);
         int cw = 64 * wave + lane;
         asm volatile("" : "+v"(cw));                             // (per layer: the per-column vector addresses are step-loop invariants - hoisted, they are spilled in the guided form)
         float vv[12];
@@ -600,47 +435,27 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             for (int qtile = 0; qtile < 2; ++qtile)
 #pragma unroll
                 for (int i4 = 0; i4 < 4; ++i4)
-                    *reinterpret_cast<op4*>(smem + LY_Y + ((2 * r + hg) * 4 + wn) * LY_KB + (32 * qtile + l31) * 64 + ((i4 ^ swz) << 4) + 8 * kh) = attk[r][qtile][i4];
+                    *reinterpret_cast<op4*>(smem + LY_Y + ((2 * r + hg) * 4 + wn) * LY_KB + (32 * qtile + l31) * 64 + ((i4 ^ tl.swz) << 4) + 8 * kh) = attk[r][qtile][i4];
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         f32x16 acc[2][2];
-        init_bias(acc, vec + V_BO);
+        tail_init_bias<LYT>(acc, tl, vec + V_BO);
         RGN_LYT(7)
-        gemm32(acc, a_offy, p_wo, p_w1a, std::true_type{}, std::integral_constant<int, 11>{});
+        tail_gemm<OP, LYT, 32, true, 11>(acc, wf, tl, a_offy, p_wo, p_w1a);   // (11: the vector loads above may stay in flight behind the ring)
         RGN_LYT(8)
         // vectors -> the wave's LDS region (wave-private: program order suffices)
         vec[V_G1 + lane] = vv[1]; vec[V_G2 + lane] = vv[2]; vec[V_B2 + lane] = vv[3]; vec[V_SPV + lane] = vv[4];
         vec[V_BF1 + lane] = vv[5]; vec[V_BF1 + 64 + lane] = vv[6]; vec[V_BF2 + lane] = vv[7]; vec[V_G3 + lane] = vv[8]; vec[V_B3 + lane] = vv[9];
-        add_resid(acc);
-        layernorm(acc, vec + V_G1, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_SPV + col4(nt, i4)); });
-        layernorm(acc, vec + V_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_B2 + col4(nt, i4)); });
-        store_img(acc, LY_X);                                    // h' replaces h in place (this wave's columns: it read them above)
+        tail_add_resid<OP, LYT>(acc, tl, LY_X);
+        tail_layernorm<LYT, 0>(acc, tl, vec + V_G1, tail_rowvec(tl, vec + V_SPV));
+        tail_layernorm<LYT, 1>(acc, tl, vec + V_G2, tail_rowvec(tl, vec + V_B2));
+        tail_store_img<OP, LYT>(acc, tl, LY_X);                  // h' replaces h in place (this wave's columns: it read them above)
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYT(9)
+        // linear1 + GELU + linear2: reads h' from X, the hidden halves go through Y (the attention output, dead since out_proj)
         f32x16 acc2[2][2];
-        init_bias(acc2, vec + V_BF2);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            init_bias(acc, vec + V_BF1 + 64 * c);
-            gemm32(acc, a_off, c ? p_w1b : p_w1a, c ? p_w2b : p_w2a, std::true_type{}, std::integral_constant<int, 0>{});   // hidden columns [512 c, 512 c + 512)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int i = 0; i < 16; i += 2) {
-                        const f32x2 gl = gelu2_p13(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
-                        acc[nt][mt][i] = gl[0];
-                        acc[nt][mt][i + 1] = gl[1];
-                    }
-            if (c == 1) __builtin_amdgcn_s_barrier();             // every wave is done reading the first half's image
-            store_img(acc, LY_Y);                                 // (c == 0: Y holds the attention output, dead since out_proj)
-            wait_lgkmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            if (c == 0) gemm32(acc2, a_offy, p_w2a, p_w1b, std::true_type{}, std::integral_constant<int, 0>{});
-            else gemm32(acc2, a_offy, p_w2b, p_w2b, std::false_type{}, std::integral_constant<int, 0>{});
-        }
+        tail_ffn<OP, LYT>(acc2, wf, tl, a_off, a_offy, LY_Y, p_w1a, p_w1b, p_w2a, p_w2b, vec + V_BF1, vec + V_BF2);
         load_qbias(g.lw[l + 1 < g.L ? l + 1 : 0].bqkv, 0);      // the next layer's (next step's first layer's) round 0: lands under norm3
 #ifndef RGN_LY_NO_PREFETCH
         if constexpr (STEPS) {
@@ -666,9 +481,9 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         }
 #endif
         RGN_LYT(10)
-        add_resid(acc2);
-        layernorm(acc2, vec + V_G3, std::integral_constant<int, 0>{}, [&](int nt, int i4) { return *reinterpret_cast<const f32x4*>(vec + V_B3 + col4(nt, i4)); });
-        store_img(acc2, LY_X);                                   // the next layer's input, in place
+        tail_add_resid<OP, LYT>(acc2, tl, LY_X);
+        tail_layernorm<LYT, 0>(acc2, tl, vec + V_G3, tail_rowvec(tl, vec + V_B3));
+        tail_store_img<OP, LYT>(acc2, tl, LY_X);                 // the next layer's input, in place
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         RGN_LYT(11)
@@ -722,7 +537,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             }
         const Pass p_wx{__builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Wx) + (size_t)(2 * wave_s) * 1024, 0, (LY_NKX * 16 - 2 * wave_s) * 2048, 0x00020000), 16 * 2048, 0};
 #pragma unroll
-        for (int s2 = 0; s2 < LY_RDM - 1; ++s2) load_g(p_wx, s2, s2);   // the embedding's first fragments fly under the update phase
+        for (int s2 = 0; s2 < LY_RDM - 1; ++s2) tail_load_g<OP, LYT>(wf, tl, p_wx, s2, s2);   // the embedding's first fragments fly under the update phase
         // the condition rows the embedding adds, in the accumulator layout (requested now, used behind the GEMM)
         op4 c0v[2][2][4];
 #pragma unroll
@@ -831,7 +646,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 for (int i = 0; i < 16; ++i) acc[a2][b2][i] = 0.f;
         {
             int a_offx[2] = {a_off[0] + LY_XIMG, a_off[1] + LY_XIMG};
-            gemm_n(acc, a_offx, p_wx, p_wx, std::false_type{}, std::integral_constant<int, 8 + 16>{}, std::integral_constant<int, 2 * LY_NKX>{});
+            tail_gemm<OP, LYT, 2 * LY_NKX, false, 8 + 16>(acc, wf, tl, a_offx, p_wx, p_wx);
         }
         if constexpr (GUIDED) {   // the same embedding with the unconditional condition rows -> image Y -> the planes (read back at the next step's pass 1)
             __builtin_amdgcn_s_barrier();                                 // Y overlaps the x' image: every wave must be out of the embedding's k-loop first
@@ -844,7 +659,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         op4 hh;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) hh[e] = (op_t)(acc[nt][mt][4 * i4 + e] + (float)c0u[nt][mt][i4][e]);
-                        *reinterpret_cast<op4*>(smem + LY_Y + img_off(nt, i4, mt)) = hh;
+                        *tail_img_run<OP, LYT>(tl, LY_Y, nt, i4, mt) = hh;
                     }
         }
 #pragma unroll
@@ -855,7 +670,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 for (int i4 = 0; i4 < 4; ++i4)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[nt][mt][4 * i4 + e] += (float)c0v[nt][mt][i4][e];
-        store_img(acc, LY_X);
+        tail_store_img<OP, LYT>(acc, tl, LY_X);
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if constexpr (GUIDED) {

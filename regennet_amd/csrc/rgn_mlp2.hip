@@ -18,10 +18,12 @@
 //     norm2, per-sample vectors) is overwritten by phase B (linear1 / linear2 biases, norm3) once the wave is past norm2
 //   * LayerNorm statistics as sum and sum of squares in ONE exchange (fp32; plain-bf16 phase only - the split-bf16 tail keeps the
 //     two-pass kernels), mean folded into the final FMA; exchange layout [stat][wave][token]: conflict-free both ways
+// The machinery of all that - tile geometry, weight ring and GEMM pass, LayerNorm, epilogue sweeps, the FFN stage - is rgn_tail.h, shared with
+// k_layers (rgn_layers.hip); this file keeps the kernel's own stage 1 (att DMA, residual tile in registers, per-sample vectors, ENC) and stage 3.
 //   LDS X: att tile image (A operand of out_proj) -> GELU(hidden half) image (A operand of linear2) -> output image
 //   LDS Y: h' image (A operand of linear1, residual of norm3)
 #include "rgn_internal.h"
-#include "rgn_device.h"
+#include "rgn_tail.h"
 
 #include <hip/hip_runtime.h>
 
@@ -80,7 +82,6 @@ template <bool F16 = false, bool ENC = false>
 __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     using C = M2;
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): planes in, planes out, weight planes
-    using op_t = typename OP::t;
     using op8 = typename OP::v8;
     using op4 = typename OP::v4;
     constexpr int MT = C::MT, NT = C::NT, NW = C::NW, R = C::R, CW = C::CW, RD = C::RD, KB = C::KB, NSAMP = C::NSAMP, VK = CW / 64;
@@ -103,176 +104,22 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.att + src), (RGN_AS3 void*)(smem + C::X + p * 1024), 16, 0, 0);
         }
     }
-    // B-operand fragment of token l31 (+ 32 mt: an immediate offset of 2 KiB) inside a k-block image [R rows][64 B] (16-byte chunks
-    // swizzled by the row), per 16-wide k-half
-    int a_off[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) a_off[ks] = l31 * 64 + (((2 * ks + kh) ^ ((l31 >> 2) & 3)) << 4);
-
-    // ---- weight ring: granule = half a k-step (16 k) of this wave's NT column blocks; W: fragment-ordered plane
-    //      [K/32][nb_all][2][64][8] (rgn_rowgemm.hip). Granule index hs = 2 kt + ks. Buffer loads: the resource (based at the wave's
-    //      first column block) is scalar and every granule offset a compile-time constant, the lane contributes lane * 16
-    struct Pass { __amdgpu_buffer_rsrc_t rs; int kstride, hs0; };   // kstride = nb_all * 2048 bytes per k-block
-    op8 wf[RD][NT];
-    const int lane16 = lane * 16;
-    auto load_g = [&](const Pass& ps, int hs_rel, int slot) {
-        const int hs = ps.hs0 + hs_rel;
-        const int soff = (hs >> 1) * ps.kstride + (hs & 1) * 1024;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            wf[slot][nt] = __builtin_bit_cast(op8, __builtin_amdgcn_raw_buffer_load_b128(ps.rs, lane16, soff + nt * 2048, 0));
-    };
-    // one GEMM pass over K = 512: acc[nt][mt] += A_image(16 k-blocks at img) . W[the wave's column blocks, granules hs0 .. hs0 + 31]^T.
-    // The ring never drains between passes: the tail of a pass requests the first RD - 1 granules of the NEXT pass (chain). `extra`:
-    // vector-memory operations issued between the granules RD - 2 and RD - 1 of this pass that may stay in flight (stage 1: the
-    // residual tile and the phase-B vectors).
-    auto gemm32 = [&](f32x16 (&acc)[NT][MT], const char* img, const Pass& cur, const Pass& nxt, auto chain, auto extra) {
-        constexpr int EX = decltype(extra)::value, AH = RD - 1;
-        constexpr bool CH = decltype(chain)::value;
-        __builtin_amdgcn_sched_barrier(0);
-        op8 af[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const op8*>(img + a_off[0] + mt * 2048);
-#pragma unroll
-        for (int hs = 0; hs < 32; ++hs) {
-            op8 afn[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                afn[mt] = af[mt];
-                if (hs + 1 < 32) afn[mt] = *reinterpret_cast<const op8*>(img + ((hs + 1) >> 1) * KB + a_off[(hs + 1) & 1] + mt * 2048);   // one granule ahead
-            }
-            if (hs + AH < 32) load_g(cur, hs + AH, (hs + AH) % RD);
-            else if (CH) load_g(nxt, hs + AH - 32, (hs + AH) % RD);
-            if (hs + AH < 32 || CH) {
-                if (hs < AH) wait_vmcnt<NT * AH + EX>();
-                else wait_vmcnt<NT * AH>();   // this granule is in; the next RD - 1 stay in flight
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = OP::mfma(wf[hs % RD][nt], af[mt], acc[nt][mt]);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) af[mt] = afn[mt];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // element (token 32 mt + l31, column CW wave + 32 nt + 8 i4 + 4 kh + e) <-> register acc[nt][mt][4 i4 + e]
-    auto col4 = [&](int nt, int i4) { return 32 * nt + 8 * i4 + 4 * kh; };          // inside the wave's column slice
-    auto img_off = [&](int nt, int i4, int mt) {                                      // its 8-byte run inside an image [16][R rows][64 B]
-        return (NT * wave + nt) * KB + mt * 2048 + l31 * 64 + ((i4 ^ ((l31 >> 2) & 3)) << 4) + 8 * kh;
-    };
-    auto init_bias = [&](f32x16 (&acc)[NT][MT], const float* bias) {                  // bias: the wave's column slice in LDS
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(bias + col4(nt, i4));
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[nt][mt][4 * i4 + e] = b[e];
-            }
-    };
-    // LayerNorm over the 512 columns of every token, in place: o = v (rstd gamma) + (shift - mean rstd gamma). One exchange of
-    // (sum, sum of squares): halves by lane ^ 32, the NW column slices through LDS ([stat][wave][token], conflict-free both ways)
-    // (exchange addresses = ONE opaque base register + immediates: left to itself the compiler forms every address with v_or
-    // into a register of its own and keeps them all alive across the kernel)
-    int red_base = C::RED + 4 * l31;
-    asm volatile("" : "+v"(red_base));
-    const float invn = 1.0f / 512.f;
-    int red_base2 = red_base + 128 * kh;                          // post-barrier reads: lane (l31, kh) reduces token 32 kh + l31
-    asm volatile("" : "+v"(red_base2));
-    auto layernorm = [&](f32x16 (&acc)[NT][MT], const float* gam, auto slot, auto shift /* (nt, i4, mt) -> f32x4 */) {
-        const char* buf = smem + red_base + decltype(slot)::value * C::REDF * 4;   // two alternating buffers: a barrier separates each write from its reads
-        const char* buf2 = smem + red_base2 + decltype(slot)::value * C::REDF * 4;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f32x2 s2 = f32x2{0.f, 0.f}, q2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    const f32x2 v = f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]};
-                    s2 += v;
-                    q2 = __builtin_elementwise_fma(v, v, q2);
-                }
-            float s = s2[0] + s2[1], q = q2[0] + q2[1];
-            half_swap(s, q);                                        // s = [s.lo | q.lo], q = [s.hi | q.hi]
-            *reinterpret_cast<float*>(const_cast<char*>(buf) + (kh * (NW * R) + wave * R + 32 * mt) * 4) = s + q;   // kh = 0: the sum, kh = 1: the sum of squares
-        }
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        f32x2 rs[MT], nm[MT];
-        {   // the halves share the work - lane (l31, kh) reduces the partials of token 32 kh + l31, two swaps hand the results over
-            float p[2][NW];
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int w = 0; w < NW; ++w) p[st][w] = *reinterpret_cast<const float*>(buf2 + (st * (NW * R) + w * R) * 4);
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int d = 1; d < NW; d *= 2)
-#pragma unroll
-                    for (int w = 0; w < NW; w += 2 * d) p[st][w] += p[st][w + d];
-            const float mean = p[0][0] * invn;
-            const float var = __builtin_fmaxf(p[1][0] * invn - mean * mean, 0.f);
-            float r0 = __builtin_amdgcn_rsqf(var + 1e-5f), n0 = -mean * r0;
-            float r1 = r0, n1 = n0;
-            asm volatile("" : "+v"(r1), "+v"(n1));               // (copies in registers of their own)
-            half_swap(r0, r1);
-            half_swap(n0, n1);
-            rs[1] = f32x2{r1, r1};
-            nm[1] = f32x2{n1, n1};
-            rs[0] = f32x2{r0, r0};
-            nm[0] = f32x2{n0, n0};
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            f32x4 ga[4], sh[4][MT];                                   // the LDS reads of a column block first, then the arithmetic
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4) {
-                ga[i4] = *reinterpret_cast<const f32x4*>(gam + col4(nt, i4));
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) sh[i4][mt] = shift(nt, i4, mt);
-            }
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int e = 0; e < 4; e += 2) {
-                        const f32x2 t = __builtin_elementwise_fma(f32x2{acc[nt][mt][4 * i4 + e], acc[nt][mt][4 * i4 + e + 1]}, rs[mt], nm[mt]);   // (v - mean) rstd
-                        const f32x2 o = __builtin_elementwise_fma(t, f32x2{ga[i4][e], ga[i4][e + 1]}, f32x2{sh[i4][mt][e], sh[i4][mt][e + 1]});
-                        acc[nt][mt][4 * i4 + e] = o[0];
-                        acc[nt][mt][4 * i4 + e + 1] = o[1];
-                    }
-        }
-    };
-    auto store_img = [&](const f32x16 (&acc)[NT][MT], char* img) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    op4 h;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) h[e] = (op_t)acc[nt][mt][4 * i4 + e];
-                    *reinterpret_cast<op4*>(img + img_off(nt, i4, mt)) = h;
-                }
-    };
+    // ---- the layer tail's shared machinery (rgn_tail.h): accumulator <-> image map, weight ring, GEMM pass, LayerNorm, epilogue sweeps, FFN stage
+    using Pass = TailPass;
+    const TailLane tl = tail_lane<C>(smem, lane, wave);
+    int a_offx[2], a_offy[2];                                        // B-operand fragment offsets into the images X and Y
+    static_assert(C::X == 0, "a_offx addresses the image at byte 0");
+    tail_a_off(a_offx, lane);
+    tail_a_off(a_offy, a_offx, C::Y);
+    op8 wf[RD][NT];                                                  // the weight ring
 
     // =============== stage 1: out_proj + residual + norm1 + folded cross-attention + norm2 -> h' (Y) ====================
-    auto wrs = [&](const __bf16* W, int cb0, int bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(W) + (size_t)cb0 * 1024, 0, bytes - cb0 * 2048, 0x00020000);
-    };
-    const Pass p_wo{wrs(g.w.Wo, NT * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{wrs(g.w.W1, NT * wave, 1024 * 512 * 2), 32 * 2048, 0},
-        p_w1b{wrs(g.w.W1, 16 + NT * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{wrs(g.w.W2, NT * wave, 512 * 1024 * 2), 16 * 2048, 0},
+    const Pass p_wo{tail_wrs(g.w.Wo, NT * wave, 512 * 512 * 2), 16 * 2048, 0}, p_w1a{tail_wrs(g.w.W1, NT * wave, 1024 * 512 * 2), 32 * 2048, 0},
+        p_w1b{tail_wrs(g.w.W1, 16 + NT * wave, 1024 * 512 * 2), 32 * 2048, 0}, p_w2a{tail_wrs(g.w.W2, NT * wave, 512 * 1024 * 2), 16 * 2048, 0},
         p_w2b{p_w2a.rs, 16 * 2048, 32};
     f32x16 acc[NT][MT];
 #pragma unroll
-    for (int s = 0; s < RD - 1; ++s) load_g(p_wo, s, s);           // right behind the att DMA: the first MFMA needs both, and nothing else
+    for (int s = 0; s < RD - 1; ++s) tail_load_g<OP, C>(wf, tl, p_wo, s, s);           // right behind the att DMA: the first MFMA needs both, and nothing else
     RGN_M2T(6)
     const int cw = CW * wave + lane;                                 // this lane's column(s) of every vector slice: cw (+ 64)
     // phase A vectors of the wave's columns: requested now, staged to the wave's LDS region after the out_proj loop - nothing
@@ -345,7 +192,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[nt][mt][i] = 0.f;
     RGN_M2T(1)
-    gemm32(acc, smem + C::X, p_wo, p_w1a, std::true_type{}, std::integral_constant<int, EXTRA>{});
+    tail_gemm<OP, C, 32, true, EXTRA>(acc, wf, tl, a_offx, p_wo, p_w1a);   // (EXTRA may stay in flight behind the ring)
     RGN_M2T(2)
     // phase A vectors -> the wave's LDS region (wave-private: no barrier, the exchange barrier of norm1 is far behind the writes)
 #pragma unroll
@@ -360,7 +207,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int i4 = 0; i4 < 4; ++i4) {
-            const f32x4 b = *reinterpret_cast<const f32x4*>(vec + C::A_BO + col4(nt, i4));
+            const f32x4 b = *reinterpret_cast<const f32x4*>(vec + C::A_BO + tail_col4(tl, nt, i4));
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -373,11 +220,10 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             const int m = m0 + 32 * mt + l31;
             spv[mt] = vec + C::A_SPV + ((m < g.M ? m : g.M - 1) / g.Tq - m0 / g.Tq) * CW;
         }
-        layernorm(acc, vec + C::A_G1, std::integral_constant<int, 0>{}, [&](int nt, int i4, int mt) { return *reinterpret_cast<const f32x4*>(spv[mt] + col4(nt, i4)); });
+        tail_layernorm<C, 0>(acc, tl, vec + C::A_G1, [&](int nt, int i4, int mt) { return *reinterpret_cast<const f32x4*>(spv[mt] + tail_col4(tl, nt, i4)); });
     }
-    if constexpr (!ENC)
-        layernorm(acc, vec + C::A_G2, std::integral_constant<int, 1>{}, [&](int nt, int i4, int) { return *reinterpret_cast<const f32x4*>(vec + C::A_B2 + col4(nt, i4)); });
-    store_img(acc, smem + C::Y);
+    if constexpr (!ENC) tail_layernorm<C, 1>(acc, tl, vec + C::A_G2, tail_rowvec(tl, vec + C::A_B2));
+    tail_store_img<OP, C>(acc, tl, C::Y);
     // phase B vectors over phase A (wave-private: program order suffices)
 #pragma unroll
     for (int v = 0; v < 5; ++v)
@@ -387,52 +233,15 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     __builtin_amdgcn_s_barrier();                                     // h' image complete
     RGN_M2T(3)
 
-    // =============== stage 2: linear1 + GELU + linear2, the hidden 1024 columns in two halves ==============================
+    // =============== stage 2: linear1 + GELU + linear2: reads h' from Y, the hidden halves go through X (the att tile is dead since stage 1) ====
     f32x16 acc2[NT][MT];
-    init_bias(acc2, vec + C::B_BF2);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        init_bias(acc, vec + C::B_BF1 + CW * c);
-        gemm32(acc, smem + C::Y, c ? p_w1b : p_w1a, c ? p_w2b : p_w2a, std::true_type{}, std::integral_constant<int, 0>{});   // hidden columns [512 c, 512 c + 512)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    const f32x2 gl = gelu2_p13(f32x2{acc[nt][mt][i], acc[nt][mt][i + 1]});
-                    acc[nt][mt][i] = gl[0];
-                    acc[nt][mt][i + 1] = gl[1];
-                }
-        if (c == 1) __builtin_amdgcn_s_barrier();                     // every wave is done reading the first half's image
-        store_img(acc, smem + C::X);                                  // (c == 0: X still holds the att tile, dead since stage 1)
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (c == 0) gemm32(acc2, smem + C::X, p_w2a, p_w1b, std::true_type{}, std::integral_constant<int, 0>{});   // linear2 over hidden k-blocks [16 c, 16 c + 16)
-        else gemm32(acc2, smem + C::X, p_w2b, p_w2b, std::false_type{}, std::integral_constant<int, 0>{});
-    }
+    tail_ffn<OP, C>(acc2, wf, tl, a_offy, a_offx, C::X, p_w1a, p_w1b, p_w2a, p_w2b, vec + C::B_BF1, vec + C::B_BF2);
     RGN_M2T(4)
 
     // =============== stage 3: + residual h' + norm3 -> output planes =====================================================
-    {
-        op4 r[NT][MT][4];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i4 = 0; i4 < 4; ++i4) r[nt][mt][i4] = *reinterpret_cast<const op4*>(smem + C::Y + img_off(nt, i4, mt));
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc2[nt][mt][4 * i4 + e] += (float)r[nt][mt][i4][e];
-    }
-    layernorm(acc2, vec + C::B_G3, std::integral_constant<int, 0>{}, [&](int nt, int i4, int) { return *reinterpret_cast<const f32x4*>(vec + C::B_B3 + col4(nt, i4)); });   // (its barrier also fences the last reads of X)
-    store_img(acc2, smem + C::X);
+    tail_add_resid<OP, C>(acc2, tl, C::Y);
+    tail_layernorm<C, 0>(acc2, tl, vec + C::B_G3, tail_rowvec(tl, vec + C::B_B3));   // (its barrier also fences the last reads of X)
+    tail_store_img<OP, C>(acc2, tl, C::X);
     wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
