@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
         if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * kh;
+                const int key = 32 * kj + mfma32_row(i, kh);
                 const bool ok = (!CAUSAL || key <= qrow) && (key < Tq);
                 st[kj][i] = ok ? st[kj][i] : -INFINITY;
                 mx = fmaxf(mx, st[kj][i]);
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) patch[l31 * OLD + 32 * dt + (i & 3) + 8 * (i >> 2) + 4 * kh] = oa[dt][i] * inv;
+        for (int i = 0; i < 16; ++i) patch[l31 * OLD + 32 * dt + mfma32_row(i, kh)] = oa[dt][i] * inv;
     wait_lgkmcnt<0>();
     __builtin_amdgcn_wave_barrier();
     constexpr int C4 = DH / 4;
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
         if (q < Tq) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(&patch[r * OLD + c]);
             const int col = hd * DH + c;
-            const size_t o = ((size_t)(col >> 5) * a.out.rows + row0 + q) * 32 + (col & 31);
+            const size_t o = plane_off(a.out.rows, row0 + q, col);
             bf16x4 h, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

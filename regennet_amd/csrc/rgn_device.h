@@ -1,6 +1,7 @@
 // Primitives shared by the kernel sources (every .hip under csrc/): vector types, address spaces, counted waits, DPP and shuffle
 // reductions, the compile-time loop, the split-bf16 conversion, the GELU / erf forms, the 16-bit operand format of the plain phase (OpFmt), the
-// XCD-affine workgroup order and the half-wave exchange. All of that is device code. One host-only section closes the file: dispatch_bools, which
+// XCD-affine workgroup order, the half-wave exchange and the row-tile DMA loop from the planes into an LDS image (layouts: rgn_layout.h). All of that
+// is device code. One host-only section closes the file: dispatch_bools, which
 // the launchers at the foot of the .hip sources use to pick a template form. Every helper has internal linkage.
 // Forms whose arithmetic differs (the GELU / erf variants, the DPP and the shuffle wave sums) are kept apart and named for what they compute.
 #pragma once
@@ -8,6 +9,8 @@
 
 #include <type_traits>
 #include <utility>
+
+#include "rgn_layout.h"
 
 #define RGN_AS1 __attribute__((address_space(1)))   // global
 #define RGN_AS3 __attribute__((address_space(3)))   // LDS
@@ -204,6 +207,22 @@ __device__ __forceinline__ float half_sum(float v) {
     asm volatile("" : "+v"(o));
     half_swap(v, o);
     return v + o;
+}
+
+// ---- plane -> LDS image (rgn_layout.h) of a tile of 64 rows x 32 NKB columns by DMA (global_load_lds, 16 bytes per lane), issued by a workgroup of NW
+// waves: 4 NKB pieces of 1 KiB (16 rows x 64 B of a k-block), wave w issues the pieces w, w + NW, ... Tile row r is plane row row0 + r; `live` rows of
+// the tile exist (the rows of a sample, or what is left of M): a row past the last live one replicates it (row-local everywhere, never stored).
+// AUX: the loads' cache policy. Completion is the caller's vmcnt wait
+template <int AUX = 0, int NKB = 16, int NW = 8, class T>
+__device__ __forceinline__ void tile_dma_in(char* img, const T* plane, int rows, size_t row0, int live, int lane, int wave) {
+    const int r16 = lane >> 2, c = lane & 3;
+#pragma unroll
+    for (int j = 0; j < 4 * NKB / NW; ++j) {
+        const int p = wave + NW * j, kb = p >> 2, r = (p & 3) * 16 + r16;
+        const int rr = r < live ? r : live - 1;
+        const size_t src = plane_chunk(rows, row0 + rr, kb, img_dma_chunk(r, c));
+        __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(plane + src), (RGN_AS3 void*)(img + p * 1024), 16, 0, AUX);
+    }
 }
 
 // ---- rotation_6d_to_matrix (utils/rotation_conversions.py:513-534): Gram-Schmidt of the two 3-vectors a1, a2, F.normalize semantics

@@ -7,17 +7,14 @@
 // the main loop and all four planes go HBM/L2 -> LDS by direct-to-LDS DMA (global_load_lds_dwordx4,
 // 1 KiB per wave-instruction, no VGPR round trip).
 //
-// Operand memory layout ("K32-blocked planes"): element (row, k) of a plane lives at
-//   ((k/32) * rows + row) * 32 + k%32          i.e. [Kp/32][rows][32] bf16
-// so the [rows x 32] slice a block needs for one k-step is ONE contiguous run of 64-byte rows: every DMA
-// wave-instruction (16 rows x 64 B) reads a contiguous, 1 KiB-aligned span = 8 full 128-byte lines.
-// (With a plain row-major [rows][K] plane each instruction would touch 16 half-used lines.)
-// The producers (LayerNorm, GEMM epilogues, attention, sampler update) write this layout directly.
+// Operand memory layout: the K32-blocked planes [Kp/32][rows][32] of rgn_layout.h (plane_off), so the [rows x 32] slice a
+// block needs for one k-step is ONE contiguous run of 64-byte rows: every DMA wave-instruction (16 rows x 64 B) reads a
+// contiguous, 1 KiB-aligned span = 8 full 128-byte lines. (With a plain row-major [rows][K] plane each instruction would
+// touch 16 half-used lines.) The producers (LayerNorm, GEMM epilogues, attention, sampler update) write this layout directly.
 //
-// LDS image of one plane tile: [rows][32] bf16, 64-byte rows, written lane-linear by the DMA. To make the
-// ds_read_b128 fragment reads conflict-free the 16-byte chunk c of row r is stored at chunk position
-// c ^ ((r>>2)&3): the permutation is applied to the per-lane global SOURCE address and again on the read
-// (both-sides-or-neither rule for global_load_lds).
+// LDS image of one plane tile: the swizzled image of rgn_layout.h, written lane-linear by the DMA. The chunk permutation that
+// makes the ds_read_b128 fragment reads conflict-free is applied to the per-lane global SOURCE address (img_dma_chunk) and
+// again on the read (img_frag): the both-sides-or-neither rule for global_load_lds.
 //
 // Loop (shipped flavour): 128x128 tile, 4 waves, 2 LDS stages of 32 KiB -> two workgroups per CU, one hiding the
 // other's barriers and epilogue. Per k-step: issue tile kt+1's DMA, counted wait (vmcnt) for tile kt, barrier, fragments
@@ -68,7 +65,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 const float* ap = g.add + n;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int ro = (i & 3) + 8 * (i >> 2);
+                    const int ro = mfma32_row(i, 0);
                     int rr = base + ro;
                     rr = rr >= g.add_mod ? rr - g.add_mod : rr;
                     r[i] = n_ok ? ap[rr * g.ldadd] : 0.f;
@@ -77,7 +74,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 const float* ap = g.add + (size_t)mb * g.ldadd + n;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int ro = (i & 3) + 8 * (i >> 2);
+                    const int ro = mfma32_row(i, 0);
                     r[i] = (!CHECK || (n_ok && mb + ro < g.M)) ? ap[(size_t)ro * g.ldadd] : 0.f;
                 }
             }
@@ -101,7 +98,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1: quad_perm [1, 0, 3, 2]
                         const float c0 = odd ? got : mine, c1 = odd ? mine : got;
                         const int ii = odd ? i + 8 : i;
-                        const unsigned m = (unsigned)(mb + (ii & 3) + 8 * (ii >> 2));
+                        const unsigned m = (unsigned)(mb + mfma32_row(ii, 0));
                         // m / Tq, m % Tq (exact: m*Tq < 2^32); Tq = 1 has no 32-bit magic (floor(2^32 / 1) + 1 wraps to 1): the quotient is m itself
                         const unsigned bb = g.Tq == 1 ? m : __umulhi(m, g.tq_magic), tt = m - bb * (unsigned)g.Tq;
                         const size_t o = (((size_t)bb * g.H + hd) * g.Tqp + tt) * g.dh + (c & ~1);
@@ -117,7 +114,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                     const float sc = which == 0 ? g.qscale : 1.0f;
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int m = mb + (i & 3) + 8 * (i >> 2);
+                        const int m = mb + mfma32_row(i, 0);
                         if (!n_ok || m >= g.M) continue;
                         const int bb = m / g.Tq, tt = m - bb * g.Tq;
                         const size_t sl = (size_t)bb * g.H + hd;
@@ -133,7 +130,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 float* cp = g.C + (size_t)mb * g.ldc + n;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int ro = (i & 3) + 8 * (i >> 2);
+                    const int ro = mfma32_row(i, 0);
                     if (!CHECK || (n_ok && mb + ro < g.M)) cp[(size_t)ro * g.ldc] = r[i];
                 }
             }
@@ -141,7 +138,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 if (!CHECK) {
                     // pair adjacent columns across lanes (lane^1) so every store is a packed bf16x2 (4 B):
                     // even lanes store rows of registers 0..7, odd lanes those of registers 8..15
-                    const size_t o = ((size_t)(n >> 5) * g.c_rows + mb) * 32 + (n & 30);
+                    const size_t o = plane_off(g.c_rows, mb, n & ~1);
                     const bool odd = lane & 1;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
@@ -150,7 +147,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1: quad_perm [1, 0, 3, 2]
                         const float lo_col = odd ? got : mine, hi_col = odd ? mine : got;   // columns n&~1, (n&~1)+1
                         const int ii = odd ? i + 8 : i;
-                        const int ro = (ii & 3) + 8 * (ii >> 2);
+                        const int ro = mfma32_row(ii, 0);
                         const __bf16 h0 = (__bf16)lo_col, h1 = (__bf16)hi_col;
                         bf16x2 hv = {h0, h1};
                         *reinterpret_cast<bf16x2*>(g.Chi + o + ro * 32) = hv;
@@ -160,10 +157,10 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         }
                     }
                 } else {
-                    const size_t o = ((size_t)(n >> 5) * g.c_rows + mb) * 32 + (n & 31);
+                    const size_t o = plane_off(g.c_rows, mb, n);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int ro = (i & 3) + 8 * (i >> 2);
+                        const int ro = mfma32_row(i, 0);
                         if (n_ok && mb + ro < g.M) {
                             const __bf16 h = (__bf16)r[i];
                             g.Chi[o + ro * 32] = h;
@@ -209,14 +206,14 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
     unsigned a_src[A_IT], w_src[W_IT];
 #pragma unroll
     for (int it = 0; it < A_IT; ++it) {
-        const int q = it * NT + tid, r = q >> 2, c = (q & 3) ^ ((r >> 2) & 3);
+        const int q = it * NT + tid, r = q >> 2, c = img_dma_chunk(r, q & 3);
         int m = m0 + r;
         m = m < g.M ? m : g.M - 1;
         a_src[it] = (unsigned)m * 64u + c * 16u;
     }
 #pragma unroll
     for (int it = 0; it < W_IT; ++it) {
-        const int q = it * NT + tid, r = q >> 2, c = (q & 3) ^ ((r >> 2) & 3);
+        const int q = it * NT + tid, r = q >> 2, c = img_dma_chunk(r, q & 3);
         int n = n0 + r;
         n = n < g.N ? n : g.N - 1;
         w_src[it] = (unsigned)n * 64u + c * 16u;
@@ -263,13 +260,13 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
     for (int t = 0; t < TM; ++t) {
         const int rr = wm * (BM / WM) + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
     }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
         const int rr = wn * (BN / WN) + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
     }
     // the three products of one C tile (a.w ~ al.wh + ah.wl + ah.wh, small terms first)
     auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {

@@ -17,7 +17,7 @@ enum KClass : int {
     KC_QKV,           // fused in_proj GEMM + attention (k_qkv_attn)
     KC_ROWLN,         // row-complete GEMM + residual + LayerNorm(s) (k_rowgemm<0>)
     KC_ROWACT,        // row-complete GEMM + activation (k_rowgemm<1>)
-    KC_MLP,           // row-persistent layer tail (k_mlp)
+    KC_MLP,           // row-persistent layer tail (k_mlp2)
     KC_SB,            // small-batch column-split GEMMs (k_sb_gemm)
     KC_STEP,          // fused step boundary: output projection + sampler update + next input embedding (k_step)
     KC_LAYERS,        // the whole decoder stack of an evaluation, one sample per workgroup (k_layers)
@@ -73,7 +73,7 @@ struct GemmArgs {
     int act;                          // 0 none, 1 gelu(erf), 2 silu, 3 relu
 };
 
-// bf16 operand planes use the "K32-blocked" layout [Kp/32][rows][32] (see rgn_gemm_x3.hip).
+// bf16 operand planes use the "K32-blocked" layout [Kp/32][rows][32] (rgn_layout.h, where all four operand layouts are defined).
 struct GemmX3Args {
     const __bf16* Ahi; const __bf16* Alo; int a_rows;   // activation planes [Kp/32][a_rows][32], a_rows >= M
     const __bf16* Whi; const __bf16* Wlo;               // weight planes [Kp/32][N][32]
@@ -201,7 +201,7 @@ hipError_t configure_mlp_x3();
 hipError_t launch_mlp_x3(const MlpX3Args& g, hipStream_t s, bool enc = false);   // (enc: as launch_mlp)
 
 // The whole decoder stack of one evaluation as one kernel, one sample (Tq <= 64 tokens) per workgroup (rgn_layers.hip): plain-bf16 phase,
-// d = 512, ff = 1024, 4 heads of 128. Weight planes fragment-ordered as for k_mlp / k_qkv_attn_rs.
+// d = 512, ff = 1024, 4 heads of 128. Weight planes fragment-ordered (rgn_layout.h) as for k_mlp2 / k_qkv_attn_rs.
 constexpr int LY_MAXL = 8;
 struct LayersArgs {
     const __bf16* h;                      // residual-stream planes (hi) [16][rows][32], advanced to the first sample's row

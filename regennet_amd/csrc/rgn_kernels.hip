@@ -16,10 +16,6 @@
 
 namespace rgn {
 
-// element (row, col) of a K32-blocked plane [cols/32][rows][32]
-__device__ __forceinline__ size_t plane_off(int rows, int row, int col) {
-    return ((size_t)(col >> 5) * rows + row) * 32 + (col & 31);
-}
 __device__ __forceinline__ void plane_put(const Planes& p, int row, int col, float v) {
     const size_t o = plane_off(p.rows, row, col);
     const __bf16 h = (__bf16)v;
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs g) {
         for (int ta = 0; ta < 2; ++ta) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int m = m0 + wm * 64 + ta * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+                const int m = m0 + wm * 64 + ta * 32 + mfma32_row(i, lane >> 5);
                 if (m >= g.M) continue;
                 float v = acc[ta][tb][i] + bias;
                 if (g.add) {
@@ -263,6 +259,7 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(GemmArgs g, int nbx, int nby)
         for (int ta = 0; ta < 2; ++ta) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
+                // (= mfma32_row(i, lane >> 5) of rgn_layout.h, spelled out: behind the function two forms of this kernel take 4 more VGPRs, one of them a wave per SIMD)
                 const int m = m0 + wm * 64 + ta * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
                 if (m >= g.M) continue;
                 float v = acc[ta][tb][i] + bias;
@@ -439,7 +436,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
         if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int key = 32 * kj + mfma32_row(i, half);
                 const bool ok = (!CAUSAL || key <= qrow) && (key < Tq);
                 st[kj][i] = ok ? st[kj][i] : -INFINITY;
                 mx = fmaxf(mx, st[kj][i]);
@@ -474,7 +471,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
         if (!CAUSAL || kj <= w) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * half;   // the key this lane's P register belongs to
+                const int key = 32 * kj + mfma32_row(i, half);   // the key this lane's P register belongs to
                 const float* vr = &slab[key * LD + l31];
 #pragma unroll
                 for (int dt = 0; dt < ND; ++dt)
@@ -487,7 +484,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_mfma(const float* __restrict__
     for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int c = 32 * dt + (i & 3) + 8 * (i >> 2) + 4 * half;       // dh index (row of O^T)
+            const int c = 32 * dt + mfma32_row(i, half);       // dh index (row of O^T)
             slab[(32 * w + l31) * LD + c] = oa[dt][i] * inv;
         }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's LDS writes have landed

@@ -104,16 +104,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
     const int lane16 = lane * 16;
     // ---- the sample's residual rows -> X by DMA: 16 k-blocks x 4 pieces of 1 KiB (16 rows x 64 B); padding rows replicate the
     //      last token (row-local everywhere, masked as keys)
-    {
-        const int r16 = lane >> 2, c = lane & 3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int p = wave + 8 * j, kb = p >> 2, r = (p & 3) * 16 + r16;
-            const int rr = r < Tq ? r : Tq - 1;
-            const size_t src = ((size_t)kb * g.rows + row0 + rr) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.h + src), (RGN_AS3 void*)(smem + LY_X + p * 1024), 16, 0, 0);
-        }
-    }
+    tile_dma_in(smem + LY_X, g.h, g.rows, row0, Tq, lane, wave);
     const int first_step = (g.stepvec || STEPS) ? *g.d_step : 0;
     // ---- the layer tail's shared machinery (rgn_tail.h): accumulator <-> image map, weight ring, GEMM pass, LayerNorm, epilogue sweeps, FFN stage.
     //      tl: the lane's opaque LDS bases, made once here. a_off / a_offy: B-operand fragment offsets into the images X and Y
@@ -186,17 +177,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                         *reinterpret_cast<f32x4*>(pk + ((nt * 2 + mt) * 4 + i4) * 256) = f32x4{accp[nt][mt][4 * i4], accp[nt][mt][4 * i4 + 1], accp[nt][mt][4 * i4 + 2], accp[nt][mt][4 * i4 + 3]};
         }
         __builtin_amdgcn_s_barrier();                                     // every wave is done reading the image
-        {
-            const int r16 = lane_p >> 2, c = lane_p & 3;
-            const size_t row0_p = (size_t)b_p * Tq;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int p = wave_p + 8 * j, kb = p >> 2, r = (p & 3) * 16 + r16;
-                const int rr = r < Tq ? r : Tq - 1;
-                const size_t src = ((size_t)kb * g.rows + g.half + row0_p + rr) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
-                __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.h + src), (RGN_AS3 void*)(smem + LY_X + p * 1024), 16, 0, 16);
-            }
-        }
+        tile_dma_in<16>(smem + LY_X, g.h, g.rows, g.half + (size_t)b_p * Tq, Tq, lane_p, wave_p);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
     }
@@ -219,7 +200,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 // (the granule offset is materialised by a volatile s_mov right here: as plain literals the ~300 offsets of a layer are hoisted
                 // out of the layer loop as loop invariants and live in spilled SGPRs)
                 int soff;
-                asm volatile("s_mov_b32 %0, %1" : "=s"(soff) : "i"((hs >> 1) * (48 * 2048) + (hs & 1) * 1024));
+                asm volatile("s_mov_b32 %0, %1" : "=s"(soff) : "i"(frag_granule(hs, 48 * 2048)));
 #pragma unroll
                 for (int t = 0; t < 3; ++t)
                     wq[slot][t] = __builtin_bit_cast(op8, __builtin_amdgcn_raw_buffer_load_b128(ps.rs, lane16, soff + t * (16 * 2048), 0));
@@ -435,7 +416,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
             for (int qtile = 0; qtile < 2; ++qtile)
 #pragma unroll
                 for (int i4 = 0; i4 < 4; ++i4)
-                    *reinterpret_cast<op4*>(smem + LY_Y + ((2 * r + hg) * 4 + wn) * LY_KB + (32 * qtile + l31) * 64 + ((i4 ^ tl.swz) << 4) + 8 * kh) = attk[r][qtile][i4];
+                    *reinterpret_cast<op4*>(smem + LY_Y + ((2 * r + hg) * 4 + wn) * LY_KB + (32 * qtile + l31) * 64 + img_slot(i4, tl.swz) + 8 * kh) = attk[r][qtile][i4];
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
         f32x16 acc[2][2];
@@ -585,7 +566,7 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
                 }
             // the four features 4 fg + {0 .. 3} of this lane's frame: one 16-byte read of the x0 tile, four x updates, ONE 8-byte store of
             // the bf16 x' run (feature 32 i2 + 4 wave + j sits in k-block i2, 16-byte chunk wave >> 1, bytes 8 (wave & 1) + 2 j of its row)
-            const int ximg_lane = lane_s * 64 + ((((wave_s >> 1) ^ ((lane_s >> 2) & 3)) << 4) + 8 * (wave_s & 1));
+            const int ximg_lane = img_run(lane_s, wave_s >> 1, wave_s & 1);
             // in-painting: buffer loads over THIS motion's [F, T] slice (values of a surplus frame or a padding feature are never used: update4
             // tests valid && 4 fg < F). This kernel sits at its 256 VGPRs, so mask and target are NOT requested in one batch like xpre (88 more
             // live registers: 54 - 96 spilled) but LY_IPD feature groups ahead of their use, under the Philox draw of the groups in between
@@ -675,6 +656,8 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         __builtin_amdgcn_s_barrier();
         if constexpr (GUIDED) {
             const __amdgpu_buffer_rsrc_t u_rs = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (int)((size_t)g.rows * 512 * 2), 0x00020000);
+            // (spelled out: behind the shared functions this loop costs the guided forms spilled registers. off = blk * LY_KB + img_chunk(r, c), the
+            //  store offset 2 * plane_chunk(g.rows, g.half + row0_s + r, blk, c) of rgn_layout.h)
             const int r16 = lane_s >> 2, c = lane_s & 3;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -697,9 +680,9 @@ __global__ __launch_bounds__(LY_NTH, 2) void k_layers(LayersArgs g) {
         for (int j = 0; j < 8; ++j) {
             const int p = wave * 8 + j, blk = p >> 2, r = (p & 3) * 16 + r16;
             if (r < Tq) {
-                const int off = blk * LY_KB + r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
+                const int off = blk * LY_KB + img_chunk(r, c);
                 __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(smem + LY_X + off), o_rs,
-                                                       (int)((((size_t)blk * g.rows + row0 + r) * 32 + c * 8) * 2), 0, RGN_LY_ST_AUX);
+                                                       (int)(plane_chunk(g.rows, row0 + r, blk, c) * 2), 0, RGN_LY_ST_AUX);
             }
         }
     }

@@ -93,17 +93,8 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
     float* vec = reinterpret_cast<float*>(smem + C::VEC) + wave * C::VECW;   // this wave's private region
     RGN_M2T(0)
     // ---- att tile -> X by DMA: 16 k-blocks x R/16 pieces of 1 KiB (16 rows x 64 B), wave w issues the pieces w, w + NW, ...
-    {
-        const int r16 = lane >> 2, c = lane & 3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int p = wave + NW * j, kb = p / (R / 16), r = (p % (R / 16)) * 16 + r16;
-            int m = m0 + r;
-            m = m < g.M ? m : g.M - 1;
-            const size_t src = ((size_t)kb * g.rows + m) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.att + src), (RGN_AS3 void*)(smem + C::X + p * 1024), 16, 0, 0);
-        }
-    }
+    static_assert(R == 64, "tile_dma_in: tiles of 64 rows");
+    tile_dma_in<0, 16, NW>(smem + C::X, g.att, g.rows, m0, g.M - m0, lane, wave);
     // ---- the layer tail's shared machinery (rgn_tail.h): accumulator <-> image map, weight ring, GEMM pass, LayerNorm, epilogue sweeps, FFN stage
     using Pass = TailPass;
     const TailLane tl = tail_lane<C>(smem, lane, wave);
@@ -156,7 +147,7 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int i4 = 0; i4 < 4; ++i4)
-                    hres[nt][mt][i4] = *reinterpret_cast<const op4*>(g.h + ((size_t)(NT * wave + nt) * g.rows + m) * 32 + 8 * i4 + 4 * kh);
+                    hres[nt][mt][i4] = *reinterpret_cast<const op4*>(g.h + plane_off(g.rows, m, 32 * (NT * wave + nt) + 8 * i4 + 4 * kh));
         }
     };
 #if RGN_M2_HRES == 0
@@ -251,11 +242,9 @@ __global__ __launch_bounds__(M2::NTH, 2) void k_mlp2(MlpArgs g) {
         for (int j = 0; j < 8; ++j) {
             const int p = wave * 8 + j, blk = p / (R / 16), r = (p % (R / 16)) * 16 + r16;
             const int m = m0 + r;
-            if (m < g.M) {
-                const int off = blk * KB + r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
-                __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(smem + C::X + off), o_rs,
-                                                       (int)((((size_t)blk * g.rows + m) * 32 + c * 8) * 2), 0, RGN_M2_ST_AUX);
-            }
+            if (m < g.M)
+                __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(smem + C::X + blk * KB + img_chunk(r, c)), o_rs,
+                                                       (int)(plane_chunk(g.rows, m, blk, c) * 2), 0, RGN_M2_ST_AUX);
         }
     }
     RGN_M2T(5)

@@ -66,15 +66,15 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             const int q = wave + NW * j, lo = q >> 5, p = q & 31, kb = p >> 1, r = (p & 1) * 16 + r16;
             int m = m0 + r;
             m = m < g.M ? m : g.M - 1;
-            const size_t src = ((size_t)kb * g.rows + m) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
+            const size_t src = plane_chunk(g.rows, m, kb, img_dma_chunk(r, c));
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)((lo ? gx.att_lo : g.att) + src), (RGN_AS3 void*)(smem + (lo ? C::XL : C::XH) + p * 1024), 16, 0, 0);
         }
     }
     asm volatile("" ::: "memory");                                    // (nothing below is issued ahead of the DMA pieces: the count further down relies on it)
-    // B-operand fragment of token l31 inside a k-block image [32 rows][64 B] (16-byte chunks swizzled by the row), per 16-wide k-half
+    // B-operand fragment of token l31 inside a k-block image [32 rows][64 B] (rgn_layout.h), per 16-wide k-half
     int a_off[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) a_off[ks] = l31 * 64 + (((2 * ks + kh) ^ ((l31 >> 2) & 3)) << 4);
+    for (int ks = 0; ks < 2; ++ks) a_off[ks] = img_frag(l31, ks, kh);
 
     // ---- weight ring: granule = half a k-step (16 k) of this wave's 2 column blocks, hi and lo planes
     struct Pass { __amdgpu_buffer_rsrc_t hi, lo; int kstride, hs0; };   // kstride = nb_all * 2048 bytes per k-block
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     const int lane16 = lane * 16;
     auto load_g = [&](const Pass& ps, int hs_rel, int slot) {
         const int hs = ps.hs0 + hs_rel;
-        const int soff = (hs >> 1) * ps.kstride + (hs & 1) * 1024;
+        const int soff = frag_granule(hs, ps.kstride);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             wh[slot][nt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ps.hi, lane16, soff + nt * 2048, 0));
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
     auto col4 = [&](int nt, int i4) { return 32 * nt + 8 * i4 + 4 * kh; };          // inside the wave's column slice
     int img_base = (NT * wave) * KB + l31 * 64 + 8 * kh;
     asm volatile("" : "+v"(img_base));
-    const int swz = (l31 >> 2) & 3;
-    auto img_off = [&](int nt, int i4) { return img_base + nt * KB + ((i4 ^ swz) << 4); };   // its 8-byte run inside an image [16][32 rows][64 B]
+    const int swz = img_swz(l31);
+    auto img_off = [&](int nt, int i4) { return img_base + nt * KB + img_slot(i4, swz); };   // its 8-byte run inside an image [16][32 rows][64 B]
     auto init_bias = [&](f32x16 (&acc)[NT], const float* bias) {                      // bias: the wave's column slice in LDS
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int i4 = 0; i4 < 4; ++i4) {
-                const size_t o = ((size_t)(cb + nt) * g.rows + m) * 32 + 8 * i4 + 4 * kh;
+                const size_t o = plane_off(g.rows, m, 32 * (cb + nt) + 8 * i4 + 4 * kh);
                 rh[nt][i4] = *reinterpret_cast<const bf16x4*>(g.h + o);
                 rl[nt][i4] = *reinterpret_cast<const bf16x4*>(gx.h_lo + o);
             }
@@ -338,9 +338,9 @@ __global__ __launch_bounds__(MX::NTH, 2) void k_mlp_x3(MlpX3Args gx) {
             const int q = wave * 8 + j, lo = q >> 5, p = q & 31, blk = p >> 1, r = (p & 1) * 16 + r16;   // waves 0-3: the hi image, 4-7: the lo image
             const int m = m0 + r;
             if (m < g.M) {
-                const int off = blk * KB + r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
+                const int off = blk * KB + img_chunk(r, c);
                 __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(smem + (lo ? C::XL : C::XH) + off), lo ? ol : oh,
-                                                       (int)((((size_t)blk * g.rows + m) * 32 + c * 8) * 2), 0, 16);   // write-through (sc1)
+                                                       (int)(plane_chunk(g.rows, m, blk, c) * 2), 0, 16);   // write-through (sc1)
             }
         }
     }

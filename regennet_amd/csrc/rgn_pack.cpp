@@ -3,6 +3,7 @@
 // fp32 [N, Kp], bf16 hi / lo planes (row-major or K32-blocked), MFMA-fragment-ordered bf16 hi / lo and fp16 planes - and the activation workspace
 // is allocated. utils/model_util.py:5-8 (load_model_wo_clip) is the reference interface this serves.
 #include "rgn_host.h"
+#include "rgn_layout.h"
 
 namespace rgnh {
 
@@ -73,7 +74,7 @@ static Lin pack_linear(rgn_ctx* c, const float* W, const float* bias, int N, int
         for (int k = 0; k < K; ++k) {
             const float v = W[(size_t)n * K + k];
             const size_t o = (size_t)n * L.Kp + k;
-            const size_t ob = blocked ? ((size_t)(k / 32) * N + n) * 32 + (k % 32) : o;
+            const size_t ob = blocked ? plane_off(N, n, k) : o;
             w[o] = v;
             hi[ob] = f2bf(v);
             lo[ob] = f2bf(v - bf2f(hi[ob]));
@@ -82,36 +83,19 @@ static Lin pack_linear(rgn_ctx* c, const float* W, const float* bias, int N, int
     L.hi = blob_put(c, hi.data(), hi.size() * 2);
     L.lo = blob_put(c, lo.data(), lo.size() * 2);
     if (frag) {
-        // fragment order [Kp/32][Np/32][ks 2][lane 64][8]: lane = 32 * ((k % 16) / 8) + n % 32 holds its 8 consecutive k
-        // (rows zero-padded to Np = a multiple of 32: only the output projection, N = F, needs it)
-        const size_t Np = align_up((size_t)N, 32);
-        std::vector<uint16_t> fr(Np * L.Kp, 0);
-        const size_t nb_all = Np / 32;
-        for (int n = 0; n < N; ++n)
-            for (int k = 0; k < K; ++k) {
-                const size_t kt = k / 32, ks = (k % 32) / 16, lane = 32 * ((k % 16) / 8) + n % 32;
-                fr[(((kt * nb_all + n / 32) * 2 + ks) * 64 + lane) * 8 + k % 8] = f2bf(W[(size_t)n * K + k]);
-            }
-        L.fr = blob_put(c, fr.data(), fr.size() * 2);
-        if (frag_lo) {   // the lo plane of the split, same order: with fr the operand pair of k_mlp_x3
-            std::vector<uint16_t> fl(Np * L.Kp, 0);
+        // fragment order [Kp/32][Np/32][ks 2][lane 64][8] (rgn_layout.h: frag_off), rows zero-padded to Np = a multiple of 32: only the output
+        // projection, N = F, needs it. One plane per conversion: bf16 hi; the lo part of the split (with fr the operand pair of k_mlp_x3); IEEE fp16
+        // (k_layers' fp16-operand form)
+        const size_t Np = align_up((size_t)N, 32), nb_all = Np / 32;
+        auto frag_plane = [&](auto conv) {
+            std::vector<uint16_t> fr(Np * L.Kp, 0);
             for (int n = 0; n < N; ++n)
-                for (int k = 0; k < K; ++k) {
-                    const size_t kt = k / 32, ks = (k % 32) / 16, lane = 32 * ((k % 16) / 8) + n % 32;
-                    const float v = W[(size_t)n * K + k];
-                    fl[(((kt * nb_all + n / 32) * 2 + ks) * 64 + lane) * 8 + k % 8] = f2bf(v - bf2f(f2bf(v)));
-                }
-            L.fr_lo = blob_put(c, fl.data(), fl.size() * 2);
-        }
-        if (frag16) {    // the same plane as IEEE fp16 (k_layers' fp16-operand form)
-            std::vector<uint16_t> fh(Np * L.Kp, 0);
-            for (int n = 0; n < N; ++n)
-                for (int k = 0; k < K; ++k) {
-                    const size_t kt = k / 32, ks = (k % 32) / 16, lane = 32 * ((k % 16) / 8) + n % 32;
-                    fh[(((kt * nb_all + n / 32) * 2 + ks) * 64 + lane) * 8 + k % 8] = f2h(W[(size_t)n * K + k]);
-                }
-            L.fr16 = blob_put(c, fh.data(), fh.size() * 2);
-        }
+                for (int k = 0; k < K; ++k) fr[frag_off(nb_all, n, k)] = conv(W[(size_t)n * K + k]);
+            return blob_put(c, fr.data(), fr.size() * 2);
+        };
+        L.fr = frag_plane([](float v) { return f2bf(v); });
+        if (frag_lo) L.fr_lo = frag_plane([](float v) { return f2bf(v - bf2f(f2bf(v))); });
+        if (frag16) L.fr16 = frag_plane([](float v) { return f2h(v); });
     }
     if (bias) {
         L.b = blob_put(c, bias, (size_t)N * 4);

@@ -5,13 +5,13 @@
 // (model/cmdm.py:227 -> TransformerDecoderLayer._sa_block with generate_square_subsequent_mask :168-171).
 // A workgroup owns TWO samples and H/2 heads (grid = ceil(Bm/2) x 2; one head each for small launches). For each of its
 // heads it computes [q_h | k_h | v_h] = x . W_h^T for both samples at once (128 x 384, split-bf16 MFMA, operands by
-// direct-to-LDS DMA from the K32-blocked planes exactly as in k_gemm_x3) and then runs the attention straight from the
+// direct-to-LDS DMA from the K32-blocked planes into swizzled images: the layouts of rgn_layout.h, as in k_gemm_x3) and then runs the attention straight from the
 // accumulators: an MFMA contraction does not care in which order the reduction index is fed as long as both operands
 // agree, and the C/D layouts of q^T, k^T (accumulated transposed: W fragment as the MFMA A operand), v and the
 // softmaxed scores agree by construction, so S^T = K.Q^T and O^T = V^T.P^T take the accumulator registers as operands
 // with no LDS staging, no transposes and no fragment reads. The only exchange is the sum of the four dh-tile partials
 // of S^T through an fp32 LDS buffer that aliases the dead pipeline stages. The head's output is stored as split planes
-// in the K32-blocked layout the out_proj GEMM consumes.
+// in the K32-blocked layout the out_proj GEMM consumes. The C/D map the register-resident attention relies on is mfma32_row / mfma32_col there.
 //
 // Why two samples x half the heads instead of one sample x all heads: the kernel is bound by the ~20 B/clk a CU pulls
 // from L2 into LDS (see rgn_gemm_x3.hip), and almost all of that is the in_proj weight stream. Pairing samples halves
@@ -189,7 +189,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
             asm volatile("" : "+v"(lim));
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                st[tl][i] = ((i & 3) + 8 * (i >> 2) <= lim) ? st[tl][i] : -INFINITY;
+                st[tl][i] = (mfma32_row(i, 0) <= lim) ? st[tl][i] : -INFINITY;
                 mx = fmaxf(mx, st[tl][i]);
             }
         }
@@ -248,7 +248,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
                 run[i4] = __builtin_bit_cast(u32x2, hv);
             }
             const __amdgpu_buffer_rsrc_t o_rs = __builtin_amdgcn_make_buffer_rsrc(g.out.hi, 0, (int)((size_t)g.out.rows * g.d * 2), 0x00020000);
-            const size_t o = ((size_t)(hd * (QA_DH / 32) + wn) * g.out.rows + row0 + q) * 32 + 8 * kh;
+            const size_t o = plane_chunk(g.out.rows, row0 + q, hd * (QA_DH / 32) + wn, kh);
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {          // runs (2 pr, 2 pr + 1) = elements 16 pr + 4 kh + {0..3} and 16 pr + 8 + 4 kh + {0..3}
                 u32x4 v;
@@ -262,7 +262,7 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
                 if (live && q < Tq) __builtin_amdgcn_raw_buffer_store_b128(v, o_rs, (int)((o + 16 * pr) * 2), 0, RGN_QA_ST_AUX);
             }
         } else if (live && q < Tq) {
-            const size_t o = ((size_t)(hd * (QA_DH / 32) + wn) * g.out.rows + row0 + q) * 32 + 4 * kh;
+            const size_t o = plane_chunk(g.out.rows, row0 + q, hd * (QA_DH / 32) + wn, 0) + 4 * kh;
 #pragma unroll
             for (int i4 = 0; i4 < 4; ++i4) {
                 op4 hv, lv;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
 
     size_t a_src;
     {
-        const int r = tid >> 2, c = (tid & 3) ^ ((r >> 2) & 3);      // tile row r: sample r / 64, token r % 64
+        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
         const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
         const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
         a_src = ((size_t)(b0 + sm) * Tq + rr) * 32 + c * 8;
@@ -312,13 +312,13 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     for (int t = 0; t < 2; ++t) {
         const int rr = wm * 64 + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
     }
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int rr = t * QA_DH + wn * 32 + l31;                    // t = 0 / 1 / 2: the wave's 32 columns of q / k / v
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
     }
     const int nk = g.Kp / 32;
     float* bias_s = reinterpret_cast<float*>(smem + 4 * (A_BYTES + W_BYTES));   // [hpb][3][128] in_proj biases, past the stages / operand buffers
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
         size_t w_src[W_IT];
 #pragma unroll
         for (int it = 0; it < W_IT; ++it) {
-            const int q = it * QA_NT + tid, r = q >> 2, c = (q & 3) ^ ((r >> 2) & 3);
+            const int q = it * QA_NT + tid, r = q >> 2, c = img_dma_chunk(r, q & 3);
             const int which = r >> 7, j = r & 127;
             w_src[it] = ((size_t)which * d + hd * QA_DH + j) * 32 + c * 8;
         }
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
 // The DMA-fed loop above moves 112 KiB through LDS per k-step (32 KiB of DMA writes + 80 KiB of fragment reads, of which
 // 48 KiB are the W fragments) against the 128 B/clk the LDS delivers: ~1400 clk per k-step for 768 clk of MFMA work
 // (tools/qkv_attn_bench -DRGN_QA_PROF). Here every wave loads its own q/k/v weight fragments straight from the
-// fragment-ordered plane ([Kp/32][3d/32][2 ks][64 lanes][8], one contiguous 1 KiB run per wave-load, as in k_rowgemm)
+// fragment-ordered plane ([Kp/32][3d/32][2 ks][64 lanes][8] of rgn_layout.h, one contiguous 1 KiB run per wave-load, as in k_rowgemm)
 // into a 4-slot register ring, 3 k-steps ahead; only the activation tile (8 KiB per k-step, loaded to registers 3 steps
 // ahead as well and written to a 2-stage LDS ring one step ahead) still passes through LDS. No direct-to-LDS DMA in the
 // loop, and the 16 k-steps are fully unrolled: the compiler's own s_waitcnt bookkeeping then stays exact (it drains
@@ -466,7 +466,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
 
     unsigned a_voff;                                                 // this thread's 16 bytes of every activation k-block (elements)
     {
-        const int r = tid >> 2, c = (tid & 3) ^ ((r >> 2) & 3);      // tile row r: sample r / 64, token r % 64
+        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
         const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
         const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
         a_voff = (unsigned)((b0 + sm) * Tq + rr) * 32u + c * 8;
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
     for (int t = 0; t < 2; ++t) {
         const int rr = wm * 64 + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
     }
     char* abuf = smem + QR_ABUF;
     float* bias_s = reinterpret_cast<float*>(abuf + 2 * STAGE);
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
     constexpr int nb_all = 3 * 512 / 32;
     unsigned a_voff;
     {
-        const int r = tid >> 2, c = (tid & 3) ^ ((r >> 2) & 3);      // tile row r: sample r / 64, token r % 64
+        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
         const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
         const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
         a_voff = (unsigned)((b0 + sm) * Tq + rr) * 32u + c * 8;
@@ -603,7 +603,7 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
     for (int t = 0; t < 2; ++t) {
         const int rr = wm * 64 + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
     }
     char* abuf = smem + QR_ABUF;                                     // [stage 2][plane 2][64 rows][64 B]
     float* bias_s = reinterpret_cast<float*>(abuf + 4 * STAGE);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
     const unsigned a_kbytes = (unsigned)g.a_rows * 64u;
     unsigned a_voff;                                                 // this thread's 16 bytes of every activation k-block
     {
-        const int r = tid >> 2, c = (tid & 3) ^ ((r >> 2) & 3);
+        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);
         const int rr = r < Tq ? r : Tq - 1;                          // padding rows replicate the last token (masked as keys, never stored as queries)
         a_voff = ((unsigned)(b * Tq + rr) * 32u + c * 8) * 2u;
     }
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
     for (int t = 0; t < QL_TT; ++t) {
         const int rr = t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
     }
     f32x16 acc[QL_TT];
 #pragma unroll
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 float mt = -INFINITY;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int key = 32 * kj + (i & 3) + 8 * (i >> 2) + 4 * kh;
+                    const int key = 32 * kj + mfma32_row(i, kh);
                     const bool ok = (key <= qrow) && (key < Tq);
                     st[i] = ok ? st[i] : -INFINITY;
                     mt = fmaxf(mt, st[i]);
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) patch[l31 * QL_OLD + 32 * dt + (i & 3) + 8 * (i >> 2) + 4 * kh] = oa[dt][i] * inv;
+            for (int i = 0; i < 16; ++i) patch[l31 * QL_OLD + 32 * dt + mfma32_row(i, kh)] = oa[dt][i] * inv;
         wait_lgkmcnt<0>();
         __builtin_amdgcn_wave_barrier();
         // 16-byte WRITE-THROUGH stores (sc1): the plane is not left dirty in the XCD L2s for the end-of-kernel write-back
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(&patch[r * QL_OLD + c]);
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(&patch[r * QL_OLD + c + 4]);
                 const int col = hd * QL_DH + c;
-                const size_t o = ((size_t)(col >> 5) * g.out.rows + row0 + q) * 32 + (col & 31);
+                const size_t o = plane_off(g.out.rows, row0 + q, col);
                 op8 h;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { h[e] = (op_t)v0[e]; h[4 + e] = (op_t)v1[e]; }

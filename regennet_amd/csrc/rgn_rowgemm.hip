@@ -14,7 +14,7 @@
 //   * A workgroup owns 64 COMPLETE rows x 512 columns (8 waves, wave w = columns [64 w, 64 w + 64)), so LayerNorm
 //     statistics never leave the workgroup and the pre-norm tensor never exists in memory.
 //   * The activation tile (64 rows x K, 64 KiB at K = 512, 128 KiB at K = 1024) is DMA'd into LDS ONCE (direct-to-LDS,
-//     same swizzled image as k_gemm_x3) and stays resident: ONE barrier before the k-loop, none inside it.
+//     the swizzled image of rgn_layout.h) and stays resident: ONE barrier before the k-loop, none inside it.
 //   * Every weight row is needed by exactly one wave of the workgroup, so weights bypass LDS: each lane loads its MFMA
 //     fragment straight from the K32-blocked plane (global_load_dwordx4) into a 4-deep register ring, 3 k-steps
 //     (12 KiB per wave, 96 KiB per CU) ahead of the MFMAs that consume it; counted s_waitcnt vmcnt keeps the ring full.
@@ -69,19 +69,9 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
     RGN_RT(0)
     // ---- activation tile -> LDS, once: k-block kb = 4 wave-instructions of 1 KiB (16 rows each); wave w issues the
     //      pieces p = w, w + 8, ... of the nk * 4 pieces (p = 4 kb + q: rows [16 q, 16 q + 16) of k-block kb)
-    {
-        const int r16 = lane >> 2, c = lane & 3;
-#pragma unroll
-        for (int j = 0; j < nk / 2; ++j) {                            // compile-time trip count: the waitcnt pass can count
-            const int p = wave + 8 * j;
-            const int kb = p >> 2, q = p & 3, r = q * 16 + r16;
-            int m = m0 + r;
-            m = m < g.M ? m : g.M - 1;
-            const __bf16* src = g.A + ((size_t)kb * g.a_rows + m) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + p * 1024), 16, 0, 0);
-        }
-    }
-    // ---- weight fragments, from the FRAGMENT-ORDERED plane [Kp/32][N/32][2 ks][64 lanes][8]: lane (l31, kh) of column
+    //      (tile_dma_in: a compile-time trip count, the waitcnt pass can count)
+    tile_dma_in<0, NK>(smem, g.A, g.a_rows, m0, g.M - m0, lane, wave);
+    // ---- weight fragments, from the FRAGMENT-ORDERED plane [Kp/32][N/32][2 ks][64 lanes][8] (rgn_layout.h): lane (l31, kh) of column
     //      block nb holds W[32 nb + l31][32 kt + 16 ks + 8 kh .. + 8], i.e. exactly its MFMA A-operand fragment, and one
     //      wave-load is one contiguous 1 KiB run (loading the same fragments from the K32-blocked plane touches sixteen
     //      half-used lines per instruction and ran the k-loop at 27 B/clk/CU)
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
     for (int mt = 0; mt < 2; ++mt) {
         const int rr = 32 * mt + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[mt][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[mt][ks] = img_frag(rr, ks, kh);
     }
     f32x16 acc[2][2];                                                 // [nt][mt]: rows (registers) = columns n, lane = token
 #pragma unroll
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
         for (int j = 0; j < 8; ++j) {
             int m = m0 + 8 * wave + j;
             m = m < g.M ? m : g.M - 1;
-            const size_t o = ((size_t)(c0 >> 5) * g.r_rows + m) * 32 + (c0 & 31);
+            const size_t o = plane_off(g.r_rows, m, c0);
             rh[j] = *reinterpret_cast<const bf16x8*>(g.Rhi + o);
             if (g.Rlo) rl[j] = *reinterpret_cast<const bf16x8*>(g.Rlo + o);
         }
@@ -180,7 +170,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
     __builtin_amdgcn_s_barrier();                                     // every wave is done reading the activation image
     if constexpr (EPI == 1) {
         // (1) act(acc + bias) as bf16 into an LDS image of the output plane tile: [16 column blocks][64 rows][64 B], the
-        //     16-byte chunk c of row r at chunk position c ^ ((r >> 2) & 3) (conflict-free 8-byte writes and 16-byte reads)
+        //     swizzled image of rgn_layout.h (conflict-free 8-byte writes and 16-byte reads)
         char* img_hi = smem;
         char* img_lo = smem + 16 * 4096;
         const int nloc = wave * 64;                                   // first tile-local column of this wave
@@ -209,7 +199,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                         l[e] = (__bf16)(v[e] - (float)h[e]);
                     }
                     const int blk = (nloc >> 5) + nt;
-                    const int off = blk * 4096 + r * 64 + ((i4 ^ ((r >> 2) & 3)) << 4) + 8 * kh;
+                    const int off = blk * 4096 + img_run(r, i4, kh);
                     *reinterpret_cast<bf16x4*>(img_hi + off) = h;
                     if (g.Clo) *reinterpret_cast<bf16x4*>(img_lo + off) = l;
                 }
@@ -233,7 +223,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                 const int m = m0 + r;
                 if (m < g.M) {
                     const int b = m / g.Tq, t = m - b * g.Tq, head = blk / bpk, cc = (blk - head * bpk) * 32 + c * 8;
-                    const int off = blk * 4096 + r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
+                    const int off = blk * 4096 + img_chunk(r, c);
                     const size_t o = (((size_t)b * g.H + head) * g.Tqp + t) * g.dh + cc;
                     *reinterpret_cast<bf16x8*>(dst + o) = *reinterpret_cast<const bf16x8*>(img_hi + off);
                 }
@@ -244,8 +234,8 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                 const int p = wave * 8 + j, blk = p >> 2, r = (p & 3) * 16 + r16;
                 const int m = m0 + r;
                 if (blk < nblk_tile && m < g.M) {
-                    const int off = blk * 4096 + r * 64 + ((c ^ ((r >> 2) & 3)) << 4);
-                    const size_t o = ((size_t)((nblk0 >> 5) + blk) * g.c_rows + m) * 32 + c * 8;
+                    const int off = blk * 4096 + img_chunk(r, c);
+                    const size_t o = plane_chunk(g.c_rows, m, (nblk0 >> 5) + blk, c);
                     *reinterpret_cast<bf16x8*>(g.Chi + o) = *reinterpret_cast<const bf16x8*>(img_hi + off);
                     if (g.Clo) *reinterpret_cast<bf16x8*>(g.Clo + o) = *reinterpret_cast<const bf16x8*>(img_lo + off);
                 }
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                 norm(v, gb, bb);
             }
             if (m < g.M) {
-                const size_t o = ((size_t)(c0 >> 5) * g.o_rows + m) * 32 + (c0 & 31);
+                const size_t o = plane_off(g.o_rows, m, c0);
                 bf16x8 h;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) h[e] = (__bf16)v[e];

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
                 if (kc + j < kb1) {
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
-                        const unsigned o = ((unsigned)(kc + j) * g.w_rows + nrow[c]) * 32 + ks * 16 + kh * 8;   // (32-bit offsets: SGPR base + one VGPR per address)
+                        const unsigned o = plane_chunk<unsigned>(g.w_rows, nrow[c], kc + j, 2 * ks + kh);   // (32-bit offsets: SGPR base + one VGPR per address)
                         wh[c][j][ks] = *reinterpret_cast<const bf16x8*>(g.Whi + o);
                         if constexpr (X3) wl[c][j][ks] = *reinterpret_cast<const bf16x8*>(g.Wlo + o);
                     }
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
             }
         }
 
-    __bf16* img = reinterpret_cast<__bf16*>(smem);                   // PRE 1: [planes][16][ROWS][32], 16-byte chunk c of row r at c ^ ((r >> 2) & 3)
+    __bf16* img = reinterpret_cast<__bf16*>(smem);                   // PRE 1: [planes][16][ROWS][32], the swizzled image of rgn_layout.h (element offsets: bytes / 2)
     if constexpr (PRE == 1) {
         // ---- LayerNorm phase: wave w owns rows 8w .. 8w+7 of the tile, 4 at a time (one per 16-lane row)
         const int rr = lane >> 4, lc = lane & 15;
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
                     h[i] = (__bf16)v;
                     l[i] = (__bf16)(v - (float)h[i]);
                 }
-                const int o = ((j * 4 + (lc >> 2)) * ROWS + r) * 32 + (((lc & 3) ^ ((r >> 2) & 3)) * 8);
+                const int o = (j * 4 + (lc >> 2)) * ROWS * 32 + img_chunk(r, lc & 3) / 2;
                 *reinterpret_cast<bf16x8*>(img + o) = h;
                 if constexpr (X3) *reinterpret_cast<bf16x8*>(img + 16 * ROWS * 32 + o) = l;
             }
@@ -246,12 +246,12 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     if constexpr (PRE == 0) {
-                        const unsigned o = ((unsigned)(kc + j) * g.a_rows + mrow) * 32 + ks * 16 + kh * 8;
+                        const unsigned o = plane_chunk<unsigned>(g.a_rows, mrow, kc + j, 2 * ks + kh);
                         ah[j][ks] = *reinterpret_cast<const bf16x8*>(g.Ahi + o);
                         if constexpr (X3) al[j][ks] = *reinterpret_cast<const bf16x8*>(g.Alo + o);
                     } else {
                         const int r = patch * 32 + l31;
-                        const int o = ((kc + j) * ROWS + r) * 32 + (((ks * 2 + kh) ^ ((r >> 2) & 3)) * 8);
+                        const int o = (kc + j) * ROWS * 32 + img_frag(r, ks, kh) / 2;
                         ah[j][ks] = *reinterpret_cast<const bf16x8*>(img + o);
                         if constexpr (X3) al[j][ks] = *reinterpret_cast<const bf16x8*>(img + 16 * ROWS * 32 + o);
                     }
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = gelu_as(v[i]);
                 ph = g.Chi; pl = g.Clo;
-                o = ((size_t)(n >> 5) * g.c_rows + m) * 32 + (n & 31);
+                o = plane_off(g.c_rows, m, n);
             } else {
                 const int which = n / g.d, cin = n - which * g.d, hd = cin / g.dh, cc = cin - hd * g.dh;
                 const int b = m / g.Tq, t = m - b * g.Tq;

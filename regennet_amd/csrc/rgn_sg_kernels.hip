@@ -4,8 +4,8 @@
 //   k_sg_tconv      9 x 1 temporal convolution of a stride-1 block: the activation window of a tile resident in LDS, nine taps V rows apart
 //   k_sg_tconv_s2   ... of a stride-2 block at the output rate on polyphase planes, + the block's convolved shortcut
 //   sg_epilogue     their common epilogue: bias (per column or per vertex), identity residual, ReLU, fp32 or split-plane output
-// LDS images, DMA (global_load_lds_dwordx4, 16 rows x 64 B per wave-instruction) and the 16-byte chunk swizzle c ^ ((row >> 2) & 3) are those of
-// k_gemm_x3 (rgn_gemm_x3.hip's header). All three kernels are PERSISTENT over output tiles.
+// LDS images, DMA (global_load_lds_dwordx4, 16 rows x 64 B per wave-instruction) and the 16-byte chunk swizzle are those of
+// k_gemm_x3, defined in rgn_layout.h. All three kernels are PERSISTENT over output tiles.
 #include "rgn_internal.h"
 #include "rgn_device.h"
 
@@ -52,16 +52,16 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             const float* ap = g.add + n;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                int rr = base + (i & 3) + 8 * (i >> 2);
+                int rr = base + mfma32_row(i, 0);
                 rr = rr >= g.add_mod ? rr - g.add_mod : rr;
                 f[i] = n_ok ? __builtin_bit_cast(unsigned, ap[rr * g.ldadd]) : 0u;
             }
         } else if constexpr ((MODE & SGE_RES_PLANES) != 0) {
             // column pairs (n & ~1, + 1) as one 4-byte load: even lanes the rows of registers 0..7, odd lanes those of registers 8..15; f[0..7] hi, f[8..15] lo
-            const size_t o = ((size_t)(n >> 5) * g.r_rows + mb) * 32 + (n & 30);
+            const size_t o = plane_off(g.r_rows, mb, n & ~1);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int ii = odd ? i + 8 : i, ro = (ii & 3) + 8 * (ii >> 2);
+                const int ii = odd ? i + 8 : i, ro = mfma32_row(ii, 0);
                 const bool ok = !CHECK || (n_ok && mb + ro < g.M);
                 f[i] = ok ? *reinterpret_cast<const unsigned*>(g.Rhi + o + ro * 32) : 0u;
                 if constexpr (!F16) f[8 + i] = ok ? *reinterpret_cast<const unsigned*>(g.Rlo + o + ro * 32) : 0u;
@@ -116,7 +116,7 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             float* cp = g.C + (size_t)mb * g.ldc + n;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int ro = (i & 3) + 8 * (i >> 2);
+                const int ro = mfma32_row(i, 0);
                 if (!CHECK || (n_ok && mb + ro < g.M)) cp[(size_t)ro * g.ldc] = r[i];
             }
         } else if constexpr ((MODE & SGE_POLY) != 0) {
@@ -130,7 +130,7 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 const float mine = odd ? r[i + 8] : r[i], give = odd ? r[i] : r[i + 8];
                 const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1
                 const float c0 = odd ? got : mine, c1 = odd ? mine : got;
-                const int ii = odd ? i + 8 : i, ro = (ii & 3) + 8 * (ii >> 2);
+                const int ii = odd ? i + 8 : i, ro = mfma32_row(ii, 0);
                 int v = v0 + ro, t = t0, nm = (int)nm0;
                 if (v >= Vv) { v -= Vv; ++t; }
                 if (t >= Tp) { t -= Tp; ++nm; }
@@ -149,13 +149,13 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             }
         } else if constexpr (!CHECK) {   // K32-blocked planes [N/32][c_rows][32]: a 32-column tile is one contiguous run of rows
             // adjacent columns paired across lane ^ 1 -> packed bf16x2 stores: even lanes rows of registers 0..7, odd lanes those of registers 8..15
-            const size_t o = ((size_t)(n >> 5) * g.c_rows + mb) * 32 + (n & 30);
+            const size_t o = plane_off(g.c_rows, mb, n & ~1);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float mine = odd ? r[i + 8] : r[i], give = odd ? r[i] : r[i + 8];
                 const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1
                 const float c0 = odd ? got : mine, c1 = odd ? mine : got;
-                const int ii = odd ? i + 8 : i, ro = (ii & 3) + 8 * (ii >> 2);
+                const int ii = odd ? i + 8 : i, ro = mfma32_row(ii, 0);
                 if constexpr (F16) {
                     f16x2 hv = {(_Float16)c0, (_Float16)c1};
                     *reinterpret_cast<f16x2*>(g.Chi + o + ro * 32) = hv;
@@ -167,10 +167,10 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 }
             }
         } else {
-            const size_t o = ((size_t)(n >> 5) * g.c_rows + mb) * 32 + (n & 31);
+            const size_t o = plane_off(g.c_rows, mb, n);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int ro = (i & 3) + 8 * (i >> 2);
+                const int ro = mfma32_row(i, 0);
                 if (n_ok && mb + ro < g.M) {
                     if constexpr (F16) reinterpret_cast<_Float16*>(g.Chi)[o + ro * 32] = (_Float16)r[i];
                     else {
@@ -250,14 +250,14 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int 
             long long gr = (long long)m0t - 4LL * V + r;
             gr = gr < row_lo ? row_lo : (gr > row_hi ? row_hi : gr);
             const int p0 = CIRC ? ((ws + r0) & RMASK) : r0, pr = p0 + (lane >> 2);   // (pieces start on multiples of 16: they never wrap)
-            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (((lane & 3) ^ ((pr >> 2) & 3)) << 4);
+            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (img_dma_chunk(pr, lane & 3) << 4);
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + pl * A_PLANE + p0 * 64), 16, 0, 0);
         }
     };
     unsigned w_lane[W_IT];                                       // this thread's 16 bytes of a weight tile (N is a multiple of BN: no column clamp)
 #pragma unroll
     for (int it = 0; it < W_IT; ++it) {
-        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = (qq & 3) ^ ((r >> 2) & 3);
+        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = img_dma_chunk(r, qq & 3);
         w_lane[it] = (unsigned)r * 64u + c * 16u;
     }
     auto w_tile = [&](int n0t, int kt, char* stage) {
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int 
     for (int t = 0; t < TN; ++t) {
         const int rr = wn * (BN / WN) + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
     }
     const int arow0 = wm * (BM / WM) + l31;
     auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int 
 #pragma unroll
                         for (int t = 0; t < TM; ++t) {
                             const int rl = arow0 + t * 32 + dt * V, rr = CIRC ? ((ws + rl) & RMASK) : rl;
-                            const int o = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+                            const int o = img_frag(rr, ks, kh);
                             ah[ks][t] = *reinterpret_cast<const bf16x8*>(smem + o);
                             al[ks][t] = *reinterpret_cast<const bf16x8*>(smem + A_PLANE + o);
                         }
@@ -489,14 +489,14 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
         if (r < rend) {
             long long gr = first + r;
             gr = gr < row_lo ? row_lo : (gr > row_hi ? row_hi : gr);
-            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (((lane & 3) ^ ((r >> 2) & 3)) << 4);
+            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (img_dma_chunk(r, lane & 3) << 4);
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(buf + pl * pb + r0 * 64), 16, 0, 0);
         }
     };
     unsigned w_lane[W_IT];
 #pragma unroll
     for (int it = 0; it < W_IT; ++it) {
-        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = (qq & 3) ^ ((r >> 2) & 3);
+        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = img_dma_chunk(r, qq & 3);
         w_lane[it] = (unsigned)r * 64u + c * 16u;
     }
     auto w_tile = [&](const __bf16* whi, const __bf16* wlo, int n0t, int kt, char* stage) {
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
     for (int t = 0; t < TN; ++t) {
         const int rr = wn * (BN / WN) + t * 32 + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
     }
     const int arow0 = wm * (BM / WM) + l31;
     auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
 #pragma unroll
                     for (int t = 0; t < TM; ++t) {
                         const int rr = arow0 + t * 32 + j * V;
-                        const int o = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+                        const int o = img_frag(rr, ks, kh);
                         ah[ks][t] = *reinterpret_cast<const bf16x8*>(abuf + o);
                         al[ks][t] = *reinterpret_cast<const bf16x8*>(abuf + apl + o);
                     }
@@ -698,14 +698,14 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
         if (r < WRX) {
             long long gr = (long long)m0t - V + r;
             gr = gr > row_hi ? row_hi : gr;
-            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (((lane & 3) ^ ((r >> 2) & 3)) << 4);
+            const char* src = a_pl[pl] + ((long long)(CBS * cb) * g.a_rows + gr) * 64 + (((lane & 3) ^ ((r >> 2) & 3)) << 4);   // (= img_dma_chunk(r, lane & 3) << 4; this kernel's four layout sites stay spelled out: behind the functions of rgn_layout.h five of its forms take 2 - 4 more VGPRs)
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + buf * XW + pl * XP + r0 * 64), 16, 0, 0);
         }
     };
     auto w_tile = [&](int n0t, int kb, char* stage) {
 #pragma unroll
         for (int it = 0; it < W_IT; ++it) {
-            const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = (qq & 3) ^ ((r >> 2) & 3);
+            const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = (qq & 3) ^ ((r >> 2) & 3);   // (= img_dma_chunk(r, qq & 3))
             int n = n0t + r;
             n = n < g.N ? n : g.N - 1;
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(w_pl[pl] + ((size_t)kb * g.N + n) * 64 + c * 16),
@@ -716,7 +716,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
         const int rr = t * 32 + l31;
-        w_off[t] = rr * 64 + ((kh ^ ((rr >> 2) & 3)) << 4);      // k half ks = 0; ks = 1 is the chunk two further on: offset ^ 32
+        w_off[t] = rr * 64 + ((kh ^ ((rr >> 2) & 3)) << 4);   // (= img_frag(rr, 0, kh)) k half ks = 0; ks = 1 is the chunk two further on: offset ^ 32
     }
     const int r = wave * 32 + l31;
 
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int src = fbase + t_v[wv * NS + s];
-            so[s] = src * 64 + ((kh ^ ((src >> 2) & 3)) << 4);
+            so[s] = src * 64 + ((kh ^ ((src >> 2) & 3)) << 4);   // (= img_frag(src, 0, kh))
             sa[s] = t_a[wv * NS + s];
         }
         unsigned live = 0;                                       // slots that carry a coefficient for at least one row of this wave (a hub vertex's long list

@@ -7,7 +7,7 @@
 //
 // for one tile of 64 token rows per workgroup. Replaces three launches per chain and step (k_gemm_x3 out, k_update,
 // k_gemm_x3 in) and their round trips: the fp32 x0 rows (20.6 MB written + read at B=256), the token-major x' planes
-// (21.6 MB written, 10.8 MB read), 31 MB of h planes. Both GEMMs use k_mlp's machinery (activation image in LDS, weights
+// (21.6 MB written, 10.8 MB read), 31 MB of h planes. Both GEMMs use k_mlp2's machinery (activation image in LDS, weights
 // streamed from the fragment-ordered planes into a 4-slot register ring).
 //
 // Phases / LDS:  A  h tile -> image (64 KiB, DMA) ; GEMM 1 (K = 512, N = F <= 352: waves 0-5)
@@ -62,26 +62,16 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
     const int step = *g.d_step;
     const StepCoef k = g.tab[step];
 
-    // ---- A: the h tile -> LDS image [16 k-blocks][64 rows][64 B] (16-byte chunk c of row r at c ^ ((r >> 2) & 3))
-    {
-        const int r16 = lane >> 2, c = lane & 3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int p = wave + 8 * j, kb = p >> 2, r = (p & 3) * 16 + r16;
-            int m = m0 + r;
-            m = m < g.M ? m : g.M - 1;
-            const size_t src = ((size_t)kb * g.rows + m) * 32 + ((c ^ ((r >> 2) & 3)) << 3);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.h + src), (RGN_AS3 void*)(smem + p * 1024), 16, 0, 0);
-            if constexpr (GUIDED)   // the unconditional evaluation's rows of the same tokens (second half of the planes) -> a second image
-                __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(g.h + src + (size_t)g.half * 32), (RGN_AS3 void*)(smem + 65536 + p * 1024), 16, 0, 0);
-        }
-    }
+    // ---- A: the h tile -> LDS image [16 k-blocks][64 rows][64 B] (rgn_layout.h); rows past M replicate the last one
+    tile_dma_in(smem, g.h, g.rows, m0, g.M - m0, lane, wave);
+    if constexpr (GUIDED)   // the unconditional evaluation's rows of the same tokens (second half of the planes) -> a second image
+        tile_dma_in(smem + 65536, g.h, g.rows, (size_t)m0 + g.half, g.M - m0, lane, wave);
     int a_off[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const int rr = 32 * mt + l31;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[mt][ks] = rr * 64 + (((2 * ks + kh) ^ ((rr >> 2) & 3)) << 4);
+        for (int ks = 0; ks < 2; ++ks) a_off[mt][ks] = img_frag(rr, ks, kh);
     }
     op8 wf[ST_PF + 1][2][2];
     const unsigned lane8 = (unsigned)lane * 8u;
@@ -261,7 +251,7 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             }
             // x' (0 in the K padding columns and the surplus rows) -> the K32-blocked image of GEMM 2's A operand
             const int r = lane, chunk = (f & 31) >> 3;
-            *reinterpret_cast<op_t*>(ximg + (f >> 5) * 4096 + r * 64 + ((chunk ^ ((r >> 2) & 3)) << 4) + (f & 7) * 2) = (op_t)nv;
+            *reinterpret_cast<op_t*>(ximg + (f >> 5) * 4096 + img_chunk(r, chunk) + (f & 7) * 2) = (op_t)nv;
         };
         static_for<NKX>([&](auto IT) __attribute__((always_inline)) {   // groups of 4 features
             constexpr int it = decltype(IT)::value;
@@ -312,12 +302,12 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
                 op4 hv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) hv[e] = (op_t)acc[nt][mt][4 * i4 + e];
-                *reinterpret_cast<op4*>(smem + (2 * wave + nt) * 4096 + r * 64 + ((i4 ^ ((r >> 2) & 3)) << 4) + 8 * kh) = hv;
+                *reinterpret_cast<op4*>(smem + (2 * wave + nt) * 4096 + img_run(r, i4, kh)) = hv;
             }
     wait_lgkmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
-        // (write-through stores, as k_mlp's: the 15 / 31 MB of h planes are not left dirty in L2 for the end-of-kernel write-back)
+        // (write-through stores, as k_mlp2's: the 15 / 31 MB of h planes are not left dirty in L2 for the end-of-kernel write-back)
         const __amdgpu_buffer_rsrc_t h_rs = __builtin_amdgcn_make_buffer_rsrc(g.hout, 0, (int)((size_t)g.rows * 512 * 2), 0x00020000);
         const int r16 = lane >> 2, c = lane & 3;
 #pragma unroll
@@ -325,18 +315,18 @@ __global__ __launch_bounds__(ST_NT, 2) void k_step(StepArgs g) {
             const int p = wave * 8 + j, blk = p >> 2, r = (p & 3) * 16 + r16;
             const int m = m0 + r;
             if (m < g.M) {
-                const op8 v = *reinterpret_cast<const op8*>(smem + blk * 4096 + r * 64 + ((c ^ ((r >> 2) & 3)) << 4));
+                const op8 v = *reinterpret_cast<const op8*>(smem + blk * 4096 + img_chunk(r, c));
                 const __bf16* cp = g.c0 + (size_t)m * 512 + blk * 32 + c * 8;
                 op8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = (op_t)((float)v[e] + (float)c0v[j][e]);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), h_rs, (int)((((size_t)blk * g.rows + m) * 32 + c * 8) * 2), 0, RGN_ST_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), h_rs, (int)(plane_chunk(g.rows, m, blk, c) * 2), 0, RGN_ST_ST_AUX);
                 if constexpr (GUIDED) {   // the unconditional evaluation sees the same x', with its own condition part
                     const op8 cu = *reinterpret_cast<const op8*>(cp + (size_t)g.half * 512);
                     op8 ou;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) ou[e] = (op_t)((float)v[e] + (float)cu[e]);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ou), h_rs, (int)((((size_t)blk * g.rows + m + g.half) * 32 + c * 8) * 2), 0, RGN_ST_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ou), h_rs, (int)(plane_chunk(g.rows, m + g.half, blk, c) * 2), 0, RGN_ST_ST_AUX);
                 }
             }
         }

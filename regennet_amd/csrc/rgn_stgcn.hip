@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_sg_agg(SgPl x, SgPl z, const int* __res
     const unsigned frame = row / (unsigned)V;
     const int w = (int)(row - frame * (unsigned)V);
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const size_t in_off = ((size_t)(c8 >> 2) * x.R) * 32 + 8 * (c8 & 3);
+    const size_t in_off = plane_chunk(x.R, 0, c8 >> 2, c8 & 3);
     const int j0 = staged ? s_ptr[k * V + w] : nz_ptr[k * V + w], j1 = staged ? s_ptr[k * V + w + 1] : nz_ptr[k * V + w + 1];
     for (int j = j0; j < j1; ++j) {
         const size_t src = in_off + (size_t)(frame * (unsigned)V + (unsigned)(staged ? s_v[j] : nz_v[j])) * 32;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void k_sg_agg(SgPl x, SgPl z, const int* __res
     }
     bf16x8 h, l;
     split_bf16(acc, h, l);
-    const size_t dst = ((size_t)(k * (C / 32) + (c8 >> 2)) * z.R + row) * 32 + 8 * (c8 & 3);
+    const size_t dst = plane_chunk(z.R, row, k * (C / 32) + (c8 >> 2), c8 & 3);
     *reinterpret_cast<bf16x8*>(z.hi + dst) = h;
     *reinterpret_cast<bf16x8*>(z.lo + dst) = l;
 }
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void k_sg_block0(SgPl x, SgPl g, const int* __
             for (int q = 0; q < K * C; ++q) acc[j] = fmaf(z[q], W[(og * 8 + j) * (K * C) + q], acc[j]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = fmaxf(acc[j], 0.f);
-        const size_t o = ((size_t)(og >> 2) * g.R + row) * 32 + 8 * (og & 3);
+        const size_t o = plane_chunk(g.R, row, og >> 2, og & 3);
         if constexpr (F16) {
             f16x8 f;
 #pragma unroll
@@ -320,7 +320,7 @@ __global__ void k_sg_zero(SgPl g, long long base, int NM, int Tr, int Tp, int V,
     bf16x8 zero;
 #pragma unroll
     for (int j = 0; j < 8; ++j) zero[j] = (__bf16)0.f;
-    const long long o = ((long long)b * g.R + base + row) * 32 + 8 * q;
+    const long long o = plane_chunk<long long>(g.R, base + row, b, q);
     *reinterpret_cast<bf16x8*>(g.hi + o) = zero;
     *reinterpret_cast<bf16x8*>(g.lo + o) = zero;
 }
@@ -373,7 +373,7 @@ __global__ void k_sg_post(const float* __restrict__ conv, const float* __restric
             val[0] += r0.x + q0.x; val[1] += r0.y + q0.y; val[2] += r0.z + q0.z; val[3] += r0.w + q0.w;
             val[4] += r1.x + q1.x; val[5] += r1.y + q1.y; val[6] += r1.z + q1.z; val[7] += r1.w + q1.w;
         } else if (res_id) {                       // identity residual: stride 1, same channel count, same geometry as conv
-            const size_t o = ((size_t)(c8 >> 2) * xin.R + srow) * 32 + 8 * (c8 & 3);
+            const size_t o = plane_chunk(xin.R, srow, c8 >> 2, c8 & 3);
             const bf16x8 h = *reinterpret_cast<const bf16x8*>(xin.hi + o), l = *reinterpret_cast<const bf16x8*>(xin.lo + o);
 #pragma unroll
             for (int e = 0; e < 8; ++e) val[e] += (float)h[e] + (float)l[e];
@@ -383,7 +383,7 @@ __global__ void k_sg_post(const float* __restrict__ conv, const float* __restric
     }
     bf16x8 h, l;
     split_bf16(val, h, l);
-    const size_t o = ((size_t)(c8 >> 2) * xout.R + orow) * 32 + 8 * (c8 & 3);
+    const size_t o = plane_chunk(xout.R, orow, c8 >> 2, c8 & 3);
     *reinterpret_cast<bf16x8*>(xout.hi + o) = h;
     *reinterpret_cast<bf16x8*>(xout.lo + o) = l;
 }
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void k_sg_pool(SgPl x, float* __restrict__ poo
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (c8 < c8n)
         for (int m = 0; m < M; ++m) {
-            const size_t o = ((size_t)(c8 >> 2) * x.R + ((size_t)(n * M + m) * Tp) * V) * 32 + 8 * (c8 & 3);
+            const size_t o = plane_chunk(x.R, ((size_t)(n * M + m) * Tp) * V, c8 >> 2, c8 & 3);
             for (int i = sl; i < T * V; i += 8) {
                 if constexpr (F16) {
                     const f16x8 h = *reinterpret_cast<const f16x8*>(x.hi + o + (size_t)i * 32);
@@ -458,7 +458,7 @@ int sg_upload_planes(rgn_stgcn_ctx* c, const std::vector<float>& W, int N, int K
     for (int n = 0; n < N; ++n)
         for (int k = 0; k < Kp; ++k) {
             const float v = W[(size_t)n * Kp + k];
-            const size_t o = ((size_t)(k / 32) * N + n) * 32 + k % 32;
+            const size_t o = plane_off(N, n, k);
             h[o] = sg_f2bf(v);
             l[o] = sg_f2bf(v - sg_bf2f(h[o]));
             if (f16) {

@@ -5,7 +5,7 @@
 //
 // A workgroup holds R = 32 MT token rows, wave w the output columns [CW w, CW w + CW), CW = 32 NT: MT x NT accumulator tiles of 32 x 32.
 //   element (token 32 mt + l31, column CW wave + 32 nt + 8 i4 + 4 kh + e)  <->  register acc[nt][mt][4 i4 + e]         (l31 = lane & 31, kh = lane >> 5)
-// An activation image is [K / 32 k-blocks][R rows][64 B] of 16-bit operands, the 16-byte chunks of a row swizzled by (row >> 2) & 3.
+// An activation image is the swizzled LDS operand image of rgn_layout.h, [K / 32 k-blocks][R rows][64 B]; the weights are its fragment-ordered plane.
 // The constants struct C of a kernel names MT, NT, NW (waves), R, RD (ring depth in granules), KB (bytes of a k-block) and RED / REDF (byte offset of
 // the statistics exchange in LDS / floats of one of its two buffers, each [2 stats][NW waves][R tokens]).
 #pragma once
@@ -33,7 +33,7 @@ __device__ __forceinline__ TailLane tail_lane(char* smem, int lane, int wave) {
     asm volatile("" : "+v"(red_base));
     int red_base2 = red_base + 128 * kh;
     asm volatile("" : "+v"(red_base2));
-    return TailLane{smem, lane * 16, wave, kh, (l31 >> 2) & 3, img_base, red_base, red_base2};
+    return TailLane{smem, lane * 16, wave, kh, img_swz(l31), img_base, red_base, red_base2};
 }
 
 // ---- tile geometry
@@ -42,7 +42,7 @@ __device__ __forceinline__ TailLane tail_lane(char* smem, int lane, int wave) {
 __device__ __forceinline__ void tail_a_off(int (&a)[2], int lane) {
     const int l31 = lane & 31, kh = lane >> 5;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) a[ks] = l31 * 64 + (((2 * ks + kh) ^ ((l31 >> 2) & 3)) << 4);
+    for (int ks = 0; ks < 2; ++ks) a[ks] = img_frag(l31, ks, kh);
 }
 __device__ __forceinline__ void tail_a_off(int (&a)[2], const int (&a0)[2], int img) {
 #pragma unroll
@@ -52,11 +52,11 @@ __device__ __forceinline__ int tail_col4(const TailLane& t, int nt, int i4) { re
 // the 8-byte run of (nt, i4, mt) inside the image at byte offset img: one address register per i4, (nt, mt) an immediate offset of the access
 template <class OP, class C>
 __device__ __forceinline__ typename OP::v4* tail_img_run(const TailLane& t, int img, int nt, int i4, int mt) {
-    return reinterpret_cast<typename OP::v4*>(t.smem + (img + t.img_base + ((i4 ^ t.swz) << 4)) + (nt * C::KB + mt * 2048));
+    return reinterpret_cast<typename OP::v4*>(t.smem + (img + t.img_base + img_slot(i4, t.swz)) + (nt * C::KB + mt * 2048));
 }
 
 // ---- weight ring: granule = half a k-step (16 k) of this wave's NT column blocks; W: fragment-ordered plane [K/32][nb_all][2][64][8]
-//      (rgn_rowgemm.hip). Granule index hs = 2 kt + ks. Buffer loads: the resource (based at the wave's first column block cb0) is scalar and
+//      (rgn_layout.h). Granule index hs = 2 kt + ks (frag_granule). Buffer loads: the resource (based at the wave's first column block cb0) is scalar and
 //      every granule offset a compile-time constant, the lane contributes lane * 16
 struct TailPass { __amdgpu_buffer_rsrc_t rs; int kstride, hs0; };   // kstride = nb_all * 2048 bytes per k-block
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tail_wrs(const __bf16* W, int cb0, int bytes) {
@@ -68,7 +68,7 @@ __device__ __forceinline__ void tail_load_g(typename OP::v8 (&wf)[C::RD][C::NT],
     // (the granule offset is materialised by a volatile s_mov right here: as plain literals the offsets of a layer are hoisted out of k_layers'
     // layer loop as loop invariants and live in spilled SGPRs. k_mlp2 has no such loop: with the s_mov it needs 57 SGPRs where plain literals took 106, its VGPRs the same)
     int soff;
-    asm volatile("s_mov_b32 %0, %1" : "=s"(soff) : "i"((hs >> 1) * ps.kstride + (hs & 1) * 1024));
+    asm volatile("s_mov_b32 %0, %1" : "=s"(soff) : "i"(frag_granule(hs, ps.kstride)));
 #pragma unroll
     for (int nt = 0; nt < C::NT; ++nt)
         wf[slot][nt] = __builtin_bit_cast(typename OP::v8, __builtin_amdgcn_raw_buffer_load_b128(ps.rs, t.lane16, soff + nt * 2048, 0));
