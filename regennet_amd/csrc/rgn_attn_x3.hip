@@ -35,9 +35,7 @@ __global__ __launch_bounds__(64 * NT) void k_attn_x3(AttnX3Args a) {
     __bf16* sh = reinterpret_cast<__bf16*>(smem);  // [2 planes][PLANE]
     // XCD-affine mapping (block id -> XCD id%8): every XCD gets one contiguous range of samples, matching the row ranges
     // the in_proj / out_proj GEMM tiles occupy on that XCD
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int vid = xcd_affine(blockIdx.x, gridDim.x);
     const int b = vid / a.H, hd = vid - b * a.H;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -114,12 +114,14 @@ struct Planes {
     int rows;     // row count of the plane (the M of the consuming GEMM)
 };
 
-// Fused in_proj GEMM + causal self-attention, one workgroup per (sample pair, half of the heads) (rgn_qkv_attn.hip)
+// Fused in_proj GEMM + self-attention at <= 64 tokens (rgn_qkv_attn.hip), three forms - qkv_attn_form says which one a launch runs. DMA-fed (k_qkv_attn: 8 waves, a
+// workgroup per sample pair and group of heads; Whi / Wlo by direct-to-LDS DMA; every width); register-streamed at d = 512 (4 waves, a workgroup per sample and
+// group of heads): plain (k_qkv_attn_rs<false>: Wfr; bf16 or fp16) and split (k_qkv_attn_rs<true>: Wfr + Wfr_lo). k_qkv_attn_long (65 .. 160 tokens) takes the same arguments.
 struct QkvAttnArgs {
     const __bf16* Ahi; const __bf16* Alo; int a_rows;   // layer input planes [Kp/32][a_rows][32] (advanced to the first sample)
     const __bf16* Whi; const __bf16* Wlo;               // in_proj weight planes [Kp/32][3d][32]
     const __bf16* Wfr;                                  // the hi plane in MFMA-fragment order [Kp/32][3d/32][2][64][8] (plain-bf16 phase, d = 512), nullable
-    const __bf16* Wfr_lo;                               // split phase, register-streamed form (k_qkv_attn_rs_x3): the lo plane in the same order, with Wfr = the bf16 hi plane; nullable
+    const __bf16* Wfr_lo;                               // split phase, register-streamed form (k_qkv_attn_rs<true>): the lo plane in the same order, with Wfr = the bf16 hi plane; nullable
     const float* bias;                                  // in_proj bias [3d]
     Planes out;                                         // attention output planes (advanced to the first sample's row)
     int Bm, Kp, d, H, Tq;
@@ -129,6 +131,10 @@ struct QkvAttnArgs {
 };
 bool qkv_attn_supported(int Tq, int dh, int d);
 hipError_t configure_qkv_attn();
+// Which form runs these arguments in the phase's arithmetic (x3: split), and its grid.y = groups of heads (a workgroup runs H / hsplit heads back to back)
+enum QkvForm { QF_DMA = 0, QF_RS, QF_RS_X3 };
+struct QkvAttnForm { QkvForm form; int hsplit; };
+QkvAttnForm qkv_attn_form(const QkvAttnArgs& g, bool x3);
 // causal = false: full self-attention (arch='offline' encoder layers; all four S^T tiles, keys >= Tq stay masked)
 hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s, bool causal = true);
 // long sequences (65 .. 160 tokens), plain-bf16 phase, d = 512: one workgroup per (sample, head) (rgn_qkv_attn_long.hip)

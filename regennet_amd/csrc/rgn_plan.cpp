@@ -850,10 +850,10 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
             } else {
                 switch (pl.attn) {
                 case AF_QKV: mac[KC_QKV] = qkv + attn; n[KC_QKV] = L; {
-                    // (launch_qkv_attn's own rule: the register-streamed forms are d = 512 instantiations that read fragment-ordered weights; every
-                    //  other width - and a mode that packs no fragment planes - runs the direct-to-LDS k_qkv_attn in both arithmetics)
-                    const bool fr0 = c->L > 0 && c->layers[0].qkv.fr != 0;
-                    const bool rs = c->d == 512 && fr0 && (!x3 || (c->layers[0].qkv.fr_lo != 0 && !c->qkv_x3_dma));
+                    // (the launcher's own rule, asked for layer 0's arguments as run_layers builds them for a whole-evaluation chain: qkv_attn_form)
+                    const Planes hp{c->h_hi, x3 ? c->h_lo : nullptr, dm.Bm * dm.Tq}, ap{c->att_hi, x3 ? c->att_lo : nullptr, dm.Bm * dm.Tq};
+                    const Phase ph{x3, false};
+                    const bool rs = c->L > 0 && qkv_attn_form(qkv_args(c, dm, 0, layer_wts(c, 0, false), dm.Bm, hp, ap, ph, false, dm.Bm), x3).form != QF_DMA;
                     kn[KC_QKV] = !rs ? (enc ? "k_qkv_attn<full>" : "k_qkv_attn")
                                      : x3 ? (enc ? "k_qkv_attn_rs_x3<full>" : "k_qkv_attn_rs_x3") : (enc ? "k_qkv_attn_rs<full>" : "k_qkv_attn_rs");
                     break;

@@ -1,25 +1,32 @@
-// Fused in_proj GEMM + causal self-attention (Tq <= 64 tokens, head dim 128): q, k, v never leave the register file.
-// Every kernel here also has a full-attention instantiation (CAUSAL = false) for the encoder layers of arch='offline' (cmdm.py:228-238).
+// Fused in_proj GEMM + self-attention (Tq <= 64 tokens, head dim 128): q, k, v never leave the register file. Causal for the decoder layers,
+// and every kernel here also has a full-attention instantiation (CAUSAL = false) for the encoder layers of arch='offline' (cmdm.py:228-238).
 //
 // Replaces, per decoder layer, the packed in_proj Linear of nn.MultiheadAttention and the attention itself
 // (model/cmdm.py:227 -> TransformerDecoderLayer._sa_block with generate_square_subsequent_mask :168-171).
-// A workgroup owns TWO samples and H/2 heads (grid = ceil(Bm/2) x 2; one head each for small launches). For each of its
-// heads it computes [q_h | k_h | v_h] = x . W_h^T for both samples at once (128 x 384, split-bf16 MFMA, operands by
-// direct-to-LDS DMA from the K32-blocked planes into swizzled images: the layouts of rgn_layout.h, as in k_gemm_x3) and then runs the attention straight from the
-// accumulators: an MFMA contraction does not care in which order the reduction index is fed as long as both operands
-// agree, and the C/D layouts of q^T, k^T (accumulated transposed: W fragment as the MFMA A operand), v and the
+// For each of its heads a workgroup computes [q_h | k_h | v_h] = x . W_h^T (64 tokens per sample x 384, operand layouts: rgn_layout.h) and then runs
+// the attention straight from the accumulators: an MFMA contraction does not care in which order the reduction index is fed as long as both
+// operands agree, and the C/D layouts of q^T, k^T (accumulated transposed: W fragment as the MFMA A operand), v and the
 // softmaxed scores agree by construction, so S^T = K.Q^T and O^T = V^T.P^T take the accumulator registers as operands
 // with no LDS staging, no transposes and no fragment reads. The only exchange is the sum of the four dh-tile partials
-// of S^T through an fp32 LDS buffer that aliases the dead pipeline stages. The head's output is stored as split planes
-// in the K32-blocked layout the out_proj GEMM consumes. The C/D map the register-resident attention relies on is mfma32_row / mfma32_col there.
+// of S^T through an fp32 LDS buffer. The head's output is stored as split planes in the K32-blocked layout the out_proj GEMM consumes.
+// The C/D map the register-resident attention relies on is mfma32_row / mfma32_col there. That attention, qa_attention, is one function;
+// what differs between the THREE FORMS is how the in_proj GEMM gets its operands (qkv_attn_form at the foot of the file decides which one runs):
 //
-// Why two samples x half the heads instead of one sample x all heads: the kernel is bound by the ~20 B/clk a CU pulls
+//   k_qkv_attn<X3>          DMA-fed: both operands by direct-to-LDS DMA from the K32-blocked planes into swizzled images, as in k_gemm_x3. 8 waves,
+//                           a workgroup owns TWO samples and H/2 heads (grid = ceil(Bm/2) x 2; one head each for small launches). Split-bf16
+//                           (X3: three MFMAs per product) or plain bf16. Every width but 512, a mode that packs no fragment-ordered weight planes,
+//                           and the split phase under the engine option QKV_X3_DMA = 1.
+//   k_qkv_attn_rs<false>    register-streamed, plain phase at d = 512 (bf16 or fp16 operands): the weights go from the fragment-ordered plane straight
+//                           into a register ring; 4 waves, ONE sample and H/2 heads per workgroup (all heads' workgroups apart while the evaluation is small).
+//   k_qkv_attn_rs<true>     the same loop in the split arithmetic (plan_query reports it as k_qkv_attn_rs_x3), split phase at d = 512: hi and lo
+//                           fragment planes side by side. Bit-equal to k_qkv_attn<true>.
+//
+// The DMA-fed form. Why two samples x half the heads instead of one sample x all heads: the kernel is bound by the ~20 B/clk a CU pulls
 // from L2 into LDS (see rgn_gemm_x3.hip), and almost all of that is the in_proj weight stream. Pairing samples halves
 // the weight bytes per sample (2.0 MiB of DMA per workgroup instead of 3.5 MiB) at the same workgroup count.
-//
 // 8 waves; wave = (sample wm, dh tile wn): wave tile 64 x 96 = both token tiles x the 32 columns wn of each of q, k, v;
 // two 64 KiB LDS stages [A 128x32 | W_h 384x32] x {hi, lo}; tile rows 0-63 / 64-127 are the tokens of sample 0 / 1
-// (padding rows replicate the last token and are masked).
+// (padding rows replicate the last token and are masked). The S^T exchange buffer aliases the dead pipeline stages.
 #include "rgn_internal.h"
 #include "rgn_device.h"
 
@@ -45,6 +52,37 @@ __device__ long long g_qa_prof[64];   // tools only: phase cycle stamps of one w
 #else
 #define RGN_QT(i)
 #endif
+
+// Sum of the four dh-tile partials of the S^T tiles T0 .. T0 + NT - 1 over the sample's waves, through slots 0 .. NT - 1 of the exchange buffer
+// [sample][slot 3][wave wn][i/4][lane] float4: every wave writes its partials, barrier, every wave sums the sample's four
+template <int T0, int NT, int N>
+__device__ __forceinline__ void qa_exchange_sum(f32x16 (&st)[N], f32x4* sred, int wm, int wn, int lane, int hslot, int tid) {
+    (void)hslot; (void)tid;
+#pragma unroll
+    for (int sl = 0; sl < NT; ++sl)
+#pragma unroll
+        for (int i4 = 0; i4 < 4; ++i4) {
+            const f32x4 v = {st[T0 + sl][4 * i4], st[T0 + sl][4 * i4 + 1], st[T0 + sl][4 * i4 + 2], st[T0 + sl][4 * i4 + 3]};
+            sred[(((wm * 3 + sl) * 4 + wn) * 4 + i4) * 64 + lane] = v;
+        }
+    wait_lgkmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    if (T0 == 0) { RGN_QT(hslot * 8 + 2) }
+#pragma unroll
+    for (int sl = 0; sl < NT; ++sl)
+#pragma unroll
+        for (int i4 = 0; i4 < 4; ++i4) {
+            f32x4 v = sred[(((wm * 3 + sl) * 4 + 0) * 4 + i4) * 64 + lane];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const f32x4 u = sred[(((wm * 3 + sl) * 4 + w) * 4 + i4) * 64 + lane];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += u[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) st[T0 + sl][4 * i4 + e] = v[e];
+        }
+}
 
 // Attention straight from the in_proj accumulators of one head (see the file header); shared by the DMA-fed and the
 // register-streamed GEMM phases. acc[token tile][q | k | v]; smem: the 96 KiB fp32 exchange buffer for the S^T partials.
@@ -120,54 +158,12 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
             st[tl] = OP::mfma(kfh[kj][sl], qh[qtile][sl], st[tl]);
         }
     }
-    // sum the partials of the four dh tiles: [sample][tile][wave wn][i/4][lane] float4
     f32x4* sred = reinterpret_cast<f32x4*>(smem);
-#pragma unroll
-    for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            const f32x4 v = {st[tl][4 * i4], st[tl][4 * i4 + 1], st[tl][4 * i4 + 2], st[tl][4 * i4 + 3]};
-            sred[(((wm * 3 + tl) * 4 + wn) * 4 + i4) * 64 + lane] = v;
-        }
-    wait_lgkmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    RGN_QT(hslot * 8 + 2)
-#pragma unroll
-    for (int tl = 0; tl < 3; ++tl)
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            f32x4 v = sred[(((wm * 3 + tl) * 4 + 0) * 4 + i4) * 64 + lane];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const f32x4 u = sred[(((wm * 3 + tl) * 4 + w) * 4 + i4) * 64 + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += u[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) st[tl][4 * i4 + e] = v[e];
-        }
+    qa_exchange_sum<0, 3>(st, sred, wm, wn, lane, hslot, tid);
     if constexpr (!CAUSAL) {   // second pass: tile 3 through tile 0's slot, once every wave's reads of it have landed
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            const f32x4 v = {st[3][4 * i4], st[3][4 * i4 + 1], st[3][4 * i4 + 2], st[3][4 * i4 + 3]};
-            sred[(((wm * 3) * 4 + wn) * 4 + i4) * 64 + lane] = v;
-        }
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            f32x4 v = sred[(((wm * 3) * 4 + 0) * 4 + i4) * 64 + lane];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const f32x4 u = sred[(((wm * 3) * 4 + w) * 4 + i4) * 64 + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += u[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) st[3][4 * i4 + e] = v[e];
-        }
+        qa_exchange_sum<3, 1>(st, sred, wm, wn, lane, hslot, tid);
     }
     RGN_QT(hslot * 8 + 4)
     // softmax over keys for the lane's two queries (l31 and 32 + l31); every wave of the sample does the same work
@@ -281,6 +277,36 @@ __device__ __forceinline__ void qa_attention(f32x16 (&acc)[2][3], const QkvAttnA
 
 #undef RGN_QA_TILES
 
+// ---- the prologue the DMA-fed and the register-streamed kernels share (k_qkv_attn_long has a tile shape and wave roles of its own) ----
+// Plane row of tile row r (sample r / 64 of the workgroup's nsamp, token r % 64): padding rows replicate the last token (masked later), and
+// the rows of a dummy second sample (an odd batch leaves the last pair half empty) those of the first
+__device__ __forceinline__ int qa_plane_row(int r, int b0, int nsamp, int Tq) {
+    const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
+    return (b0 + sm) * Tq + (tk < Tq ? tk : Tq - 1);
+}
+// byte offsets of the wave's A fragments in an activation image: [token tile][k half] of sample wm
+__device__ __forceinline__ void qa_frag_offsets(int (&a_off)[2][2], int wm, int l31, int kh) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(wm * 64 + t * 32 + l31, ks, kh);
+}
+// in_proj biases of the workgroup's hpb heads from hd0 on -> LDS [hpb][q | k | v][128] (visible to every wave after the first barrier of the k-loop)
+__device__ __forceinline__ void qa_stage_bias(float* bias_s, const QkvAttnArgs& g, int hd0, int hpb, int tid, int nt) {
+    for (int i = tid; i < hpb * QA_WROWS; i += nt) {
+        const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
+        bias_s[i] = g.bias[(r >> 7) * g.d + (hd0 + hh) * QA_DH + (r & 127)];
+    }
+}
+__device__ __forceinline__ void qa_zero(f32x16 (&acc)[2][3]) {
+#pragma unroll
+    for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[ta][t][i] = 0.f;
+}
+
 template <bool X3, bool CAUSAL = true>
 __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     constexpr int NPL = X3 ? 2 : 1;
@@ -300,20 +326,10 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     const int hpb = g.H / (int)gridDim.y, hd0 = blockIdx.y * hpb;    // heads of this workgroup
     const int nsamp = g.Bm - b0 < QA_NS ? g.Bm - b0 : QA_NS;         // an odd batch leaves the last pair half empty
 
-    size_t a_src;
-    {
-        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
-        const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
-        const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
-        a_src = ((size_t)(b0 + sm) * Tq + rr) * 32 + c * 8;
-    }
+    // this thread's 16 bytes of every activation k-block (elements): chunk c of tile row tid / 4
+    const size_t a_src = (size_t)qa_plane_row(tid >> 2, b0, nsamp, Tq) * 32 + img_dma_chunk(tid >> 2, tid & 3) * 8;
     int a_off[2][2], w_off[3][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int rr = wm * 64 + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
-    }
+    qa_frag_offsets(a_off, wm, l31, kh);
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int rr = t * QA_DH + wn * 32 + l31;                    // t = 0 / 1 / 2: the wave's 32 columns of q / k / v
@@ -322,11 +338,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     }
     const int nk = g.Kp / 32;
     float* bias_s = reinterpret_cast<float*>(smem + 4 * (A_BYTES + W_BYTES));   // [hpb][3][128] in_proj biases, past the stages / operand buffers
-    for (int i = tid; i < hpb * QA_WROWS; i += QA_NT) {
-        const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
-        bias_s[i] = g.bias[(r >> 7) * d + (hd0 + hh) * QA_DH + (r & 127)];
-    }
-    // (visible to every wave after the first barrier of the k-loop)
+    qa_stage_bias(bias_s, g, hd0, hpb, tid, QA_NT);
 
     for (int hd = hd0; hd < hd0 + hpb; ++hd) {
         // ---------------- GEMM: [128 x Kp] . W_h[384 x Kp]^T ----------------------------------------------------
@@ -352,12 +364,7 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
         };
         constexpr int LPT = NPL * (1 + W_IT);                        // 8 (x3)
         f32x16 acc[2][3];
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[ta][t][i] = 0.f;
+        qa_zero(acc);
         RGN_QT((hd - hd0) * 8 + 0)
 #pragma unroll
         for (int t0 = 0; t0 < NSTG - 1; ++t0)
@@ -428,30 +435,48 @@ __global__ __launch_bounds__(QA_NT, 1) void k_qkv_attn(QkvAttnArgs g) {
     }
 }
 
-// ---- plain-bf16 phase, d = 512: the same kernel with the in_proj weights streamed into REGISTERS -------------------------
-// The DMA-fed loop above moves 112 KiB through LDS per k-step (32 KiB of DMA writes + 80 KiB of fragment reads, of which
-// 48 KiB are the W fragments) against the 128 B/clk the LDS delivers: ~1400 clk per k-step for 768 clk of MFMA work
-// (tools/qkv_attn_bench -DRGN_QA_PROF). Here every wave loads its own q/k/v weight fragments straight from the
+// ---- d = 512: the same kernel with the in_proj weights streamed into REGISTERS, k_qkv_attn_rs<X3, F16, CAUSAL> -------------------------
+// The scheme (both arithmetics). The DMA-fed loop above moves 112 KiB through LDS per k-step in the plain-bf16 build (32 KiB of DMA writes +
+// 80 KiB of fragment reads, of which 48 KiB are the W fragments) against the 128 B/clk the LDS delivers: ~1400 clk per k-step for 768 clk of
+// MFMA work (tools/qkv_attn_bench -DRGN_QA_PROF). Here every wave loads its own q/k/v weight fragments straight from the
 // fragment-ordered plane ([Kp/32][3d/32][2 ks][64 lanes][8] of rgn_layout.h, one contiguous 1 KiB run per wave-load, as in k_rowgemm)
-// into a 4-slot register ring, 3 k-steps ahead; only the activation tile (8 KiB per k-step, loaded to registers 3 steps
-// ahead as well and written to a 2-stage LDS ring one step ahead) still passes through LDS. No direct-to-LDS DMA in the
+// into a register ring, WQ fragments ahead; only the activation tile (8 KiB per plane and k-step, loaded to registers DA steps
+// ahead and written to a 2-stage LDS ring one step ahead) still passes through LDS. No direct-to-LDS DMA in the
 // loop, and the 16 k-steps are fully unrolled: the compiler's own s_waitcnt bookkeeping then stays exact (it drains
 // vmcnt at loop back-edges and before the first LDS read behind a DMA).
-constexpr int QR_NK = 16, QR_WQ = 18;                          // weight fragment ring (6 fragments per k-step)
-constexpr int QR_DA = 4, QR_ARING = QR_DA + 1;                // activation pieces: QR_DA ahead (they must be in LDS one step early)
-// QR_NS = 1 sample per workgroup (4 waves). LDS: [exchange buffer 48 KiB | activation ring [2][64 rows][64 B] | biases].
+// QR_NS = 1 sample per workgroup (4 waves). LDS: [exchange buffer 48 KiB | activation ring [2 stages][planes][64 rows][64 B] | biases].
 // Two INDEPENDENT 4-wave workgroups per CU (one wave each per SIMD) instead of one 8-wave workgroup of two samples whose two waves per
 // SIMD move through the phases in lockstep - the attention phase and the ring fill of one workgroup (no MFMA work, no weight requests)
 // then run under the other's k-loop: 36.4 -> 35.4 us alone at B = 256, 28 -> 21 us at B = 128, +3 - 4.5 % on
 // the whole step, same results bit for bit.
+//
+// What the split form (X3; round 6) changes: two planes - the hi and lo fragment planes side by side in the weight ring, the activation stage = hi | lo
+// (16 KiB per pair of stages) - three MFMAs per product, and rings half as deep in k-steps (the registers are the same: 72 for the weights). Its
+// DMA-fed twin k_qkv_attn<true> moves 64 KiB of operands per k-step through the ~20 B/clk direct-to-LDS path against 2304 cycles of MFMA (3400
+// measured). Every accumulator sees the MFMAs of k_qkv_attn<true> in the same order (k-block, k half; lo x hi, hi x lo, hi x hi): the two forms agree
+// bit for bit (tests/test_hip_parity.py), "QKV_X3_DMA" = 1 keeps the direct-to-LDS form. The kernel itself runs 53 us where the direct-to-LDS form ran
+// 73 (rocprofv3, the evaluation schedule at B = 256) - and the CALL gains 1 - 3 %: the split steps run three kernel chains side by side and are short
+// of L2 bandwidth chip-wide (k_mlp_x3 streams 5.2 MB of weight fragments per 32-row tile), so time a chain's in_proj gives back is taken by its
+// neighbours' layer tails. One sample per workgroup: 5.71 ms per ddim5 call at B = 256 against 5.79 with two (whose sample halves request the same
+// weight fragments at the same time) and 5.78 with the direct-to-LDS form, 3.04 / 3.06 / 3.14 at B = 64 (profiles/r06_qkv_x3_forms.txt).
+constexpr int QR_NK = 16;
 constexpr int QR_NS = 1, QR_NT = QR_NS * 256;
 constexpr int QR_ABUF = QR_NS * 48 * 1024;
-constexpr int QR_LDS = QR_ABUF + 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
-template <bool F16 = false, bool CAUSAL = true>
+template <bool X3> struct QrRing {                                // ring depths and LDS bytes of the two arithmetics
+    static constexpr int NPL = X3 ? 2 : 1;                        // planes: hi (| lo)
+    static constexpr int WQ = X3 ? 9 : 18;                        // weight fragment ring (6 fragments - X3: (hi, lo) pairs - per k-step): 3 / 1.5 k-steps' worth
+    static constexpr int DA = X3 ? 2 : 4, ARING = DA + 1;         // activation pieces: DA ahead (they must be in LDS one step early)
+    static constexpr int LDS = QR_ABUF + 2 * NPL * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
+};
+constexpr int QR_LDS = QrRing<false>::LDS, QX_LDS = QrRing<true>::LDS;
+// (Wfr: g.Wfr as an argument of its own; the lo plane is g.Wfr_lo)
+template <bool X3, bool F16 = false, bool CAUSAL = true>
 __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const __bf16* __restrict__ Wfr) {
+    static_assert(!(X3 && F16), "the split form is bf16 (hi, lo) pairs");
     using OP = OpFmt<F16>;                // bf16 or fp16 operands (rgn_device.h): input plane, weight plane, q / k / v / p, output plane
     using op8 = typename OP::v8;
-    constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;
+    using R = QrRing<X3>;
+    constexpr int NS = QR_NS, NT = QR_NT, NPL = R::NPL, STAGE = NS * QA_ROWS * 64;   // STAGE: one plane of one stage; a stage = hi (| lo)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -461,99 +486,110 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
     const int hpb = g.H / (int)gridDim.y, hd0 = blockIdx.y * hpb;
     const int nsamp = g.Bm - b0 < NS ? g.Bm - b0 : NS;
     RGN_QL(0)
-    constexpr int nb_all = 3 * 512 / 32;                             // d = 512 (launch_qkv_attn): compile-time weight offsets - as run-time
+    constexpr int nb_all = 3 * 512 / 32;                             // d = 512 (qkv_attn_form): compile-time weight offsets - as run-time
                                                                      // values the 96 k-step offsets of a head live in SGPRs and spill to VGPR lanes
-
-    unsigned a_voff;                                                 // this thread's 16 bytes of every activation k-block (elements)
-    {
-        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
-        const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
-        const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
-        a_voff = (unsigned)((b0 + sm) * Tq + rr) * 32u + c * 8;
-    }
+    // this thread's 16 bytes of every activation k-block (elements): chunk c of tile row tid / 4
+    const unsigned a_voff = (unsigned)qa_plane_row(tid >> 2, b0, nsamp, Tq) * 32u + img_dma_chunk(tid >> 2, tid & 3) * 8;
     // buffer loads: descriptor + uniform k-step offset in SGPRs, one 32-bit VGPR per lane address (with flat addresses the
     // compiler materialises a 64-bit address pair per unrolled k-step and spills)
-    const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Ahi), 0, (int)((size_t)g.a_rows * g.Kp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Wfr), 0, 3 * d * g.Kp * 2, 0x00020000);
+    const __bf16* const a_pl[2] = {g.Ahi, g.Alo};
+    const __bf16* const w_pl[2] = {Wfr, g.Wfr_lo};
+    __amdgpu_buffer_rsrc_t a_rs[NPL], w_rs[NPL];
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) {
+        a_rs[pl] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a_pl[pl]), 0, (int)((size_t)g.a_rows * g.Kp * 2), 0x00020000);
+        w_rs[pl] = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(w_pl[pl]), 0, 3 * d * g.Kp * 2, 0x00020000);
+    }
     const unsigned a_kbytes = (unsigned)g.a_rows * 64u;
     int a_off[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int rr = wm * 64 + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
-    }
-    char* abuf = smem + QR_ABUF;
-    float* bias_s = reinterpret_cast<float*>(abuf + 2 * STAGE);
-    for (int i = tid; i < hpb * QA_WROWS; i += NT) {
-        const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
-        bias_s[i] = g.bias[(r >> 7) * d + (hd0 + hh) * QA_DH + (r & 127)];
-    }
+    qa_frag_offsets(a_off, wm, l31, kh);
+    char* abuf = smem + QR_ABUF;                                     // [stage 2][plane NPL][64 rows][64 B]
+    float* bias_s = reinterpret_cast<float*>(abuf + 2 * NPL * STAGE);
+    qa_stage_bias(bias_s, g, hd0, hpb, tid, NT);
 
     for (int hd = hd0; hd < hd0 + hpb; ++hd) {
         unsigned wofs[3];                                            // fragment block of this wave's 32 columns of q / k / v (elements)
 #pragma unroll
         for (int t = 0; t < 3; ++t) wofs[t] = (unsigned)((t * d + hd * QA_DH) / 32 + wn) * 1024u + lane * 8;
         f32x16 acc[2][3];
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[ta][t][i] = 0.f;
+        qa_zero(acc);
         RGN_QT((hd - hd0) * 8 + 0)
-        // Weight fragments: a ring of QR_WQ = 18 fragments (3 k-steps' worth) recycled ONE AT A TIME: fragment q = 6 kt + 3 ks + t
-        // is consumed by two MFMAs and its registers immediately take fragment q + 18 - the same 72 VGPRs as three whole-step
+        // Weight fragments: a ring of WQ fragments per plane (plain: 18 = 3 k-steps' worth) recycled ONE AT A TIME: fragment q = 6 kt + 3 ks + t
+        // is consumed by its MFMAs and its registers immediately take fragment q + WQ - the same 72 VGPRs as three whole-step
         // slots, but every load is issued three k-steps (not two) ahead of its use and the loads are spread between the MFMAs.
-        op8 wq[QR_WQ];
-        u32x4 areg[QR_ARING];
-        auto issue_a = [&](int kt) { areg[kt % QR_ARING] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, a_voff * 2, kt * a_kbytes, 0)); };
+        op8 wq[NPL][R::WQ];
+        u32x4 areg[NPL][R::ARING];
+        auto issue_a = [&](int kt) {
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl)
+                areg[pl][kt % R::ARING] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs[pl], a_voff * 2, kt * a_kbytes, 0));
+        };
         auto issue_q = [&](int q) {                                  // q compile-time after unrolling
             const int kt = q / 6, ks = (q % 6) / 3, t = q % 3;
-            wq[q % QR_WQ] = __builtin_bit_cast(op8, __builtin_amdgcn_raw_buffer_load_b128(w_rs, wofs[t] * 2, (kt * nb_all * 1024 + ks * 512) * 2, 0));
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl)
+                wq[pl][q % R::WQ] = __builtin_bit_cast(op8, __builtin_amdgcn_raw_buffer_load_b128(w_rs[pl], wofs[t] * 2, (kt * nb_all * 1024 + ks * 512) * 2, 0));
+        };
+        auto stage_a = [&](int kt) {                                 // k-block kt of the activation tile: registers -> its stage
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<u32x4*>(abuf + ((kt & 1) * NPL + pl) * STAGE + tid * 16) = areg[pl][kt % R::ARING];
         };
 #pragma unroll
-        for (int kt = 0; kt < QR_DA; ++kt) issue_a(kt);
+        for (int kt = 0; kt < R::DA; ++kt) issue_a(kt);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q = 0; q < QR_WQ; ++q) issue_q(q);
+        for (int q = 0; q < R::WQ; ++q) issue_q(q);
         __builtin_amdgcn_sched_barrier(0);
-        *reinterpret_cast<u32x4*>(abuf + tid * 16) = areg[0];        // stage 0 <- k-block 0
+        stage_a(0);
 #pragma unroll
         for (int kt = 0; kt < QR_NK; ++kt) {
             wait_lgkmcnt<0>();
             __builtin_amdgcn_s_barrier();                            // k-block kt is in its stage; everyone left stage (kt + 1) % 2
-            const char* sb = abuf + (kt & 1) * STAGE;
-            op8 af[2][2];
+            const char* sb = abuf + (kt & 1) * NPL * STAGE;
+            op8 af[NPL][2][2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int ta = 0; ta < 2; ++ta) af[ks][ta] = *reinterpret_cast<const op8*>(sb + a_off[ta][ks]);
+                for (int ta = 0; ta < 2; ++ta)
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) af[pl][ks][ta] = *reinterpret_cast<const op8*>(sb + pl * STAGE + a_off[ta][ks]);
             __builtin_amdgcn_sched_barrier(0);
-            if (kt + QR_DA < QR_NK) issue_a(kt + QR_DA);
+            if (kt + R::DA < QR_NK) issue_a(kt + R::DA);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int grp = 0; grp < 6; ++grp) {
-                const int ks = grp / 3, t = grp % 3, q = kt * 6 + grp;
+                const int ks = grp / 3, t = grp % 3, q = kt * 6 + grp, s = q % R::WQ;
 #ifdef RGN_QA_LIFE
                 if (kt == 0 && grp == 1 && hd == hd0) { RGN_QL(1) }
 #endif
 #pragma unroll
                 for (int ta = 0; ta < 2; ++ta) {
-                    if (t < 2)     // q, k tiles transposed (lane = token, registers = dh)
-                        acc[ta][t] = OP::mfma(wq[q % QR_WQ], af[ks][ta], acc[ta][t]);
-                    else           // v tile: lane = dh, registers = tokens
-                        acc[ta][t] = OP::mfma(af[ks][ta], wq[q % QR_WQ], acc[ta][t]);
+                    if (t < 2) {   // q, k tiles transposed (lane = token, registers = dh)
+                        if constexpr (X3) {
+                            acc[ta][t] = OP::mfma(wq[0][s], af[1][ks][ta], acc[ta][t]);
+                            acc[ta][t] = OP::mfma(wq[1][s], af[0][ks][ta], acc[ta][t]);
+                        }
+                        acc[ta][t] = OP::mfma(wq[0][s], af[0][ks][ta], acc[ta][t]);
+                    } else {       // v tile: lane = dh, registers = tokens
+                        if constexpr (X3) {
+                            acc[ta][t] = OP::mfma(af[1][ks][ta], wq[0][s], acc[ta][t]);
+                            acc[ta][t] = OP::mfma(af[0][ks][ta], wq[1][s], acc[ta][t]);
+                        }
+                        acc[ta][t] = OP::mfma(af[0][ks][ta], wq[0][s], acc[ta][t]);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (q + QR_WQ < 6 * QR_NK) issue_q(q + QR_WQ);
-                if (grp == 2 && kt + 1 < QR_NK)                      // next k-block of the activation tile -> the other stage
-                    *reinterpret_cast<u32x4*>(abuf + ((kt + 1) & 1) * STAGE + tid * 16) = areg[(kt + 1) % QR_ARING];
+                if (q + R::WQ < 6 * QR_NK) issue_q(q + R::WQ);
+                if (grp == 2 && kt + 1 < QR_NK) stage_a(kt + 1);     // next k-block of the activation tile -> the other stage
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        if constexpr (X3) {
+            wait_lgkmcnt<0>();
+            __builtin_amdgcn_s_barrier();                            // (the exchange buffer does not alias the ring, but every wave must have left the k-loop's last stage reads)
+        }
         RGN_QT((hd - hd0) * 8 + 1)
-        qa_attention<false, F16, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
+        qa_attention<X3, F16, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
         RGN_QT((hd - hd0) * 8 + 6)
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
@@ -562,192 +598,52 @@ __global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs(QkvAttnArgs g, const _
     RGN_QL(2)
 }
 
-// ---- split-bf16 phase, d = 512: the register-streamed form of the SPLIT arithmetic (round 6) ---------------------------------------
-// k_qkv_attn<true> above moves 64 KiB of operands per k-step through the ~20 B/clk direct-to-LDS path against 2304 cycles of MFMA (3400 measured):
-// the same weight stream through the vector-memory path into register rings, hi and lo fragment planes side by side, leaves only the activation tile
-// (hi | lo, 16 KiB per k-step pair of stages) in LDS. One sample (4 waves) per workgroup, two workgroups per CU like k_qkv_attn_rs. Every accumulator
-// sees the MFMAs of k_qkv_attn<true> in the same order (k-block, k half; lo x hi, hi x lo, hi x hi): the two forms agree bit for bit
-// (tests/test_hip_parity.py), "QKV_X3_DMA" = 1 keeps the direct-to-LDS form. The kernel itself runs 53 us where the direct-to-LDS form ran 73 (rocprofv3, the
-// evaluation schedule at B = 256) - and the CALL gains 1 - 3 %: the split steps run three kernel chains side by side and are short of L2 bandwidth chip-wide
-// (k_mlp_x3 streams 5.2 MB of weight fragments per 32-row tile), so time a chain's in_proj gives back is taken by its neighbours' layer tails.
-// One sample per workgroup: 5.71 ms per ddim5 call at B = 256 against 5.79 with two (whose sample halves request the same weight fragments at the same
-// time) and 5.78 with the direct-to-LDS form, 3.04 / 3.06 / 3.14 at B = 64 (profiles/r06_qkv_x3_forms.txt).
-constexpr int QX_WQ = 9, QX_DA = 2, QX_ARING = QX_DA + 1;        // ring depths: 1.5 k-steps of (hi, lo) weight fragment pairs, activation pieces 2 ahead
-constexpr int QX_LDS = QR_ABUF + 2 * 2 * QR_NS * QA_ROWS * 64 + 8 * QA_WROWS * 4;
-template <bool CAUSAL = true>
-__global__ __launch_bounds__(QR_NT, 2) void k_qkv_attn_rs_x3(QkvAttnArgs g) {
-    constexpr int NS = QR_NS, NT = QR_NT, STAGE = NS * QA_ROWS * 64;   // one plane of one stage; a stage = hi | lo
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int l31 = lane & 31, kh = lane >> 5;
-    const int b0 = xcd_affine(blockIdx.x, gridDim.x) * NS, Tq = g.Tq, d = g.d;
-    const int hpb = g.H / (int)gridDim.y, hd0 = blockIdx.y * hpb;
-    const int nsamp = g.Bm - b0 < NS ? g.Bm - b0 : NS;
-    constexpr int nb_all = 3 * 512 / 32;
-    unsigned a_voff;
-    {
-        const int r = tid >> 2, c = img_dma_chunk(r, tid & 3);      // tile row r: sample r / 64, token r % 64
-        const int sm = (r >> 6) < nsamp ? (r >> 6) : 0, tk = r & 63;
-        const int rr = tk < Tq ? tk : Tq - 1;                        // padding rows replicate the last token (masked later)
-        a_voff = (unsigned)((b0 + sm) * Tq + rr) * 32u + c * 8;
-    }
-    const __amdgpu_buffer_rsrc_t ah_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Ahi), 0, (int)((size_t)g.a_rows * g.Kp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t al_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Alo), 0, (int)((size_t)g.a_rows * g.Kp * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wh_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Wfr), 0, 3 * d * g.Kp * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wl_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(g.Wfr_lo), 0, 3 * d * g.Kp * 2, 0x00020000);
-    const unsigned a_kbytes = (unsigned)g.a_rows * 64u;
-    int a_off[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int rr = wm * 64 + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
-    }
-    char* abuf = smem + QR_ABUF;                                     // [stage 2][plane 2][64 rows][64 B]
-    float* bias_s = reinterpret_cast<float*>(abuf + 4 * STAGE);
-    for (int i = tid; i < hpb * QA_WROWS; i += NT) {
-        const int hh = i / QA_WROWS, r = i - hh * QA_WROWS;
-        bias_s[i] = g.bias[(r >> 7) * d + (hd0 + hh) * QA_DH + (r & 127)];
-    }
-    for (int hd = hd0; hd < hd0 + hpb; ++hd) {
-        unsigned wofs[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) wofs[t] = (unsigned)((t * d + hd * QA_DH) / 32 + wn) * 1024u + lane * 8;
-        f32x16 acc[2][3];
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[ta][t][i] = 0.f;
-        bf16x8 wqh[QX_WQ], wql[QX_WQ];
-        u32x4 arh[QX_ARING], arl[QX_ARING];
-        auto issue_a = [&](int kt) {
-            arh[kt % QX_ARING] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ah_rs, a_voff * 2, kt * a_kbytes, 0));
-            arl[kt % QX_ARING] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(al_rs, a_voff * 2, kt * a_kbytes, 0));
-        };
-        auto issue_q = [&](int q) {                                  // q compile-time after unrolling
-            const int kt = q / 6, ks = (q % 6) / 3, t = q % 3;
-            wqh[q % QX_WQ] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wh_rs, wofs[t] * 2, (kt * nb_all * 1024 + ks * 512) * 2, 0));
-            wql[q % QX_WQ] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wl_rs, wofs[t] * 2, (kt * nb_all * 1024 + ks * 512) * 2, 0));
-        };
-#pragma unroll
-        for (int kt = 0; kt < QX_DA; ++kt) issue_a(kt);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < QX_WQ; ++q) issue_q(q);
-        __builtin_amdgcn_sched_barrier(0);
-        *reinterpret_cast<u32x4*>(abuf + tid * 16) = arh[0];         // stage 0 <- k-block 0
-        *reinterpret_cast<u32x4*>(abuf + STAGE + tid * 16) = arl[0];
-#pragma unroll
-        for (int kt = 0; kt < QR_NK; ++kt) {
-            wait_lgkmcnt<0>();
-            __builtin_amdgcn_s_barrier();                            // k-block kt is in its stage; everyone left stage (kt + 1) % 2
-            const char* sb = abuf + (kt & 1) * 2 * STAGE;
-            bf16x8 ah[2][2], al[2][2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int ta = 0; ta < 2; ++ta) {
-                    ah[ks][ta] = *reinterpret_cast<const bf16x8*>(sb + a_off[ta][ks]);
-                    al[ks][ta] = *reinterpret_cast<const bf16x8*>(sb + STAGE + a_off[ta][ks]);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            if (kt + QX_DA < QR_NK) issue_a(kt + QX_DA);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int grp = 0; grp < 6; ++grp) {
-                const int ks = grp / 3, t = grp % 3, q = kt * 6 + grp;
-#pragma unroll
-                for (int ta = 0; ta < 2; ++ta) {
-                    if (t < 2) {   // q, k tiles transposed (lane = token, registers = dh)
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wqh[q % QX_WQ], al[ks][ta], acc[ta][t], 0, 0, 0);
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wql[q % QX_WQ], ah[ks][ta], acc[ta][t], 0, 0, 0);
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wqh[q % QX_WQ], ah[ks][ta], acc[ta][t], 0, 0, 0);
-                    } else {       // v tile: lane = dh, registers = tokens
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks][ta], wqh[q % QX_WQ], acc[ta][t], 0, 0, 0);
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][ta], wql[q % QX_WQ], acc[ta][t], 0, 0, 0);
-                        acc[ta][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][ta], wqh[q % QX_WQ], acc[ta][t], 0, 0, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (q + QX_WQ < 6 * QR_NK) issue_q(q + QX_WQ);
-                if (grp == 2 && kt + 1 < QR_NK) {                    // next k-block of the activation tile -> the other stage
-                    *reinterpret_cast<u32x4*>(abuf + ((kt + 1) & 1) * 2 * STAGE + tid * 16) = arh[(kt + 1) % QX_ARING];
-                    *reinterpret_cast<u32x4*>(abuf + ((kt + 1) & 1) * 2 * STAGE + STAGE + tid * 16) = arl[(kt + 1) % QX_ARING];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();                                // (the exchange buffer does not alias the ring, but every wave must have left the k-loop's last stage reads)
-        qa_attention<true, false, CAUSAL>(acc, g, smem, bias_s + (hd - hd0) * QA_WROWS + wn * 32, hd, hd - hd0, wm, wn, nsamp, b0, lane, tid);
-        wait_lgkmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-    }
-}
-
 bool qkv_attn_supported(int Tq, int dh, int d) { return Tq <= QA_ROWS && dh == QA_DH && d % 32 == 0 && d / dh <= 8 && d >= 128; }
 static int qa_lds(bool x3) { return 2 * (x3 ? 2 : 1) * (QA_NS * QA_ROWS * 64 + QA_WROWS * 64) + 8 * QA_WROWS * 4 /* biases of <= 8 heads (odd H: one workgroup runs them all) */; }
 hipError_t configure_qkv_attn() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<true>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
-    if (e != hipSuccess) return e;
-    // (the plain-bf16 build is given the same allocation: its operand buffers, one plane each, alias its 64 KiB of stages)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
-    if (e != hipSuccess) return e;
-    // the full-attention forms (encoder layers): the same allocations - the fourth S^T tile passes through the causal exchange buffer
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, qa_lds(true));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs_x3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_qkv_attn_rs<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, QR_LDS);
+    // every instantiation (the full-attention forms take the causal allocations: the fourth S^T tile passes through the causal exchange buffer;
+    // the plain-bf16 DMA-fed build is given the split one's: its operand buffers, one plane each, alias its 64 KiB of stages)
+    const struct { const void* kernel; int lds; } forms[] = {
+        {reinterpret_cast<const void*>(k_qkv_attn<true, true>), qa_lds(true)},          {reinterpret_cast<const void*>(k_qkv_attn<true, false>), qa_lds(true)},
+        {reinterpret_cast<const void*>(k_qkv_attn<false, true>), qa_lds(true)},         {reinterpret_cast<const void*>(k_qkv_attn<false, false>), qa_lds(true)},
+        {reinterpret_cast<const void*>(k_qkv_attn_rs<false, false, true>), QR_LDS},     {reinterpret_cast<const void*>(k_qkv_attn_rs<false, false, false>), QR_LDS},
+        {reinterpret_cast<const void*>(k_qkv_attn_rs<false, true, true>), QR_LDS},
+        {reinterpret_cast<const void*>(k_qkv_attn_rs<true, false, true>), QX_LDS},      {reinterpret_cast<const void*>(k_qkv_attn_rs<true, false, false>), QX_LDS}};
+    for (const auto& f : forms)
+        if (hipError_t e = hipFuncSetAttribute(f.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, f.lds); e != hipSuccess) return e;
+    return hipSuccess;
 }
-hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s, bool causal) {
-    if (!x3 && g.Wfr && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // plain-bf16 phase: weights streamed to registers (32-bit buffer offsets)
+// THE form rule: launch_qkv_attn dispatches on it and rgn_plan_query reports it.
+QkvAttnForm qkv_attn_form(const QkvAttnArgs& g, bool x3) {
+    // register-streamed: d = 512 instantiations (compile-time weight offsets, 16 k-steps) that read fragment-ordered weight planes - the split one both of
+    // them and the lo activation plane - through 32-bit buffer offsets; every other width, and a mode that packs no fragment planes, runs the DMA-fed form
+    const bool rs = g.Wfr && (!x3 || (g.Wfr_lo && g.Alo)) && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31);
+    if (rs) {
         // Heads per workgroup: two (half the in_proj weight requests per sample) once the evaluation alone fills the chip with 4-wave
         // workgroups - >= 256 samples over all chains: 512 workgroups, two per CU - and ONE head per workgroup below that (B = 64 / 128 /
         // 192 at 60 frames: 116.9 / 131.0 / 154.1 vs 135.6 / 139.7 / 158.0 ms per 250-step call; B = 256: 360 vs 369 motions/s the other way)
         const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
-        const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;
-        if (g.f16 && !causal) return hipErrorInvalidValue;          // (encoder handles have no fp16 phase)
-        if (g.f16)     // fp16 operands (the schedule's fp16 sub-phase)
-            hipLaunchKernelGGL((k_qkv_attn_rs<true>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
-        else if (!causal)
-            hipLaunchKernelGGL((k_qkv_attn_rs<false, false>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
-        else
-            hipLaunchKernelGGL((k_qkv_attn_rs<false>), dim3(g.Bm, hsplit), dim3(QR_NT), QR_LDS, s, g, g.Wfr);
-        return hipGetLastError();
+        return {x3 ? QF_RS_X3 : QF_RS, (beval < 256 || g.H % 2) ? g.H : 2};
     }
-    // heads per workgroup: half of them (the weight stream per sample is what bounds the kernel), but one head each while
+    // DMA-fed: half of the heads (the weight stream per sample is what bounds the kernel), but one head each while
     // the launch is small (<= 64 workgroups): a small batch is latency-bound and the heads of a workgroup run back to back
-    if (g.f16) return hipErrorInvalidValue;                         // (only the register-streamed plain form has the fp16 instantiation)
-    if (x3 && g.Wfr && g.Wfr_lo && g.Alo && g.Kp == 32 * QR_NK && g.d == 512 && (size_t)g.a_rows * g.Kp * 2 < (1ull << 31)) {   // split phase, weights streamed to registers
-        const int beval = g.Bm_eval > 0 ? g.Bm_eval : g.Bm;
-        const int hsplit = (beval < 256 || g.H % 2) ? g.H : 2;      // (the plain form's rule)
-        if (causal) hipLaunchKernelGGL(k_qkv_attn_rs_x3<true>, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
-        else hipLaunchKernelGGL(k_qkv_attn_rs_x3<false>, dim3(g.Bm, hsplit), dim3(QR_NT), QX_LDS, s, g);
-        return hipGetLastError();
-    }
     const int pairs = (g.Bm + QA_NS - 1) / QA_NS;
-    const int hsplit = (pairs * g.H <= 64) ? g.H : (g.H % 2 == 0 ? 2 : 1);
-    const dim3 grid(pairs, hsplit);
-    if (!causal) {
-        if (x3) hipLaunchKernelGGL((k_qkv_attn<true, false>), grid, dim3(QA_NT), qa_lds(true), s, g);
-        else hipLaunchKernelGGL((k_qkv_attn<false, false>), grid, dim3(QA_NT), qa_lds(true), s, g);
-    } else if (x3)
-        hipLaunchKernelGGL((k_qkv_attn<true>), grid, dim3(QA_NT), qa_lds(true), s, g);
+    return {QF_DMA, (pairs * g.H <= 64) ? g.H : (g.H % 2 == 0 ? 2 : 1)};
+}
+hipError_t launch_qkv_attn(const QkvAttnArgs& g, bool x3, hipStream_t s, bool causal) {
+    const QkvAttnForm f = qkv_attn_form(g, x3);
+    // fp16 operands (the schedule's fp16 sub-phase): only the register-streamed plain form has the instantiation, and encoder handles have no fp16 phase
+    if (g.f16 && (f.form != QF_RS || !causal)) return hipErrorInvalidValue;
+    if (f.form == QF_DMA)
+        dispatch_bools([&](auto X, auto C) {
+            hipLaunchKernelGGL((k_qkv_attn<decltype(X)::value, decltype(C)::value>), dim3((g.Bm + QA_NS - 1) / QA_NS, f.hsplit), dim3(QA_NT), qa_lds(true), s, g);
+        }, x3, causal);
     else
-        hipLaunchKernelGGL((k_qkv_attn<false>), grid, dim3(QA_NT), qa_lds(true), s, g);
+        dispatch_bools([&](auto X, auto F, auto C) {
+            constexpr bool X3 = decltype(X)::value, F16 = decltype(F)::value, CAUSAL = decltype(C)::value;
+            if constexpr (!F16 || (!X3 && CAUSAL))
+                hipLaunchKernelGGL((k_qkv_attn_rs<X3, F16, CAUSAL>), dim3(g.Bm, f.hsplit), dim3(QR_NT), QrRing<X3>::LDS, s, g, g.Wfr);
+        }, f.form == QF_RS_X3, g.f16 != 0, causal);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // Stand-alone micro-benchmark of the fused in_proj + attention kernel (tools only; not part of the library).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DRGN_QA_PROF=100] -I regennet_amd/csrc tools/qkv_attn_bench.hip \
 //         regennet_amd/csrc/rgn_qkv_attn.hip regennet_amd/csrc/rgn_qkv_attn_long.hip -o tools/bin/qkv_attn_bench
-// Times k_qkv_attn at Bm samples x Tq tokens (default 256 x 60, d = 512, H = 4); with -DRGN_QA_PROF=<block> it also
+// Times k_qkv_attn at Bm samples x Tq tokens (default 256 x 60, d = 512, H = 4): the split arithmetic, BF16=1 the plain one; RS=1 the
+// register-streamed form of either (k_qkv_attn_rs), otherwise the DMA-fed one. With -DRGN_QA_PROF=<block> it also
 // prints the cycle stamps of that workgroup's phases (GEMM loop / operand split + partial scores / reduction + softmax + PV).
 #include "rgn_internal.h"
 
@@ -39,7 +40,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&Ohi, (size_t)M * d * 2)); CK(hipMalloc(&Olo, (size_t)M * d * 2)); CK(hipMalloc(&bias, 3 * d * 4)); CK(hipMemset(bias, 0, 3 * d * 4));
     QkvAttnArgs g{};
     g.Ahi = Ahi; g.Alo = Alo; g.a_rows = M; g.Whi = Whi; g.Wlo = Wlo; g.bias = bias;
-    if (getenv("RS")) g.Wfr = Whi;   // RS=1 (with BF16=1): the register-streamed weight loop (any bytes do for timing)
+    if (getenv("RS")) { g.Wfr = Whi; if (x3) g.Wfr_lo = Wlo; }   // RS=1: the register-streamed weight loop, plain (with BF16=1) or split (any bytes do for timing)
     g.out.hi = Ohi; g.out.lo = x3 ? Olo : nullptr; g.out.rows = M; g.Bm = Bm; g.Kp = Kp; g.d = d; g.H = H; g.Tq = Tq; g.qscale = 0.0884f;
     CK(configure_qkv_attn());
     const bool longk = getenv("LONG") != nullptr;   // LONG=1 BF16=1: k_qkv_attn_long (give Tq = 150)
@@ -77,7 +78,7 @@ int main(int argc, char** argv) {
 #endif
 #ifdef RGN_QA_LIFE
     {   // -DRGN_QA_LIFE (RS=1 BF16=1): start / first MFMA operands landed / end of every workgroup of the last launch, 10 ns units
-        const int nwg = Bm * (Bm < 256 ? H : 2);   // grid = samples x head groups (launch_qkv_attn's rule)
+        const int nwg = Bm * qkv_attn_form(g, x3).hsplit;   // grid = samples x head groups
         std::vector<long long> t(nwg * 3); qa_life_read(t.data(), nwg * 3);
         long long t0 = t[0], t1 = t[2];
         for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, t[3 * i]); t1 = std::max(t1, t[3 * i + 2]); }
