@@ -24,10 +24,12 @@
 // barrier per step and the DMA issued between MFMA groups (ILV = true, tools only) halves the bytes per MFMA and its
 // loop runs at ~80 % MFMA occupancy, but at M = 15360 it leaves only 120-240 tiles for 256 CUs and nothing to hide its
 // 256 KiB-per-tile epilogue behind: end to end it only ties (70 vs 72 us on linear1), so it is not shipped.
+//
+// The product of a fragment pair, the MFMA groups of the interleaved k-step, the fragment offsets and the paired-column plane store are the family's
+// (rgn_dma_gemm.h: this kernel is the ancestor of the recogniser's three in rgn_sg_kernels.hip); here stand the stage DMA, the two loops and x3_epilogue.
 #include <algorithm>
 #include <cstdlib>
-#include "rgn_internal.h"
-#include "rgn_device.h"
+#include "rgn_dma_gemm.h"
 
 #include <hip/hip_runtime.h>
 
@@ -61,12 +63,12 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             const int mb = mw + ta * 32 + 4 * kh;      // row of register 0
             float r[16];
             if (EPI == 2 && g.add && g.add_mod > 0) {      // addend row = row % add_mod (a per-vertex bias: rows run (frame, vertex); add_mod >= 28)
+                // (= dg_vertex_addend, spelled out: behind the function the 256 x 128 form takes 13 more VGPRs)
                 const int base = (int)((unsigned)mb % (unsigned)g.add_mod);
                 const float* ap = g.add + n;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int ro = mfma32_row(i, 0);
-                    int rr = base + ro;
+                    int rr = base + mfma32_row(i, 0);
                     rr = rr >= g.add_mod ? rr - g.add_mod : rr;
                     r[i] = n_ok ? ap[rr * g.ldadd] : 0.f;
                 }
@@ -93,22 +95,12 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                     const bool odd = lane & 1;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const float mine = (odd ? r[i + 8] : r[i]) * sc;
-                        const float give = (odd ? r[i] : r[i + 8]) * sc;
-                        const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1: quad_perm [1, 0, 3, 2]
-                        const float c0 = odd ? got : mine, c1 = odd ? mine : got;
-                        const int ii = odd ? i + 8 : i;
-                        const unsigned m = (unsigned)(mb + mfma32_row(ii, 0));
+                        float c0, c1;
+                        dg_pair_exchange((odd ? r[i + 8] : r[i]) * sc, (odd ? r[i] : r[i + 8]) * sc, odd, c0, c1);
+                        const unsigned m = (unsigned)(mb + dg_pair_row(i, odd));
                         // m / Tq, m % Tq (exact: m*Tq < 2^32); Tq = 1 has no 32-bit magic (floor(2^32 / 1) + 1 wraps to 1): the quotient is m itself
                         const unsigned bb = g.Tq == 1 ? m : __umulhi(m, g.tq_magic), tt = m - bb * (unsigned)g.Tq;
-                        const size_t o = (((size_t)bb * g.H + hd) * g.Tqp + tt) * g.dh + (c & ~1);
-                        const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
-                        bf16x2 hv = {h0, h1};
-                        *reinterpret_cast<bf16x2*>(ph + o) = hv;
-                        if (pl) {
-                            bf16x2 lv = {(__bf16)(c0 - (float)h0), (__bf16)(c1 - (float)h1)};
-                            *reinterpret_cast<bf16x2*>(pl + o) = lv;
-                        }
+                        dg_store_pair<false, true>(ph, pl, (((size_t)bb * g.H + hd) * g.Tqp + tt) * g.dh + (c & ~1), c0, c1);
                     }
                 } else {                                              // edge blocks
                     const float sc = which == 0 ? g.qscale : 1.0f;
@@ -136,25 +128,13 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             }
             if (!QKV && g.Chi) {   // K32-blocked planes [N/32][c_rows][32]: a 32-column tile is one contiguous run of rows
                 if (!CHECK) {
-                    // pair adjacent columns across lanes (lane^1) so every store is a packed bf16x2 (4 B):
-                    // even lanes store rows of registers 0..7, odd lanes those of registers 8..15
                     const size_t o = plane_off(g.c_rows, mb, n & ~1);
                     const bool odd = lane & 1;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const float mine = odd ? r[i + 8] : r[i];          // value this lane contributes to its own store
-                        const float give = odd ? r[i] : r[i + 8];          // value the partner needs
-                        const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1: quad_perm [1, 0, 3, 2]
-                        const float lo_col = odd ? got : mine, hi_col = odd ? mine : got;   // columns n&~1, (n&~1)+1
-                        const int ii = odd ? i + 8 : i;
-                        const int ro = mfma32_row(ii, 0);
-                        const __bf16 h0 = (__bf16)lo_col, h1 = (__bf16)hi_col;
-                        bf16x2 hv = {h0, h1};
-                        *reinterpret_cast<bf16x2*>(g.Chi + o + ro * 32) = hv;
-                        if (g.Clo) {
-                            bf16x2 lv = {(__bf16)(lo_col - (float)h0), (__bf16)(hi_col - (float)h1)};
-                            *reinterpret_cast<bf16x2*>(g.Clo + o + ro * 32) = lv;
-                        }
+                        float c0, c1;
+                        dg_pair_columns(r, i, odd, c0, c1);
+                        dg_store_pair<false, true>(g.Chi, g.Clo, o + dg_pair_row(i, odd) * 32, c0, c1);
                     }
                 } else {
                     const size_t o = plane_off(g.c_rows, mb, n);
@@ -196,10 +176,8 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int nwg = nbx * nby, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int vid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int m0 = (vid / nbx) * BM, n0 = (vid % nbx) * BN;
+    const DgTile t = dg_tile<BM, BN>(xcd_affine(blockIdx.x, nbx * nby), nbx);
+    const int m0 = t.m0, n0 = t.n0;
 
     // per-thread DMA source byte offsets inside one k-block of a plane (k-invariant, 32-bit: a plane k-block is
     // rows x 64 B); the k-dependent part is a wave-uniform base pointer, so the DMA uses the SGPR-base + VGPR-offset form
@@ -246,39 +224,15 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
-    // fragment read offsets: row rr (within the block tile), chunk c = 2*ks + khalf at position c ^ ((rr>>2)&3)
+    dg_zero(acc);
+    // fragment read offsets of this wave's rows within the block tile
     const int l31 = lane & 31, kh = lane >> 5;
     int a_off[TM][2], w_off[TN][2];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int rr = wm * (BM / WM) + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_off[t][ks] = img_frag(rr, ks, kh);
-    }
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int rr = wn * (BN / WN) + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
-    }
-    // the three products of one C tile (a.w ~ al.wh + ah.wl + ah.wh, small terms first)
-    auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {
-        if (X3) {
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, w_h, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_l, c, 0, 0, 0);
-        }
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_h, c, 0, 0, 0);
-    };
+    dg_frag_off(a_off, wm * (BM / WM), l31, kh);
+    dg_frag_off(w_off, wn * (BN / WN), l31, kh);
 
 #ifdef RGN_GEMM_PROF
-    const bool prof = (bid == RGN_GEMM_PROF) && (tid == 0 || tid == NT - 64);
+    const bool prof = ((int)blockIdx.x == RGN_GEMM_PROF) && (tid == 0 || tid == NT - 64);
     long long* pp = g_prof + (tid ? 512 : 0);
 #define RGN_T(i) if (prof) pp[kt * 6 + i] = clock64();
 #else
@@ -286,37 +240,24 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
 #endif
     const int nk = g.Kp / 32;
     if constexpr (ILV) {
-        constexpr int NG = 2 * TN;                               // MFMA groups per k-step: (K half, N tile), TM tiles each
-        constexpr int PPG = (LPT + TN - 1) / TN;                 // DMA pieces after each group of the first K half
+        constexpr int PPG = (LPT + TN - 1) / TN;                 // DMA pieces after each MFMA group of the first K half
         auto step = [&](int kt, bool more) {
             const char* sb = smem + (kt & 1) * STAGE;
             char* nb = smem + ((kt + 1) & 1) * STAGE;
-            bf16x8 ah[2][TM], al[2][TM], wh[2], wl[2];
-            auto fetch = [&](int grp) {                          // fragments of group grp = ks*TN + tb
-                const int ks = grp / TN, tb = grp % TN;
-                if (tb == 0) {
+            auto a_frag = [&](int ks, bf16x8 (&ah)[2][TM], bf16x8 (&al)[2][TM]) {
 #pragma unroll
-                    for (int t = 0; t < TM; ++t) {
-                        ah[ks][t] = *reinterpret_cast<const bf16x8*>(sb + a_off[t][ks]);
-                        if (X3) al[ks][t] = *reinterpret_cast<const bf16x8*>(sb + A_BYTES + a_off[t][ks]);
-                    }
+                for (int i = 0; i < TM; ++i) {
+                    ah[ks][i] = *reinterpret_cast<const bf16x8*>(sb + a_off[i][ks]);
+                    if (X3) al[ks][i] = *reinterpret_cast<const bf16x8*>(sb + A_BYTES + a_off[i][ks]);
                 }
-                wh[grp & 1] = *reinterpret_cast<const bf16x8*>(sb + NPL * A_BYTES + w_off[tb][ks]);
-                if (X3) wl[grp & 1] = *reinterpret_cast<const bf16x8*>(sb + NPL * A_BYTES + W_BYTES + w_off[tb][ks]);
             };
-            fetch(0);
-#pragma unroll
-            for (int grp = 0; grp < NG; ++grp) {
-                if (grp + 1 < NG) fetch(grp + 1);
-#pragma unroll
-                for (int ta = 0; ta < TM; ++ta) mma3(acc[ta][grp % TN], ah[grp / TN][ta], al[grp / TN][ta], wh[grp & 1], wl[grp & 1]);
+            dg_kstep<TM, TN, false, X3>(acc, sb + NPL * A_BYTES, W_BYTES, w_off, a_frag, [&](int grp) {
                 if (grp < TN && more) {
 #pragma unroll
                     for (int q = 0; q < PPG; ++q)
                         if (grp * PPG + q < LPT) piece(grp * PPG + q, kt + 1, nb);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            });
         };
         issue(0, 0);
         for (int kt = 0; kt < nk; ++kt) {
@@ -352,7 +293,7 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
 #pragma unroll
                 for (int ta = 0; ta < TM; ++ta)
 #pragma unroll
-                    for (int tb = 0; tb < TN; ++tb) mma3(acc[ta][tb], ah[ks][ta], al[ks][ta], wh[ks][tb], wl[ks][tb]);
+                    for (int tb = 0; tb < TN; ++tb) dg_mma<false, X3>(acc[ta][tb], ah[ks][ta], al[ks][ta], wh[ks][tb], wl[ks][tb]);
             }
         };
         issue(0, 0);
@@ -378,67 +319,63 @@ __global__ __launch_bounds__(64 * WM * WN, (2 * 2 * (BM + BN) * 64 <= 80 * 1024)
     }
 #undef RGN_T
 
-    const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
+    const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);   // (= dg_close, spelled out: through its visitor the 128 x 128 forms take 4 more SGPRs, the 256 x 256 plain form 3 fewer VGPRs)
     if (interior) x3_epilogue<TM, TN, EPI, false>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
     else x3_epilogue<TM, TN, EPI, true>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
 }
 
+// k_gemm_x3's forms for one tile shape, named once: fn(kernel, planes per operand) for (arithmetic, attention-ready scatter). The scatter exists for the
+// default tile only
+template <int BM, int BN, int WM, int WN, bool ILV>
+constexpr bool x3_form_exists(bool qkv) { return !qkv || (BM == 128 && !ILV); }
+template <int BM, int BN, int WM, int WN, bool ILV, class Fn>
+static hipError_t x3_form(bool x3, bool qkv, Fn fn) {
+    return dispatch_bools([&](auto X, auto Q) {
+        if constexpr (x3_form_exists<BM, BN, WM, WN, ILV>(decltype(Q)::value))
+            return fn(k_gemm_x3<BM, BN, WM, WN, decltype(X)::value, ILV, decltype(Q)::value ? 1 : 0>, decltype(X)::value ? 2 : 1);
+        else
+            return hipErrorInvalidValue;
+    }, x3, qkv);
+}
 template <int BM, int BN, int WM, int WN, bool ILV>
 static hipError_t x3_launch(const GemmX3Args& g, bool x3, hipStream_t s, bool configure_only) {
-    const int lds = 2 * (x3 ? 2 : 1) * (BM * 64 + BN * 64);
     if (configure_only) {
-        const int big = 2 * 2 * (BM * 64 + BN * 64), small = 2 * (BM * 64 + BN * 64);
-        hipError_t e;
-#define RGN_CFG(X3V, QV, BYTES)                                                                                        \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_x3<BM, BN, WM, WN, X3V, ILV, QV>),                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);                                        \
-        if (e != hipSuccess) return e;
-        RGN_CFG(true, 0, big) RGN_CFG(false, 0, small)
-        if constexpr (BM == 128 && !ILV) { RGN_CFG(true, 1, big) RGN_CFG(false, 1, small) }
-#undef RGN_CFG
-        return hipSuccess;
+        hipError_t e = hipSuccess;
+        for (int m = 0; m < 4 && e == hipSuccess; ++m)
+            if (x3_form_exists<BM, BN, WM, WN, ILV>(m & 2))
+                e = x3_form<BM, BN, WM, WN, ILV>(m & 1, m & 2, [](auto kern, int npl) {
+                    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * npl * (BM * 64 + BN * 64));
+                });
+        return e;
     }
-    const int nbx = (g.N + BN - 1) / BN, nby = (g.M + BM - 1) / BM;
-    const dim3 grid(nbx * nby), block(64 * WM * WN);
-    const bool qkv = g.Qhi != nullptr;
-    if constexpr (BM == 128 && !ILV) {   // the attention-ready scatter exists for the default tile only
-        if (qkv) {
-            if (x3) hipLaunchKernelGGL((k_gemm_x3<BM, BN, WM, WN, true, ILV, 1>), grid, block, lds, s, g, nbx, nby);
-            else hipLaunchKernelGGL((k_gemm_x3<BM, BN, WM, WN, false, ILV, 1>), grid, block, lds, s, g, nbx, nby);
-            return hipGetLastError();
-        }
-    } else if (qkv) {
-        return hipErrorInvalidValue;
-    }
-    if (x3) hipLaunchKernelGGL((k_gemm_x3<BM, BN, WM, WN, true, ILV, 0>), grid, block, lds, s, g, nbx, nby);
-    else hipLaunchKernelGGL((k_gemm_x3<BM, BN, WM, WN, false, ILV, 0>), grid, block, lds, s, g, nbx, nby);
-    return hipGetLastError();
+    return x3_form<BM, BN, WM, WN, ILV>(x3, g.Qhi != nullptr, [&](auto kern, int npl) {
+        const int nbx = (g.N + BN - 1) / BN, nby = (g.M + BM - 1) / BM;
+        hipLaunchKernelGGL(kern, dim3(nbx * nby), dim3(64 * WM * WN), 2 * npl * (BM * 64 + BN * 64), s, g, nbx, nby);
+        return hipGetLastError();
+    });
 }
 
 // ---- the ST-GCN evaluator's GEMMs (rgn_stgcn.hip): millions of rows x 64 / 128 / 256 channels, split-bf16 throughout. 256-row tiles with
-//      the interleaved one-barrier loop; the tile is as wide as the layer (a 64-channel layer on a 128-wide tile would idle half its MFMAs)
-template <int BN, int WN>
-static hipError_t sg_launch(const GemmX3Args& g, hipStream_t s, bool configure_only) {
-    constexpr int BM = 256, WM = 4;
-    const int lds = 2 * 2 * (BM * 64 + BN * 64);
-    if (configure_only)
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_x3<BM, BN, WM, WN, true, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const int nbx = (g.N + BN - 1) / BN, nby = (g.M + BM - 1) / BM;
-    hipLaunchKernelGGL((k_gemm_x3<BM, BN, WM, WN, true, true, 2>), dim3(nbx * nby), dim3(64 * WM * WN), lds, s, g, nbx, nby);
-    return hipGetLastError();
+//      the interleaved one-barrier loop; the tile is as wide as the layer (a 64-channel layer on a 128-wide tile would idle half its MFMAs).
+//      256 channels: two 128-wide column blocks. The 256-wide tile (123 spilled SGPRs + 576 B of scratch in this form) was measured anyway: 23.2 / 53.2 ms
+//      per forward at 60 / 150 frames against 23.0 / 53.2 - the wide blocks are not bound by operand bytes per MFMA (profiles/r05/sg_tile256.txt)
+template <class Fn>
+static hipError_t x3_sg_form(bool narrow, Fn fn) {           // the two forms, named once: fn(kernel, BN, threads)
+    return narrow ? fn(k_gemm_x3<256, 64, 4, 1, true, true, 2>, 64, 256) : fn(k_gemm_x3<256, 128, 4, 2, true, true, 2>, 128, 512);
 }
 hipError_t launch_gemm_x3_sg(const GemmX3Args& g, hipStream_t s) {
-    if (g.N <= 64) return sg_launch<64, 1>(g, s, false);
-    // 256 channels: two 128-wide column blocks. The 256-wide tile (123 spilled SGPRs + 576 B of scratch in this form) was measured anyway: 23.2 / 53.2 ms
-    // per forward at 60 / 150 frames against 23.0 / 53.2 - the wide blocks are not bound by operand bytes per MFMA (profiles/r05/sg_tile256.txt)
-    return sg_launch<128, 2>(g, s, false);
+    return x3_sg_form(g.N <= 64, [&](auto kern, int BN, int threads) {
+        const int nbx = (g.N + BN - 1) / BN, nby = (g.M + 255) / 256;
+        hipLaunchKernelGGL(kern, dim3(nbx * nby), dim3(threads), 2 * 2 * (256 * 64 + BN * 64), s, g, nbx, nby);
+        return hipGetLastError();
+    });
 }
 hipError_t configure_gemm_x3_sg() {
-    GemmX3Args g{};
-    hipError_t e = sg_launch<64, 1>(g, nullptr, true);
-    return e != hipSuccess ? e : sg_launch<128, 2>(g, nullptr, true);
+    hipError_t e = hipSuccess;
+    for (int narrow = 0; narrow < 2 && e == hipSuccess; ++narrow)
+        e = x3_sg_form(narrow, [](auto kern, int BN, int) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * (256 * 64 + BN * 64)); });
+    return e;
 }
-
 
 // variant 0 = 128x128 / 4 waves (two workgroups per CU): the default. variant 1 = 256x256 / 8 waves / interleaved DMA (one
 // workgroup per CU): its loop is ~1.45x faster per output but it needs several tiles per CU to hide its 256 KiB-per-tile

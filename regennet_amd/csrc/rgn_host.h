@@ -50,14 +50,6 @@ struct ProfEv {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// round-to-nearest-even fp32 -> bf16 bits
-inline uint16_t f2bf(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 // round-to-nearest-even fp32 -> IEEE fp16 bits (subnormals kept, overflow -> inf: the caller has checked the range)
 inline uint16_t f2h(float f) {
     uint32_t u;
@@ -75,12 +67,6 @@ inline uint16_t f2h(float f) {
     if (rem > halfway || (rem == halfway && (q & 1u))) ++q;
     const uint32_t bits = e < -14 ? q : (uint32_t)((e + 15 - 1) << 10) + q;   // (q carries the implicit one: + (e + 14) << 10)
     return (uint16_t)(sign | bits);
-}
-inline float bf2f(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
 }
 
 }  // namespace rgnh

@@ -1,5 +1,5 @@
 // The four data layouts the MFMA kernels of this directory stand on, defined ONCE: the index arithmetic of the packer (rgn_pack.cpp, host), of
-// the kernels (device) and of the stand-alone check tests/layout_check.cpp (host, no GPU) is this text. Nothing of HIP is included; every function
+// the kernels (device) and of the stand-alone check tests/layout_check.cpp (host, no GPU) is this text. Nothing of HIP is included; every layout function
 // is constexpr, so the static_asserts at the foot travel with every build. (A few sites spell an expression out, with a comment naming the function
 // it equals, where the register allocation moved with the text: profiles/layout_refactor_resources.txt lists them.)
 //
@@ -20,8 +20,12 @@
 //    A GRANULE is half a k-block (ks) of one 32-column block: 1 KiB; the register-streamed kernels address granule hs = 2 kt + ks.
 //
 // 4. The 32 x 32 MFMA C/D map: register i of lane l holds row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31 of the tile.
+//
+// ... and the element the host packers (rgn_pack.cpp, rgn_stgcn.hip) put into the bf16 planes: f2bf / bf2f.
 #pragma once
 #include <cstddef>
+#include <cstdint>
+#include <cstring>
 
 #if defined(__HIP__) || defined(__CUDACC__)
 #define RGN_HD __attribute__((host)) __attribute__((device))
@@ -63,6 +67,21 @@ RGN_HD constexpr inline int frag_granule(int hs, int kstride) { return (hs >> 1)
 // ---- 4. 32 x 32 MFMA accumulator: register i of a lane in half kh = lane >> 5
 RGN_HD constexpr inline int mfma32_row(int i, int kh) { return (i & 3) + 8 * (i >> 2) + 4 * kh; }
 RGN_HD constexpr inline int mfma32_col(int lane) { return lane & 31; }
+
+// ---- host: fp32 -> bf16 bits (round to nearest even; a NaN stays one) and back. A split-bf16 plane pair holds hi = f2bf(v), lo = f2bf(v - bf2f(hi))
+inline uint16_t f2bf(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline float bf2f(uint16_t h) {
+    uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
 
 // ---- what every build checks (the exhaustive form is tests/layout_check.cpp)
 namespace layout_detail {

@@ -4,10 +4,10 @@
 //   k_sg_tconv      9 x 1 temporal convolution of a stride-1 block: the activation window of a tile resident in LDS, nine taps V rows apart
 //   k_sg_tconv_s2   ... of a stride-2 block at the output rate on polyphase planes, + the block's convolved shortcut
 //   sg_epilogue     their common epilogue: bias (per column or per vertex), identity residual, ReLU, fp32 or split-plane output
-// LDS images, DMA (global_load_lds_dwordx4, 16 rows x 64 B per wave-instruction) and the 16-byte chunk swizzle are those of
-// k_gemm_x3, defined in rgn_layout.h. All three kernels are PERSISTENT over output tiles.
-#include "rgn_internal.h"
-#include "rgn_device.h"
+// All three are PERSISTENT over output tiles and members of the DMA-fed GEMM family of rgn_dma_gemm.h: the product order, the weight-tile DMA, the MFMA
+// groups of a k-step, the tile walk with its counted wait and the paired-column store are defined there. What stands here is each kernel's own: window
+// geometry and refill, tap order, the shortcut's register fragments, the in-register aggregation.
+#include "rgn_dma_gemm.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,13 +30,7 @@ __device__ __forceinline__ float f16_bits_to_float(unsigned b) { return (float)_
 //   SGE_RELU | SGE_PLANES (output as split planes, else fp32)
 //   SGE_POLY         the planes are written POLYPHASE for a stride-2 consumer: input row (sequence, frame t < T of T + 4, vertex) -> region t & 1 (poly_region
 //                    rows each), frame t >> 1 of ceil(T / 2) + 4; the input's pad frames are not written (the consumer's pads are zeroed by the host's k_sg_zero)
-// The callers' counted wait behind an epilogue (`stores_behind`: vmcnt <= the stores of one tile) is an upper bound on what may stay outstanding, not the
-// guarantee that the next k-step's DMA has landed: a wave whose 32 rows are all pad rows SKIPS its polyphase stores (s_cbranch_execz in the ISA). The guarantee
-// there is the in-order retirement of vmcnt: SGE_POLY (the only mode with conditional stores on the counted path) always comes with SGE_RES_PLANES, whose residual
-// loads are issued AFTER that DMA and consumed BEFORE the first store - the DMA has retired by then whatever the number of stores. The other modes issue
-// exactly the counted stores on the interior path (CHECK = false); edge tiles (CHECK = true) are followed by a full wait.
-// What a 32 x 32 tile needs from memory is requested one tile AHEAD of its use: vmcnt retires in order, so a load queued behind the previous tile's
-// stores would wait for their acknowledgements - 2 TM TN round trips to memory per workgroup tile in x3_epilogue's order.
+// (what the callers' counted wait behind an epilogue may assume, and why a tile's operands are fetched one tile ahead: STORES_BEHIND, rgn_dma_gemm.h)
 enum { SGE_VERTEX_BIAS = 1, SGE_RELU = 2, SGE_PLANES = 4, SGE_RES_PLANES = 8, SGE_POLY = 16 };
 template <int TM, int TN, bool CHECK, int MODE, bool F16 = false>
 __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[TM][TN], int mw, int nw, int lane) {
@@ -48,14 +42,7 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
         const int n = nw + tb * 32 + l31, mb = mw + ta * 32 + 4 * kh;
         const bool n_ok = !CHECK || n < g.N;
         if constexpr ((MODE & SGE_VERTEX_BIAS) != 0) {
-            const int base = (int)((unsigned)mb % (unsigned)g.add_mod);
-            const float* ap = g.add + n;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                int rr = base + mfma32_row(i, 0);
-                rr = rr >= g.add_mod ? rr - g.add_mod : rr;
-                f[i] = n_ok ? __builtin_bit_cast(unsigned, ap[rr * g.ldadd]) : 0u;
-            }
+            dg_vertex_addend(g, mb, n, n_ok, f);
         } else if constexpr ((MODE & SGE_RES_PLANES) != 0) {
             // column pairs (n & ~1, + 1) as one 4-byte load: even lanes the rows of registers 0..7, odd lanes those of registers 8..15; f[0..7] hi, f[8..15] lo
             const size_t o = plane_off(g.r_rows, mb, n & ~1);
@@ -127,44 +114,22 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
             const size_t cb = (size_t)(n >> 5) * g.c_rows;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float mine = odd ? r[i + 8] : r[i], give = odd ? r[i] : r[i + 8];
-                const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1
-                const float c0 = odd ? got : mine, c1 = odd ? mine : got;
-                const int ii = odd ? i + 8 : i, ro = mfma32_row(ii, 0);
+                float c0, c1;
+                dg_pair_columns(r, i, odd, c0, c1);
+                const int ro = dg_pair_row(i, odd);
                 int v = v0 + ro, t = t0, nm = (int)nm0;
                 if (v >= Vv) { v -= Vv; ++t; }
                 if (t >= Tp) { t -= Tp; ++nm; }
-                if (t < Tr && (!CHECK || mb + ro < g.M)) {
-                    const size_t o = (cb + (size_t)(t & 1) * g.poly_region + ((size_t)nm * Tpo + (t >> 1)) * Vv + v) * 32 + (n & 30);
-                    if constexpr (F16) {
-                        f16x2 hv = {(_Float16)c0, (_Float16)c1};
-                        *reinterpret_cast<f16x2*>(g.Chi + o) = hv;
-                    } else {
-                        const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
-                        bf16x2 hv = {h0, h1}, lv = {(__bf16)(c0 - (float)h0), (__bf16)(c1 - (float)h1)};
-                        *reinterpret_cast<bf16x2*>(g.Chi + o) = hv;
-                        *reinterpret_cast<bf16x2*>(g.Clo + o) = lv;
-                    }
-                }
+                if (t < Tr && (!CHECK || mb + ro < g.M))
+                    dg_store_pair<F16>(g.Chi, g.Clo, (cb + (size_t)(t & 1) * g.poly_region + ((size_t)nm * Tpo + (t >> 1)) * Vv + v) * 32 + (n & 30), c0, c1);
             }
         } else if constexpr (!CHECK) {   // K32-blocked planes [N/32][c_rows][32]: a 32-column tile is one contiguous run of rows
-            // adjacent columns paired across lane ^ 1 -> packed bf16x2 stores: even lanes rows of registers 0..7, odd lanes those of registers 8..15
             const size_t o = plane_off(g.c_rows, mb, n & ~1);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float mine = odd ? r[i + 8] : r[i], give = odd ? r[i] : r[i + 8];
-                const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xf, 0xf, true));   // lane ^ 1
-                const float c0 = odd ? got : mine, c1 = odd ? mine : got;
-                const int ii = odd ? i + 8 : i, ro = mfma32_row(ii, 0);
-                if constexpr (F16) {
-                    f16x2 hv = {(_Float16)c0, (_Float16)c1};
-                    *reinterpret_cast<f16x2*>(g.Chi + o + ro * 32) = hv;
-                } else {
-                    const __bf16 h0 = (__bf16)c0, h1 = (__bf16)c1;
-                    bf16x2 hv = {h0, h1}, lv = {(__bf16)(c0 - (float)h0), (__bf16)(c1 - (float)h1)};
-                    *reinterpret_cast<bf16x2*>(g.Chi + o + ro * 32) = hv;
-                    *reinterpret_cast<bf16x2*>(g.Clo + o + ro * 32) = lv;
-                }
+                float c0, c1;
+                dg_pair_columns(r, i, odd, c0, c1);
+                dg_store_pair<F16>(g.Chi, g.Clo, o + dg_pair_row(i, odd) * 32, c0, c1);
             }
         } else {
             const size_t o = plane_off(g.c_rows, mb, n);
@@ -213,20 +178,15 @@ template <int BM, int BN, int WM, int MODE, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int ntiles, int V) {
     constexpr int NT = 512, TAPS = 9;
     [[maybe_unused]] constexpr bool PROF = !F16 && BM == 256 && BN == 256 && MODE == (SGE_RELU | SGE_PLANES | SGE_RES_PLANES);   // (tools: SG_STAMP)
-    constexpr int ST_PER = (F16 && (MODE & SGE_PLANES)) ? 8 : 16;   // stores per 32 x 32 tile of the epilogue (planes: hi [+ lo] of 8 column pairs)
     constexpr int WN = 8 / WM;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int W_BYTES = BN * 64, W_STAGE = 2 * W_BYTES;      // one plane tile; a stage = hi | lo
-    constexpr int W_IT = BN * 8 / NT;                            // DMA instructions per thread per weight tile (hi + lo): 1 / 2 / 4
     static_assert(TM >= 1 && TN >= 1 && BN * 8 % NT == 0 && (BN * 4) % 64 == 0 && BM % (32 * WM) == 0 && BM % 64 == 0, "tile shape");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, kh = lane >> 5;
-    const int G = gridDim.x, bid = blockIdx.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    const int slot = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);   // workgroups of one XCD take neighbouring tiles (they share windows)
     // BM = 256: the window is BM + 8 V rows in place. BM = 512 (> 8 V): CIRCULAR - a window needs its rows [0, BM) at tap 0 while the previous window's
     // tap 8 still reads its rows [8 V, 8 V + BM), so the buffer holds 2 BM = 1024 rows and every window starts SP = BM - 8 V rows in front of the last:
     // its first SP rows land in rows nobody uses, rows [SP, BM) follow the previous window's dying strips, the top 8 V rows come under its own taps 0-3.
@@ -254,102 +214,55 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int 
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + pl * A_PLANE + p0 * 64), 16, 0, 0);
         }
     };
-    unsigned w_lane[W_IT];                                       // this thread's 16 bytes of a weight tile (N is a multiple of BN: no column clamp)
-#pragma unroll
-    for (int it = 0; it < W_IT; ++it) {
-        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = img_dma_chunk(r, qq & 3);
-        w_lane[it] = (unsigned)r * 64u + c * 16u;
-    }
-    auto w_tile = [&](int n0t, int kt, char* stage) {
-#pragma unroll
-        for (int it = 0; it < W_IT; ++it) {
-            const int pl = (it * NT + (tid & ~63)) / (BN * 4);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(w_pl[pl] + ((size_t)kt * g.N + n0t) * 64 + w_lane[it]),
-                                             (RGN_AS3 void*)(stage + pl * W_BYTES + (it * NT + (tid & ~63) - pl * (BN * 4)) * 16), 16, 0, 0);
-        }
-    };
+    unsigned w_lane[BN / 64];
+    dg_w_lanes<BN>(w_lane, tid);
+    auto w_tile = [&](int n0t, int kt, char* stage) { dg_w_tile<BN>(w_pl[0], w_pl[1], (size_t)kt * g.N + n0t, w_lane, stage, tid); };
     int w_off[TN][2];
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int rr = wn * (BN / WN) + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
-    }
+    dg_frag_off(w_off, wn * (BN / WN), l31, kh);
     const int arow0 = wm * (BM / WM) + l31;
-    auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {
-        if constexpr (F16) {                                     // (a_l, w_l: the next channel block's fragments)
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_h), __builtin_bit_cast(f16x8, w_h), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_l), __builtin_bit_cast(f16x8, w_l), c, 0, 0, 0);
-        } else {
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, w_h, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_l, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_h, c, 0, 0, 0);
-        }
-    };
 
-    int tile = slot;
-    int m0 = (tile / nbx) * BM, n0 = (tile % nbx) * BN;
+    DgTile t = dg_tile<BM, BN>(xcd_affine(blockIdx.x, gridDim.x), nbx);
     // prologue: rows [0, 8 V + SP) of the first window (its top rows follow under taps 0-3 like every window's) and the first weight tile
     {
         const int np = (8 * V + SP) / 16;                        // pieces per plane
-        for (int q = wave; q < 2 * np; q += 8) a_piece(m0, 0, q / np, (q % np) * 16, 8 * V + SP, 0);
-        w_tile(n0, 0, wst);
+        for (int q = wave; q < 2 * np; q += 8) a_piece(t.m0, 0, q / np, (q % np) * 16, 8 * V + SP, 0);
+        w_tile(t.n0, 0, wst);
     }
     unsigned gstep = 0;                                          // k-steps done: weight stage gstep & 1
     int ws = 0;                                                  // first physical row of the current window
     bool stores_behind = false;
     while (true) {
-        const int tnext = tile + G;
-        const bool more = tnext < ntiles;
-        const int m0n = (tnext / nbx) * BM, n0n = (tnext % nbx) * BN;
+        const DgTile tn = dg_tile<BM, BN>(t.tile + (int)gridDim.x, nbx);
+        const bool more = tn.tile < ntiles;
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+        dg_zero(acc);
         for (int cb = 0; cb < ncb; ++cb) {
             const bool wlast = cb + 1 == ncb;
 #pragma unroll 1
             for (int dt = 0; dt < TAPS; ++dt, ++gstep) {
                 SG_STAMP(0)
-                if (stores_behind) wait_vmcnt<ST_PER * TM * TN>();   // this k-step's DMA is older than the 16 (F16: 8) TM TN stores of the tile just written
-                else wait_vmcnt<0>();                            // everything this thread requested up to the last k-step has landed ...
-                stores_behind = false;
+                dg_step_wait<dg_tile_stores(MODE & SGE_PLANES, F16) * TM * TN>(stores_behind);
                 SG_STAMP(1)
-                __builtin_amdgcn_s_barrier();                    // ... everyone's has, and everyone is done reading the previous k-step
+                __builtin_amdgcn_s_barrier();                    // everyone's requests have landed, and everyone is done reading the previous k-step
                 SG_STAMP(2)
-                const char* wsb = wst + (gstep & 1) * W_STAGE;
                 // fragments: the tap's rows start dt V further down the window (the 16-byte chunk swizzle follows the LDS row)
-                bf16x8 ah[2][TM], al[2][TM], wh[2], wl[2];
-                auto fetch = [&](int grp) {                      // grp = ks * TN + tb
-                    const int ks = grp / TN, tb = grp % TN;
-                    if (tb == 0) {
+                auto a_frag = [&](int ks, bf16x8 (&ah)[2][TM], bf16x8 (&al)[2][TM]) {
 #pragma unroll
-                        for (int t = 0; t < TM; ++t) {
-                            const int rl = arow0 + t * 32 + dt * V, rr = CIRC ? ((ws + rl) & RMASK) : rl;
-                            const int o = img_frag(rr, ks, kh);
-                            ah[ks][t] = *reinterpret_cast<const bf16x8*>(smem + o);
-                            al[ks][t] = *reinterpret_cast<const bf16x8*>(smem + A_PLANE + o);
-                        }
+                    for (int i = 0; i < TM; ++i) {
+                        const int rl = arow0 + i * 32 + dt * V, rr = CIRC ? ((ws + rl) & RMASK) : rl;
+                        const int o = img_frag(rr, ks, kh);
+                        ah[ks][i] = *reinterpret_cast<const bf16x8*>(smem + o);
+                        al[ks][i] = *reinterpret_cast<const bf16x8*>(smem + A_PLANE + o);
                     }
-                    wh[grp & 1] = *reinterpret_cast<const bf16x8*>(wsb + w_off[tb][ks]);
-                    wl[grp & 1] = *reinterpret_cast<const bf16x8*>(wsb + W_BYTES + w_off[tb][ks]);
                 };
-                fetch(0);
-#pragma unroll
-                for (int grp = 0; grp < 2 * TN; ++grp) {
-                    if (grp + 1 < 2 * TN) fetch(grp + 1);
-#pragma unroll
-                    for (int ta = 0; ta < TM; ++ta) mma3(acc[ta][grp % TN], ah[grp / TN][ta], al[grp / TN][ta], wh[grp & 1], wl[grp & 1]);
+                dg_kstep<TM, TN, F16>(acc, wst + (gstep & 1) * W_STAGE, W_BYTES, w_off, a_frag, [&](int grp) {
                     if (grp == 0) {
-                        // the path's load for this k-step, behind the first MFMA group: next weight tile, the dead strip's successor, the window's top quarter
+                        // the path's load for this k-step: next weight tile, the dead strip's successor, the window's top quarter
                         const bool klast = wlast && dt == TAPS - 1;
-                        if (!klast) w_tile(n0, dt + 1 < TAPS ? wk(cb, dt + 1) : wk(cb + 1, 0), wst + ((gstep + 1) & 1) * W_STAGE);
-                        else if (more) w_tile(n0n, 0, wst + ((gstep + 1) & 1) * W_STAGE);
+                        if (!klast) w_tile(t.n0, dt + 1 < TAPS ? wk(cb, dt + 1) : wk(cb + 1, 0), wst + ((gstep + 1) & 1) * W_STAGE);
+                        else if (more) w_tile(tn.n0, 0, wst + ((gstep + 1) & 1) * W_STAGE);
                         if (!wlast || more) {
-                            const int m0w = wlast ? m0n : m0, cbw = wlast ? 0 : cb + 1;
+                            const int m0w = wlast ? tn.m0 : t.m0, cbw = wlast ? 0 : cb + 1;
                             if constexpr (!CIRC) {
                                 if (dt >= 1) a_piece(m0w, cbw, wave >> 2, (dt - 1) * V + 16 * (wave & 3), dt * V, 0);   // V <= 64 rows: four pieces per plane
                             } else {
@@ -365,63 +278,51 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv(GemmX3Args g, int nbx, int 
 #pragma unroll
                                 for (int j = 0; j < (2 * PPT + 7) / 8; ++j) {
                                     const int p = wave + 8 * j;
-                                    if (p < 2 * PPT) a_piece(m0, cb, p / PPT, 8 * V + (BM / 4) * dt + 16 * (p % PPT), WR, 0);
+                                    if (p < 2 * PPT) a_piece(t.m0, cb, p / PPT, 8 * V + (BM / 4) * dt + 16 * (p % PPT), WR, 0);
                                 }
                             } else {
                                 // the top 8 V rows, 2 V per tap (tap dt + 1 reads rows below (dt + 1) V + BM <= BM + 2 V (dt + 1))
-                                for (int p = wave & 3; 16 * p < 2 * V; p += 4) a_piece(m0, cb, wave >> 2, BM + 2 * V * dt + 16 * p, BM + 2 * V * (dt + 1), ws);
+                                for (int p = wave & 3; 16 * p < 2 * V; p += 4) a_piece(t.m0, cb, wave >> 2, BM + 2 * V * dt + 16 * p, BM + 2 * V * (dt + 1), ws);
                             }
                         }
                     }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                });
                 SG_STAMP(4)
             }
             if constexpr (CIRC) ws = (ws - SP) & RMASK;
         }
-        const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-        if (interior) {
-            sg_epilogue<TM, TN, false, MODE, F16>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
-            stores_behind = true;
-        } else sg_epilogue<TM, TN, true, MODE, F16>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
+        stores_behind = dg_close<BM, BN>(g, t.m0, t.n0, [&](auto CHECK) { sg_epilogue<TM, TN, decltype(CHECK)::value, MODE, F16>(g, acc, t.m0 + wm * (BM / WM), t.n0 + wn * (BN / WN), lane); });
         if (!more) break;
-        tile = tnext; m0 = m0n; n0 = n0n;
+        t = tn;
     }
 }
 static int tconv_lds_bytes(int BM, int BN, int V) { return 2 * (BM > 256 ? 2 * BM : BM + 8 * V) * 64 + 2 * 2 * BN * 64; }
-template <int BM, int BN, int WM, int MODE, bool F16 = false>
-static hipError_t tconv_launch(const GemmX3Args& g, int V, hipStream_t s, bool configure_only) {
-    if (configure_only)
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_tconv<BM, BN, WM, MODE, F16>), hipFuncAttributeMaxDynamicSharedMemorySize, std::min(160 * 1024, tconv_lds_bytes(BM, BN, 64)));
-    const int nbx = (g.N + BN - 1) / BN, ntiles = nbx * ((g.M + BM - 1) / BM);
-    hipLaunchKernelGGL((k_sg_tconv<BM, BN, WM, MODE, F16>), dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_lds_bytes(BM, BN, V), s, g, nbx, ntiles, V);
-    return hipGetLastError();
-}
 // (8 V >= 256: tap 0 reads window rows [0, 256), and only the first 8 V rows of a window are in place before its own taps run)
 bool sg_tconv_supported(int N, int Kp, int V) { return (N == 64 || N == 128 || N == 256) && Kp == 9 * N && V % 4 == 0 && V >= 32 && V <= 64; }
-// tail 0: C = conv + bias (fp32);  1: planes relu(conv + bias);  2: planes relu(conv + bias + (Rhi + Rlo));  3: as 2, written polyphase (poly_*)
-template <int BM, int BN, int WM>
-static hipError_t tconv_dispatch(const GemmX3Args& g, int V, int tail, hipStream_t s, bool configure_only) {
-    if (configure_only) {
-        hipError_t e = tconv_launch<BM, BN, WM, 0>(g, V, s, true);
-        if (e != hipSuccess) return e;
-        e = tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES>(g, V, s, true);
-        if (e == hipSuccess) e = tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES>(g, V, s, true);
-        if (e == hipSuccess) e = tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY>(g, V, s, true);
-        if (e == hipSuccess) e = tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES, true>(g, V, s, true);
-        if (e == hipSuccess) e = tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES, true>(g, V, s, true);
-        return e != hipSuccess ? e : tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY, true>(g, V, s, true);
-    }
-    if (g.f16) {                                                 // the fp16 form exists for the plane tails only (rgn_stgcn.hip refuses the rest)
-        if (tail == 1) return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES, true>(g, V, s, false);
-        if (tail == 2) return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES, true>(g, V, s, false);
-        if (tail == 3) return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY, true>(g, V, s, false);
-        return hipErrorInvalidValue;
-    }
-    if (tail == 0) return tconv_launch<BM, BN, WM, 0>(g, V, s, false);
-    if (tail == 1) return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES>(g, V, s, false);
-    if (tail == 2) return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES>(g, V, s, false);
-    return tconv_launch<BM, BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY>(g, V, s, false);
+// k_sg_tconv's forms, named once: fn(kernel, BM, BN) for (tile shape, tail, arithmetic). tail 0: C = conv + bias (fp32);  1: planes relu(conv + bias);
+// 2: planes relu(conv + bias + (Rhi + Rlo));  3: as 2, written polyphase (poly_*). The fp16 form exists for the plane tails only (rgn_stgcn.hip refuses the rest)
+enum { TC_256x64 = 0, TC_256x128, TC_256x256, TC_512x64, TC_512x128, TC_SHAPES };
+template <int BM, int BN, int WM, class Fn>
+static hipError_t tconv_tail_form(int tail, bool f16, Fn fn) {
+    auto pick = [&](auto MODE) {
+        return dispatch_bools([&](auto F) {
+            if constexpr (decltype(F)::value && decltype(MODE)::value == 0) return hipErrorInvalidValue;
+            else return fn(k_sg_tconv<BM, BN, WM, decltype(MODE)::value, decltype(F)::value>, BM, BN);
+        }, f16);
+    };
+    if (tail == 0) return pick(std::integral_constant<int, 0>{});
+    if (tail == 1) return pick(std::integral_constant<int, SGE_RELU | SGE_PLANES>{});
+    if (tail == 2) return pick(std::integral_constant<int, SGE_RELU | SGE_PLANES | SGE_RES_PLANES>{});
+    if (tail == 3) return pick(std::integral_constant<int, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY>{});
+    return hipErrorInvalidValue;
+}
+template <class Fn>
+static hipError_t tconv_form(int shape, int tail, bool f16, Fn fn) {
+    if (shape == TC_256x64) return tconv_tail_form<256, 64, 8>(tail, f16, fn);
+    if (shape == TC_256x128) return tconv_tail_form<256, 128, 4>(tail, f16, fn);
+    if (shape == TC_256x256) return tconv_tail_form<256, 256, 8>(tail, f16, fn);
+    if (shape == TC_512x64) return tconv_tail_form<512, 64, 8>(tail, f16, fn);
+    return tconv_tail_form<512, 128, 8>(tail, f16, fn);
 }
 // Tile shapes. Per k-step the L2 -> LDS path (~20 B/clk) carries the weight tile + V rows + (taps 0-3) a quarter of the window top against
 // TM TN x 6 MFMAs per wave: 256 x 64 tiles (768 MFMA cycles per SIMD, 21 KB) and 256 x 128 (1536, 29 KB) sit at or past the path's rate; a 256-wide tile
@@ -430,25 +331,15 @@ static hipError_t tconv_dispatch(const GemmX3Args& g, int V, int tail, hipStream
 // 128-channel kernels), and 384-row tiles (4 x 2 waves of 96 rows) measured 5 - 15 % SLOWER than 256 (profiles/r05/stgcn_tconv_shapes.txt).
 hipError_t launch_sg_tconv(const GemmX3Args& g, int V, int tail, bool small, hipStream_t s) {   // small: 256-row tiles, <= 128 wide (tools / tests)
     const bool tall = !small && V % 8 == 0 && 8 * V <= 512;         // (the circular window: 2 V-row pieces, SP = 512 - 8 V >= 0)
-    if (g.N == 64) return tall ? tconv_dispatch<512, 64, 8>(g, V, tail, s, false) : tconv_dispatch<256, 64, 8>(g, V, tail, s, false);
-    if (g.N == 128 && tall) return tconv_dispatch<512, 128, 8>(g, V, tail, s, false);
     // (256 x 256 on 4 x 2 waves - 64 x 128 per wave, a third fewer fragment reads from LDS than 8 x 1 - measured the same within 0.3 % in both arithmetics:
     //  profiles/r06_recogniser_experiments.txt)
-    if (g.N == 256 && !small && tconv_lds_bytes(256, 256, V) <= 160 * 1024) return tconv_dispatch<256, 256, 8>(g, V, tail, s, false);
-    return tconv_dispatch<256, 128, 4>(g, V, tail, s, false);
-}
-template <int MODE, bool F16 = false>
-__global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, int ntiles, int V, long long o_rows);
-hipError_t configure_sg_tconv() {
-    GemmX3Args g{};
-    hipError_t e = tconv_dispatch<256, 64, 8>(g, 0, 0, nullptr, true);
-    if (e == hipSuccess) e = tconv_dispatch<256, 128, 4>(g, 0, 0, nullptr, true);
-    if (e == hipSuccess) e = tconv_dispatch<256, 256, 8>(g, 0, 0, nullptr, true);
-    if (e == hipSuccess) e = tconv_dispatch<512, 64, 8>(g, 0, 0, nullptr, true);
-    if (e == hipSuccess) e = tconv_dispatch<512, 128, 8>(g, 0, 0, nullptr, true);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_tconv_s2<SGE_RELU | SGE_PLANES>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_tconv_s2<SGE_RELU | SGE_PLANES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return e;
+    const int shape = g.N == 64 ? (tall ? TC_512x64 : TC_256x64) : g.N == 128 && tall ? TC_512x128
+                    : g.N == 256 && !small && tconv_lds_bytes(256, 256, V) <= 160 * 1024 ? TC_256x256 : TC_256x128;
+    return tconv_form(shape, tail, g.f16 != 0, [&](auto kern, int BM, int BN) {
+        const int nbx = (g.N + BN - 1) / BN, ntiles = nbx * ((g.M + BM - 1) / BM);
+        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_lds_bytes(BM, BN, V), s, g, nbx, ntiles, V);
+        return hipGetLastError();
+    });
 }
 
 // ---- the 9 x 1 temporal convolution of a STRIDE-2 block, at the output rate, on polyphase planes (region E: even frames, region O: odd frames, same
@@ -461,17 +352,13 @@ hipError_t configure_sg_tconv() {
 // into registers, requested one k-step ahead. Epilogue: planes relu(acc + bias), bias = b2' + br'. Persistent over tiles like k_sg_tconv.
 template <int MODE, bool F16>
 __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, int ntiles, int V, long long o_rows) {
-    constexpr int BM = 256, BN = 128, NT = 512, WM = 4, WN = 2, TM = 2, TN = 2;
-    constexpr int ST_PER = (F16 && (MODE & SGE_PLANES)) ? 8 : 16;
-    constexpr int W_BYTES = BN * 64, W_STAGE = 2 * W_BYTES, W_IT = BN * 8 / NT;
+    constexpr int BM = 256, BN = 128, WM = 4, WN = 2, TM = 2, TN = 2;
+    constexpr int W_BYTES = BN * 64, W_STAGE = 2 * W_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, kh = lane >> 5;
-    const int G = gridDim.x, bid = blockIdx.x;
-    const int q8 = G >> 3, r8 = G & 7, xcd = bid & 7;
-    const int slot = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     const int WE = BM + 4 * V, WO = BM + 3 * V, EP = WE * 64, OP = WO * 64;   // window rows, bytes per plane
     char* const ebuf = smem;                                     // E hi | E lo
     char* const obuf = smem + 2 * EP;                            // O hi | O lo
@@ -493,39 +380,14 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(buf + pl * pb + r0 * 64), 16, 0, 0);
         }
     };
-    unsigned w_lane[W_IT];
-#pragma unroll
-    for (int it = 0; it < W_IT; ++it) {
-        const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = img_dma_chunk(r, qq & 3);
-        w_lane[it] = (unsigned)r * 64u + c * 16u;
-    }
+    unsigned w_lane[BN / 64];
+    dg_w_lanes<BN>(w_lane, tid);
     auto w_tile = [&](const __bf16* whi, const __bf16* wlo, int n0t, int kt, char* stage) {
-#pragma unroll
-        for (int it = 0; it < W_IT; ++it) {
-            const int pl = (it * NT + (tid & ~63)) / (BN * 4);
-            const char* base = reinterpret_cast<const char*>(pl ? wlo : whi);
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(base + ((size_t)kt * g.N + n0t) * 64 + w_lane[it]),
-                                             (RGN_AS3 void*)(stage + pl * W_BYTES + (it * NT + (tid & ~63) - pl * (BN * 4)) * 16), 16, 0, 0);
-        }
+        dg_w_tile<BN>(reinterpret_cast<const char*>(whi), reinterpret_cast<const char*>(wlo), (size_t)kt * g.N + n0t, w_lane, stage, tid);
     };
     int w_off[TN][2];
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int rr = wn * (BN / WN) + t * 32 + l31;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) w_off[t][ks] = img_frag(rr, ks, kh);
-    }
+    dg_frag_off(w_off, wn * (BN / WN), l31, kh);
     const int arow0 = wm * (BM / WM) + l31;
-    auto mma3 = [&](f32x16& c, const bf16x8& a_h, const bf16x8& a_l, const bf16x8& w_h, const bf16x8& w_l) {
-        if constexpr (F16) {                                     // (a_l, w_l: the next channel block's fragments)
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_h), __builtin_bit_cast(f16x8, w_h), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_l), __builtin_bit_cast(f16x8, w_l), c, 0, 0, 0);
-        } else {
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, w_h, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_l, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_h, c, 0, 0, 0);
-        }
-    };
     // the shortcut's operand fragments of this lane's rows, k-block cr (straight from the input planes, region E)
     bf16x8 sh[2][TM], sl[2][TM];
     auto shortcut_fetch = [&](int m0t, int cr) {
@@ -542,70 +404,51 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
         }
     };
 
-    int tile = slot;
-    int m0 = (tile / nbx) * BM, n0 = (tile % nbx) * BN;
+    DgTile t = dg_tile<BM, BN>(xcd_affine(blockIdx.x, gridDim.x), nbx);
     {   // prologue: all of E and the low 3 V rows of O of the first window (O's top follows under the E taps like every window's), the first weight tile
         const int ne = (WE + 15) / 16, no = (3 * V + 15) / 16;
-        for (int q = wave; q < 2 * ne; q += 8) a_piece((long long)m0 - 2 * V, 0, q / ne, (q % ne) * 16, WE, ebuf, EP);
-        for (int q = wave; q < 2 * no; q += 8) a_piece(o_rows + m0 - 2 * V, 0, q / no, (q % no) * 16, 3 * V, obuf, OP);
-        w_tile(g.Whi, w1lo, n0, 0, wst);
+        for (int q = wave; q < 2 * ne; q += 8) a_piece((long long)t.m0 - 2 * V, 0, q / ne, (q % ne) * 16, WE, ebuf, EP);
+        for (int q = wave; q < 2 * no; q += 8) a_piece(o_rows + t.m0 - 2 * V, 0, q / no, (q % no) * 16, 3 * V, obuf, OP);
+        w_tile(g.Whi, w1lo, t.n0, 0, wst);
     }
     unsigned gstep = 0;
     bool stores_behind = false;
     while (true) {
-        const int tnext = tile + G;
-        const bool more = tnext < ntiles;
-        const int m0n = (tnext / nbx) * BM, n0n = (tnext % nbx) * BN;
+        const DgTile tn = dg_tile<BM, BN>(t.tile + (int)gridDim.x, nbx);
+        const bool more = tn.tile < ntiles;
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+        dg_zero(acc);
         const int nsteps = ncb * 9 + k2;
         for (int st = 0; st < nsteps; ++st, ++gstep) {
             const bool shortcut = st >= ncb * 9;
             const int cb = shortcut ? ncb - 1 : st / 9, i9 = shortcut ? 9 : st - cb * 9;      // i9: 0..4 E taps, 5..8 O taps
             const bool isE = i9 < 5;
             const int j = isE ? i9 : i9 - 5;
-            if (stores_behind) wait_vmcnt<ST_PER * TM * TN>();
-            else wait_vmcnt<0>();
-            stores_behind = false;
+            dg_step_wait<dg_tile_stores(MODE & SGE_PLANES, F16) * TM * TN>(stores_behind);
             __builtin_amdgcn_s_barrier();
-            const char* wsb = wst + (gstep & 1) * W_STAGE;
             const char* abuf = isE ? ebuf : obuf;
             const int apl = isE ? EP : OP;
-            bf16x8 ah[2][TM], al[2][TM], wh[2], wl[2];
-            if (shortcut) {                                      // (both k halves now: the next k-block's fragments are requested into sh / sl under this step)
+            auto a_frag = [&](int ks, bf16x8 (&ah)[2][TM], bf16x8 (&al)[2][TM]) {
+                if (shortcut) {                                  // (both k halves at once: the next k-block's fragments are requested into sh / sl under this step)
+                    if (ks == 0) {
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
+                        for (int k2s = 0; k2s < 2; ++k2s)
 #pragma unroll
-                    for (int t = 0; t < TM; ++t) {
-                        ah[ks][t] = sh[ks][t];
-                        al[ks][t] = sl[ks][t];
+                            for (int i = 0; i < TM; ++i) {
+                                ah[k2s][i] = sh[k2s][i];
+                                al[k2s][i] = sl[k2s][i];
+                            }
                     }
-            }
-            auto fetch = [&](int grp) {                          // grp = ks * TN + tb
-                const int ks = grp / TN, tb = grp % TN;
-                if (tb == 0 && !shortcut) {
+                } else {
 #pragma unroll
-                    for (int t = 0; t < TM; ++t) {
-                        const int rr = arow0 + t * 32 + j * V;
-                        const int o = img_frag(rr, ks, kh);
-                        ah[ks][t] = *reinterpret_cast<const bf16x8*>(abuf + o);
-                        al[ks][t] = *reinterpret_cast<const bf16x8*>(abuf + apl + o);
+                    for (int i = 0; i < TM; ++i) {
+                        const int o = img_frag(arow0 + i * 32 + j * V, ks, kh);
+                        ah[ks][i] = *reinterpret_cast<const bf16x8*>(abuf + o);
+                        al[ks][i] = *reinterpret_cast<const bf16x8*>(abuf + apl + o);
                     }
                 }
-                wh[grp & 1] = *reinterpret_cast<const bf16x8*>(wsb + w_off[tb][ks]);
-                wl[grp & 1] = *reinterpret_cast<const bf16x8*>(wsb + W_BYTES + w_off[tb][ks]);
             };
-            fetch(0);
-#pragma unroll
-            for (int grp = 0; grp < 2 * TN; ++grp) {
-                if (grp + 1 < 2 * TN) fetch(grp + 1);
-#pragma unroll
-                for (int ta = 0; ta < TM; ++ta) mma3(acc[ta][grp % TN], ah[grp / TN][ta], al[grp / TN][ta], wh[grp & 1], wl[grp & 1]);
+            dg_kstep<TM, TN, F16>(acc, wst + (gstep & 1) * W_STAGE, W_BYTES, w_off, a_frag, [&](int grp) {
                 if (grp == 0) {
                     char* nstage = wst + ((gstep + 1) & 1) * W_STAGE;
                     // the next k-step's weight tile (tap order E 0, 2, 4, 6, 8 then O 1, 3, 5, 7: step i of a channel block is tap i < 5 ? 2 i : 2 (i - 5) + 1)
@@ -613,44 +456,55 @@ __global__ __launch_bounds__(512, 1) void k_sg_tconv_s2(GemmX3Args g, int nbx, i
                         const int s1 = st + 1;
                         if (s1 < ncb * 9) {
                             const int c1 = s1 / 9, i1 = s1 - c1 * 9;
-                            w_tile(g.Whi, w1lo, n0, CBS * c1 * 9 + (i1 < 5 ? 2 * i1 : 2 * (i1 - 5) + 1), nstage);
-                        } else w_tile(g.W2hi, w2lo, n0, CBS * (s1 - ncb * 9), nstage);
-                    } else if (more) w_tile(g.Whi, w1lo, n0n, 0, nstage);
+                            w_tile(g.Whi, w1lo, t.n0, CBS * c1 * 9 + (i1 < 5 ? 2 * i1 : 2 * (i1 - 5) + 1), nstage);
+                        } else w_tile(g.W2hi, w2lo, t.n0, CBS * (s1 - ncb * 9), nstage);
+                    } else if (more) w_tile(g.Whi, w1lo, tn.n0, 0, nstage);
                     if (!shortcut) {
                         const bool wlast = cb + 1 == ncb;
                         const bool nextw = !wlast || more;       // a next pair of windows exists: (this tile, cb + 1) or (next tile, 0)
-                        const long long firstn = (long long)(wlast ? m0n : m0) - 2 * V;
+                        const long long firstn = (long long)(wlast ? tn.m0 : t.m0) - 2 * V;
                         const int cbn = wlast ? 0 : cb + 1;
                         if (isE) {
                             if (j >= 1 && nextw) a_piece(firstn, cbn, wave >> 2, (j - 1) * V + 16 * (wave & 3), j * V, ebuf, EP);       // E strip of the next window
-                            if (j < 4) a_piece(o_rows + m0 - 2 * V, cb, wave >> 2, 3 * V + 64 * j + 16 * (wave & 3), WO, obuf, OP);       // this window's O top
+                            if (j < 4) a_piece(o_rows + t.m0 - 2 * V, cb, wave >> 2, 3 * V + 64 * j + 16 * (wave & 3), WO, obuf, OP);       // this window's O top
                         } else {
                             if (j >= 1 && nextw) a_piece(o_rows + firstn, cbn, wave >> 2, (j - 1) * V + 16 * (wave & 3), j * V, obuf, OP);   // O strip of the next window
                             if (nextw) a_piece(firstn, cbn, wave >> 2, 4 * V + 64 * j + 16 * (wave & 3), WE, ebuf, EP);                  // the next window's E top
                         }
                     }
                     // the shortcut's fragments for the next k-step
-                    if (st + 1 >= ncb * 9 && st + 1 < nsteps) shortcut_fetch(m0, st + 1 - ncb * 9);
+                    if (st + 1 >= ncb * 9 && st + 1 < nsteps) shortcut_fetch(t.m0, st + 1 - ncb * 9);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            });
         }
-        const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-        if (interior) {
-            sg_epilogue<TM, TN, false, MODE, F16>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
-            stores_behind = true;
-        } else sg_epilogue<TM, TN, true, MODE, F16>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane);
+        stores_behind = dg_close<BM, BN>(g, t.m0, t.n0, [&](auto CHECK) { sg_epilogue<TM, TN, decltype(CHECK)::value, MODE, F16>(g, acc, t.m0 + wm * (BM / WM), t.n0 + wn * (BN / WN), lane); });
         if (!more) break;
-        tile = tnext; m0 = m0n; n0 = n0n;
+        t = tn;
     }
 }
 static int tconv_s2_lds_bytes(int V) { return 2 * (256 + 4 * V) * 64 + 2 * (256 + 3 * V) * 64 + 2 * 2 * 128 * 64; }
 bool sg_tconv_s2_supported(int N, int Kp, int V) { return (N == 128 || N == 256) && Kp == 9 * N && V % 4 == 0 && V >= 16 && V <= 64 && tconv_s2_lds_bytes(V) <= 160 * 1024; }
+template <class Fn>
+static hipError_t tconv_s2_form(bool f16, Fn fn) {           // k_sg_tconv_s2's forms, named once
+    return dispatch_bools([&](auto F) { return fn(k_sg_tconv_s2<SGE_RELU | SGE_PLANES, decltype(F)::value>); }, f16);
+}
 hipError_t launch_sg_tconv_s2(const GemmX3Args& g, int V, long long o_rows, hipStream_t s) {
     const int nbx = g.N / 128, ntiles = nbx * ((g.M + 255) / 256);
-    if (g.f16) hipLaunchKernelGGL((k_sg_tconv_s2<SGE_RELU | SGE_PLANES, true>), dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_s2_lds_bytes(V), s, g, nbx, ntiles, V, o_rows);
-    else hipLaunchKernelGGL((k_sg_tconv_s2<SGE_RELU | SGE_PLANES>), dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_s2_lds_bytes(V), s, g, nbx, ntiles, V, o_rows);
-    return hipGetLastError();
+    return tconv_s2_form(g.f16 != 0, [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_s2_lds_bytes(V), s, g, nbx, ntiles, V, o_rows);
+        return hipGetLastError();
+    });
+}
+hipError_t configure_sg_tconv() {
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < TC_SHAPES * 8 && e == hipSuccess; ++m)
+        if (!((m & 4) && (m & 3) == 0))                          // (every shape x tail x arithmetic that exists)
+            e = tconv_form(m >> 3, m & 3, m & 4, [](auto kern, int BM, int BN) {
+                return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, std::min(160 * 1024, tconv_lds_bytes(BM, BN, 64)));
+            });
+    for (int f = 0; f < 2 && e == hipSuccess; ++f)
+        e = tconv_s2_form(f, [](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    return e;
 }
 
 // ---- graph aggregation + 1 x 1 convolution of an ST-GCN block as ONE kernel (rgn_stgcn.hip) -------------------------------------------------------
@@ -669,9 +523,8 @@ hipError_t launch_sg_tconv_s2(const GemmX3Args& g, int V, long long o_rows, hipS
 template <int BN, bool ALLK, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int ntiles, int V, int KP, unsigned slot_k, const int* __restrict__ sl_v, const float* __restrict__ sl_a) {
     constexpr int BM = 256, NT = 512, TN = BN / 32, NS = 8;
-    constexpr int ST_PER = F16 ? 8 : 16;                         // plane stores per 32 x 32 tile of the epilogue
+    constexpr int MODE = SGE_VERTEX_BIAS | SGE_RELU | SGE_PLANES;
     constexpr int W_BYTES = BN * 64, W_STAGE = 2 * W_BYTES * (ALLK ? 4 : 1);
-    constexpr int W_IT = BN * 8 / NT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -702,16 +555,9 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
             __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + buf * XW + pl * XP + r0 * 64), 16, 0, 0);
         }
     };
-    auto w_tile = [&](int n0t, int kb, char* stage) {
-#pragma unroll
-        for (int it = 0; it < W_IT; ++it) {
-            const int q = it * NT + tid, pl = (it * NT + (tid & ~63)) / (BN * 4), qq = q - pl * (BN * 4), r = qq >> 2, c = (qq & 3) ^ ((r >> 2) & 3);   // (= img_dma_chunk(r, qq & 3))
-            int n = n0t + r;
-            n = n < g.N ? n : g.N - 1;
-            __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)(w_pl[pl] + ((size_t)kb * g.N + n) * 64 + c * 16),
-                                             (RGN_AS3 void*)(stage + pl * W_BYTES + (it * NT + (tid & ~63) - pl * (BN * 4)) * 16), 16, 0, 0);
-        }
-    };
+    unsigned w_lane[BN / 64];
+    dg_w_lanes<BN>(w_lane, tid);
+    auto w_tile = [&](int n0t, int kb, char* stage) { dg_w_tile<BN>(w_pl[0], w_pl[1], (size_t)kb * g.N + n0t, w_lane, stage, tid); };
     int w_off[TN];
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
@@ -720,20 +566,18 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
     }
     const int r = wave * 32 + l31;
 
-    // workgroups of one XCD take neighbouring tiles: a tile's window overlaps its neighbours' by V rows on either side, which then come from that XCD's L2
-    const int G = gridDim.x, q8 = G >> 3, r8 = G & 7, xcd = blockIdx.x & 7;
-    int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + ((int)blockIdx.x >> 3);
-    int m0 = (tile / nbx) * BM, n0 = (tile % nbx) * BN;
-    for (int p = wave; p < npieces; p += 8) x_piece(m0, 0, p, 0);
+    // (neighbouring tiles on one XCD: a tile's window overlaps its neighbours' by V rows on either side)
+    DgTile t = dg_tile<BM, BN>(xcd_affine(blockIdx.x, gridDim.x), nbx);
+    for (int p = wave; p < npieces; p += 8) x_piece(t.m0, 0, p, 0);
     if constexpr (ALLK) {
-        for (int kk = 0; kk < KP; ++kk) w_tile(n0, wkb(0, kk), wst + kk * 2 * W_BYTES);
-    } else w_tile(n0, 0, wst);
+        for (int kk = 0; kk < KP; ++kk) w_tile(t.n0, wkb(0, kk), wst + kk * 2 * W_BYTES);
+    } else w_tile(t.n0, 0, wst);
     unsigned gstep = 0, widx = 0;                                // k-steps / windows consumed so far: stage gstep & 1, window buffer widx & 1
     bool stores_behind = false;                                  // the previous tile's stores were issued after everything the next wait is for
     while (true) {
         // This lane's row keeps its vertex w for the whole tile, so its lists do too: NS slots of (source row in the window, coefficient), slot s serving
         // partition (slot_k >> 4 s) & 15 - a partition owns as many slots as its longest list; shorter lists are padded with (own row, 0).
-        const int wv = (int)((unsigned)(m0 + r) % (unsigned)V);
+        const int wv = (int)((unsigned)(t.m0 + r) % (unsigned)V);
         const int fbase = V + r - wv;                            // window row of vertex 0 of this row's frame
         int so[NS];
         float sa[NS];
@@ -746,36 +590,30 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
         unsigned live = 0;                                       // slots that carry a coefficient for at least one row of this wave (a hub vertex's long list
 #pragma unroll                                                   //  pads everyone else's: most waves skip most of its slots)
         for (int s = 0; s < NS; ++s) live |= (__builtin_amdgcn_ballot_w64(sa[s] != 0.f) != 0ull ? 1u : 0u) << s;
-        const int tnext = tile + (int)gridDim.x;
-        const bool more = tnext < ntiles;
-        const int m0n = (tnext / nbx) * BM, n0n = (tnext % nbx) * BN;
+        const DgTile tn = dg_tile<BM, BN>(t.tile + (int)gridDim.x, nbx);
+        const bool more = tn.tile < ntiles;
         f32x16 acc[1][TN];
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[0][b][i] = 0.f;
+        dg_zero(acc);
 
         for (int cb = 0; cb < ncb; ++cb, ++widx) {
             const char* xw = smem + (widx & 1) * XW;
             const bool wlast = cb + 1 == ncb;
             for (int k = 0; k < KP; ++k) {
                 if (!ALLK || k == 0) {
-                    if (stores_behind) wait_vmcnt<ST_PER * TN>();    // the DMA of this step is older than the 16 (F16: 8) TN stores of the tile just written
-                    else wait_vmcnt<0>();
-                    stores_behind = false;
+                    dg_step_wait<dg_tile_stores(true, F16) * TN>(stores_behind);
                     __builtin_amdgcn_s_barrier();                // the tile(s) of this step (and, at k = 0, the window) are in LDS; the previous step is read out
                     if constexpr (!ALLK) {
                         const bool klast = k + 1 == KP;
-                        if (!(klast && wlast)) w_tile(n0, klast ? wkb(cb + 1, 0) : wkb(cb, k + 1), wst + ((gstep + 1) & 1) * W_STAGE);
-                        else if (more) w_tile(n0n, 0, wst + ((gstep + 1) & 1) * W_STAGE);
+                        if (!(klast && wlast)) w_tile(t.n0, klast ? wkb(cb + 1, 0) : wkb(cb, k + 1), wst + ((gstep + 1) & 1) * W_STAGE);
+                        else if (more) w_tile(tn.n0, 0, wst + ((gstep + 1) & 1) * W_STAGE);
                         if (!wlast || more)
                             for (int i = 0; i < ppk; ++i) {
                                 const int p = (k * ppk + i) * 8 + wave;
-                                if (p < npieces) x_piece(wlast ? m0n : m0, wlast ? 0 : cb + 1, p, (widx + 1) & 1);
+                                if (p < npieces) x_piece(wlast ? tn.m0 : t.m0, wlast ? 0 : cb + 1, p, (widx + 1) & 1);
                             }
                     } else if (!wlast || more) {                 // every partition's tile of the next channel block, and its whole window
-                        for (int kk = 0; kk < KP; ++kk) w_tile(wlast ? n0n : n0, wkb(wlast ? 0 : cb + 1, kk), wst + ((gstep + 1) & 1) * W_STAGE + kk * 2 * W_BYTES);
-                        for (int p = wave; p < npieces; p += 8) x_piece(wlast ? m0n : m0, wlast ? 0 : cb + 1, p, (widx + 1) & 1);
+                        for (int kk = 0; kk < KP; ++kk) w_tile(wlast ? tn.n0 : t.n0, wkb(wlast ? 0 : cb + 1, kk), wst + ((gstep + 1) & 1) * W_STAGE + kk * 2 * W_BYTES);
+                        for (int p = wave; p < npieces; p += 8) x_piece(wlast ? tn.m0 : t.m0, wlast ? 0 : cb + 1, p, (widx + 1) & 1);
                     }
                 }
                 const char* wsb = wst + (gstep & 1) * W_STAGE + (ALLK ? k * 2 * W_BYTES : 0);
@@ -818,8 +656,7 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
                         for (int tb = 0; tb < TN; ++tb) {
                             const int o = w_off[tb] ^ (32 * ks);
                             const f16x8 wf = *reinterpret_cast<const f16x8*>(wsb + o), wf2 = *reinterpret_cast<const f16x8*>(wsb + W_BYTES + o);
-                            acc[0][tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, wf, acc[0][tb], 0, 0, 0);
-                            acc[0][tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af2, wf2, acc[0][tb], 0, 0, 0);
+                            dg_mma<true>(acc[0][tb], af, af2, wf, wf2);
                         }
                     } else {
                         bf16x8 ah, al;
@@ -832,50 +669,46 @@ __global__ __launch_bounds__(512, 1) void k_sg_gcn(GemmX3Args g, int nbx, int nt
                         for (int tb = 0; tb < TN; ++tb) {
                             const int o = w_off[tb] ^ (32 * ks);
                             const bf16x8 wh = *reinterpret_cast<const bf16x8*>(wsb + o), wl = *reinterpret_cast<const bf16x8*>(wsb + W_BYTES + o);
-                            acc[0][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh, acc[0][tb], 0, 0, 0);
-                            acc[0][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wl, acc[0][tb], 0, 0, 0);
-                            acc[0][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wh, acc[0][tb], 0, 0, 0);
+                            dg_mma<false>(acc[0][tb], ah, al, wh, wl);
                         }
                     }
                 }
                 if (!ALLK || k + 1 == KP) ++gstep;
             }
         }
-        const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-        if (interior) {
-            sg_epilogue<1, TN, false, SGE_VERTEX_BIAS | SGE_RELU | SGE_PLANES, F16>(g, acc, m0 + wave * 32, n0, lane);
-            stores_behind = true;                                // (exactly 16 TN stores, all issued after the next k-step's DMA)
-        } else sg_epilogue<1, TN, true, SGE_VERTEX_BIAS | SGE_RELU | SGE_PLANES, F16>(g, acc, m0 + wave * 32, n0, lane);
+        stores_behind = dg_close<BM, BN>(g, t.m0, t.n0, [&](auto CHECK) { sg_epilogue<1, TN, decltype(CHECK)::value, MODE, F16>(g, acc, t.m0 + wave * 32, t.n0, lane); });
         if (!more) break;
-        tile = tnext; m0 = m0n; n0 = n0n;
+        t = tn;
     }
 }
 static int gcn_lds_bytes(int BN, int V, bool allk = false) { return 2 * 2 * (256 + 2 * V) * 64 + 2 * 2 * BN * 64 * (allk ? 4 : 1) + 2 * 4 * 8 * V; }
 bool sg_gcn_supported(int N, int Kp, int V, int KP) {
     return (N == 64 || N == 128 || N == 256) && KP >= 1 && KP <= 8 && Kp % (32 * KP) == 0 && V % 4 == 0 && V >= 16 && V <= 64 && gcn_lds_bytes(64, V) <= 160 * 1024;
 }
-template <int BN, bool ALLK>
-static hipError_t gcn_launch(const GemmX3Args& g, int V, int KP, unsigned slot_k, const int* sl_v, const float* sl_a, hipStream_t s) {
-    const int nbx = (g.N + BN - 1) / BN, ntiles = nbx * ((g.M + 255) / 256);
-    if (g.f16) hipLaunchKernelGGL((k_sg_gcn<BN, ALLK, true>), dim3(std::min(ntiles, sg_cu_count())), dim3(512), gcn_lds_bytes(BN, V, ALLK), s, g, nbx, ntiles, V, KP, slot_k, sl_v, sl_a);
-    else hipLaunchKernelGGL((k_sg_gcn<BN, ALLK>), dim3(std::min(ntiles, sg_cu_count())), dim3(512), gcn_lds_bytes(BN, V, ALLK), s, g, nbx, ntiles, V, KP, slot_k, sl_v, sl_a);
-    return hipGetLastError();
+template <class Fn>
+static hipError_t gcn_form(int bn, bool allk, bool f16, Fn fn) {   // k_sg_gcn's forms, named once: fn(kernel, BN, ALLK)
+    return dispatch_bools([&](auto F) {
+        constexpr bool H = decltype(F)::value;
+        if (bn == 256) return fn(k_sg_gcn<256, false, H>, 256, false);
+        if (bn == 128) return fn(k_sg_gcn<128, false, H>, 128, false);
+        return allk ? fn(k_sg_gcn<64, true, H>, 64, true) : fn(k_sg_gcn<64, false, H>, 64, false);
+    }, f16);
 }
 hipError_t launch_sg_gcn(const GemmX3Args& g, int V, int KP, unsigned slot_k, const int* sl_v, const float* sl_a, int cap, bool per_block_barrier, hipStream_t s) {   // cap: widest tile (tools / tests)
-    if (g.N >= 256 && cap >= 256 && gcn_lds_bytes(256, V) <= 160 * 1024) return gcn_launch<256, false>(g, V, KP, slot_k, sl_v, sl_a, s);
-    if (g.N >= 128 && cap >= 128 && gcn_lds_bytes(128, V) <= 160 * 1024) return gcn_launch<128, false>(g, V, KP, slot_k, sl_v, sl_a, s);
-    if (!per_block_barrier && KP <= 4 && gcn_lds_bytes(64, V, true) <= 160 * 1024) return gcn_launch<64, true>(g, V, KP, slot_k, sl_v, sl_a, s);
-    return gcn_launch<64, false>(g, V, KP, slot_k, sl_v, sl_a, s);
+    const int bn = g.N >= 256 && cap >= 256 && gcn_lds_bytes(256, V) <= 160 * 1024 ? 256 : g.N >= 128 && cap >= 128 && gcn_lds_bytes(128, V) <= 160 * 1024 ? 128 : 64;
+    const bool allk = bn == 64 && !per_block_barrier && KP <= 4 && gcn_lds_bytes(64, V, true) <= 160 * 1024;
+    return gcn_form(bn, allk, g.f16 != 0, [&](auto kern, int BN, bool ALLK) {
+        const int nbx = (g.N + BN - 1) / BN, ntiles = nbx * ((g.M + 255) / 256);
+        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, sg_cu_count())), dim3(512), gcn_lds_bytes(BN, V, ALLK), s, g, nbx, ntiles, V, KP, slot_k, sl_v, sl_a);
+        return hipGetLastError();
+    });
 }
 hipError_t configure_sg_gcn() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<256, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<64, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<64, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<128, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sg_gcn<256, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < 8 && e == hipSuccess; ++m)               // (64, 64 ALLK, 128, 256) x arithmetic
+        e = gcn_form((m & 3) == 3 ? 256 : (m & 3) == 2 ? 128 : 64, (m & 3) == 1, m & 4, [](auto kern, int, bool) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
     return e;
 }
 

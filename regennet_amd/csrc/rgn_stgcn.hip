@@ -13,7 +13,7 @@
 //                                                                            next block's planes - polyphase (even | odd frames) in front of a
 //   (stride 2: taps on the even / odd frame regions, + the 1x1 shortcut)    k_sg_tconv_s2 stride-2 block, which then runs at the output rate
 //
-// The kernels live in rgn_sg_kernels.hip; this file holds the load-time folding, the plane geometry and the block loop, plus the small kernels around
+// The kernels live in rgn_sg_kernels.hip (what they share with each other and with k_gemm_x3: rgn_dma_gemm.h); this file holds the load-time folding, the plane geometry and the block loop, plus the small kernels around
 // them (input layout + data_bn, pad zeroing, pooling) and the forms the fused kernels replaced (k_sg_agg + row-shifted k_gemm_x3 + k_sg_post), which
 // still serve graphs and shapes the fused kernels do not take and can be selected per handle (rgn_stgcn_set_option; every form is tested).
 //
@@ -438,19 +438,9 @@ int sg_upload(rgn_stgcn_ctx* c, float** p, const std::vector<float>& v) {
     return RGN_OK;
 }
 inline size_t up32(size_t x) { return (x + 31) / 32 * 32; }
-inline uint16_t sg_f2bf(float f) {   // round-to-nearest-even fp32 -> bf16 bits
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float sg_bf2f(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
+// physical rows of a block's planes for `seqs` sequences of T frames: T + 4 frames each - or, in front of a stride-2 block, the POLYPHASE form: two regions
+// (even / odd frames) of ceil(T / 2) + 4 frames per sequence each, so that the block's temporal convolution runs at the OUTPUT rate
+inline size_t sg_plane_rows(size_t seqs, int T, bool poly, int V) { return seqs * (poly ? 2 * ((size_t)(T + 1) / 2 + SG_PAD) : (size_t)T + SG_PAD) * V; }
 // W [N][Kp] (row-major fp32, Kp % 32 == 0) -> split-bf16 weight planes [Kp/32][N][32] (the B operand layout of k_gemm_x3)
 // ... and, with `f16`, the same layout as one IEEE fp16 plane (rne); a weight beyond the fp16 range is recorded in c->f16_refused under `name`
 int sg_upload_planes(rgn_stgcn_ctx* c, const std::vector<float>& W, int N, int Kp, __bf16** hi, __bf16** lo, __bf16** f16 = nullptr, const char* name = "") {
@@ -459,8 +449,8 @@ int sg_upload_planes(rgn_stgcn_ctx* c, const std::vector<float>& W, int N, int K
         for (int k = 0; k < Kp; ++k) {
             const float v = W[(size_t)n * Kp + k];
             const size_t o = plane_off(N, n, k);
-            h[o] = sg_f2bf(v);
-            l[o] = sg_f2bf(v - sg_bf2f(h[o]));
+            h[o] = f2bf(v);
+            l[o] = f2bf(v - bf2f(h[o]));
             if (f16) {
                 if (!(std::fabs(v) < 6.0e4f) && c->f16_refused.empty()) c->f16_refused = std::string(name) + " (folded with its BatchNorm) holds " + std::to_string(v);
                 const _Float16 hv = (_Float16)v;
@@ -758,9 +748,7 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
         c->guard = (size_t)SG_PAD * V;
         size_t xmax = 0, zmax = 0, gmax = 0, cmax = 0;     // elements per plane / fp32 tensor
         {
-            // physical rows of a block's input: sequences of T + 4 frames - or, for a stride-2 block, the polyphase form: two regions (even / odd frames)
-            // of ceil(T / 2) + 4 frames per sequence each, so that its temporal convolution runs at the OUTPUT rate
-            auto phys = [&](int T, bool poly) { return (size_t)c->cfg.max_batch * M * (poly ? 2 * ((size_t)(T + 1) / 2 + SG_PAD) : (size_t)T + SG_PAD) * V; };
+            auto phys = [&](int T, bool poly) { return sg_plane_rows((size_t)c->cfg.max_batch * M, T, poly, V); };
             int T = c->cfg.num_frames;
             for (int i = 0; i < 10; ++i) {
                 const SgBlock& b = c->blocks[i];
@@ -843,7 +831,7 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
                                                     " (this graph / shape, or an SG_NO_* switch)");
         };
         __bf16 *(*x)[2] = &c->xa, *(*xn)[2] = &c->xb;
-        auto phys = [&](int Tf, bool poly) { return (size_t)NM * (poly ? 2 * ((size_t)(Tf + 1) / 2 + SG_PAD) : (size_t)Tf + SG_PAD) * V; };
+        auto phys = [&](int Tf, bool poly) { return sg_plane_rows((size_t)NM, Tf, poly, V); };
         for (int i = 0; i < 10; ++i) {
             const SgBlock& b = c->blocks[i];
             // a stride-2 block reads POLYPHASE planes (written so by the block in front of it): region E = the even frames of every sequence, region O = the odd
@@ -863,8 +851,7 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
             g1.f16 = gf16 ? 1 : 0;
             if (fused) SG_HIP(c, launch_sg_gcn(g1, V, K, b.slot_k, b.sl_v, b.sl_a, gcn_bn, gcn_step32, s));   // z is formed in registers, fragment by fragment
             else if (i == 0 && !no_block0 && b.ci == 6 && K == 3 && b.co == 64 && b.W1s) {
-                if (f16) hipLaunchKernelGGL((k_sg_block0<6, 3, 64, true>), blocks1d(rows), dim3(256), 0, s, xp, gp, b.nz_ptr, b.nz_v, b.nz_a, b.W1s, b.b1, rows, V);
-                else hipLaunchKernelGGL((k_sg_block0<6, 3, 64, false>), blocks1d(rows), dim3(256), 0, s, xp, gp, b.nz_ptr, b.nz_v, b.nz_a, b.W1s, b.b1, rows, V);
+                dispatch_bools([&](auto F) { hipLaunchKernelGGL((k_sg_block0<6, 3, 64, decltype(F)::value>), blocks1d(rows), dim3(256), 0, s, xp, gp, b.nz_ptr, b.nz_v, b.nz_a, b.W1s, b.b1, rows, V); }, f16);
             } else {
                 if (b.ci % 32 == 0) hipLaunchKernelGGL(k_sg_agg, dim3((unsigned)((rows * 4 + 255) / 256), (unsigned)(K * (b.ci / 32))), dim3(256), 0, s, xp, zp, b.nz_ptr, b.nz_v, b.nz_a, rows, V, K, b.ci);
                 else if (b.ci == 6 && K == 3) hipLaunchKernelGGL((k_sg_agg_small_t<6, 3>), blocks1d(rows), dim3(256), 0, s, xp, zp, b.nz_ptr, b.nz_v, b.nz_a, rows, V);
@@ -933,8 +920,7 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
             std::swap(x, xn);
             T = To;
         }
-        if (f16) hipLaunchKernelGGL(k_sg_pool<true>, dim3(N), dim3(256), 0, s, planes(*x, (size_t)NM * (T + SG_PAD) * V), c->pooled, M, T, V, 256);
-        else hipLaunchKernelGGL(k_sg_pool<false>, dim3(N), dim3(256), 0, s, planes(*x, (size_t)NM * (T + SG_PAD) * V), c->pooled, M, T, V, 256);
+        dispatch_bools([&](auto F) { hipLaunchKernelGGL(k_sg_pool<decltype(F)::value>, dim3(N), dim3(256), 0, s, planes(*x, phys(T, false)), c->pooled, M, T, V, 256); }, f16);
         if (features) SG_HIP(c, hipMemcpyAsync(features, c->pooled, (size_t)N * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (yhat) {
             GemmArgs gf = sg_gemm(c->pooled, 256, c->Wf, 256, 256, c->bf, yhat, c->cfg.num_class, N, c->cfg.num_class);
