@@ -250,6 +250,34 @@ RGN_API int rgn_rot2xyz(rgn_handle h, const float* x_dev, const uint8_t* mask_de
                         const float* glob_rot_host /*[3] or NULL*/, float* xyz_dev, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/,
                         void* stream);
 
+/* Replaces the loss arithmetic of GaussianDiffusion.training_losses (diffusion/gaussian_diffusion.py:1313-1391, with masked_l2 :213-225 and the
+ * three rot2xyz passes of :1254-1258) for a model output that is already on the device: one row of seven terms per motion,
+ *   terms_dev fp32 [B, 7] = rot_mse (:1313), rcxyz_mse (:1317-1321), vel_mse (:1357-1362), fc (:1329-1343), orient (:1367-1377), body (:1378-1383),
+ *           transl (:1384-1391)
+ * each sum(mask (a - b)^2) / (sum(mask) n_entries) with n_entries = a.shape[1] * a.shape[2] of the tensor the reference hands to masked_l2 - so
+ * orient and transl ([B,1,T]) divide by T and body ([B,J,T]) by J T on top of the frame count - and the velocity terms under mask[..., 1:]. A motion
+ * whose mask leaves no frame (no frame pair) divides 0 by 0 and gets NaN, as in the reference. All seven are always computed; with RGN_LOSS_FC
+ * unset the fc column is 0 and the foot joints are not looked at.
+ *   target_dev, output_dev, cmotion_dev fp32 [B, R, 6, T], rot6d rows, R = J + 1: J rotation rows and one last row that the chain and vel_mse leave out
+ *   mask_dev uint8 [B, T]: the storage of y['mask'][:, 0, 0, :]
+ *   rest_joints_host [J, 3], parents_host [J]: the skeleton, as for rgn_rot2xyz (xyz = rot2xyz(sample, mask=None, vertstrans=False): every frame,
+ *           joint 0 subtracted); foot_joints_host [4]: the joints of the fc term (the reference: 7, 10, 8, 11)
+ *   transl_row: the row whose channels 0..2 the transl term compares (the reference: 55); vel_threshold: ground-truth foot speed per frame up to
+ *           which a foot counts as planted
+ * orient's angle is the norm of the reference's matrix_to_axis_angle (utils/rotation_conversions.py:98-120, :482-510), not an acos of the trace.
+ * Arithmetic: fp64 from the fp32 inputs, each term rounded to fp32 once (an fp32 evaluation of the reference differs from it by that evaluation's own
+ * rounding). One workgroup per motion, sums in a fixed order: a motion's row does not depend on the batch and is the same on every run. The call keeps no
+ * state and can be captured into a graph.
+ * The arguments are checked before the handle or the device is touched - RGN_ERR_INVALID_ARG for a null pointer, B or T < 1, J outside [1, 64], a
+ * parent table that is not a tree in index order, R != J + 1, a foot joint outside [0, J), transl_row outside [0, R), an unknown flag - with text in
+ * rgn_last_error(h), or rgn_last_error(NULL) when h is NULL (which is itself RGN_ERR_INVALID_ARG once the other arguments have passed). */
+enum { RGN_LOSS_FC = 1 };
+enum { RGN_LOSS_ROT_MSE = 0, RGN_LOSS_RCXYZ_MSE, RGN_LOSS_VEL_MSE, RGN_LOSS_FC_TERM, RGN_LOSS_ORIENT, RGN_LOSS_BODY, RGN_LOSS_TRANSL, RGN_LOSS_NTERMS };
+RGN_API int rgn_loss_terms(rgn_handle h, const float* target_dev, const float* output_dev, const float* cmotion_dev, const uint8_t* mask_dev,
+                           int32_t B, int32_t T, int32_t R, int32_t J, const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/,
+                           const int32_t* foot_joints_host /*[4]*/, int32_t transl_row, float vel_threshold, int32_t flags /*RGN_LOSS_FC*/,
+                           float* terms_dev /*[B,7]*/, void* stream);
+
 /* ---- Mesh vertices: jointstype='vertices' ----
  * Replaces the body layer the reference keeps in Rotation2xyz.smpl_model / Rotation2xyz_x.smpl_model (model/rotation2xyz.py:14-15 / :161-162, a CPU
  * smplx layer over a licensed model file): the mesh data of a BODY FILE (tools/make_skeleton.py --mesh), resident on `device`.

@@ -24,6 +24,8 @@ FLAG_UNCOND, FLAG_GUIDED = 1, 2
 POSE_REP = {"rot6d": 0, "rotvec": 1, "rotquat": 2, "rotmat": 3}     # RGN_POSE_*; channels per rotation below
 POSE_REP_CHANNELS = {"rot6d": 6, "rotvec": 3, "rotquat": 4, "rotmat": 9}
 R2X_TRANSLATION, R2X_GLOB, R2X_VERTSTRANS = 1, 2, 4
+LOSS_FC = 1                                                          # RGN_LOSS_FC
+LOSS_TERMS = ("rot_mse", "rcxyz_mse", "vel_mse", "fc", "orient", "body", "transl")      # the columns of rgn_loss_terms (RGN_LOSS_*)
 
 
 class RgnError(RuntimeError):
@@ -73,6 +75,7 @@ SYMBOLS = {
     "rgn_rot6d_to_matrix": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "rgn_gaussian_filter1d": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "rgn_rot2xyz": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rgn_loss_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp]),
     "rgn_profile_enable": (C.c_int, [_vp, _i32]),
     "rgn_profile_query": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "rgn_profile_bracket_overhead": (C.c_int, [_vp, C.POINTER(C.c_double)]),
@@ -325,6 +328,20 @@ class Engine:
         self._ck(self.lib.rgn_rot2xyz(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), len(pa), rj.ctypes.data_as(C.c_void_p),
                                       pa.ctypes.data_as(C.c_void_p), int(pose_rep), int(num_person), int(flags),
                                       None if gr is None else gr.ctypes.data_as(C.c_void_p), _ptr(xyz), _ptr(rotmat), C.c_void_p(stream)))
+
+    def loss_terms(self, target, output, cmotion, mask, rest_joints, parents, foot_joints, transl_row, vel_threshold, flags, terms, stream):
+        """rgn_loss_terms: target / output / cmotion fp32 [B, J + 1, 6, T] and mask (bool / uint8 [B, T]), contiguous on the engine's device -> terms
+        fp32 [B, 7] (columns: LOSS_TERMS); rest_joints [J, 3], parents [J] and foot_joints [4] are host arrays."""
+        rj = np.ascontiguousarray(rest_joints, dtype=np.float32)
+        pa = np.ascontiguousarray(parents, dtype=np.int32)
+        fj = np.ascontiguousarray(foot_joints, dtype=np.int32).reshape(4)
+        B, R, F, T = target.shape
+        assert rj.shape == (len(pa), 3) and F == 6 and tuple(output.shape) == tuple(cmotion.shape) == (B, R, F, T)
+        assert tuple(mask.shape) == (B, T) and mask.element_size() == 1 and tuple(terms.shape) == (B, len(LOSS_TERMS))
+        assert all(a.is_contiguous() for a in (target, output, cmotion, mask, terms))
+        self._ck(self.lib.rgn_loss_terms(self.h, _ptr(target), _ptr(output), _ptr(cmotion), _ptr(mask), int(B), int(T), int(R), len(pa),
+                                         rj.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p), fj.ctypes.data_as(C.c_void_p), int(transl_row),
+                                         float(vel_threshold), int(flags), _ptr(terms), C.c_void_p(stream)))
 
     def profile_enable(self, on):
         self._ck(self.lib.rgn_profile_enable(self.h, int(bool(on))))

@@ -539,6 +539,42 @@ int rgn_rot2xyz(rgn_handle h, const float* x, const uint8_t* mask, int32_t B, in
     });
 }
 
+int rgn_loss_terms(rgn_handle h, const float* target, const float* output, const float* cmotion, const uint8_t* mask, int32_t B, int32_t T, int32_t R,
+                   int32_t J, const float* rest_joints, const int32_t* parents, const int32_t* foot_joints, int32_t transl_row, float vel_threshold,
+                   int32_t flags, float* terms, void* stream) {
+    return rgn_guard(h, "rgn_loss_terms", [&]() -> int {
+        // the arguments first, the handle after them: what is wrong with a call can be asked without a device (text: rgn_last_error(NULL))
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_loss_terms: " + m);
+            g_create_error = "rgn_loss_terms: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        if (!target || !output || !cmotion || !mask || !terms || !rest_joints || !parents || !foot_joints)
+            return bad("null target, output, cmotion, mask, terms, rest_joints, parents or foot_joints");
+        if (B < 1 || T < 1) return bad("B < 1 or T < 1");
+        if (J < 1 || J > FK_MAX_JOINTS) return bad("J outside [1, 64]");
+        FkSkel sk;
+        int at = -1;
+        if (const char* why = fk_build_skel(J, rest_joints, parents, sk, at))
+            return bad(at < 0 ? std::string(why) : "parents[" + std::to_string(at) + "] outside [0, " + std::to_string(at) + ")");
+        if (R != J + 1) return bad("R = " + std::to_string(R) + " rows, J + 1 = " + std::to_string(J + 1) + " expected (J rotation rows and the translation row)");
+        for (int k = 0; k < 4; ++k)
+            if (foot_joints[k] < 0 || foot_joints[k] >= J)
+                return bad("foot_joints[" + std::to_string(k) + "] = " + std::to_string(foot_joints[k]) + " outside [0, " + std::to_string(J) + ")");
+        if (transl_row < 0 || transl_row >= R) return bad("transl_row " + std::to_string(transl_row) + " outside [0, " + std::to_string(R) + ")");
+        if (flags & ~RGN_LOSS_FC) return bad("unknown flag");
+        if (!h) return bad("null handle");
+        RGN_HIP(h, hipSetDevice(h->cfg.device));
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_loss_terms: weights not finalized");
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = h->stream;
+        int rc = stream_enter(h, us);
+        if (rc) return rc;
+        const int foot[4] = {foot_joints[0], foot_joints[1], foot_joints[2], foot_joints[3]};
+        RGN_LAUNCH(h, KC_MISC, s, launch_loss_terms(target, output, cmotion, mask, terms, B, T, J, foot, transl_row, vel_threshold, flags, sk, s));
+        return stream_exit(h, us);
+    });
+}
+
 int rgn_profile_enable(rgn_handle h, int32_t on) {
     return rgn_guard(h, "rgn_profile_enable", [&]() -> int {
         if (!h) return RGN_ERR_INVALID_ARG;

@@ -104,32 +104,34 @@ __device__ __forceinline__ void fk_local_matrices(float* g, const FkFrame& fr, l
 }
 
 // phase 2: the chain, depth by depth (a barrier per depth). Joint i's transform replaces its local matrix in g[i] (planes 0..8 rotation, 9..11 posed
-// position); emit(i, pos, gi) runs on the thread that formed it, gi = g[i] + this lane.
-template <class Emit>
-__device__ __forceinline__ void fk_chain(float* g, const FkSkel& sk, int fl, int w, Emit&& emit) {
+// position); emit(i, pos, gi) runs on the thread that formed it, gi = g[i] + this lane. The image's scalar type follows g and its tile width is FRAMES
+// (13 planes of FRAMES per joint, FK_THREADS / FRAMES workers): k_fk and k_lbs_chain run float x FK_FRAMES, k_loss_terms (rgn_loss.hip) double x 16.
+template <int FRAMES = FK_FRAMES, class S, class Emit>
+__device__ __forceinline__ void fk_chain(S* g, const FkSkel& sk, int fl, int w, Emit&& emit) {
+    constexpr int JSTRIDE = 13 * FRAMES, WORKERS = FK_THREADS / FRAMES;
     for (int l = 0; l < sk.nlevels; ++l) {
-        for (int q = sk.level[l] + w; q < sk.level[l + 1]; q += FK_WORKERS) {
+        for (int q = sk.level[l] + w; q < sk.level[l + 1]; q += WORKERS) {
             const int i = sk.order[q], par = sk.parent[i];
-            float* gi = g + i * FK_JSTRIDE + fl;
-            float pos[3];
+            S* gi = g + i * JSTRIDE + fl;
+            S pos[3];
             if (par < 0) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) pos[c] = sk.rel[0][c];
             } else {
-                const float* gp = g + par * FK_JSTRIDE + fl;
-                float a[9], m[9];
+                const S* gp = g + par * JSTRIDE + fl;
+                S a[9], m[9];
 #pragma unroll
-                for (int k = 0; k < 9; ++k) { a[k] = gp[k * FK_FRAMES]; m[k] = gi[k * FK_FRAMES]; }
-                const float r0 = sk.rel[i][0], r1 = sk.rel[i][1], r2 = sk.rel[i][2];
+                for (int k = 0; k < 9; ++k) { a[k] = gp[k * FRAMES]; m[k] = gi[k * FRAMES]; }
+                const S r0 = sk.rel[i][0], r1 = sk.rel[i][1], r2 = sk.rel[i][2];
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {       // the 4x4 product of the chain, row r: rotation part and translation column
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) gi[(3 * r + c) * FK_FRAMES] = a[3 * r] * m[c] + a[3 * r + 1] * m[3 + c] + a[3 * r + 2] * m[6 + c];
-                    pos[r] = a[3 * r] * r0 + a[3 * r + 1] * r1 + a[3 * r + 2] * r2 + gp[(9 + r) * FK_FRAMES];
+                    for (int c = 0; c < 3; ++c) gi[(3 * r + c) * FRAMES] = a[3 * r] * m[c] + a[3 * r + 1] * m[3 + c] + a[3 * r + 2] * m[6 + c];
+                    pos[r] = a[3 * r] * r0 + a[3 * r + 1] * r1 + a[3 * r + 2] * r2 + gp[(9 + r) * FRAMES];
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) gi[(9 + c) * FK_FRAMES] = pos[c];
+            for (int c = 0; c < 3; ++c) gi[(9 + c) * FRAMES] = pos[c];
             emit(i, pos, gi);
         }
         __syncthreads();

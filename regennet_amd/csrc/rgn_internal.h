@@ -370,6 +370,11 @@ struct FkSkel {
 // x [B, R, C*P, T] -> xyz [B, J, 3*P, T] (+ rotmat [B,P,T,J,3,3] when not null); pose_rep / flags: RGN_POSE_* / RGN_R2X_* (regennet_hip.h)
 hipError_t launch_fk(const float* x, const uint8_t* mask, float* xyz, float* rotmat, int B, int T, int P, int J, int pose_rep, int flags,
                      const FkSkel& sk, hipStream_t s);
+// ---- rgn_loss.hip: the seven terms of training_losses, one workgroup per motion (rgn_loss_terms). target / output / cmotion [B, J + 1, 6, T],
+// mask [B, T] -> terms [B, 7]; foot[4]: the joints of the fc term; flags: RGN_LOSS_*
+size_t loss_lds_bytes(int J);
+hipError_t launch_loss_terms(const float* target, const float* output, const float* cmotion, const uint8_t* mask, float* terms, int B, int T, int J,
+                             const int* foot, int transl_row, float vel_threshold, int flags, const FkSkel& sk, hipStream_t s);
 // The skeleton argument checks of rgn_rot2xyz / rgn_rot2verts and the table their kernels take by value. nullptr when `sk` was filled, else the text of
 // the complaint (without the entry point's name); `at` receives the offending joint for the parent-table complaint, else -1. Host only.
 inline const char* fk_build_skel(int J, const float* rest_joints, const int32_t* parents, FkSkel& sk, int& at) {

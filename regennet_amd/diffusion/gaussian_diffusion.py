@@ -1,5 +1,6 @@
 """Host side of the diffusion sampler — mirror of the reference's `diffusion/gaussian_diffusion.py`
-(sampling half only; training losses, PLMS, classifier guidance are out of scope).
+(the sampling half, and `training_losses` as an EVALUATION of the objective: its terms for given motions, no backward; PLMS and classifier
+guidance are out of scope).
 
 The schedule tables are fp64 NumPy exactly as the reference builds them (gaussian_diffusion.py:172-209);
 the step loop itself runs inside libregennet_hip.so (rgn_sample_range): per step one denoiser evaluation
@@ -75,8 +76,8 @@ def _engine_of(model):
 
 
 class GaussianDiffusion:
-    """Sampling utilities. Constructor keywords follow gaussian_diffusion.py:121-143 (loss weights are accepted
-    and stored; they only matter for training, which is out of scope)."""
+    """Sampling utilities. Constructor keywords follow gaussian_diffusion.py:121-143; the loss weights (lambda_*, vel_threshold, num_person,
+    body_model) are stored and read by training_losses."""
 
     def __init__(self, *, betas, model_mean_type, model_var_type, loss_type, rescale_timesteps=False, **loss_kwargs):
         self.model_mean_type = model_mean_type
@@ -139,6 +140,96 @@ class GaussianDiffusion:
         assert noise.shape == x_start.shape
         return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
+
+    # ---- the training objective, evaluated (gaussian_diffusion.py:213-225, :1239-1403) ---------------
+    FC_DATASETS = ("humanact12", "uestc", "ntu", "chi3d")       # where the foot-contact term applies (:1331)
+    LOSS_ROWS, LOSS_TRANSL_ROW = 56, 55                         # 55 joints + the translation row: what :1333 and :1386 hard-code
+    LOSS_FOOT_JOINTS = (7, 10, 8, 11)                           # l_ankle, l_foot, r_ankle, r_foot in the reference's order (:1333-1334)
+
+    def masked_l2(self, a, b, mask):
+        """gaussian_diffusion.py:213-225: sum(mask (a - b)^2) / (sum(mask) * a.shape[1] * a.shape[2]) per motion; an empty mask gives 0 / 0."""
+        loss = ((a - b) ** 2 * mask.float()).flatten(1).sum(1)
+        return loss / (mask.flatten(1).sum(1) * (a.shape[1] * a.shape[2]))
+
+    def _lambda(self, name):
+        return float(getattr(self, name, 0.0) or 0.0)
+
+    def _loss_dict(self, terms, dataset=None):
+        """terms [B, 7] (the columns of rgn_loss_terms) -> the reference's dict: rot_mse always, every other term only when its weight is
+        positive (fc: only for a dataset of FC_DATASETS, :1331), and `loss` weighted as :1393-1399."""
+        from .. import _lib
+        col = {k: terms[:, i] for i, k in enumerate(_lib.LOSS_TERMS)}
+        name = dataset if isinstance(dataset, str) else getattr(dataset, "dataname", None)
+        out = {"rot_mse": col["rot_mse"]}
+        if self._lambda("lambda_rcxyz") > 0.0:
+            out["rcxyz_mse"] = col["rcxyz_mse"]
+        if self._lambda("lambda_fc") > 0.0 and getattr(self, "data_rep", "rot6d") == "rot6d" and name in self.FC_DATASETS:
+            out["fc"] = col["fc"]
+        if self._lambda("lambda_vel") > 0.0:
+            out["vel_mse"] = col["vel_mse"]
+        for k in ("orient", "body", "transl"):
+            if self._lambda("lambda_" + k) > 0.0:
+                out[k] = col[k]
+        out["loss"] = out["rot_mse"] + 0.0 + \
+            (self._lambda("lambda_vel") * out.get("vel_mse", 0.0)) + \
+            (self._lambda("lambda_rcxyz") * out.get("rcxyz_mse", 0.0)) + \
+            (self._lambda("lambda_fc") * out.get("fc", 0.0)) + \
+            (self._lambda("lambda_orient") * out.get("orient", 0.0)) + \
+            (self._lambda("lambda_body") * out.get("body", 0.0)) + \
+            (self._lambda("lambda_transl") * out.get("transl", 0.0))
+        return out
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, dataset=None):
+        """gaussian_diffusion.py:1239-1403 as an evaluation: q_sample, ONE denoiser evaluation (the model's ordinary forward) and one kernel
+        (rgn_loss_terms) that forms all seven terms from the output, x_start and y['cmotion'] - the three rot2xyz passes of :1254-1258 happen
+        inside it and no joint tensor is written. Returns the reference's dict of [B] tensors; nothing is differentiable.
+        `model`: a CMDM in eval mode holding a skeleton (set_skeleton), bare or as the `.module` of a wrapper, as in the reference's
+        `enc = model.model.module`. `dataset`: an object with `.dataname`, or the name itself; the fc term needs one of FC_DATASETS."""
+        if self.loss_type != LossType.MSE:
+            raise NotImplementedError(f"{self.loss_type}: only LossType.MSE is evaluated (what the reference's factory sets, model_util.py:85)")
+        if self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE):
+            raise NotImplementedError("learned variances are not produced by CMDM (learn_sigma=False, model_util.py:81)")
+        if self._lambda("lambda_vel_rcxyz") > 0.0:
+            raise NotImplementedError("lambda_vel_rcxyz is never set by the reference's factory (model_util.py:95-117) and is not evaluated")
+        if self.model_mean_type not in (ModelMeanType.START_X, ModelMeanType.EPSILON):
+            raise NotImplementedError("the target of ModelMeanType.PREVIOUS_X is not evaluated: CMDM predicts x_start (model_util.py:77)")
+        enc = getattr(model, "model", model) if hasattr(model, "timestep_map") else model      # SpacedDiffusion's wrapper
+        enc = getattr(enc, "module", enc)
+        _engine_of(enc)
+        if model_kwargs is None or "y" not in model_kwargs:
+            raise KeyError("model_kwargs['y'] with 'mask' and 'cmotion' is required (gaussian_diffusion.py:1253, :1365)")
+        y = model_kwargs["y"]
+        mask, cmotion = y["mask"], y["cmotion"]
+        B, R, F, T = x_start.shape
+        if R != self.LOSS_ROWS or F != 6:
+            raise ValueError(f"x_start {tuple(x_start.shape)}: the interaction terms read the translation from row 55 and the feet from joints 7, 8, 10 "
+                             f"and 11 of a [B, {self.LOSS_ROWS}, 6, T] rot6d motion (gaussian_diffusion.py:1333, :1386)")
+        if int(getattr(self, "num_person", 1)) != 1 or getattr(self, "data_rep", "rot6d") != "rot6d" or getattr(enc, "pose_rep", "rot6d") != "rot6d" \
+                or not (getattr(enc, "glob", True) and getattr(enc, "translation", True)):
+            raise NotImplementedError("training_losses is evaluated for one person in rot6d with global rotation and translation row (model_util.py:66-72)")
+        from ..model.rotation2xyz import SKELETON_JOINTSTYPES
+        if getattr(self, "body_model", "smpl") not in SKELETON_JOINTSTYPES:
+            raise NotImplementedError(f"body_model={getattr(self, 'body_model', None)!r}: the joint terms use the skeleton's own joints {SKELETON_JOINTSTYPES}")
+        r2x = enc.rot2xyz
+        if not hasattr(r2x, "skeleton"):
+            r2x(x=None)                                             # raises the model's "needs a skeleton" error
+        if noise is None:
+            noise = th.randn_like(x_start)
+        x_t = self.q_sample(x_start, t, noise=noise)
+        with th.no_grad():
+            model_output = model(x_t, self._scale_timesteps(t), **model_kwargs)
+        target = x_start if self.model_mean_type == ModelMeanType.START_X else noise
+        assert model_output.shape == target.shape == x_start.shape
+        from .. import _lib
+        from ..utils import dist_util
+        eng = enc._engine
+        dev = model_output.device
+        f32 = lambda a: a.detach().to(device=dev, dtype=th.float32).contiguous()      # noqa: E731
+        mk = mask.to(dev).bool().expand(B, 1, 1, T)[:, 0, 0, :].contiguous()
+        terms = th.empty((B, len(_lib.LOSS_TERMS)), device=dev, dtype=th.float32)
+        eng.loss_terms(f32(target), f32(model_output), f32(cmotion), mk, r2x.rest_joints(), r2x.skeleton["parents"], self.LOSS_FOOT_JOINTS, self.LOSS_TRANSL_ROW,
+                       float(getattr(self, "vel_threshold", 0.01)), _lib.LOSS_FC, terms, dist_util.stream_handle(dev))
+        return self._loss_dict(terms.to(x_start.device), dataset)
 
     # ---- per-call API (one denoiser evaluation on the HIP path + torch elementwise glue) ----------
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):

@@ -62,6 +62,10 @@ class SpacedDiffusion(GaussianDiffusion):
         return model if isinstance(model, _WrappedModel) else _WrappedModel(
             model, self.timestep_map, self.rescale_timesteps, self.original_num_steps)
 
+    def training_losses(self, model, *args, **kwargs):
+        # respace.py:94-97: t indexes the spaced schedule, the denoiser sees the original timesteps
+        return super().training_losses(self._wrap_model(model), *args, **kwargs)
+
     def _scale_timesteps(self, t):
         return t
 

@@ -90,6 +90,12 @@ def add_edit_options(p):
     g.add_argument("--input_motions", default="", type=str, help=".npy [N, njoints, nfeats, T]: the motions to edit (--synthetic: synthetic ones)")
 
 
+def add_score_options(p):
+    """regennet_amd.eval.score: the grid of timesteps and where the table goes (the weights are the model group's lambda_* / --vel_threshold)."""
+    g = p.add_argument_group("score")
+    g.add_argument("--t_grid", default=10, type=int, help="score every motion at this many evenly spaced timesteps of the (respaced) schedule")
+
+
 def _group_keys(parser, args, title):
     for grp in parser._action_groups:
         if grp.title == title:
@@ -97,7 +103,7 @@ def _group_keys(parser, args, title):
     raise ValueError("group_name was not found.")
 
 
-def cgenerate_args(argv=None, edit=False):
+def cgenerate_args(argv=None, edit=False, score=False):
     p = argparse.ArgumentParser()
     add_base_options(p)
     add_data_options(p)
@@ -107,6 +113,8 @@ def cgenerate_args(argv=None, edit=False):
     add_diffusion_options(p)
     if edit:
         add_edit_options(p)
+    if score:
+        add_score_options(p)
     args = p.parse_args(argv)
     if args.model_path:
         args_path = os.path.join(os.path.dirname(args.model_path), "args.json")
@@ -128,3 +136,23 @@ def cgenerate_args(argv=None, edit=False):
 def edit_args(argv=None):
     """The reference's edit_args (parser_util.py:259-264) on this CLI's flag set: cgenerate's groups + the edit group."""
     return cgenerate_args(argv, edit=True)
+
+
+LOSS_FLAGS = ("lambda_rcxyz", "lambda_vel", "lambda_fc", "lambda_orient", "lambda_body", "lambda_transl", "vel_threshold")
+
+
+def score_args(argv=None):
+    """cgenerate's flag set + the score group. The weights of the objective come from args.json beside --model_path (what the checkpoint was
+    trained with); without one orient, body and transl stand at 1 like the reference's training defaults (parser_util.py:131-136). A weight
+    given on the command line wins over both."""
+    args = cgenerate_args(argv, score=True)
+    if not args.model_path:
+        args.lambda_orient = args.lambda_body = args.lambda_transl = 1.0
+    given = argparse.ArgumentParser(add_help=False, argument_default=argparse.SUPPRESS)
+    for name in LOSS_FLAGS:
+        given.add_argument("--" + name, type=float)
+    for k, v in vars(given.parse_known_args(argv)[0]).items():
+        setattr(args, k, v)
+    if args.t_grid < 1:
+        raise SystemExit("--t_grid must be at least 1")
+    return args
