@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "rgn_internal.h"
 #include "rgn_layout.h"
 
 #define RGN_AS1 __attribute__((address_space(1)))   // global
@@ -97,6 +98,13 @@ __device__ __forceinline__ void split_bf16(const float (&v)[8], bf16x8& hi, bf16
         hi[j] = (__bf16)v[j];
         lo[j] = (__bf16)(v[j] - (float)hi[j]);
     }
+}
+// ... and one element (row, col) into split planes of the K32-blocked layout (lo may be absent)
+__device__ __forceinline__ void plane_put(const Planes& p, int row, int col, float v) {
+    const size_t o = plane_off(p.rows, row, col);
+    const __bf16 h = (__bf16)v;
+    p.hi[o] = h;
+    if (p.lo) p.lo[o] = (__bf16)(v - (float)h);
 }
 
 // ---- GELU (erf form) and erf ----

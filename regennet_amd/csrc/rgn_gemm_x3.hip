@@ -100,7 +100,7 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const unsigned m = (unsigned)(mb + dg_pair_row(i, odd));
                         // m / Tq, m % Tq (exact: m*Tq < 2^32); Tq = 1 has no 32-bit magic (floor(2^32 / 1) + 1 wraps to 1): the quotient is m itself
                         const unsigned bb = g.Tq == 1 ? m : __umulhi(m, g.tq_magic), tt = m - bb * (unsigned)g.Tq;
-                        dg_store_pair<false, true>(ph, pl, (((size_t)bb * g.H + hd) * g.Tqp + tt) * g.dh + (c & ~1), c0, c1);
+                        dg_store_pair<false, true>(ph, pl, attn_slab_off(g.H, g.Tqp, g.dh, bb, hd, tt, c & ~1), c0, c1);
                     }
                 } else {                                              // edge blocks
                     const float sc = which == 0 ? g.qscale : 1.0f;
@@ -109,10 +109,9 @@ __device__ __forceinline__ void x3_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                         const int m = mb + mfma32_row(i, 0);
                         if (!n_ok || m >= g.M) continue;
                         const int bb = m / g.Tq, tt = m - bb * g.Tq;
-                        const size_t sl = (size_t)bb * g.H + hd;
                         const float x = r[i] * sc;
                         const __bf16 h = (__bf16)x;
-                        const size_t o = (sl * g.Tqp + tt) * g.dh + c;
+                        const size_t o = attn_slab_off(g.H, g.Tqp, g.dh, bb, hd, tt, c);
                         ph[o] = h;
                         if (pl) pl[o] = (__bf16)(x - (float)h);
                     }

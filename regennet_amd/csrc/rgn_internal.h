@@ -299,7 +299,7 @@ struct Dims {
     int d, H, dh, ff, L;
 };
 
-// ---- launchers (rgn_kernels.hip) ----------------------------------------------------------------
+// ---- launchers (rgn_kernels.hip; the attention ones: rgn_attn.hip) --------------------------------
 hipError_t launch_gemm(const GemmArgs& g, int precision, hipStream_t s);
 hipError_t launch_gemm_x3(const GemmX3Args& g, bool x3, int variant, hipStream_t s);
 hipError_t configure_gemm_x3();
@@ -321,6 +321,9 @@ hipError_t launch_sg_tconv_s2(const GemmX3Args& g, int V, long long o_rows, hipS
 bool sg_gcn_supported(int N, int Kp, int V, int KP);
 hipError_t launch_sg_gcn(const GemmX3Args& g, int V, int KP, unsigned slot_k, const int* sl_v, const float* sl_a, int widest_tile, bool per_block_barrier, hipStream_t s);
 hipError_t configure_sg_gcn();
+// ---- attention kernels (rgn_attn.hip). attn_tiles_supported: the slab-staged MFMA kernels (k_attn_x3; k_attn_mfma behind launch_attention)
+// take (Tq, dh); launch_attention runs the scalar k_attention where they do not
+bool attn_tiles_supported(int Tq, int dh);
 hipError_t configure_attention(int Tq, int dh);
 struct AttnX3Args {
     const __bf16 *Qhi, *Qlo, *Khi, *Klo, *Vthi, *Vtlo;   // layouts above
@@ -328,7 +331,6 @@ struct AttnX3Args {
     int Bm, H, dh, d, Tq, Tqp;
     bool x3;
 };
-bool attn_x3_supported(int Tq, int dh);
 hipError_t configure_attn_x3(int Tq, int dh);
 hipError_t launch_attn_x3(const AttnX3Args& a, hipStream_t s, bool causal = true);   // (causal = false: every wave visits every key tile)
 hipError_t launch_attention(const float* qkv, float* out, Planes op, const Dims& dm, hipStream_t s, bool causal = true);

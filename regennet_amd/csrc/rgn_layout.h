@@ -1,4 +1,4 @@
-// The four data layouts the MFMA kernels of this directory stand on, defined ONCE: the index arithmetic of the packer (rgn_pack.cpp, host), of
+// The five data layouts the MFMA kernels of this directory stand on, defined ONCE: the index arithmetic of the packer (rgn_pack.cpp, host), of
 // the kernels (device) and of the stand-alone check tests/layout_check.cpp (host, no GPU) is this text. Nothing of HIP is included; every layout function
 // is constexpr, so the static_asserts at the foot travel with every build. (A few sites spell an expression out, with a comment naming the function
 // it equals, where the register allocation moved with the text: profiles/layout_refactor_resources.txt lists them.)
@@ -20,6 +20,10 @@
 //    A GRANULE is half a k-block (ks) of one 32-column block: 1 KiB; the register-streamed kernels address granule hs = 2 kt + ks.
 //
 // 4. The 32 x 32 MFMA C/D map: register i of lane l holds row (i & 3) + 8 (i >> 2) + 4 (l >> 5), column l & 31 of the tile.
+//
+// 5. The ATTENTION-READY slab [sample * H + head][Tqp][dh] of 16-bit elements: q, k and v of one (sample, head) as Tqp = 32 ceil(Tq / 32) token rows of
+//    dh contiguous elements, one contiguous slab per head. The in_proj epilogues (rgn_gemm_x3.hip, rgn_rowgemm.hip, rgn_sb.hip) scatter into it,
+//    k_attn_x3 (rgn_attn.hip) stages a head's slab through LDS; rows Tq .. Tqp - 1 are never written and never read.
 //
 // ... and the element the host packers (rgn_pack.cpp, rgn_stgcn.hip) put into the bf16 planes: f2bf / bf2f.
 #pragma once
@@ -67,6 +71,10 @@ RGN_HD constexpr inline int frag_granule(int hs, int kstride) { return (hs >> 1)
 // ---- 4. 32 x 32 MFMA accumulator: register i of a lane in half kh = lane >> 5
 RGN_HD constexpr inline int mfma32_row(int i, int kh) { return (i & 3) + 8 * (i >> 2) + 4 * kh; }
 RGN_HD constexpr inline int mfma32_col(int lane) { return lane & 31; }
+
+// ---- 5. attention-ready slab [B * H][Tqp][dh]; offsets in ELEMENTS
+RGN_HD constexpr inline size_t attn_slab_base(int H, int Tqp, int dh, size_t b, int hd) { return (b * H + hd) * Tqp * dh; }
+RGN_HD constexpr inline size_t attn_slab_off(int H, int Tqp, int dh, size_t b, int hd, int t, int c) { return ((b * H + hd) * Tqp + t) * dh + c; }
 
 // ---- host: fp32 -> bf16 bits (round to nearest even; a NaN stays one) and back. A split-bf16 plane pair holds hi = f2bf(v), lo = f2bf(v - bf2f(hi))
 inline uint16_t f2bf(float f) {
@@ -116,6 +124,8 @@ static_assert(layout_detail::chunks_permute(), "the chunk map permutes 0 .. 3 in
 static_assert(layout_detail::roles_agree(), "fragment (r, ks, kh) is logical chunk 2 ks + kh; an accumulator run is half a chunk");
 static_assert(layout_detail::cd_rows_permute(), "the C/D row map covers the 32 rows of a tile");
 static_assert(plane_off(300, 7, 37) == plane_chunk(300, 7, 1, 0) + 5, "a plane element lies in chunk (col % 32) / 8 of k-block col / 32");
+static_assert(attn_slab_off(4, 64, 128, 3, 2, 0, 0) == attn_slab_base(4, 64, 128, 3, 2) && attn_slab_base(4, 64, 128, 3, 2) == (size_t)(3 * 4 + 2) * 64 * 128, "a head's slab is Tqp x dh elements, heads of a sample back to back");
+static_assert(attn_slab_off(4, 64, 128, 3, 2, 59, 127) + 1 == attn_slab_off(4, 64, 128, 3, 2, 60, 0), "a token row of a head is dh contiguous elements");
 static_assert(frag_off(16, 33, 49) * 2 == frag_granule(3, 16 * 2048) + 2048 + frag_lane(33, 49) * 16 + frag_elem(49) * 2, "granule, column block, lane, element");
 
 }  // namespace rgn

@@ -321,7 +321,7 @@ int finalize_weights(rgn_ctx* c) {
         RGN_HIP(c, hipMemset(c->ffn_lo, 0, M * ffp * 2));
         RGN_HIP(c, configure_gemm_x3());
         // measured slower than GEMM + k_layernorm at B=256 (heavy epilogue, 64-row tiles): opt-in only
-        c->attn_x3 = attn_x3_supported(c->Tq, d / c->H);
+        c->attn_x3 = attn_tiles_supported(c->Tq, d / c->H);
         if (c->attn_x3) {
             c->Tqp = (c->Tq + 31) / 32 * 32;
             const size_t n = Bm * c->H * (size_t)c->Tqp * (d / c->H);

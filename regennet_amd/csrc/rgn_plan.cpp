@@ -862,7 +862,7 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
                 case AF_ROWGEMM_ATTN: mac[KC_ROWACT] += qkv; n[KC_ROWACT] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;
                 case AF_GEMM_ATTN: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3"; break;
                 default: mac[KC_GEMM] += qkv; n[KC_GEMM] += L; mac[KC_ATTN] = attn; n[KC_ATTN] = L;
-                    kn[KC_ATTN] = f32 ? (enc ? "k_attn_mfma<full>" : "k_attn_mfma") : (enc ? "k_attention<full>" : "k_attention"); break;
+                    kn[KC_ATTN] = attn_tiles_supported(c->Tq, c->d / c->H) ? (enc ? "k_attn_mfma<full>" : "k_attn_mfma") : (enc ? "k_attention<full>" : "k_attention"); break;   // (as launch_attention picks)
                 }
                 switch (pl.tail) {
                 case TF_MLP_X3: mac[KC_MLP] = tail; n[KC_MLP] = L; kn[KC_MLP] = enc ? "k_mlp_x3<enc>" : "k_mlp_x3"; break;

@@ -13,11 +13,12 @@
 //   q, k   accumulated transposed (W as the MFMA A operand: lane = token, registers = dh) and written as [token][dh] slabs;
 //   v      accumulated the same way and scattered (2-byte LDS writes) into the transposed slab V^T[dh][token]:
 //          the layouts k_attn_x3 stages through LDS, produced in place (Q 42.5 + K 42.5 + V^T 41 KiB).
-//   attention (waves 0-4, one 32-query tile each; rgn_attn_x3.hip's scheme): S^T = K . Q^T from the slabs, softmax in
+//   attention (waves 0-4, one 32-query tile each; rgn_attn.h's scheme): S^T = K . Q^T from the slabs, softmax in
 //          registers, O^T = V^T . P^T with P from the S^T accumulators, result transposed through the dead Q/K slabs and stored as
 //          the hi plane of the K32-blocked layout the out_proj GEMM consumes.
 #include "rgn_internal.h"
 #include "rgn_device.h"
+#include "rgn_attn.h"
 
 #include <hip/hip_runtime.h>
 
@@ -26,15 +27,14 @@ namespace rgn {
 namespace {
 constexpr int QL_NW = 12, QL_NT = 64 * QL_NW;                        // waves / threads
 constexpr int QL_TT = 5, QL_TQP = 32 * QL_TT, QL_DH = 128, QL_NK = 16;
-constexpr int QL_KLD = QL_DH + 8, QL_VLD = QL_TQP + 4;               // slab row strides (bf16): conflict-free ds_read_b128 / b64
-constexpr int QL_Q = 0, QL_K = QL_Q + QL_TQP * QL_KLD * 2, QL_V = QL_K + QL_TQP * QL_KLD * 2;
-constexpr int QL_A = QL_V + QL_DH * QL_VLD * 2;                      // activation ring: 2 stages x [160 rows][64 B]
+typedef AttnSlab<QL_TT, QL_DH> QS;                                   // slab row strides, k16 steps, dh tiles and the patch stride: rgn_attn.h
+constexpr int QL_Q = 0, QL_K = QL_Q + QL_TQP * QS::KLD * 2, QL_V = QL_K + QL_TQP * QS::KLD * 2;
+constexpr int QL_A = QL_V + QL_DH * QS::VLD * 2;                      // activation ring: 2 stages x [160 rows][64 B]
 constexpr int QL_ASTAGE = QL_NT * 16;                                // (every thread moves 16 bytes per k-block: rows 160 .. 191 are never read)
 constexpr int QL_BIAS = QL_A + 2 * QL_ASTAGE;                        // [3][128] floats
 constexpr int QL_LDS = QL_BIAS + 3 * QL_DH * 4;
 constexpr int QL_D = 3, QL_RING = QL_D + 1, QL_DA = 4, QL_ARING = QL_DA + 1;
-constexpr int QL_OLD = QL_DH + 4;                                    // fp32 output patch row stride
-static_assert(QL_TT * 32 * QL_OLD * 4 <= QL_V, "output patches alias the Q and K slabs");
+static_assert(QL_TT * QS::PATCH * 4 <= QL_V, "output patches alias the Q and K slabs");
 static_assert(QL_LDS <= 160 * 1024, "LDS");
 }  // namespace
 
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 op4 h;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) h[e] = (op_t)(acc[t][4 * i4 + e] + bq[e]);
-                *reinterpret_cast<op4*>(sQ + (t * 32 + l31) * QL_KLD + wn * 32 + 8 * i4 + 4 * kh) = h;
+                *reinterpret_cast<op4*>(sQ + (t * 32 + l31) * QS::KLD + wn * 32 + 8 * i4 + 4 * kh) = h;
             }
         }
     } else if (which == 1) {
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 op4 h;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) h[e] = (op_t)acc[t][4 * i4 + e];
-                *reinterpret_cast<op4*>(sK + (t * 32 + l31) * QL_KLD + wn * 32 + 8 * i4 + 4 * kh) = h;
+                *reinterpret_cast<op4*>(sK + (t * 32 + l31) * QS::KLD + wn * 32 + 8 * i4 + 4 * kh) = h;
             }
     } else {   // v -> V^T[dh][token]: 2-byte writes, a wave's 32 lanes (consecutive tokens) fill one 64-byte run
 #pragma unroll
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
 #pragma unroll
             for (int t = 0; t < QL_TT; ++t)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) sV[(wn * 32 + 8 * i4 + 4 * kh + e) * QL_VLD + t * 32 + l31] = (op_t)(acc[t][4 * i4 + e] + bv[e]);
+                for (int e = 0; e < 4; ++e) sV[(wn * 32 + 8 * i4 + 4 * kh + e) * QS::VLD + t * 32 + l31] = (op_t)(acc[t][4 * i4 + e] + bv[e]);
         }
     }
     wait_lgkmcnt<0>();
@@ -179,9 +179,9 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
     //      each with its own running maximum / sum (flash-style); a secondary dumps its unnormalised O^T accumulators (a register
     //      image: the primary's lanes hold the same elements) + (max, sum) into the dead V^T slab / activation ring / bias area, and
     //      the primary of the tile merges: O = sum_u e^(m_u - m) O_u / sum_u e^(m_u - m) l_u.
-    constexpr int NS = QL_DH / 16, ND = QL_DH / 32;
+    constexpr int NS = QS::NS, ND = QS::ND;
     constexpr int DUMP = ND * 16 * 64 * 4 + 64 * 8;                  // 16 KiB of accumulators + (m, l) per lane
-    static_assert(QL_V + 4 * DUMP <= QL_LDS && QL_TT * 32 * QL_OLD * 4 <= QL_V, "dumps behind the output patches");
+    static_assert(QL_V + 4 * DUMP <= QL_LDS && QL_TT * QS::PATCH * 4 <= QL_V, "dumps behind the output patches");
     const int w = wave;
     const int qt = w < 5 ? w : (w == 5 ? 2 : (w == 6 ? 3 : 4));
     const int k0 = w < 2 ? 0 : (w < 4 ? w - 1 : (w == 4 ? 4 : (w == 8 ? 2 : 0)));
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
     if (w < 9) {
         op8 qh[NS];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) qh[s] = *reinterpret_cast<const op8*>(sQ + qrow * QL_KLD + 16 * s + 8 * kh);
+        for (int s = 0; s < NS; ++s) qh[s] = *reinterpret_cast<const op8*>(sQ + qrow * QS::KLD + 16 * s + 8 * kh);
         // key tiles one at a time with a running maximum / sum (flash-style): one S^T tile of registers instead of five
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt)
@@ -207,50 +207,24 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 for (int i = 0; i < 16; ++i) st[i] = 0.f;
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
-                    const op8 kf = *reinterpret_cast<const op8*>(sK + (32 * kj + l31) * QL_KLD + 16 * s + 8 * kh);
+                    const op8 kf = *reinterpret_cast<const op8*>(sK + (32 * kj + l31) * QS::KLD + 16 * s + 8 * kh);
                     st = OP::mfma(kf, qh[s], st);
                 }
-                // key = 32 kj + (i&3) + 8 (i>>2) + 4 kh, query = qrow (a unit's first key tile holds a valid key for every real
-                // query - key 0, or the keys below the query's own tile, or the diagonal - so the maximum is finite)
-                float mt = -INFINITY;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = 32 * kj + mfma32_row(i, kh);
-                    const bool ok = (key <= qrow) && (key < Tq);
-                    st[i] = ok ? st[i] : -INFINITY;
-                    mt = fmaxf(mt, st[i]);
-                }
+                // (a unit's first key tile holds a valid key for every real query - key 0, or the keys below the query's own tile, or the
+                // diagonal - so the maximum is finite)
+                float mt = attn_mask_max<true>(st, kj, kh, qrow, Tq, -INFINITY);
                 mt = half_max(mt);                                    // (one v_permlane32_swap instead of a ds_bpermute round trip: rgn_device.h)
                 const float m_new = fmaxf(fmaxf(m_run, mt), -1e30f);   // (a unit with no valid key at all - rows beyond Tq only - stays finite)
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * qs2);   // (first tile: exp2(-inf) = 0)
                 const float nm = -m_new * qs2;
-                float ls = 0.f;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    st[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(st[i], qs2, nm));
-                    ls += st[i];
-                }
+                const float ls = attn_exp2_sum(st, qs2, nm, 0.f);
                 l_run = l_run * alpha + ls;
                 m_run = m_new;
 #pragma unroll
                 for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) oa[dt][i] *= alpha;
-#pragma unroll
-                for (int step = 0; step < 2; ++step) {
-                    op8 ph;     // B operand: this lane's 8 keys = registers 8*step .. 8*step+7
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) ph[j] = (op_t)st[8 * step + j];
-                    const int kb = 32 * kj + 16 * step + 4 * kh;      // keys kb..kb+3 and kb+8..kb+11
-#pragma unroll
-                    for (int dt = 0; dt < ND; ++dt) {
-                        const int o = (32 * dt + l31) * QL_VLD + kb;
-                        u32x4 vh;
-                        vh.lo = *reinterpret_cast<const u32x2*>(sV + o);
-                        vh.hi = *reinterpret_cast<const u32x2*>(sV + o + 8);
-                        oa[dt] = OP::mfma(__builtin_bit_cast(op8, vh), ph, oa[dt]);
-                    }
-                }
+                attn_pv_tile<OP, QS::VLD>(oa, st, sV, kj, l31, kh);
             }
         }
         l_run = half_sum(l_run);
@@ -303,11 +277,8 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
                 }
         }
         inv = 1.0f / l_run;
-        float* patch = reinterpret_cast<float*>(smem) + w * (32 * QL_OLD);
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) patch[l31 * QL_OLD + 32 * dt + mfma32_row(i, kh)] = oa[dt][i] * inv;
+        float* patch = reinterpret_cast<float*>(smem) + w * QS::PATCH;
+        attn_o_to_patch<QS::OLD>(patch, oa, inv, l31, kh);
         wait_lgkmcnt<0>();
         __builtin_amdgcn_wave_barrier();
         // 16-byte WRITE-THROUGH stores (sc1): the plane is not left dirty in the XCD L2s for the end-of-kernel write-back
@@ -319,8 +290,8 @@ __global__ __launch_bounds__(QL_NT, 1) void k_qkv_attn_long(QkvAttnArgs g, const
             const int idx = lane + 64 * it, r = idx / C8, c = (idx - r * C8) * 8;
             const int q = 32 * w + r;
             if (q < Tq) {
-                const f32x4 v0 = *reinterpret_cast<const f32x4*>(&patch[r * QL_OLD + c]);
-                const f32x4 v1 = *reinterpret_cast<const f32x4*>(&patch[r * QL_OLD + c + 4]);
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(&patch[r * QS::OLD + c]);
+                const f32x4 v1 = *reinterpret_cast<const f32x4*>(&patch[r * QS::OLD + c + 4]);
                 const int col = hd * QL_DH + c;
                 const size_t o = plane_off(g.out.rows, row0 + q, col);
                 op8 h;

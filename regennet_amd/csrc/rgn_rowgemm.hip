@@ -214,7 +214,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
         const int r16 = lane >> 2, c = lane & 3;
         if (g.act == 2) {
             // packed in_proj of a long sequence (N = 3 d, d = 512 = one column chunk each for q, k, v): the "attention-ready"
-            // layout [sample * H + head][Tqp][dh] k_attn_x3 reads; a row's 32-column block is a 64-byte run of its head's row
+            // layout (rgn_layout.h, layout 5) k_attn_x3 reads; a row's 32-column block is a 64-byte run of its head's row
             __bf16* dst = blockIdx.y == 0 ? g.Qhi : (blockIdx.y == 1 ? g.Khi : g.Vhi);
             const int bpk = g.dh >> 5;                                 // 32-column blocks per head
 #pragma unroll
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(RG_NT, (EPI == 1 && NK <= 16) ? RGN_RG_ACT_WAVES : 
                 if (m < g.M) {
                     const int b = m / g.Tq, t = m - b * g.Tq, head = blk / bpk, cc = (blk - head * bpk) * 32 + c * 8;
                     const int off = blk * 4096 + img_chunk(r, c);
-                    const size_t o = (((size_t)b * g.H + head) * g.Tqp + t) * g.dh + cc;
+                    const size_t o = attn_slab_off(g.H, g.Tqp, g.dh, b, head, t, cc);
                     *reinterpret_cast<bf16x8*>(dst + o) = *reinterpret_cast<const bf16x8*>(img_hi + off);
                 }
             }

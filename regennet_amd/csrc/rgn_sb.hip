@@ -15,7 +15,7 @@
 // the fp32 residual stream of the next pre-norm sum.
 //
 //   per layer:  qkv  = PRE_LN(norm3 of the previous layer | identity) -> in_proj -> attention-ready q/k/v planes
-//               attn = k_attn_x3 (rgn_attn_x3.hip)
+//               attn = k_attn_x3 (rgn_attn.hip)
 //               proj = PRE_PLANES(attention output) -> out_proj + bias + residual -> fp32 pre-norm rows
 //               ff1  = PRE_LN(norm1, + folded cross-attention vectors, norm2) -> linear1 + GELU -> planes
 //               ff2  = PRE_PLANES -> linear2 + bias + residual -> fp32 pre-norm rows
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256 * NP) void k_sb_gemm(SbArgs g) {
                 ph = which == 0 ? g.Qhi : (which == 1 ? g.Khi : g.Vhi);
                 pl = which == 0 ? g.Qlo : (which == 1 ? g.Klo : g.Vlo);
                 if (which == 0) sc = g.qscale;
-                o = (((size_t)b * g.H + hd) * g.Tqp + t) * g.dh + cc;
+                o = attn_slab_off(g.H, g.Tqp, g.dh, b, hd, t, cc);
             }
             bf16x4 h, l;
 #pragma unroll

@@ -121,6 +121,28 @@ static void cd_map() {
     for (int l = 0; l < 64; ++l) CHECK(mfma32_col(l) == l % 32, "C/D column of lane %d", l);
 }
 
+// 7. attention-ready slab: bijection onto B H Tqp dh elements, a token row of a head is dh contiguous elements, a head's slab Tqp dh contiguous
+//    elements starting at its base, and the literal the in_proj epilogues used to spell
+static void attn_slab(int B, int H, int Tqp, int dh) {
+    const size_t total = (size_t)B * H * Tqp * dh;
+    std::vector<int> hit(total, 0);
+    for (int b = 0; b < B; ++b)
+        for (int hd = 0; hd < H; ++hd) {
+            const size_t base = attn_slab_base(H, Tqp, dh, b, hd);
+            CHECK(base == ((size_t)b * H + hd) * Tqp * dh, "slab base of (%d, %d)", b, hd);
+            for (int t = 0; t < Tqp; ++t)
+                for (int c = 0; c < dh; ++c) {
+                    const size_t o = attn_slab_off(H, Tqp, dh, b, hd, t, c);
+                    CHECK(o == (((size_t)b * H + hd) * Tqp + t) * dh + c, "slab H %d Tqp %d dh %d (%d, %d, %d, %d): %zu", H, Tqp, dh, b, hd, t, c, o);
+                    CHECK(o == base + (size_t)t * dh + c, "slab (%d, %d, %d, %d) is not row t, column c of its head's slab", b, hd, t, c);
+                    CHECK(o == attn_slab_off(H, Tqp, dh, b, hd, t, 0) + c, "slab row (%d, %d, %d) is not contiguous at column %d", b, hd, t, c);
+                    CHECK(o < total, "slab (%d, %d, %d, %d) -> %zu out of range", b, hd, t, c, o);
+                    if (o < total) hit[o]++;
+                }
+        }
+    for (size_t i = 0; i < total; ++i) CHECK(hit[i] == 1, "slab H %d Tqp %d dh %d offset %zu hit %d times", H, Tqp, dh, i, hit[i]);
+}
+
 int main() {
     for (int R : {32, 64}) {
         image_chunk_map(R);
@@ -132,6 +154,8 @@ int main() {
     const int nk[4][2] = {{32, 32}, {352, 512}, {512, 352}, {1536, 512}};
     for (const auto& s : nk) fragment(s[0], s[1]);
     cd_map();
+    const int slabs[4][4] = {{1, 1, 32, 16}, {3, 4, 64, 128}, {2, 32, 96, 16}, {5, 8, 160, 64}};   // B, H, Tqp, dh
+    for (const auto& s : slabs) attn_slab(s[0], s[1], s[2], s[3]);
     if (g_fail) std::printf("%d layout checks failed\n", g_fail);
     else std::printf("layout ok\n");
     return g_fail ? 1 : 0;

@@ -123,6 +123,17 @@ def _x3(case, label, engine="throughput", want=(), never=(), calls=1):
     return errs
 
 
+def _f32(case, label, want=(), never=()):
+    """precision f32 against the oracle (1e-3), after the plan names what it should."""
+    model, diffusion = case.build("f32")
+    _check_plan(case.kernels(model, True), want, never)
+    err = float(np.abs(case.sample(model, diffusion).cpu().numpy() - case.ref).max())
+    _close(model)
+    print(f"\n[geometry] {label} {_tag(case.over)} B={case.B} T={case.cfg['num_frames']} f32: vs oracle {err:.2e}")
+    assert err < BOUND, (label, case.over, err)
+    return err
+
+
 def _sched(case, label, tail, want_plain=(), want_split=(), never_plain=(), calls=1, **attrs):
     """The precision schedule with `tail` split-bf16 steps behind S - tail plain-bf16 ones (throughput kernels), against the oracle, bounded by
     twice the error of precision="bf16" on the same case + 2e-3."""
@@ -187,14 +198,18 @@ def test_head_counts_on_the_fused_in_proj_attention_kernel(over, T, B):
 
 
 # ---- 2. head dim classes at d = 512 ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("engine", ["throughput", "small-batch"])
+@pytest.mark.parametrize("engine", ["throughput", "small-batch", "f32"])
 @pytest.mark.parametrize("T", [60, 100])
 @pytest.mark.parametrize("over", gc.HEADS_D512, ids=_tag)
 def test_head_dim_classes_at_d512(over, T, engine):
     """k_attn_x3 at dh = 64, 32, 16: behind k_rowgemm's in_proj in the plain phase where dh % 32 == 0 (H = 8, 16), behind the generic GEMM
-    otherwise (H = 32) and in the split phase; the small-batch engine (rgn_sb.hip) with dh != 128."""
+    otherwise (H = 32) and in the split phase; the small-batch engine (rgn_sb.hip) with dh != 128. precision f32 on the same cases: k_attn_mfma at
+    those head dims (60 tokens: two key tiles, 28 live rows in the second; 100: four, 4 live rows in the last) under the parity bound."""
     H = over["num_heads"]
     case = Case(dict(over, num_frames=T), 3, seed=H)
+    if engine == "f32":
+        _f32(case, "heads/d512", want=["k_gemm_f32", "k_attn_mfma"], never=["k_attention", "k_attn_x3"])
+        return
     if engine == "small-batch":
         _x3(case, "heads/d512", engine, want=["k_sb_gemm", "k_attn_x3"])
         _rows(case, "heads/d512", engine)
@@ -220,7 +235,8 @@ def test_one_token_sequences_through_the_scattering_in_proj():
 @pytest.mark.parametrize("over", gc.PLAIN_ATTN, ids=_tag)
 def test_fp32_attention_inside_the_bf16_modes(over, T, etd):
     """Heads of 8 (d = 512 / H = 64, d = 64 / H = 8) and more than 160 tokens fall to AF_PLAIN: the generic in_proj GEMM + the fp32 k_attention,
-    in both bf16 modes; the small-batch engine is off for such handles."""
+    in both bf16 modes; the small-batch engine is off for such handles. precision f32 runs (and reports) the same k_attention there, never
+    k_attn_mfma, whose tiles stop at 160 tokens and start at heads of 16."""
     case = Case(dict(over, num_frames=T, emb_trans_dec=etd), 3, seed=T)
     model, _ = case.build("bf16_x3tail")                               # (the default engine selection: no "/throughput")
     for split in (False, True):
@@ -229,6 +245,7 @@ def test_fp32_attention_inside_the_bf16_modes(over, T, etd):
     _x3(case, "attn/fp32", want=["k_attention"], never=["k_attn_x3", "k_sb_gemm", "k_qkv_attn"])
     _sched(case, "attn/fp32", 3, want_plain=["k_attention"], want_split=["k_attention"], never_plain=["k_attn_x3", "k_qkv_attn_long"])
     _rows(case, "attn/fp32")
+    _f32(case, "attn/fp32", want=["k_gemm_f32", "k_attention"], never=["k_attn_mfma", "k_attn_x3"])
 
 
 # ---- 4. FFN width ---------------------------------------------------------------------------------------------------------------------

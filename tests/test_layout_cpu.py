@@ -1,9 +1,10 @@
-"""CPU: the operand plane, LDS image, fragment plane and MFMA C/D layouts of regennet_amd/csrc/rgn_layout.h, checked exhaustively on the host.
+"""CPU: the operand plane, LDS image, fragment plane, MFMA C/D and attention-ready slab layouts of regennet_amd/csrc/rgn_layout.h, checked exhaustively on the host.
 
 tests/layout_check.cpp includes only that header - the text the kernels and the packer compile - and checks over small domains that the image chunk
 map is a bijection, that a DMA lane fetching the chunk the source rule names fills the image as the readers expect, that an element written through the
 accumulator-run offset is read back through the fragment offset, that the plane and fragment-plane offsets are bijections equal to the packer's
-former literals, the granule / lane rule of the fragment plane, and that the C/D row map covers a tile."""
+former literals, the granule / lane rule of the fragment plane, that the C/D row map covers a tile, and that the attention-ready slab offset is a bijection in which a
+token row of a head is dh contiguous elements and a head's slab starts at its base."""
 import os
 import shutil
 import subprocess

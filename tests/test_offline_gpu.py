@@ -246,6 +246,10 @@ def test_offline_plan_names_the_full_and_encoder_instantiations():
     for plan in (split, plain):
         kinds = " ".join(v["kernel"] for v in plan.values())
         assert "k_layers" not in kinds and "k_step" not in kinds and "k_qkv_attn_long" not in kinds, plan
+    model, diffusion = build_hip(cfg, sd, resp="10", precision="f32")      # (61 tokens, heads of 128: the MFMA tiles, full form)
+    model(x, torch.full((64,), 5, dtype=torch.long, device="cuda"), y=y_to_device(y))
+    f32 = model._engine.plan_query(64, split_phase=True)
+    assert f32["attention"]["kernel"] == "k_attn_mfma<full>" and f32["gemm_mfma"]["kernel"] == "k_gemm_f32", f32
 
 
 def test_offline_auto_regressive_matches_reference_frame_loop():
