@@ -249,6 +249,25 @@ RGN_API int rgn_rot2xyz(rgn_handle h, const float* x_dev, const uint8_t* mask_de
                         int32_t pose_rep, int32_t num_person, int32_t flags /*RGN_R2X_TRANSLATION | _GLOB | _VERTSTRANS*/,
                         const float* glob_rot_host /*[3] or NULL*/, float* xyz_dev, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/,
                         void* stream);
+/* rgn_rot2xyz with a body shape PER FRAME, read on the device: what the reference's wrappers do when they are given a `betas` tensor with one row
+ * per frame (model/rotation2xyz.py:289-292 hand it straight to the body layer). Joint j's rest position in frame (b, p, t) is
+ *   rest_joints[j] + sum_{k < nb} shape_joints[j, :, k] * betas[b * beta_stride_b + p * beta_stride_p + t * beta_stride_t + k]
+ * summed in k order in fp32, and the joint 0 that is subtracted is that frame's own.
+ *   shape_joints_dev fp32 [J, 3, nb] (the skeleton file's `shape_joints`, or its first nb directions re-packed), nb in [1, 16]
+ *   betas_dev        fp32; the three strides are in ELEMENTS and >= 0, and 0 broadcasts along that axis: a contiguous [B, nb] is (nb, 0, 0),
+ *                    [B, P, nb] is (P nb, nb, 0), [B, T, nb] is (T nb, 0, nb), [B, P, T, nb] is (P T nb, T nb, nb). A frame with mask == 0 never
+ *                    reads its betas (they may be NaN, or lie outside the allocation).
+ * Everything else, rotmat_dev included, is rgn_rot2xyz's, bit for bit; the result of a frame depends on that frame's rows and betas alone. The call
+ * enqueues on `stream`, allocates nothing, keeps no state and can be captured into a graph.
+ * The arguments are checked before the handle or the device is touched - RGN_ERR_INVALID_ARG for everything rgn_rot2xyz refuses, a null
+ * shape_joints_dev or betas_dev, nb outside [1, 16], a negative stride - with text in rgn_last_error(h), or rgn_last_error(NULL) when h is NULL
+ * (which is itself RGN_ERR_INVALID_ARG once the other arguments have passed). */
+RGN_API int rgn_rot2xyz_shaped(rgn_handle h, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T, int32_t J,
+                               const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/,
+                               const float* shape_joints_dev /*[J,3,nb]*/, int32_t nb, const float* betas_dev, int64_t beta_stride_b,
+                               int64_t beta_stride_p, int64_t beta_stride_t, int32_t pose_rep, int32_t num_person, int32_t flags,
+                               const float* glob_rot_host /*[3] or NULL*/, float* xyz_dev, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/,
+                               void* stream);
 
 /* Replaces the loss arithmetic of GaussianDiffusion.training_losses (diffusion/gaussian_diffusion.py:1313-1391, with masked_l2 :213-225 and the
  * three rot2xyz passes of :1254-1258) for a model output that is already on the device: one row of seven terms per motion,
@@ -312,6 +331,22 @@ RGN_API int rgn_rot2verts(rgn_body_handle b, const float* x_dev, const uint8_t* 
                           int32_t flags, const float* glob_rot_host /*[3] or NULL*/, const float* betas_host /*[nb] or NULL*/,
                           float* verts_dev /*[B,V,3P,T]*/, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes,
                           void* stream);
+/* rgn_rot2verts with a body shape PER FRAME, read on the device; shape_joints_dev, nb, betas_dev and the three strides are rgn_rot2xyz_shaped's
+ * (rest_joints_host is the file's, WITHOUT betas), and nb may be smaller than the body's count of shape directions: the rest count as 0.
+ *   v_posed = v_template + [shapedirs; posedirs]^T . [betas; (R_j - I)_{j >= 1}]      one sum on the fp32-input MFMA, the shape terms first, each in k order
+ * - no shaped template is ever formed - and the chain and A_j take the frame's own rest joints. rest_joints and shape_joints must belong together
+ * with the body's shapedirs (shape_joints = J_regressor . shapedirs) for joints and surface to move together.
+ *   work_dev  rgn_rot2verts_shaped_workspace bytes (per tile of 32 frames: the skinning transforms, and the betas ahead of the pose feature)
+ * Masked tiles, stream, allocation, state and graph capture as for rgn_rot2verts. The arguments are checked before the handle or the device is touched:
+ * RGN_ERR_INVALID_ARG for what rgn_rot2xyz_shaped refuses, then for a NULL handle, nb larger than the body's, a bad parent table, a short workspace;
+ * text in rgn_body_last_error(b), or rgn_body_last_error(NULL) when b is NULL. */
+RGN_API int rgn_rot2verts_shaped_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes);
+RGN_API int rgn_rot2verts_shaped(rgn_body_handle b, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T,
+                                 const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/,
+                                 const float* shape_joints_dev /*[J,3,nb]*/, int32_t nb, const float* betas_dev, int64_t beta_stride_b,
+                                 int64_t beta_stride_p, int64_t beta_stride_t, int32_t pose_rep, int32_t num_person, int32_t flags,
+                                 const float* glob_rot_host /*[3] or NULL*/, float* verts_dev /*[B,V,3P,T]*/,
+                                 float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes, void* stream);
 
 /* ---- Rendering: z-buffer rasteriser over the vertices rgn_rot2verts writes ----
  * Replaces render/crendermotion.py:20-42 (render_video: centring, the frame loop, the colours) and render/renderer.py:51-150 (Renderer: pyrender on

@@ -75,6 +75,7 @@ SYMBOLS = {
     "rgn_rot6d_to_matrix": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "rgn_gaussian_filter1d": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "rgn_rot2xyz": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rgn_rot2xyz_shaped": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rgn_loss_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp]),
     "rgn_profile_enable": (C.c_int, [_vp, _i32]),
     "rgn_profile_query": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
@@ -101,6 +102,9 @@ SYMBOLS.update({
     "rgn_body_last_error": (C.c_char_p, [_vp]),
     "rgn_rot2verts_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
     "rgn_rot2verts": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rgn_rot2verts_shaped_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "rgn_rot2verts_shaped": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _u64,
+                                       _vp]),
 })
 
 RENDER_MAX_PERSONS = 8                 # RGN_RENDER_MAX_PERSONS
@@ -329,6 +333,20 @@ class Engine:
                                       pa.ctypes.data_as(C.c_void_p), int(pose_rep), int(num_person), int(flags),
                                       None if gr is None else gr.ctypes.data_as(C.c_void_p), _ptr(xyz), _ptr(rotmat), C.c_void_p(stream)))
 
+    def rot2xyz_shaped(self, x, mask, rest_joints, parents, shape_joints, betas, strides, pose_rep, num_person, flags, glob_rot, xyz, rotmat, stream):
+        """rgn_rot2xyz_shaped: rot2xyz with shape_joints (fp32 [J, 3, nb]) and betas (fp32) on the engine's device; strides = (b, p, t) in elements
+        of `betas`, 0 to broadcast."""
+        rj = np.ascontiguousarray(rest_joints, dtype=np.float32)
+        pa = np.ascontiguousarray(parents, dtype=np.int32)
+        gr = None if glob_rot is None else np.ascontiguousarray(glob_rot, dtype=np.float32).reshape(3)
+        assert rj.shape == (len(pa), 3) and x.is_contiguous() and xyz.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        assert shape_joints.is_contiguous() and tuple(shape_joints.shape[:2]) == (len(pa), 3) and shape_joints.element_size() == betas.element_size() == 4
+        sb, sp, st = (int(s) for s in strides)
+        self._ck(self.lib.rgn_rot2xyz_shaped(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), len(pa), rj.ctypes.data_as(C.c_void_p),
+                                             pa.ctypes.data_as(C.c_void_p), _ptr(shape_joints), int(shape_joints.shape[2]), _ptr(betas), sb, sp, st,
+                                             int(pose_rep), int(num_person), int(flags), None if gr is None else gr.ctypes.data_as(C.c_void_p),
+                                             _ptr(xyz), _ptr(rotmat), C.c_void_p(stream)))
+
     def loss_terms(self, target, output, cmotion, mask, rest_joints, parents, foot_joints, transl_row, vel_threshold, flags, terms, stream):
         """rgn_loss_terms: target / output / cmotion fp32 [B, J + 1, 6, T] and mask (bool / uint8 [B, T]), contiguous on the engine's device -> terms
         fp32 [B, 7] (columns: LOSS_TERMS); rest_joints [J, 3], parents [J] and foot_joints [4] are host arrays."""
@@ -469,6 +487,27 @@ class BodyEngine:
         self._ck(self.lib.rgn_rot2verts(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, int(pose_rep), int(num_person),
                                         int(flags), pgr, pbe, _ptr(verts), _ptr(rotmat), _ptr(work), int(work.numel() * work.element_size()),
                                         C.c_void_p(stream)))
+
+    def workspace_bytes_shaped(self, B, T, num_person):
+        n = C.c_uint64()
+        self._ck(self.lib.rgn_rot2verts_shaped_workspace(self.h, int(B), int(T), int(num_person), C.byref(n)))
+        return n.value
+
+    def rot2verts_shaped(self, x, mask, rest_joints, parents, shape_joints, betas, strides, pose_rep, num_person, flags, glob_rot, verts, rotmat, work,
+                         stream):
+        """rgn_rot2verts_shaped: rot2verts with shape_joints (fp32 [J, 3, nb], nb <= self.nb) and betas (fp32) on the body's device; strides =
+        (b, p, t) in elements of `betas`, 0 to broadcast; rest_joints: the file's, without betas; work: a uint8 tensor of at least
+        workspace_bytes_shaped(B, T, num_person)."""
+        rj, prj = _host(rest_joints, np.float32)
+        pa, ppa = _host(parents, np.int32)
+        gr, pgr = _host(None if glob_rot is None else np.asarray(glob_rot).reshape(3), np.float32)
+        assert rj.shape == (self.J, 3) and pa.shape == (self.J,)
+        assert x.is_contiguous() and verts.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        assert shape_joints.is_contiguous() and tuple(shape_joints.shape[:2]) == (self.J, 3) and shape_joints.element_size() == betas.element_size() == 4
+        sb, sp, st = (int(s) for s in strides)
+        self._ck(self.lib.rgn_rot2verts_shaped(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, _ptr(shape_joints),
+                                               int(shape_joints.shape[2]), _ptr(betas), sb, sp, st, int(pose_rep), int(num_person), int(flags), pgr,
+                                               _ptr(verts), _ptr(rotmat), _ptr(work), int(work.numel() * work.element_size()), C.c_void_p(stream)))
 
 
 class RenderEngine:

@@ -539,6 +539,42 @@ int rgn_rot2xyz(rgn_handle h, const float* x, const uint8_t* mask, int32_t B, in
     });
 }
 
+int rgn_rot2xyz_shaped(rgn_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t T, int32_t J, const float* rest_joints,
+                       const int32_t* parents, const float* shape_joints, int32_t nb, const float* betas, int64_t beta_stride_b, int64_t beta_stride_p,
+                       int64_t beta_stride_t, int32_t pose_rep, int32_t num_person, int32_t flags, const float* glob_rot, float* xyz, float* rotmat,
+                       void* stream) {
+    return rgn_guard(h, "rgn_rot2xyz_shaped", [&]() -> int {
+        // the arguments first, the handle after them (text: rgn_last_error(NULL) while there is no handle)
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2xyz_shaped: " + m);
+            g_create_error = "rgn_rot2xyz_shaped: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        if (!x || !xyz || !rest_joints || !parents) return bad("null x, xyz, rest_joints or parents");
+        if (const char* why = fk_check_shape(shape_joints, nb, betas, beta_stride_b, beta_stride_p, beta_stride_t)) return bad(why);
+        if (B < 1 || T < 1) return bad("B < 1 or T < 1");
+        if (J < 1 || J > FK_MAX_JOINTS) return bad("J outside [1, 64]");
+        if (num_person < 1) return bad("num_person < 1");
+        if (pose_rep < RGN_POSE_ROT6D || pose_rep > RGN_POSE_ROTMAT) return bad("unknown pose_rep");
+        if (flags & ~(RGN_R2X_TRANSLATION | RGN_R2X_GLOB | RGN_R2X_VERTSTRANS)) return bad("unknown flag");
+        if (!(flags & RGN_R2X_GLOB) && !glob_rot) return bad("glob_rot is required when RGN_R2X_GLOB is not set");
+        FkSkel sk;
+        int at = -1;
+        if (const char* why = fk_build_skel(J, rest_joints, parents, sk, at))
+            return bad(at < 0 ? std::string(why) : "parents[" + std::to_string(at) + "] outside [0, " + std::to_string(at) + ")");
+        if (!(flags & RGN_R2X_GLOB)) axis_angle_to_matrix_f32(glob_rot, sk.glob);
+        if (!h) return bad("null handle");
+        RGN_HIP(h, hipSetDevice(h->cfg.device));
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_rot2xyz_shaped: weights not finalized");
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = h->stream;
+        int rc = stream_enter(h, us);
+        if (rc) return rc;
+        const FkShape sh{shape_joints, betas, beta_stride_b, beta_stride_p, beta_stride_t, nb};
+        RGN_LAUNCH(h, KC_MISC, s, launch_fk_shaped(x, mask, xyz, rotmat, B, T, num_person, J, pose_rep, flags, sk, sh, s));
+        return stream_exit(h, us);
+    });
+}
+
 int rgn_loss_terms(rgn_handle h, const float* target, const float* output, const float* cmotion, const uint8_t* mask, int32_t B, int32_t T, int32_t R,
                    int32_t J, const float* rest_joints, const int32_t* parents, const int32_t* foot_joints, int32_t transl_row, float vel_threshold,
                    int32_t flags, float* terms, void* stream) {

@@ -103,11 +103,56 @@ __device__ __forceinline__ void fk_local_matrices(float* g, const FkFrame& fr, l
     }
 }
 
+// Joint i's parent-relative rest offset as fk_chain asks for it, rel(i, r): the call's one rest skeleton, from the by-value table ...
+struct FkRestRel {
+    const FkSkel& sk;
+    template <class S>
+    __device__ __forceinline__ void operator()(int i, S (&r)[3]) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = sk.rel[i][c];
+    }
+};
+
+// ... or this lane's own (rgn_rot2xyz_shaped / rgn_rot2verts_shaped): rel[i] + sum_k (shape_joints[i] - shape_joints[parent(i)])[.][k] beta[k], the
+// frame's betas in registers, shape_joints [J][3][nb] read from global memory at an address the half-wave shares. Nothing of it goes through LDS.
+// (FkShape: rgn_internal.h)
+
+// The betas of the lane's frame. A masked frame, or a lane past the end, reads none and counts as shape 0.
+__device__ __forceinline__ void fk_load_betas(const FkShape& sh, const FkFrame& fr, float (&be)[FK_MAX_BETAS]) {
+    const bool rd = fr.live && fr.keep;
+    const float* bp = sh.betas + (fr.b * sh.sb + fr.p * sh.sp + fr.t * sh.st);
+#pragma unroll
+    for (int k = 0; k < FK_MAX_BETAS; ++k) be[k] = (rd && k < sh.nb) ? bp[k] : 0.f;
+}
+
+// r += sum_k (shape_joints[i] - shape_joints[par])[.][k] be[k] in k order; par < 0: joint i's own shape directions (the absolute rest position)
+__device__ __forceinline__ void fk_shape_add(const FkShape& sh, int i, int par, const float (&be)[FK_MAX_BETAS], float (&r)[3]) {
+    const float* si = sh.sj + (size_t)i * 3 * sh.nb;
+    const float* sp = sh.sj + (size_t)(par < 0 ? 0 : par) * 3 * sh.nb;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < FK_MAX_BETAS; ++k)
+            if (k < sh.nb) r[c] = fmaf(par < 0 ? si[c * sh.nb + k] : si[c * sh.nb + k] - sp[c * sh.nb + k], be[k], r[c]);
+}
+
+struct FkShapedRel {
+    const FkSkel& sk;
+    const FkShape& sh;
+    const float (&be)[FK_MAX_BETAS];
+    __device__ __forceinline__ void operator()(int i, float (&r)[3]) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = sk.rel[i][c];
+        fk_shape_add(sh, i, sk.parent[i], be, r);
+    }
+};
+
 // phase 2: the chain, depth by depth (a barrier per depth). Joint i's transform replaces its local matrix in g[i] (planes 0..8 rotation, 9..11 posed
 // position); emit(i, pos, gi) runs on the thread that formed it, gi = g[i] + this lane. The image's scalar type follows g and its tile width is FRAMES
 // (13 planes of FRAMES per joint, FK_THREADS / FRAMES workers): k_fk and k_lbs_chain run float x FK_FRAMES, k_loss_terms (rgn_loss.hip) double x 16.
-template <int FRAMES = FK_FRAMES, class S, class Emit>
-__device__ __forceinline__ void fk_chain(S* g, const FkSkel& sk, int fl, int w, Emit&& emit) {
+// rel(i, r) gives joint i's offset from its parent's rest position (joint 0: its rest position) for this lane.
+template <int FRAMES = FK_FRAMES, class S, class Rel, class Emit>
+__device__ __forceinline__ void fk_chain_rel(S* g, const FkSkel& sk, int fl, int w, Rel&& rel, Emit&& emit) {
     constexpr int JSTRIDE = 13 * FRAMES, WORKERS = FK_THREADS / FRAMES;
     for (int l = 0; l < sk.nlevels; ++l) {
         for (int q = sk.level[l] + w; q < sk.level[l + 1]; q += WORKERS) {
@@ -115,14 +160,14 @@ __device__ __forceinline__ void fk_chain(S* g, const FkSkel& sk, int fl, int w, 
             S* gi = g + i * JSTRIDE + fl;
             S pos[3];
             if (par < 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) pos[c] = sk.rel[0][c];
+                rel(0, pos);
             } else {
                 const S* gp = g + par * JSTRIDE + fl;
-                S a[9], m[9];
+                S a[9], m[9], rl[3];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) { a[k] = gp[k * FRAMES]; m[k] = gi[k * FRAMES]; }
-                const S r0 = sk.rel[i][0], r1 = sk.rel[i][1], r2 = sk.rel[i][2];
+                rel(i, rl);
+                const S r0 = rl[0], r1 = rl[1], r2 = rl[2];
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {       // the 4x4 product of the chain, row r: rotation part and translation column
 #pragma unroll
@@ -136,6 +181,11 @@ __device__ __forceinline__ void fk_chain(S* g, const FkSkel& sk, int fl, int w, 
         }
         __syncthreads();
     }
+}
+
+template <int FRAMES = FK_FRAMES, class S, class Emit>
+__device__ __forceinline__ void fk_chain(S* g, const FkSkel& sk, int fl, int w, Emit&& emit) {
+    fk_chain_rel<FRAMES>(g, sk, fl, w, FkRestRel{sk}, emit);
 }
 
 }  // namespace rgn

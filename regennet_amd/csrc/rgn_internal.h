@@ -372,6 +372,24 @@ struct FkSkel {
 // x [B, R, C*P, T] -> xyz [B, J, 3*P, T] (+ rotmat [B,P,T,J,3,3] when not null); pose_rep / flags: RGN_POSE_* / RGN_R2X_* (regennet_hip.h)
 hipError_t launch_fk(const float* x, const uint8_t* mask, float* xyz, float* rotmat, int B, int T, int P, int J, int pose_rep, int flags,
                      const FkSkel& sk, hipStream_t s);
+// The body shape of every frame, read on the device (rgn_rot2xyz_shaped / rgn_rot2verts_shaped): frame (b, p, t)'s betas are
+// betas[b sb + p sp + t st + k], k < nb, and joint i's rest position is the skeleton's plus sum_k sj[i][.][k] betas[k].
+constexpr int FK_MAX_BETAS = 16;
+struct FkShape {
+    const float* sj;                 // shape_joints [J][3][nb], device
+    const float* betas;              // device
+    long long sb, sp, st;            // strides in floats; 0 broadcasts along that axis
+    int32_t nb;                      // 1 .. FK_MAX_BETAS
+};
+hipError_t launch_fk_shaped(const float* x, const uint8_t* mask, float* xyz, float* rotmat, int B, int T, int P, int J, int pose_rep, int flags,
+                            const FkSkel& sk, const FkShape& sh, hipStream_t s);
+// The argument checks the two shaped calls share, made before a handle is looked at: the complaint's text, or nullptr.
+inline const char* fk_check_shape(const float* shape_joints, int nb, const float* betas, long long sb, long long sp, long long st) {
+    if (!shape_joints || !betas) return "null shape_joints_dev or betas_dev";
+    if (nb < 1 || nb > FK_MAX_BETAS) return "nb outside [1, 16]";
+    if (sb < 0 || sp < 0 || st < 0) return "negative beta stride";
+    return nullptr;
+}
 // ---- rgn_loss.hip: the seven terms of training_losses, one workgroup per motion (rgn_loss_terms). target / output / cmotion [B, J + 1, 6, T],
 // mask [B, T] -> terms [B, 7]; foot[4]: the joints of the fc term; flags: RGN_LOSS_*
 size_t loss_lds_bytes(int J);

@@ -20,6 +20,10 @@
 // A workgroup is 4 waves on one frame tile; wave w takes every 4th vertex tile of the workgroup's range. Masking is by FRAME TILE: a tile whose 32
 // frames are all masked costs no arithmetic in either kernel and is filled with 0 (+ translation); a tile with some live frames computes all 32
 // lanes (a lane is a frame, an MFMA column) and selects 0 for the masked ones afterwards. No atomics, no cross-workgroup traffic, 64-bit indices.
+//
+// rgn_rot2verts_shaped: a body shape per frame, read on the device. k_lbs_shape is not launched and no shaped template exists; k_lbs_chain<true> takes
+// each lane's rest joints from its betas and writes them as further rows AHEAD of pf, k_lbs_skin<true> walks the shape planes and the posedirs planes
+// as one operand from v_template:   v_posed = v_template + [shapedirs; posedirs]^T . [betas; pf].   The <false> forms are the kernels described above.
 #include "rgn_fk.h"
 
 #include <cstring>
@@ -65,9 +69,14 @@ __global__ void k_lbs_shape(const float* __restrict__ vt, const float* __restric
 }
 
 // ---- stage 1: rows -> A, pf, hdr per frame tile ---------------------------------------------------------------------------------------------
+// SHAPED (rgn_rot2verts_shaped): the frame's betas sit in registers; the chain's offsets and A_j's rest joint come from them (rgn_fk.h), and they are
+// written as the first nbp rows of the tile's feature image, ahead of the pose feature, for the shape blend that rides k_lbs_skin's k-loop.
+// k_lbs_chain<false> looks at neither `sh` nor `nbp`.
+template <bool SHAPED>
 __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restrict__ x, const uint8_t* __restrict__ mask, float* __restrict__ rotmat,
                                                           float* __restrict__ hdr, float* __restrict__ Aw, float* __restrict__ pfw, int B, int T, int P, int J,
-                                                          int C, int rep, int flags, unsigned long long identity, const FkSkel sk, const LbsRest rest) {
+                                                          int C, int rep, int flags, unsigned long long identity, const FkSkel sk, const LbsRest rest,
+                                                          const FkShape sh, int nbp) {
     extern __shared__ __attribute__((aligned(16))) float g[];       // [J][13][32]
     const int fl = threadIdx.x & (FK_FRAMES - 1), w = threadIdx.x / FK_FRAMES;
     const long long tile = blockIdx.x;
@@ -81,7 +90,17 @@ __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restric
     }
     const bool any = __syncthreads_or(keep);        // a fully masked tile costs no arithmetic (the matrices rotmat asks for excepted)
     if (!any && !rotmat) return;
-    const int K = 9 * (J - 1);
+    const int K = 9 * (J - 1), k0 = SHAPED ? nbp : 0, KT = k0 + K;      // the tile's feature image: [k0 beta rows | K pose rows][32]
+    [[maybe_unused]] float be[FK_MAX_BETAS];
+    if constexpr (SHAPED) {
+        fk_load_betas(sh, fr, be);
+        if (w == 0 && any) {
+            float* pb = pfw + tile * KT * FK_FRAMES + fl;
+#pragma unroll
+            for (int k = 0; k < FK_MAX_BETAS; ++k)
+                if (k < nbp) pb[k * FK_FRAMES] = be[k];
+        }
+    }
     fk_local_matrices(g, fr, T, J, rep, flags & RGN_R2X_GLOB, sk, fl, w, [&](int i, float (&m)[9]) {
         if (rotmat && fr.live) {                    // the matrices as rgn_rot2xyz returns them: before identity joints are replaced
             float* rm = rotmat + (fr.f * J + i) * 9;
@@ -93,16 +112,18 @@ __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restric
             for (int k = 0; k < 9; ++k) m[k] = (k & 3) == 0 ? 1.f : 0.f;
         }
         if (i > 0 && any) {                         // pose feature (R_i - I), row-major
-            float* pf = pfw + (tile * K + 9 * (i - 1)) * FK_FRAMES + fl;
+            float* pf = pfw + (tile * KT + k0 + 9 * (i - 1)) * FK_FRAMES + fl;
 #pragma unroll
             for (int k = 0; k < 9; ++k) pf[k * FK_FRAMES] = (k & 3) == 0 ? m[k] - 1.f : m[k];
         }
     });
     if (!any) return;
     __syncthreads();
-    fk_chain(g, sk, fl, w, [&](int i, const float (&pos)[3], const float* gi) {
+    auto emit = [&](int i, const float (&pos)[3], const float* gi) {
         float* a = Aw + (tile * J + i) * 12 * FK_FRAMES + fl;
-        const float j0 = rest.j[i][0], j1 = rest.j[i][1], j2 = rest.j[i][2];
+        float ji[3] = {rest.j[i][0], rest.j[i][1], rest.j[i][2]};
+        if constexpr (SHAPED) fk_shape_add(sh, i, -1, be, ji);          // the frame's own rest joint
+        const float j0 = ji[0], j1 = ji[1], j2 = ji[2];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {               // A_i = [Rg | tg - Rg . j_i]
             const float r0 = gi[(3 * r) * FK_FRAMES], r1 = gi[(3 * r + 1) * FK_FRAMES], r2 = gi[(3 * r + 2) * FK_FRAMES];
@@ -111,7 +132,9 @@ __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restric
             a[(4 * r + 2) * FK_FRAMES] = r2;
             a[(4 * r + 3) * FK_FRAMES] = pos[r] - (r0 * j0 + r1 * j1 + r2 * j2);
         }
-    });
+    };
+    if constexpr (SHAPED) fk_chain_rel(g, sk, fl, w, FkShapedRel{sk, sh, be}, emit);
+    else fk_chain(g, sk, fl, w, emit);
 }
 
 // ---- stage 2: pose blend + skinning, one wave per (32 frames x 32 vertices) ------------------------------------------------------------------
@@ -122,10 +145,15 @@ __device__ __forceinline__ void lbs_load_pd(float (&a)[4][3], const float* __res
         for (int c = 0; c < 3; ++c) a[u][c] = p[(size_t)(6 * u + c) * Vp];
 }
 
+// SHAPED (rgn_rot2verts_shaped): the shape blend rides the same k-loop. The body keeps its shape directions as nbp further planes directly AHEAD of the
+// posedirs planes, the shaped chain kernel writes the frame's betas as nbp rows ahead of the pose feature, so `pd` / `Kp` / `krows` name the longer
+// operands and `vsh` the template's planes: v_posed = v_template + [shapedirs; posedirs]^T . [betas; pf], summed in that order like v_shaped was.
+// k_lbs_skin<false> does not look at `krows`.
+template <bool SHAPED>
 __global__ __launch_bounds__(LBS_THREADS, 2) void k_lbs_skin(const float* __restrict__ vsh, const float* __restrict__ hdr, const float* __restrict__ Aw,
                                                              const float* __restrict__ pfw, const float* __restrict__ pd, const float* __restrict__ Wt,
                                                              float* __restrict__ out, int B, int T, int P, int V, int Vp, int J, int Jp, int Kp, int pose,
-                                                             int tiles_per_wg, int addtr) {
+                                                             int tiles_per_wg, int addtr, int krows) {
     extern __shared__ __attribute__((aligned(16))) float spf[];     // [Kp][32]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fl = lane & 31, h = lane >> 5;
     const long long tile = blockIdx.x, NF = (long long)B * P * T, f = tile * FK_FRAMES + fl;
@@ -139,7 +167,7 @@ __global__ __launch_bounds__(LBS_THREADS, 2) void k_lbs_skin(const float* __rest
     const bool any = __syncthreads_or(keep);
     float* __restrict__ ob = out + ((b * V * 3 * P + 3 * p) * (long long)T + t);                // + vertex * 3 P T + channel * T
     const long long vstride = (long long)3 * P * T;
-    const int K = 9 * (J - 1);
+    const int K = SHAPED ? krows : 9 * (J - 1);     // rows of the tile's feature image in the workspace
     if (any && pose) {
         const float* src = pfw + tile * K * FK_FRAMES;
         for (int i = threadIdx.x; i < Kp * FK_FRAMES; i += LBS_THREADS) spf[i] = i < K * FK_FRAMES ? src[i] : 0.f;
@@ -212,15 +240,18 @@ __global__ __launch_bounds__(LBS_THREADS, 2) void k_lbs_skin(const float* __rest
     }
 }
 
+
 }  // namespace
 
 // ---- the handle ------------------------------------------------------------------------------------------------------------------------------
 struct rgn_body_ctx {
-    int device = 0, V = 0, Vp = 0, J = 0, Jp = 0, nb = 0, K = 0, Kp = 0;
+    int device = 0, V = 0, Vp = 0, J = 0, Jp = 0, nb = 0, nbp = 0, K = 0, Kp = 0;
     bool pose = false;
     unsigned long long identity = 0;
-    float* blob = nullptr;                          // v_template [V,3] | shapedirs [V,3,nb] | posedirs [Kp][3][Vp] | weights [Jp][Vp]
-    float *vt = nullptr, *sd = nullptr, *pd = nullptr, *wt = nullptr;
+    // v_template [V,3] | shapedirs [V,3,nb] | v_template as planes [3][Vp] | shapedirs as planes [nbp][3][Vp] | posedirs [Kp][3][Vp] | weights [Jp][Vp]
+    // (the shape planes end where the posedirs planes begin: the shaped skinning kernel walks both as one operand of nbp + Kp rows)
+    float* blob = nullptr;
+    float *vt = nullptr, *sd = nullptr, *vtp = nullptr, *sdp = nullptr, *pd = nullptr, *wt = nullptr;
     std::string err;
     int fail(int code, const std::string& m) {
         err = m;
@@ -267,6 +298,18 @@ LbsWork carve(const rgn_body_ctx* c, long long NF) {
     return w;
 }
 
+// ... of rgn_rot2verts_shaped: no shaped template, and nbp beta rows ahead of each tile's pose feature
+LbsWork carve_shaped(const rgn_body_ctx* c, long long NF) {
+    const uint64_t ntiles = (uint64_t)((NF + FK_FRAMES - 1) / FK_FRAMES);
+    LbsWork w;
+    w.vsh = 0;
+    w.hdr = 0;
+    w.A = w.hdr + ntiles * 4 * FK_FRAMES;
+    w.pf = w.A + ntiles * c->J * 12 * FK_FRAMES;
+    w.bytes = (w.pf + ntiles * (c->nbp + c->K) * FK_FRAMES) * sizeof(float);
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -306,15 +349,23 @@ int rgn_body_create(int32_t device, int32_t V, int32_t J, int32_t nb, const floa
         c->J = J;
         c->Jp = round_up(J, 2);
         c->nb = nb;
+        c->nbp = round_up(nb, LBS_KGROUP);
         c->K = 9 * (J - 1);
         c->Kp = round_up(c->K, LBS_KGROUP);
         c->pose = posedirs != nullptr && J > 1;     // (no posedirs: no pose blend shapes)
         c->identity = identity;
         const size_t n_vt = (size_t)3 * V, n_sd = (size_t)3 * V * nb, n_pd = c->pose ? (size_t)c->Kp * 3 * c->Vp : 0, n_wt = (size_t)c->Jp * c->Vp;
-        std::vector<float> host(n_vt + n_sd + n_pd + n_wt, 0.f);
-        float *hvt = host.data(), *hsd = hvt + n_vt, *hpd = hsd + n_sd, *hwt = hpd + n_pd;
+        const size_t n_vtp = nb ? (size_t)3 * c->Vp : 0, n_sdp = (size_t)c->nbp * 3 * c->Vp;
+        std::vector<float> host(n_vt + n_sd + n_vtp + n_sdp + n_pd + n_wt, 0.f);
+        float *hvt = host.data(), *hsd = hvt + n_vt, *hvtp = hsd + n_sd, *hsdp = hvtp + n_vtp, *hpd = hsdp + n_sdp, *hwt = hpd + n_pd;
         std::memcpy(hvt, v_template, n_vt * sizeof(float));
         if (n_sd) std::memcpy(hsd, shapedirs, n_sd * sizeof(float));
+        if (nb)                                     // the same component planes for the template and the shape directions (pad rows and vertices 0)
+            for (int v = 0; v < V; ++v)
+                for (int cc = 0; cc < 3; ++cc) {
+                    hvtp[(size_t)cc * c->Vp + v] = v_template[3 * v + cc];
+                    for (int k = 0; k < nb; ++k) hsdp[((size_t)k * 3 + cc) * c->Vp + v] = shapedirs[((size_t)3 * v + cc) * nb + k];
+                }
         if (c->pose)                                // [K][3 V] -> [Kp][3][Vp]: component planes, so that a lane's 32 vertices are consecutive floats
             for (int k = 0; k < c->K; ++k)
                 for (int v = 0; v < V; ++v)
@@ -330,15 +381,24 @@ int rgn_body_create(int32_t device, int32_t V, int32_t J, int32_t nb, const floa
         }
         c->vt = c->blob;
         c->sd = c->vt + n_vt;
-        c->pd = c->sd + n_sd;
+        c->vtp = c->sd + n_sd;
+        c->sdp = c->vtp + n_vtp;
+        c->pd = c->sdp + n_sdp;
         c->wt = c->pd + n_pd;
         // (set here, not in the call: rgn_rot2verts may be running under a stream capture.) Dynamic LDS on top of the few static bytes of the
         // block-wide vote: k_lbs_chain J x 13 x 32 floats <= 104 KB; k_lbs_skin Kp x 32 floats <= 71 KB, which keeps two workgroups on a CU
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_chain), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_chain<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            FK_MAX_JOINTS * FK_JSTRIDE * (int)sizeof(float));
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_skin), hipFuncAttributeMaxDynamicSharedMemorySize,
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_skin<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     round_up(9 * (FK_MAX_JOINTS - 1), LBS_KGROUP) * FK_FRAMES * (int)sizeof(float));
+        // ... and their shaped forms: the same chain image; the feature image longer by at most 16 beta rows (<= 73 KB: still two workgroups on a CU)
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_chain<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    FK_MAX_JOINTS * FK_JSTRIDE * (int)sizeof(float));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_skin<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (LBS_MAX_BETAS + round_up(9 * (FK_MAX_JOINTS - 1), LBS_KGROUP)) * FK_FRAMES * (int)sizeof(float));
         if (e != hipSuccess) {
             (void)hipFree(dev);
             return bad(RGN_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
@@ -407,15 +467,78 @@ int rgn_rot2verts(rgn_body_handle h, const float* x, const uint8_t* mask, int32_
         const unsigned ntiles = (unsigned)((NF + FK_FRAMES - 1) / FK_FRAMES);
         hipLaunchKernelGGL(k_lbs_shape, dim3((3 * h->Vp + 255) / 256), dim3(256), 0, s, h->vt, h->sd, wf + w.vsh, h->V, h->Vp, h->nb, be);
         LBS_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(k_lbs_chain, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, x, mask, rotmat, wf + w.hdr, wf + w.A, wf + w.pf, B, T,
-                           num_person, J, C, pose_rep, flags, h->identity, sk, rest);
+        hipLaunchKernelGGL(k_lbs_chain<false>, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, x, mask, rotmat, wf + w.hdr, wf + w.A, wf + w.pf, B, T,
+                           num_person, J, C, pose_rep, flags, h->identity, sk, rest, FkShape{}, 0);
         LBS_HIP(h, hipGetLastError());
         const int vtiles = h->Vp / 32;
         // vertex tiles per workgroup (one pf image in LDS serves them all): 8 where that still leaves a few workgroups per CU, else one per wave
         const int tpw = (long long)ntiles * ((vtiles + 7) / 8) >= 2048 ? 8 : LBS_WAVES;
         const bool addtr = (flags & RGN_R2X_TRANSLATION) && (flags & RGN_R2X_VERTSTRANS);
-        hipLaunchKernelGGL(k_lbs_skin, dim3(ntiles, (vtiles + tpw - 1) / tpw), dim3(LBS_THREADS), h->pose ? (size_t)h->Kp * FK_FRAMES * sizeof(float) : 0, s,
-                           wf + w.vsh, wf + w.hdr, wf + w.A, wf + w.pf, h->pd, h->wt, verts, B, T, num_person, h->V, h->Vp, J, h->Jp, h->Kp, h->pose ? 1 : 0, tpw, addtr ? 1 : 0);
+        hipLaunchKernelGGL(k_lbs_skin<false>, dim3(ntiles, (vtiles + tpw - 1) / tpw), dim3(LBS_THREADS), h->pose ? (size_t)h->Kp * FK_FRAMES * sizeof(float) : 0, s,
+                           wf + w.vsh, wf + w.hdr, wf + w.A, wf + w.pf, h->pd, h->wt, verts, B, T, num_person, h->V, h->Vp, J, h->Jp, h->Kp, h->pose ? 1 : 0, tpw, addtr ? 1 : 0, 0);
+        LBS_HIP(h, hipGetLastError());
+        return RGN_OK;
+    });
+}
+
+int rgn_rot2verts_shaped_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes) {
+    return body_guard(b, "rgn_rot2verts_shaped_workspace", [&]() -> int {
+        if (!b) return RGN_ERR_INVALID_ARG;
+        if (!nbytes) return b->fail(RGN_ERR_INVALID_ARG, "rgn_rot2verts_shaped_workspace: null nbytes");
+        if (B < 1 || T < 1 || num_person < 1) return b->fail(RGN_ERR_INVALID_ARG, "rgn_rot2verts_shaped_workspace: B, T or num_person < 1");
+        *nbytes = carve_shaped(b, (long long)B * num_person * T).bytes;
+        return RGN_OK;
+    });
+}
+
+int rgn_rot2verts_shaped(rgn_body_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t T, const float* rest_joints, const int32_t* parents,
+                         const float* shape_joints, int32_t nb, const float* betas, int64_t beta_stride_b, int64_t beta_stride_p, int64_t beta_stride_t,
+                         int32_t pose_rep, int32_t num_person, int32_t flags, const float* glob_rot, float* verts, float* rotmat, void* work,
+                         uint64_t work_bytes, void* stream) {
+    return body_guard(h, "rgn_rot2verts_shaped", [&]() -> int {
+        // the arguments first, the handle after them (text: rgn_body_last_error(NULL) while there is no handle)
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_rot2verts_shaped: " + m);
+            g_body_create_error = "rgn_rot2verts_shaped: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        if (!x || !verts || !rest_joints || !parents) return bad("null x, verts, rest_joints or parents");
+        if (const char* why = fk_check_shape(shape_joints, nb, betas, beta_stride_b, beta_stride_p, beta_stride_t)) return bad(why);
+        if (B < 1 || T < 1) return bad("B < 1 or T < 1");
+        if (num_person < 1) return bad("num_person < 1");
+        if (pose_rep < RGN_POSE_ROT6D || pose_rep > RGN_POSE_ROTMAT) return bad("unknown pose_rep");
+        if (flags & ~(RGN_R2X_TRANSLATION | RGN_R2X_GLOB | RGN_R2X_VERTSTRANS)) return bad("unknown flag");
+        if (!(flags & RGN_R2X_GLOB) && !glob_rot) return bad("glob_rot is required when RGN_R2X_GLOB is not set");
+        if (!h) return bad("null handle");
+        if (nb > h->nb) return bad(std::to_string(nb) + " betas, but the body holds " + std::to_string(h->nb) + " shape directions");
+        const int J = h->J;
+        FkSkel sk;
+        int at = -1;
+        if (const char* why = fk_build_skel(J, rest_joints, parents, sk, at))
+            return bad(at < 0 ? std::string(why) : "parents[" + std::to_string(at) + "] outside [0, " + std::to_string(at) + ")");
+        if (!(flags & RGN_R2X_GLOB)) axis_angle_to_matrix_f32(glob_rot, sk.glob);
+        const long long NF = (long long)B * num_person * T;
+        const LbsWork w = carve_shaped(h, NF);
+        float* const wf = reinterpret_cast<float*>(work);
+        if (!work || work_bytes < w.bytes)
+            return bad("workspace of " + std::to_string(work_bytes) + " bytes, " + std::to_string(w.bytes) + " needed (rgn_rot2verts_shaped_workspace)");
+        LbsRest rest;
+        std::memcpy(rest.j, rest_joints, sizeof(float) * 3 * J);
+        const FkShape sh{shape_joints, betas, beta_stride_b, beta_stride_p, beta_stride_t, nb};
+        LBS_HIP(h, hipSetDevice(h->device));
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        const int C = pose_rep == RGN_POSE_ROT6D ? 6 : pose_rep == RGN_POSE_ROTVEC ? 3 : pose_rep == RGN_POSE_ROTQUAT ? 4 : 9;
+        const unsigned ntiles = (unsigned)((NF + FK_FRAMES - 1) / FK_FRAMES);
+        hipLaunchKernelGGL(k_lbs_chain<true>, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, x, mask, rotmat, wf + w.hdr, wf + w.A,
+                           wf + w.pf, B, T, num_person, J, C, pose_rep, flags, h->identity, sk, rest, sh, h->nbp);
+        LBS_HIP(h, hipGetLastError());
+        const int vtiles = h->Vp / 32;
+        const int tpw = (long long)ntiles * ((vtiles + 7) / 8) >= 2048 ? 8 : LBS_WAVES;         // (as rgn_rot2verts)
+        const bool addtr = (flags & RGN_R2X_TRANSLATION) && (flags & RGN_R2X_VERTSTRANS);
+        const int Kp = h->nbp + (h->pose ? h->Kp : 0);                                         // k-rows of the one operand: shape planes, then posedirs
+        hipLaunchKernelGGL(k_lbs_skin<true>, dim3(ntiles, (vtiles + tpw - 1) / tpw), dim3(LBS_THREADS), (size_t)Kp * FK_FRAMES * sizeof(float), s, h->vtp,
+                           wf + w.hdr, wf + w.A, wf + w.pf, h->sdp, h->wt, verts, B, T, num_person, h->V, h->Vp, J, h->Jp, Kp, 1, tpw, addtr ? 1 : 0,
+                           h->nbp + h->K);
         LBS_HIP(h, hipGetLastError());
         return RGN_OK;
     });

@@ -134,6 +134,7 @@ class Rotation2xyz:
         self.skeleton = check_body(skeleton) if with_mesh else check_skeleton(skeleton)
         self.mesh = self.skeleton.get("mesh", None)     # None: a skeleton file, joints only
         self._body, self._work = None, None             # (BodyEngine, its device), workspace tensor: made at the first 'vertices' call
+        self._sj_dev = {}                               # (device, nb) -> shape_joints on that device, for per-frame betas
         self.model = model
         self.smpl_model = None          # (the reference keeps its body layer here; there is none)
         sj = self.skeleton["shape_joints"]
@@ -167,6 +168,58 @@ class Rotation2xyz:
                 raise ValueError(f"betas {b.shape}: expected [nb] or [N, nb]")
         return b
 
+    def shape_plan(self, betas, beta, betas_per_motion, mask, B, T, P, vertices=False):
+        """Which route a call's shape arguments take, decided and checked on the host: None where the call has ONE shape and rest_joints() serves
+        it (betas None, 1-D, or 2-D with equal rows: today's path, today's bits), else ('frames' | 'motions', rows) for the per-frame kernels.
+          betas [N_live, nb] with differing rows  the reference's meaning: row n is the n-th unmasked frame in (b, t) order, for every person
+          betas_per_motion [B, nb] | [B, P, nb]   one shape per motion, or per motion and person
+        Fewer betas than the file's shape directions count the rest as 0; more, or a file without them, is a ValueError."""
+        if betas_per_motion is not None:
+            if betas is not None or beta != 0:
+                raise ValueError("betas_per_motion and betas / beta are mutually exclusive: give the shapes one way")
+            rows = torch.as_tensor(betas_per_motion).detach()
+            if rows.ndim not in (2, 3) or tuple(rows.shape[:-1]) not in ((B,), (B, P)):
+                raise ValueError(f"betas_per_motion {tuple(rows.shape)}: expected [B, nb] = [{B}, nb] or [B, P, nb] = [{B}, {P}, nb]")
+            kind = "motions"
+        else:
+            if betas is None or getattr(betas, "ndim", 0) != 2:
+                return None
+            rows = torch.as_tensor(betas).detach()
+            if rows.shape[0] == 0 or bool((rows == rows[:1]).all()):
+                return None
+            n_live = B * T if mask is None else int(torch.as_tensor(mask).reshape(B, T).bool().sum())
+            if rows.shape[0] != n_live:
+                raise ValueError(f"betas has {rows.shape[0]} rows, but the mask leaves {n_live} frames (one row per unmasked frame, in (b, t) order)")
+            kind = "frames"
+        sj, nb = self.skeleton["shape_joints"], int(rows.shape[-1])
+        if sj is None or sj.shape[2] == 0:
+            raise ValueError("per-frame betas need `shape_joints` in the skeleton file")
+        if vertices and self.mesh["shapedirs"] is None:
+            raise ValueError("per-frame betas need `shapedirs` in the body file")
+        if not 1 <= nb <= sj.shape[2]:
+            raise ValueError(f"{nb} betas but the {'body' if vertices else 'skeleton'} file holds {sj.shape[2]} shape directions")
+        return kind, rows
+
+    def device_shape(self, plan, mask, B, T, P, dev):
+        """shape_plan's rows on the device -> (betas fp32, (stride_b, stride_p, stride_t) in elements, shape_joints fp32 [J, 3, nb]) as
+        rgn_rot2xyz_shaped / rgn_rot2verts_shaped take them. `mask`: bool [B, T] on dev, or None."""
+        kind, rows = plan
+        nb = int(rows.shape[-1])
+        rows = rows.to(device=dev, dtype=torch.float32).contiguous()
+        if kind == "motions":
+            bt, strides = rows, ((nb, 0, 0) if rows.ndim == 2 else (P * nb, nb, 0))
+        else:
+            if mask is None:
+                bt = rows.reshape(B, T, nb)
+            else:                               # scattered to [B, T, nb]; the masked frames' rows are never read
+                bt = torch.zeros((B, T, nb), device=dev, dtype=torch.float32)
+                bt[mask] = rows
+            strides = (T * nb, 0, nb)
+        key = (str(dev), nb)
+        if key not in self._sj_dev:             # the first nb directions, re-packed [J, 3, nb]: made once per device
+            self._sj_dev[key] = torch.from_numpy(np.ascontiguousarray(self.skeleton["shape_joints"][:, :, :nb], dtype=np.float32)).to(dev)
+        return bt, strides, self._sj_dev[key]
+
     def body_engine(self, dev):
         """The device-resident mesh data for `dev`: created at first use, rebuilt when the model has moved."""
         if self._body is None or self._body[1] != dev:
@@ -176,7 +229,7 @@ class Rotation2xyz:
         return self._body[0]
 
     def __call__(self, x, mask, pose_rep, translation, glob, jointstype, vertstrans, betas=None, beta=0, glob_rot=None, num_person=1,
-                 get_rotations_back=False, **kwargs):
+                 get_rotations_back=False, betas_per_motion=None, **kwargs):
         if pose_rep == "xyz":
             return x
         if not glob and glob_rot is None:
@@ -200,8 +253,9 @@ class Rotation2xyz:
             raise ValueError(f"x {tuple(x.shape)}: a {J}-joint skeleton with pose_rep={pose_rep!r}, glob={bool(glob)}, translation={bool(translation)}, "
                              f"num_person={P} takes [B, {want}, {C * P}, T]")
         model = self.model
+        plan = self.shape_plan(betas, beta, betas_per_motion, mask, B, T, P, vertices)      # not None: a shape per frame, read on the device
         if vertices:
-            return self._vertices(x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back)
+            return self._vertices(x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan)
         eng = model._engine if (model._engine is not None and not model._engine_stale) else model._get_engine(B, T)[0]
         dev = next(model.parameters()).device
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
@@ -210,8 +264,13 @@ class Rotation2xyz:
         rot = torch.empty((B, P, T, J, 3, 3), device=dev, dtype=torch.float32) if get_rotations_back else None
         flags = (_lib.R2X_TRANSLATION if translation else 0) | (_lib.R2X_GLOB if glob else 0) | (_lib.R2X_VERTSTRANS if vertstrans else 0)
         gr = None if glob else np.asarray(glob_rot, dtype=np.float32).reshape(3)
-        eng.rot2xyz(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, out, rot,
-                    dist_util.stream_handle(dev))
+        if plan is not None:
+            shape = self.device_shape(plan, mc, B, T, P, dev)
+            eng.rot2xyz_shaped(xc, mc, self.skeleton["rest_joints"], self.skeleton["parents"], shape[2], shape[0], shape[1], _lib.POSE_REP[pose_rep], P,
+                               flags, gr, out, rot, dist_util.stream_handle(dev))
+        else:
+            eng.rot2xyz(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, out, rot,
+                        dist_util.stream_handle(dev))
         out = out.to(x.device)
         if get_rotations_back:      # Rotation2xyz (:152-153): the last person's matrices of the unmasked frames, without and with joint 0
             r = rot[:, -1] if mc is None else rot[:, -1][mc]
@@ -219,13 +278,16 @@ class Rotation2xyz:
             return out, r[:, 1:], r[:, 0]
         return out
 
-    def _vertices(self, x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back):
-        """jointstype='vertices' (:236-249 / :303-321): [B, V, 3 P, T] by linear blend skinning on the device (rgn_rot2verts)."""
+    def _vertices(self, x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan=None):
+        """jointstype='vertices' (:236-249 / :303-321): [B, V, 3 P, T] by linear blend skinning on the device (rgn_rot2verts; with a shape per
+        frame rgn_rot2verts_shaped)."""
         J, V = len(self.skeleton["parents"]), self.mesh["v_template"].shape[0]
         B, T = x.shape[0], x.shape[-1]
         dev = next(self.model.parameters()).device
         body = self.body_engine(dev)
-        b = self.betas_vector(betas, beta)
+        mc = None if mask is None else mask.to(device=dev).reshape(B, T).bool().contiguous()
+        shape = None if plan is None else self.device_shape(plan, mc, B, T, P, dev)
+        b = np.zeros(1) if shape is not None else self.betas_vector(betas, beta)
         bv = None
         if b.any():
             if body.nb == 0:
@@ -235,17 +297,20 @@ class Rotation2xyz:
             bv = np.zeros(body.nb, np.float32)
             bv[:len(b)] = b
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
-        mc = None if mask is None else mask.to(device=dev).reshape(B, T).bool().contiguous()
         out = torch.empty((B, V, 3 * P, T), device=dev, dtype=torch.float32)
         rot = torch.empty((B, P, T, J, 3, 3), device=dev, dtype=torch.float32) if get_rotations_back else None
-        need = body.workspace_bytes(B, T, P)
+        need = body.workspace_bytes(B, T, P) if shape is None else body.workspace_bytes_shaped(B, T, P)
         if self._work is None or self._work.numel() < need:
             self._work = torch.empty(need, device=dev, dtype=torch.uint8)
         flags = (_lib.R2X_TRANSLATION if translation else 0) | (_lib.R2X_GLOB if glob else 0) | (_lib.R2X_VERTSTRANS if vertstrans else 0)
         gr = None if glob else np.asarray(glob_rot, dtype=np.float32).reshape(3)
         with torch.cuda.device(dev):
-            body.rot2verts(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, bv, out, rot,
-                           self._work, dist_util.stream_handle(dev))
+            if shape is not None:
+                body.rot2verts_shaped(xc, mc, self.skeleton["rest_joints"], self.skeleton["parents"], shape[2], shape[0], shape[1],
+                                      _lib.POSE_REP[pose_rep], P, flags, gr, out, rot, self._work, dist_util.stream_handle(dev))
+            else:
+                body.rot2verts(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, bv, out, rot,
+                               self._work, dist_util.stream_handle(dev))
         out = out.to(x.device)
         if get_rotations_back:
             r = rot[:, -1] if mc is None else rot[:, -1][mc]

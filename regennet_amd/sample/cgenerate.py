@@ -10,7 +10,9 @@ skeleton) it also stores 'motion', the joint positions `model.rot2xyz` gives for
 kinematics on the device, no body model needed. With `--vertices` and a `--skeleton` that carries a mesh (a body file of
 `tools/make_skeleton.py --mesh`; `synthetic`: synth.make_body) it also stores 'vertices' [N, V, 3, T] and 'faces', the meshes the reference
 renders from (visualize/vis_utils.py:35-41), and `--obj_dir DIR` writes them as DIR/sample{i:02d}/frame{t:03d}.obj. `--render_dir DIR` draws them on the
-device (utils/render.py; `--render_size N`, default 1024 as render/crendermotion.py:109-110) and writes DIR/sample{i:02d}/frame{t:03d}.png."""
+device (utils/render.py; `--render_size N`, default 1024 as render/crendermotion.py:109-110) and writes DIR/sample{i:02d}/frame{t:03d}.png.
+`--betas_npz FILE` ('betas' [N, nb]; `synthetic`: seeded N(0, 1)) gives every generated sample its own body shape - joints and meshes alike, read
+per frame on the device (`betas_per_motion`) - cycled over repetitions like the actor clips, and stores 'betas' beside them."""
 import os
 import time
 import types
@@ -60,17 +62,37 @@ def set_skeleton(model, args):
     return True
 
 
-def joint_positions(model, args, sample, y, jointstype=None):
-    """The reference's closing call (cgenerate.py:154-158) on this model's rot2xyz: [B, njoints, nfeats, T] -> [B, J, 3, T]."""
+def load_betas(args, n, nb):
+    """--betas_npz FILE | synthetic -> fp32 [N, nb'] body shapes, one per generated sample (None without the option). `synthetic`: `n` seeded
+    N(0, 1) shapes over the skeleton's `nb` directions."""
+    if not getattr(args, "betas_npz", ""):
+        return None
+    if not args.skeleton:
+        raise SystemExit("--betas_npz shapes the joints and meshes of --skeleton: give one")
+    if args.betas_npz == "synthetic":
+        return np.random.Generator(np.random.PCG64(args.seed)).standard_normal((n, nb)).astype(np.float32)
+    with np.load(args.betas_npz, allow_pickle=False) as z:
+        if "betas" not in z.files:
+            raise SystemExit(f"--betas_npz: {args.betas_npz} holds no 'betas'")
+        betas = np.ascontiguousarray(z["betas"], dtype=np.float32)
+    if betas.ndim != 2 or not len(betas) or not 1 <= betas.shape[1] <= nb:
+        raise SystemExit(f"--betas_npz: 'betas' {betas.shape} is not [N, nb] with 1 <= nb <= {nb} (the skeleton file's shape directions)")
+    return betas
+
+
+def joint_positions(model, args, sample, y, jointstype=None, betas=None):
+    """The reference's closing call (cgenerate.py:154-158) on this model's rot2xyz: [B, njoints, nfeats, T] -> [B, J, 3, T]; betas [B, nb]: a body
+    shape per motion (--betas_npz)."""
     pose_rep = "xyz" if model.data_rep in ("xyz", "hml_vec") else model.data_rep
     mask = None if pose_rep == "xyz" else y["mask"].reshape(sample.shape[0], sample.shape[-1]).bool()
+    shapes = {} if betas is None or pose_rep == "xyz" else {"betas_per_motion": torch.from_numpy(np.ascontiguousarray(betas))}
     return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=jointstype or args.body_model, vertstrans=True,
-                         num_person=1, betas=None, beta=0, glob_rot=None, get_rotations_back=False)
+                         num_person=1, betas=None, beta=0, glob_rot=None, get_rotations_back=False, **shapes)
 
 
-def vertex_positions(model, args, sample, y):
+def vertex_positions(model, args, sample, y, betas=None):
     """... and the call the reference's mesh export makes (visualize/vis_utils.py:35-41): jointstype='vertices' -> [B, V, 3, T]."""
-    return joint_positions(model, args, sample, y, jointstype="vertices")
+    return joint_positions(model, args, sample, y, jointstype="vertices", betas=betas)
 
 
 def mesh_results(model, args, all_vertices, lengths):
@@ -139,7 +161,8 @@ def main(argv=None):
     with_motion = set_skeleton(inner, args)
     with_vertices = with_motion and args.vertices
     nverts = inner.rot2xyz.mesh["v_template"].shape[0] if with_vertices else 0
-    all_outputs, all_cmotions, all_motions, all_vertices, time_all = [], [], [], [], 0.0
+    shapes = load_betas(args, args.num_samples, inner.rot2xyz.num_betas if with_motion else 0)     # [N, nb] | None: cycled like the actor clips
+    all_outputs, all_cmotions, all_motions, all_vertices, all_betas, time_all = [], [], [], [], [], 0.0
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
 
     def make_y(rep_i):
@@ -178,11 +201,15 @@ def main(argv=None):
             print("Generating time consumption: %s ms" % ((t_end - t_start) * 1000))
         all_outputs.append(dist_util.all_gather_samples(smooth, B).cpu().numpy())
         all_cmotions.append(dist_util.all_gather_samples(y["cmotion"], B).cpu().numpy())
+        betas = None
+        if shapes is not None:                     # sample i of this repetition wears shape (i + rep_i B) mod N
+            all_betas.append(shapes[(np.arange(B) + rep_i * B) % len(shapes)])
+            betas = all_betas[-1][lo:hi]
         if with_motion:                            # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
-            motion = joint_positions(inner, args, smooth, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
+            motion = joint_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
             all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if with_vertices:
-            verts = vertex_positions(inner, args, smooth, y) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)
+            verts = vertex_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)
             all_vertices.append(dist_util.all_gather_samples(verts, B).cpu().numpy())
         if rank == 0:
             print(f"created {len(all_outputs) * B} samples")
@@ -195,6 +222,7 @@ def main(argv=None):
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
         np.save(npy_path, {**({"motion": np.concatenate(all_motions)} if with_motion else {}),
+                           **({"betas": np.concatenate(all_betas)} if all_betas else {}),
                            **(mesh_results(inner, args, all_vertices, np.full((len(all_outputs) * B,), n_frames)) if with_vertices else {}),
                            "output": np.concatenate(all_outputs), "cmotion": np.concatenate(all_cmotions),
                            "lengths": np.full((len(all_outputs) * B,), n_frames), "num_samples": args.num_samples,

@@ -126,6 +126,8 @@ def main(argv=None):
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
     with_motion = set_skeleton(inner, args)
+    if getattr(args, "betas_npz", ""):
+        raise SystemExit("--betas_npz is served by cgenerate and render; the edit CLI draws every motion on the file's one shape")
 
     def make_y(rep_i):
         idx = (np.arange(lo, hi) + rep_i * B) % len(clips)

@@ -36,6 +36,23 @@ def load_results(path, num_person):
     return out, texts
 
 
+def load_betas(spec, n, nb, num_person, seed=0):
+    """--betas_npz FILE | synthetic -> fp32 [N, num_person, nb'] (None without the option). The file's 'betas' is [N, 2, nb], actor then reactor;
+    one person is the reactor alone, like 'output'. `synthetic`: `n` seeded N(0, 1) pairs over the body's `nb` directions."""
+    if not spec:
+        return None
+    if spec == "synthetic":
+        betas = np.random.Generator(np.random.PCG64(seed)).standard_normal((n, 2, nb)).astype(np.float32)
+    else:
+        with np.load(spec, allow_pickle=False) as z:
+            if "betas" not in z.files:
+                raise SystemExit(f"--betas_npz: {spec} holds no 'betas'")
+            betas = np.ascontiguousarray(z["betas"], dtype=np.float32)
+        if betas.ndim != 3 or not len(betas) or betas.shape[1] != 2 or not 1 <= betas.shape[2] <= nb:
+            raise SystemExit(f"--betas_npz: 'betas' {betas.shape} is not [N, 2, nb] (actor, reactor) with 1 <= nb <= {nb} (the body file's shape directions)")
+    return np.ascontiguousarray(betas[:, 2 - num_person:])
+
+
 def write_mp4(path, frames, fps=30):
     """Only where imageio is there (crendermotion.py:21, 40-42); returns whether it wrote."""
     try:
@@ -67,6 +84,8 @@ def main(argv=None):
     p.add_argument("--out", default="", help="default: 'rendered' beside the data file (crendermotion.py:115)")
     p.add_argument("--size", default=1024, type=int, help="width and height (crendermotion.py:109-110)")
     p.add_argument("--sigma", default=3.0, type=float, help="temporal smoothing (crendermotion.py:79); 0: none")
+    p.add_argument("--betas_npz", default="", help="npz with 'betas' [N, 2, nb]: the body shape of actor and reactor per sample (cycled); "
+                                                   "'synthetic': seeded N(0, 1) shapes")
     p.add_argument("--no_crop", action="store_true")
     p.add_argument("--device", default=0, type=int)
     args = p.parse_args(argv)
@@ -78,6 +97,7 @@ def main(argv=None):
         raise SystemExit(f"{args.skeleton} is a skeleton file without mesh arrays (write a body file with tools/make_skeleton.py --mesh)")
     model, eng = postprocessing_engine(dev)
     rot2xyz = Rotation2xyz(body, model)
+    betas = load_betas(args.betas_npz, N, rot2xyz.num_betas, args.num_person)
     renderer = MeshRenderer(body["mesh"]["faces"], dev)
     out_dir = args.out or os.path.join(os.path.dirname(os.path.abspath(args.data_path)), "rendered")
     n_png = n_mp4 = 0
@@ -88,7 +108,8 @@ def main(argv=None):
             eng.gaussian_filter1d(xi, sm, xi.numel() // T, T, float(args.sigma), dist_util.stream_handle(dev))
             xi = sm
         verts = rot2xyz(xi, torch.ones((1, T), dtype=torch.bool), pose_rep="rot6d", translation=True, glob=True, jointstype="vertices", vertstrans=True,
-                        num_person=args.num_person, glob_rot=[3.141592653589793, 0, 0])
+                        num_person=args.num_person, glob_rot=[3.141592653589793, 0, 0],
+                        **({} if betas is None else {"betas_per_motion": torch.from_numpy(betas[i % len(betas)][None])}))
         frames = renderer.render(verts, width=args.size, height=args.size, cam=DEFAULT_CAM, setting=args.setting, center=True)[0]
         box = None if args.no_crop else crop_to_content(frames)
         if box is not None:

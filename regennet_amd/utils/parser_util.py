@@ -72,6 +72,9 @@ def add_generate_options(p):
                    help="skeleton npz (tools/make_skeleton.py) or 'synthetic': also store 'motion', the joint positions model.rot2xyz gives")
     g.add_argument("--vertices", action="store_true",
                    help="also store 'vertices' [N,V,3,T] and 'faces': needs a --skeleton with mesh arrays (tools/make_skeleton.py --mesh; 'synthetic': synth.make_body)")
+    g.add_argument("--betas_npz", default="", type=str,
+                   help="with --skeleton: npz with 'betas' [N,nb], the reactor's body shape per generated sample (cycled over repetitions like the actor "
+                        "clips), for 'motion' and 'vertices'; 'synthetic': seeded N(0,1) shapes; results.npy stores 'betas'")
     g.add_argument("--obj_dir", default="", type=str, help="with --vertices: write DIR/sample{i:02d}/frame{t:03d}.obj")
     g.add_argument("--render_dir", default="", type=str, help="with --vertices: render the meshes on the device and write DIR/sample{i:02d}/frame{t:03d}.png")
     g.add_argument("--render_size", default=1024, type=int, help="with --render_dir: width and height of the frames (render/crendermotion.py:109-110: 1024)")
