@@ -348,6 +348,49 @@ RGN_API int rgn_rot2verts_shaped(rgn_body_handle b, const float* x_dev, const ui
                                  const float* glob_rot_host /*[3] or NULL*/, float* verts_dev /*[B,V,3P,T]*/,
                                  float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes, void* stream);
 
+/* ---- Regressed joint types: jointstype 'vibe' / 'a2m' / 'a2mpl' ----
+ * Replaces what the reference's SMPL layer appends to the chain's joints (model/smpl.py:76-98): the vertex joints its smplx parent picks,
+ * vertices[:, vertex_joints], and the extra joints vertices2joints(J_regressor_extra, vertices); all_joints = [J chain joints | Np picked | Jr regressed].
+ *   vertex_joints_host [Np] vertex ids in [0, V); regressor_host [Jr, V], finite (rows need not be non-negative or sum to 1); Np or Jr may be 0, not
+ *   both, and Np + Jr <= 32.
+ * Called once after rgn_body_create (again: the data are replaced). The body is compacted HERE: S = the picks united with the regressor's non-zero
+ * columns, ascending, padded to a multiple of 32; v_template, shapedirs, posedirs and lbs_weights are laid down again restricted to S, and the
+ * [Np + Jr] x |S| weights as an MFMA operand (picks are selections: exact). RGN_ERR_INVALID_ARG with text in rgn_body_last_error(b) (NULL handle:
+ * rgn_body_last_error(NULL)) for bad counts, a missing array, a pick outside [0, V), a non-finite weight. */
+RGN_API int rgn_body_set_joint_regressors(rgn_body_handle b, int32_t Np, const int32_t* vertex_joints_host /*[Np]*/, int32_t Jr,
+                                          const float* regressor_host /*[Jr,V]*/);
+/* Bytes of device memory rgn_rot2joints needs: per tile of 32 frames the skinning transforms, the pose feature and the chain's J joint translations,
+ * plus the shaped template of the |S| (padded) vertices. Nothing in it depends on V; no buffer of B * V anything exists. */
+RGN_API int rgn_rot2joints_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes);
+/* Replaces Rotation2xyz.__call__ (model/rotation2xyz.py:17-155) for the joint types that index the SMPL layer's all_joints (model/smpl.py:66-98):
+ *   joints[b, m] = all_joints[map[m]], frames with mask == 0 set to 0, row `root` (an OUTPUT row, JOINTSTYPE_ROOT) subtracted from every row, and
+ *   with TRANSLATION and VERTSTRANS the translation row added as rgn_rot2xyz adds it.
+ * The arguments are rgn_rot2verts's, with in place of verts_dev: n_map in [1, 64], map_host [n_map] with entries in [0, J + Np + Jr) (repeats
+ * allowed; passed to the kernel by value), root in [0, n_map), and
+ *   joints_dev fp32 [B, n_map, 3 * num_person, T]
+ *   work_dev   rgn_rot2joints_workspace bytes
+ * Only the vertices of S are skinned - by the wave body of rgn_rot2verts, so a picked row, before the root row is subtracted, is that call's vertex
+ * bit for bit - and they are weighed into joints in registers on the same MFMA shape (exact fp32 products, sums in an order the body alone fixes,
+ * no atomics); no vertex is ever written. Masked tiles, stream, allocation, state and graph capture as for rgn_rot2verts. The arguments are checked
+ * before the handle or the device is touched, then the handle: RGN_ERR_INVALID_ARG for what rgn_rot2verts refuses, n_map outside [1, 64], a null
+ * map, root outside [0, n_map), a negative map entry, a NULL handle, a body without regressors, a map entry >= J + Np + Jr, a short workspace;
+ * text in rgn_body_last_error(b), or rgn_body_last_error(NULL) when b is NULL. */
+RGN_API int rgn_rot2joints(rgn_body_handle b, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T,
+                           const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/, int32_t pose_rep, int32_t num_person,
+                           int32_t flags, const float* glob_rot_host /*[3] or NULL*/, const float* betas_host /*[nb] or NULL*/, int32_t n_map,
+                           const int32_t* map_host /*[n_map]*/, int32_t root, float* joints_dev /*[B,n_map,3P,T]*/,
+                           float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev, uint64_t work_bytes, void* stream);
+/* rgn_rot2joints with a body shape PER FRAME: the beta arguments of rgn_rot2verts_shaped, with their meaning and their checks. A masked frame's
+ * betas are never read. */
+RGN_API int rgn_rot2joints_shaped_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes);
+RGN_API int rgn_rot2joints_shaped(rgn_body_handle b, const float* x_dev, const uint8_t* mask_dev /*nullable*/, int32_t B, int32_t T,
+                                  const float* rest_joints_host /*[J,3]*/, const int32_t* parents_host /*[J]*/,
+                                  const float* shape_joints_dev /*[J,3,nb]*/, int32_t nb, const float* betas_dev, int64_t beta_stride_b,
+                                  int64_t beta_stride_p, int64_t beta_stride_t, int32_t pose_rep, int32_t num_person, int32_t flags,
+                                  const float* glob_rot_host /*[3] or NULL*/, int32_t n_map, const int32_t* map_host /*[n_map]*/, int32_t root,
+                                  float* joints_dev /*[B,n_map,3P,T]*/, float* rotmat_dev /*nullable [B,P,T,J,3,3]*/, void* work_dev,
+                                  uint64_t work_bytes, void* stream);
+
 /* ---- Rendering: z-buffer rasteriser over the vertices rgn_rot2verts writes ----
  * Replaces render/crendermotion.py:20-42 (render_video: centring, the frame loop, the colours) and render/renderer.py:51-150 (Renderer: pyrender on
  * OSMesa, one scene rebuild per frame). The geometry is the reference's - camera, centring, colours, light positions, background; its PBR material

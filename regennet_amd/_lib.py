@@ -105,6 +105,12 @@ SYMBOLS.update({
     "rgn_rot2verts_shaped_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
     "rgn_rot2verts_shaped": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _u64,
                                        _vp]),
+    "rgn_body_set_joint_regressors": (C.c_int, [_vp, _i32, _vp, _i32, _vp]),
+    "rgn_rot2joints_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "rgn_rot2joints": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp]),
+    "rgn_rot2joints_shaped_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(_u64)]),
+    "rgn_rot2joints_shaped": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp,
+                                        _vp, _vp, _u64, _vp]),
 })
 
 RENDER_MAX_PERSONS = 8                 # RGN_RENDER_MAX_PERSONS
@@ -508,6 +514,57 @@ class BodyEngine:
         self._ck(self.lib.rgn_rot2verts_shaped(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, _ptr(shape_joints),
                                                int(shape_joints.shape[2]), _ptr(betas), sb, sp, st, int(pose_rep), int(num_person), int(flags), pgr,
                                                _ptr(verts), _ptr(rotmat), _ptr(work), int(work.numel() * work.element_size()), C.c_void_p(stream)))
+
+    def set_joint_regressors(self, vertex_joints, regressor):
+        """rgn_body_set_joint_regressors: vertex_joints int [Np] | None, regressor fp32 [Jr, V] | None (host). The body is cut to the vertices
+        they touch, once; a second call replaces the data."""
+        vj, pvj = _host(() if vertex_joints is None else vertex_joints, np.int32)
+        reg, preg = _host(np.zeros((0, self.V), np.float32) if regressor is None else regressor, np.float32)
+        assert vj.ndim == 1 and reg.ndim == 2 and reg.shape[1] == self.V, (vj.shape, reg.shape, self.V)
+        self._ck(self.lib.rgn_body_set_joint_regressors(self.h, len(vj), pvj if len(vj) else None, len(reg), preg if len(reg) else None))
+        self.Np, self.Jr = len(vj), len(reg)
+
+    def joints_workspace_bytes(self, B, T, num_person):
+        n = C.c_uint64()
+        self._ck(self.lib.rgn_rot2joints_workspace(self.h, int(B), int(T), int(num_person), C.byref(n)))
+        return n.value
+
+    def joints_workspace_bytes_shaped(self, B, T, num_person):
+        n = C.c_uint64()
+        self._ck(self.lib.rgn_rot2joints_shaped_workspace(self.h, int(B), int(T), int(num_person), C.byref(n)))
+        return n.value
+
+    def rot2joints(self, x, mask, rest_joints, parents, pose_rep, num_person, flags, glob_rot, betas, jmap, root, joints, rotmat, work, stream):
+        """rgn_rot2joints: rot2verts's arguments, with in place of verts the joint type - jmap int [n] into [J chain joints | Np picked | Jr
+        regressed] (host), root (an output row) - and joints fp32 [B, n, 3 * num_person, T]; work: at least joints_workspace_bytes(...)."""
+        rj, prj = _host(rest_joints, np.float32)
+        pa, ppa = _host(parents, np.int32)
+        gr, pgr = _host(None if glob_rot is None else np.asarray(glob_rot).reshape(3), np.float32)
+        be, pbe = _host(betas, np.float32)
+        jm, pjm = _host(np.asarray(jmap).reshape(-1), np.int32)
+        assert rj.shape == (self.J, 3) and pa.shape == (self.J,) and (be is None or be.shape == (self.nb,))
+        assert x.is_contiguous() and joints.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        assert tuple(joints.shape[1:3]) == (len(jm), 3 * int(num_person)), (tuple(joints.shape), len(jm), num_person)
+        self._ck(self.lib.rgn_rot2joints(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, int(pose_rep), int(num_person),
+                                         int(flags), pgr, pbe, len(jm), pjm, int(root), _ptr(joints), _ptr(rotmat), _ptr(work),
+                                         int(work.numel() * work.element_size()), C.c_void_p(stream)))
+
+    def rot2joints_shaped(self, x, mask, rest_joints, parents, shape_joints, betas, strides, pose_rep, num_person, flags, glob_rot, jmap, root, joints,
+                          rotmat, work, stream):
+        """rgn_rot2joints_shaped: rot2joints with the shape arguments of rot2verts_shaped; work: at least joints_workspace_bytes_shaped(...)."""
+        rj, prj = _host(rest_joints, np.float32)
+        pa, ppa = _host(parents, np.int32)
+        gr, pgr = _host(None if glob_rot is None else np.asarray(glob_rot).reshape(3), np.float32)
+        jm, pjm = _host(np.asarray(jmap).reshape(-1), np.int32)
+        assert rj.shape == (self.J, 3) and pa.shape == (self.J,)
+        assert x.is_contiguous() and joints.is_contiguous() and (mask is None or (mask.is_contiguous() and mask.element_size() == 1))
+        assert tuple(joints.shape[1:3]) == (len(jm), 3 * int(num_person)), (tuple(joints.shape), len(jm), num_person)
+        assert shape_joints.is_contiguous() and tuple(shape_joints.shape[:2]) == (self.J, 3) and shape_joints.element_size() == betas.element_size() == 4
+        sb, sp, st = (int(s) for s in strides)
+        self._ck(self.lib.rgn_rot2joints_shaped(self.h, _ptr(x), _ptr(mask), int(x.shape[0]), int(x.shape[-1]), prj, ppa, _ptr(shape_joints),
+                                                int(shape_joints.shape[2]), _ptr(betas), sb, sp, st, int(pose_rep), int(num_person), int(flags), pgr,
+                                                len(jm), pjm, int(root), _ptr(joints), _ptr(rotmat), _ptr(work),
+                                                int(work.numel() * work.element_size()), C.c_void_p(stream)))
 
 
 class RenderEngine:

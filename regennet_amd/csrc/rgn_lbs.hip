@@ -24,7 +24,13 @@
 // rgn_rot2verts_shaped: a body shape per frame, read on the device. k_lbs_shape is not launched and no shaped template exists; k_lbs_chain<true> takes
 // each lane's rest joints from its betas and writes them as further rows AHEAD of pf, k_lbs_skin<true> walks the shape planes and the posedirs planes
 // as one operand from v_template:   v_posed = v_template + [shapedirs; posedirs]^T . [betas; pf].   The <false> forms are the kernels described above.
+//
+// rgn_rot2joints / rgn_rot2joints_shaped: the joint types the reference's SMPL layer regresses from the mesh (model/smpl.py:76-98, under
+// model/rotation2xyz.py:17-155) - index maps into [chain joints | vertices[:, vertex_joints] | J_regressor_extra . vertices]. The body is cut to the
+// vertices those touch at rgn_body_set_joint_regressors (rgn_lbs_compact.h), k_lbs_chain also leaves its joint translations, and k_lbs_joints runs
+// k_lbs_skin's wave body (lbs_wave_tile: one definition, two callers) over the cut body and weighs each skinned tile into joints in registers.
 #include "rgn_fk.h"
+#include "rgn_lbs_compact.h"
 
 #include <cstring>
 #include <memory>
@@ -50,7 +56,12 @@ struct LbsRest {
     float j[FK_MAX_JOINTS][3];                       // rest joints (absolute), for A_j's translation column
 };
 struct LbsWork {                                    // the workspace, carved up: offsets in floats, and its size
-    uint64_t vsh, hdr, A, pf, bytes;
+    uint64_t vsh, hdr, A, pf, jw, bytes;            // (jw: the chain's joint translations, rgn_rot2joints alone)
+};
+constexpr int LBS_MAX_MAP = 64;
+struct LbsMap {                                     // a joint type: output row m is all_joints[idx[m]], all_joints = [J chain joints | Np picked | Jr regressed]
+    int32_t n, root;
+    uint8_t idx[LBS_MAX_MAP];
 };
 
 inline int round_up(int a, int m) { return (a + m - 1) / m * m; }
@@ -71,12 +82,12 @@ __global__ void k_lbs_shape(const float* __restrict__ vt, const float* __restric
 // ---- stage 1: rows -> A, pf, hdr per frame tile ---------------------------------------------------------------------------------------------
 // SHAPED (rgn_rot2verts_shaped): the frame's betas sit in registers; the chain's offsets and A_j's rest joint come from them (rgn_fk.h), and they are
 // written as the first nbp rows of the tile's feature image, ahead of the pose feature, for the shape blend that rides k_lbs_skin's k-loop.
-// k_lbs_chain<false> looks at neither `sh` nor `nbp`.
+// k_lbs_chain<false> looks at neither `sh` nor `nbp`. jw (rgn_rot2joints; else null): the chain's joint translations too, [tile][J][3][32].
 template <bool SHAPED>
 __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restrict__ x, const uint8_t* __restrict__ mask, float* __restrict__ rotmat,
                                                           float* __restrict__ hdr, float* __restrict__ Aw, float* __restrict__ pfw, int B, int T, int P, int J,
                                                           int C, int rep, int flags, unsigned long long identity, const FkSkel sk, const LbsRest rest,
-                                                          const FkShape sh, int nbp) {
+                                                          const FkShape sh, int nbp, float* __restrict__ jw) {
     extern __shared__ __attribute__((aligned(16))) float g[];       // [J][13][32]
     const int fl = threadIdx.x & (FK_FRAMES - 1), w = threadIdx.x / FK_FRAMES;
     const long long tile = blockIdx.x;
@@ -132,6 +143,10 @@ __global__ __launch_bounds__(FK_THREADS) void k_lbs_chain(const float* __restric
             a[(4 * r + 2) * FK_FRAMES] = r2;
             a[(4 * r + 3) * FK_FRAMES] = pos[r] - (r0 * j0 + r1 * j1 + r2 * j2);
         }
+        if (jw) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) jw[((tile * J + i) * 3 + r) * FK_FRAMES + fl] = pos[r];
+        }
     };
     if constexpr (SHAPED) fk_chain_rel(g, sk, fl, w, FkShapedRel{sk, sh, be}, emit);
     else fk_chain(g, sk, fl, w, emit);
@@ -143,6 +158,68 @@ __device__ __forceinline__ void lbs_load_pd(float (&a)[4][3], const float* __res
     for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int c = 0; c < 3; ++c) a[u][c] = p[(size_t)(6 * u + c) * Vp];
+}
+
+// The wave body k_lbs_skin and k_lbs_joints share: 32 frames (lanes) x the 32 vertices from v0 - pose (and shape) blend from the tile's feature image
+// in LDS, then per output channel r the blend of transforms and its application. sink(r, q, v, o) sees channel r of vertex v = v0 + 8 (q / 4) + 4 h
+// + (q % 4) for this lane's frame, unmasked and untranslated: register q of the accumulator arrangement. vsh: the start planes [3][Vp]; At: the frame
+// tile's transforms [J][12][32]; pd / Wt: the planes rgn_body_create (or the compaction, with Vp := Sp) laid down.
+template <class Sink>
+__device__ __forceinline__ void lbs_wave_tile(const float* __restrict__ vsh, const float* __restrict__ At, const float* spf, const float* __restrict__ pd,
+                                              const float* __restrict__ Wt, int Vp, int v0, int J, int Jp, int Kp, int pose, int lane, Sink&& sink) {
+    const int fl = lane & 31, h = lane >> 5;
+    f32x16 vp[3];                               // v_posed: [c] register q = vertex v0 + 8 (q / 4) + 4 h + (q % 4), this lane's frame
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) vp[c][q] = vsh[(size_t)c * Vp + v0 + 8 * (q >> 2) + 4 * h + (q & 3)];
+    if (pose) {
+        const float* pl = pd + (size_t)(3 * h) * Vp + v0 + fl;      // + (6 s + c) Vp: row 2 s + h, component c
+        float an[4][3];
+        lbs_load_pd(an, pl, Vp);
+        for (int g = 0; g < Kp / LBS_KGROUP; ++g) {
+            float ac[4][3];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ac[u][c] = an[u][c];
+            if ((g + 1) * LBS_KGROUP < Kp) lbs_load_pd(an, pl + (size_t)(g + 1) * 24 * Vp, Vp);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float bv = spf[(g * 4 + u) * 64 + lane];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) vp[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u][c], bv, vp[c], 0, 0, 0);
+            }
+        }
+    }
+    const float* wl = Wt + (size_t)h * Vp + v0 + fl;                // + 2 s Vp
+    const float* al = At + h * 12 * FK_FRAMES + fl;                 // + 2 s * 12 * 32 + component * 32
+#pragma unroll 1
+    for (int r = 0; r < 3; ++r) {
+        f32x16 tm[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) tm[c][q] = 0.f;
+        for (int s = 0; s < Jp / 2; ++s) {
+            const float wv = wl[(size_t)2 * s * Vp];
+            const bool in = 2 * s + h < J;      // (the pad joint of an odd J: weight 0, and no read past the tile's transforms)
+            float bv[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) bv[c] = in ? al[(2 * s * 12 + 4 * r + c) * FK_FRAMES] : 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) tm[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, bv[c], tm[c], 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int v = v0 + 8 * (q >> 2) + 4 * h + (q & 3);
+            float o = tm[0][q] * vp[0][q];
+            o = fmaf(tm[1][q], vp[1][q], o);
+            o = fmaf(tm[2][q], vp[2][q], o);
+            o += tm[3][q];
+            sink(r, q, v, o);
+        }
+    }
 }
 
 // SHAPED (rgn_rot2verts_shaped): the shape blend rides the same k-loop. The body keeps its shape directions as nbp further planes directly AHEAD of the
@@ -183,63 +260,93 @@ __global__ __launch_bounds__(LBS_THREADS, 2) void k_lbs_skin(const float* __rest
                     for (int c = 0; c < 3; ++c) __builtin_nontemporal_store(addtr ? 0.f + tr[c] : 0.f, ob + (v0 + i) * vstride + c * (long long)T);
             continue;
         }
-        f32x16 vp[3];                               // v_posed: [c] register q = vertex v0 + 8 (q / 4) + 4 h + (q % 4), this lane's frame
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) vp[c][q] = vsh[(size_t)c * Vp + v0 + 8 * (q >> 2) + 4 * h + (q & 3)];
-        if (pose) {
-            const float* pl = pd + (size_t)(3 * h) * Vp + v0 + fl;      // + (6 s + c) Vp: row 2 s + h, component c
-            float an[4][3];
-            lbs_load_pd(an, pl, Vp);
-            for (int g = 0; g < Kp / LBS_KGROUP; ++g) {
-                float ac[4][3];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) ac[u][c] = an[u][c];
-                if ((g + 1) * LBS_KGROUP < Kp) lbs_load_pd(an, pl + (size_t)(g + 1) * 24 * Vp, Vp);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float bv = spf[(g * 4 + u) * 64 + lane];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) vp[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u][c], bv, vp[c], 0, 0, 0);
-                }
-            }
-        }
-        const float* wl = Wt + (size_t)h * Vp + v0 + fl;                // + 2 s Vp
-        const float* al = Aw + (tile * J + h) * 12 * FK_FRAMES + fl;    // + 2 s * 12 * 32 + component * 32
-#pragma unroll 1
-        for (int r = 0; r < 3; ++r) {
-            f32x16 tm[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) tm[c][q] = 0.f;
-            for (int s = 0; s < Jp / 2; ++s) {
-                const float wv = wl[(size_t)2 * s * Vp];
-                const bool in = 2 * s + h < J;      // (the pad joint of an odd J: weight 0, and no read past the tile's transforms)
-                float bv[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) bv[c] = in ? al[(2 * s * 12 + 4 * r + c) * FK_FRAMES] : 0.f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) tm[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, bv[c], tm[c], 0, 0, 0);
-            }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int v = v0 + 8 * (q >> 2) + 4 * h + (q & 3);
-                float o = tm[0][q] * vp[0][q];
-                o = fmaf(tm[1][q], vp[1][q], o);
-                o = fmaf(tm[2][q], vp[2][q], o);
-                o += tm[3][q];
-                o = keep ? o : 0.f;
-                if (addtr) o += tr[r];
-                if (live && v < V) __builtin_nontemporal_store(o, ob + v * vstride + r * (long long)T);
-            }
-        }
+        lbs_wave_tile(vsh, Aw + tile * J * 12 * FK_FRAMES, spf, pd, Wt, Vp, v0, J, Jp, Kp, pose, lane, [&](int r, int, int v, float o) {
+            o = keep ? o : 0.f;
+            if (addtr) o += tr[r];
+            if (live && v < V) __builtin_nontemporal_store(o, ob + v * vstride + r * (long long)T);
+        });
     }
 }
 
+// ---- the regressed joint types: skin the vertices of S in registers, weigh them into joints, never write them -------------------------------------
+// One workgroup per frame tile; wave w walks every 4th vertex tile of the compacted body (vsh / pd / Wt: its planes, Sp vertices) through the wave body
+// above. A skinned tile leaves that body in the accumulator arrangement, which IS a B operand (K x N: register q of half-wave h gives k = h of k-step
+// q, frames on N) of the same MFMA shape, so   joints[row, t] += W[row, v] . vertex[v, t]   is 16 MFMAs per channel against Wj, the joint weights
+// permuted at load time to the vertex order of the registers (rgn_lbs_compact.h). Exact products; a picked row's only non-zero is a 1, so it is that
+// vertex. Each wave sums its tiles in order, the four partial sums meet in LDS (over the feature image, which is done with) and are added in wave
+// order, and the epilogue gathers all_joints[map[m]] - chain joints from the chain's translations jw, the rest from the sums -, zeroes masked frames,
+// subtracts row `root` and adds the translation as k_fk does. The order of every sum depends on the body alone.
+template <bool SHAPED>
+__global__ __launch_bounds__(LBS_THREADS) void k_lbs_joints(const float* __restrict__ vsh, const float* __restrict__ hdr, const float* __restrict__ Aw,
+                                                            const float* __restrict__ pfw, const float* __restrict__ jw, const float* __restrict__ pd,
+                                                            const float* __restrict__ Wt, const float* __restrict__ Wj, float* __restrict__ out, int B, int T,
+                                                            int P, int Sp, int J, int Jp, int Kp, int pose, int addtr, int krows, const LbsMap map) {
+    extern __shared__ __attribute__((aligned(16))) float spf[];     // [Kp][32], then the partial sums [4 waves][3][32 rows][32 frames]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fl = lane & 31, h = lane >> 5;
+    const long long tile = blockIdx.x, NF = (long long)B * P * T, f = tile * FK_FRAMES + fl;
+    const bool live = f < NF;
+    const long long fc = live ? f : NF - 1;
+    const int t = (int)(fc % T), p = (int)((fc / T) % P);
+    const long long b = fc / ((long long)T * P);
+    const float* hd = hdr + tile * 4 * FK_FRAMES + fl;
+    const float tr[3] = {hd[0], hd[FK_FRAMES], hd[2 * FK_FRAMES]};
+    const bool keep = hd[3 * FK_FRAMES] != 0.f;
+    const bool any = __syncthreads_or(keep);
+    float* __restrict__ ob = out + ((b * map.n * 3 * P + 3 * p) * (long long)T + t);            // + row * 3 P T + channel * T
+    const long long mstride = (long long)3 * P * T;
+    const int rows = 3 * map.n;                     // (row, channel) pairs: a thread keeps its frame (256 = 8 x 32) and walks every 8th
+    if (!any) {                                     // every frame of the tile is masked: 0, then the translation
+        if (live)
+            for (int e = threadIdx.x >> 5; e < rows; e += LBS_THREADS / 32) {
+                const int m = e / 3, c = e - 3 * m;
+                ob[m * mstride + c * (long long)T] = addtr ? 0.f + (c == 0 ? tr[0] : c == 1 ? tr[1] : tr[2]) : 0.f;
+            }
+        return;
+    }
+    const int K = SHAPED ? krows : 9 * (J - 1);
+    if (pose) {
+        const float* src = pfw + tile * K * FK_FRAMES;
+        for (int i = threadIdx.x; i < Kp * FK_FRAMES; i += LBS_THREADS) spf[i] = i < K * FK_FRAMES ? src[i] : 0.f;
+        __syncthreads();
+    }
+    f32x16 acc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[c][q] = 0.f;
+    for (int it = wave; it < Sp / 32; it += LBS_WAVES) {
+        float wa[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) wa[q] = Wj[((size_t)it * 16 + q) * 64 + lane];
+        lbs_wave_tile(vsh, Aw + tile * J * 12 * FK_FRAMES, spf, pd, Wt, Sp, it * 32, J, Jp, Kp, pose, lane, [&](int r, int q, int, float o) {
+            if (r == 0) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q], o, acc[0], 0, 0, 0);
+            else if (r == 1) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q], o, acc[1], 0, 0, 0);
+            else acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q], o, acc[2], 0, 0, 0);
+        });
+    }
+    __syncthreads();                                // every wave is done with the feature image
+    constexpr int WSTRIDE = 3 * 32 * FK_FRAMES;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) spf[wave * WSTRIDE + (c * 32 + 8 * (q >> 2) + 4 * h + (q & 3)) * FK_FRAMES + fl] = acc[c][q];
+    __syncthreads();
+    auto joint = [&](int a, int c) -> float {       // all_joints[a], channel c, this thread's frame
+        if (a < J) return jw[((tile * J + a) * 3 + c) * FK_FRAMES + fl];
+        const float* pp = spf + (c * 32 + (a - J)) * FK_FRAMES + fl;
+        return ((pp[0] + pp[WSTRIDE]) + pp[2 * WSTRIDE]) + pp[3 * WSTRIDE];
+    };
+    float rt[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rt[c] = joint(map.idx[map.root], c);
+    if (live)
+        for (int e = threadIdx.x >> 5; e < rows; e += LBS_THREADS / 32) {
+            const int m = e / 3, c = e - 3 * m;
+            float v = keep ? joint(map.idx[m], c) - (c == 0 ? rt[0] : c == 1 ? rt[1] : rt[2]) : 0.f;       // masked: 0, then the root row (0 - 0)
+            if (addtr) v += c == 0 ? tr[0] : c == 1 ? tr[1] : tr[2];
+            ob[m * mstride + c * (long long)T] = v;
+        }
+}
 
 }  // namespace
 
@@ -252,6 +359,11 @@ struct rgn_body_ctx {
     // (the shape planes end where the posedirs planes begin: the shaped skinning kernel walks both as one operand of nbp + Kp rows)
     float* blob = nullptr;
     float *vt = nullptr, *sd = nullptr, *vtp = nullptr, *sdp = nullptr, *pd = nullptr, *wt = nullptr;
+    // rgn_body_set_joint_regressors: the arrays as rgn_body_create took them (host), and the body cut to S on the device (rgn_lbs_compact.h)
+    std::vector<float> h_vt, h_sd, h_pd, h_wt;
+    float* jblob = nullptr;
+    float *jvt = nullptr, *jsd = nullptr, *jvtp = nullptr, *jsdp = nullptr, *jpd = nullptr, *jwt = nullptr, *jwj = nullptr;
+    int Np = 0, Jr = 0, nS = 0, Sp = 0;
     std::string err;
     int fail(int code, const std::string& m) {
         err = m;
@@ -308,6 +420,123 @@ LbsWork carve_shaped(const rgn_body_ctx* c, long long NF) {
     w.pf = w.A + ntiles * c->J * 12 * FK_FRAMES;
     w.bytes = (w.pf + ntiles * (c->nbp + c->K) * FK_FRAMES) * sizeof(float);
     return w;
+}
+
+// ... of rgn_rot2joints / rgn_rot2joints_shaped: the chain's outputs with its joint translations, and (one shape) the shaped template of the Sp
+// vertices of S. Nothing in it grows with V.
+LbsWork carve_joints(const rgn_body_ctx* c, long long NF, bool shaped) {
+    const uint64_t ntiles = (uint64_t)((NF + FK_FRAMES - 1) / FK_FRAMES);
+    LbsWork w;
+    w.vsh = 0;
+    w.hdr = w.vsh + (shaped ? 0 : (uint64_t)3 * c->Sp);
+    w.A = w.hdr + ntiles * 4 * FK_FRAMES;
+    w.pf = w.A + ntiles * c->J * 12 * FK_FRAMES;
+    w.jw = w.pf + ntiles * ((shaped ? c->nbp : 0) + c->K) * FK_FRAMES;
+    w.bytes = (w.jw + ntiles * c->J * 3 * FK_FRAMES) * sizeof(float);
+    return w;
+}
+
+constexpr int LBS_JOINTS_SUMS = LBS_WAVES * 3 * 32 * FK_FRAMES * (int)sizeof(float);       // k_lbs_joints' partial sums in LDS: 48 KB
+
+struct JointsArgs {                                 // what rgn_rot2joints and rgn_rot2joints_shaped share
+    const float* x;
+    const uint8_t* mask;
+    int32_t B, T;
+    const float* rest_joints;
+    const int32_t* parents;
+    int32_t pose_rep, num_person, flags;
+    const float* glob_rot;
+    int32_t n_map;
+    const int32_t* map;
+    int32_t root;
+    float *joints, *rotmat;
+    void* work;
+    uint64_t work_bytes;
+    void* stream;
+};
+
+// betas: the one shape (host, nullable) of rgn_rot2joints; sh: the per-frame shape arguments of rgn_rot2joints_shaped
+template <bool SHAPED>
+int rot2joints(rgn_body_ctx* h, const char* fn, const JointsArgs& a, const float* betas, const FkShape& sh) {
+    auto bad = [&](const std::string& m) -> int {
+        if (h) return h->fail(RGN_ERR_INVALID_ARG, std::string(fn) + ": " + m);
+        g_body_create_error = std::string(fn) + ": " + m;
+        return RGN_ERR_INVALID_ARG;
+    };
+    if (!a.x || !a.joints || !a.rest_joints || !a.parents) return bad("null x, joints, rest_joints or parents");
+    if constexpr (SHAPED)
+        if (const char* why = fk_check_shape(sh.sj, sh.nb, sh.betas, sh.sb, sh.sp, sh.st)) return bad(why);
+    if (a.B < 1 || a.T < 1) return bad("B < 1 or T < 1");
+    if (a.num_person < 1) return bad("num_person < 1");
+    if (a.pose_rep < RGN_POSE_ROT6D || a.pose_rep > RGN_POSE_ROTMAT) return bad("unknown pose_rep");
+    if (a.flags & ~(RGN_R2X_TRANSLATION | RGN_R2X_GLOB | RGN_R2X_VERTSTRANS)) return bad("unknown flag");
+    if (!(a.flags & RGN_R2X_GLOB) && !a.glob_rot) return bad("glob_rot is required when RGN_R2X_GLOB is not set");
+    if (a.n_map < 1 || a.n_map > LBS_MAX_MAP) return bad("n_map outside [1, 64]");
+    if (!a.map) return bad("null map");
+    if (a.root < 0 || a.root >= a.n_map) return bad("root outside [0, n_map)");
+    for (int i = 0; i < a.n_map; ++i)
+        if (a.map[i] < 0) return bad("map[" + std::to_string(i) + "] < 0");
+    if (!h) return bad("null handle");
+    if (!h->jblob) return bad("the body holds no joint regressors (rgn_body_set_joint_regressors)");
+    const int J = h->J, nall = J + h->Np + h->Jr;
+    LbsMap map{};
+    map.n = a.n_map;
+    map.root = a.root;
+    for (int i = 0; i < a.n_map; ++i) {
+        if (a.map[i] >= nall) return bad("map[" + std::to_string(i) + "] = " + std::to_string(a.map[i]) + " outside [0, J + Np + Jr) = [0, " + std::to_string(nall) + ")");
+        map.idx[i] = (uint8_t)a.map[i];
+    }
+    if constexpr (SHAPED) {
+        if (sh.nb > h->nb) return bad(std::to_string(sh.nb) + " betas, but the body holds " + std::to_string(h->nb) + " shape directions");
+    } else {
+        if (betas && h->nb == 0) return bad("betas given, but the body holds no shapedirs");
+    }
+    FkSkel sk;
+    int at = -1;
+    if (const char* why = fk_build_skel(J, a.rest_joints, a.parents, sk, at))
+        return bad(at < 0 ? std::string(why) : "parents[" + std::to_string(at) + "] outside [0, " + std::to_string(at) + ")");
+    if (!(a.flags & RGN_R2X_GLOB)) axis_angle_to_matrix_f32(a.glob_rot, sk.glob);
+    const long long NF = (long long)a.B * a.num_person * a.T;
+    const LbsWork w = carve_joints(h, NF, SHAPED);
+    float* const wf = reinterpret_cast<float*>(a.work);
+    if (!a.work || a.work_bytes < w.bytes)
+        return bad("workspace of " + std::to_string(a.work_bytes) + " bytes, " + std::to_string(w.bytes) + " needed (" + fn + "_workspace)");
+    LbsRest rest;
+    std::memcpy(rest.j, a.rest_joints, sizeof(float) * 3 * J);
+    LBS_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
+    const int C = a.pose_rep == RGN_POSE_ROT6D ? 6 : a.pose_rep == RGN_POSE_ROTVEC ? 3 : a.pose_rep == RGN_POSE_ROTQUAT ? 4 : 9;
+    const unsigned ntiles = (unsigned)((NF + FK_FRAMES - 1) / FK_FRAMES);
+    if constexpr (!SHAPED) {
+        LbsBetas be{};
+        if (betas) {
+            be.n = h->nb;
+            std::memcpy(be.b, betas, sizeof(float) * h->nb);
+        }
+        hipLaunchKernelGGL(k_lbs_shape, dim3((3 * h->Sp + 255) / 256), dim3(256), 0, s, h->jvt, h->jsd, wf + w.vsh, h->nS, h->Sp, h->nb, be);
+        LBS_HIP(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_lbs_chain<SHAPED>, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, a.x, a.mask, a.rotmat, wf + w.hdr, wf + w.A,
+                       wf + w.pf, a.B, a.T, a.num_person, J, C, a.pose_rep, a.flags, h->identity, sk, rest, sh, SHAPED ? h->nbp : 0, wf + w.jw);
+    LBS_HIP(h, hipGetLastError());
+    const bool addtr = (a.flags & RGN_R2X_TRANSLATION) && (a.flags & RGN_R2X_VERTSTRANS);
+    const int pose = SHAPED ? 1 : (h->pose ? 1 : 0);
+    const int Kp = SHAPED ? h->nbp + (h->pose ? h->Kp : 0) : h->Kp;
+    const size_t image = pose ? (size_t)Kp * FK_FRAMES * sizeof(float) : 0;
+    hipLaunchKernelGGL(k_lbs_joints<SHAPED>, dim3(ntiles), dim3(LBS_THREADS), image > (size_t)LBS_JOINTS_SUMS ? image : (size_t)LBS_JOINTS_SUMS, s,
+                       SHAPED ? h->jvtp : wf + w.vsh, wf + w.hdr, wf + w.A, wf + w.pf, wf + w.jw, SHAPED ? h->jsdp : h->jpd, h->jwt, h->jwj, a.joints, a.B, a.T,
+                       a.num_person, h->Sp, J, h->Jp, Kp, pose, addtr ? 1 : 0, SHAPED ? h->nbp + h->K : 0, map);
+    LBS_HIP(h, hipGetLastError());
+    return RGN_OK;
+}
+
+int joints_workspace(rgn_body_ctx* b, const char* fn, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes, bool shaped) {
+    if (!b) return RGN_ERR_INVALID_ARG;
+    if (!nbytes) return b->fail(RGN_ERR_INVALID_ARG, std::string(fn) + ": null nbytes");
+    if (B < 1 || T < 1 || num_person < 1) return b->fail(RGN_ERR_INVALID_ARG, std::string(fn) + ": B, T or num_person < 1");
+    if (!b->jblob) return b->fail(RGN_ERR_INVALID_ARG, std::string(fn) + ": the body holds no joint regressors (rgn_body_set_joint_regressors)");
+    *nbytes = carve_joints(b, (long long)B * num_person * T, shaped).bytes;
+    return RGN_OK;
 }
 
 }  // namespace
@@ -372,6 +601,10 @@ int rgn_body_create(int32_t device, int32_t V, int32_t J, int32_t nb, const floa
                     for (int cc = 0; cc < 3; ++cc) hpd[((size_t)k * 3 + cc) * c->Vp + v] = posedirs[(size_t)k * 3 * V + 3 * v + cc];
         for (int v = 0; v < V; ++v)                 // [V][J] -> [Jp][Vp]
             for (int j = 0; j < J; ++j) hwt[(size_t)j * c->Vp + v] = lbs_weights[(size_t)v * J + j];
+        c->h_vt.assign(v_template, v_template + n_vt);                  // kept for rgn_body_set_joint_regressors, which cuts them to its vertices
+        if (n_sd) c->h_sd.assign(shapedirs, shapedirs + n_sd);
+        if (c->pose) c->h_pd.assign(posedirs, posedirs + (size_t)c->K * 3 * V);
+        c->h_wt.assign(lbs_weights, lbs_weights + (size_t)V * J);
         void* dev = nullptr;
         if (hipMalloc(&dev, host.size() * sizeof(float)) != hipSuccess) return bad(RGN_ERR_HIP, "hipMalloc of the mesh data failed");
         c->blob = reinterpret_cast<float*>(dev);
@@ -414,6 +647,7 @@ int rgn_body_destroy(rgn_body_handle b) {
         (void)hipSetDevice(b->device);
         (void)hipDeviceSynchronize();
         if (b->blob) (void)hipFree(b->blob);
+        if (b->jblob) (void)hipFree(b->jblob);
         delete b;
         return RGN_OK;
     });
@@ -468,7 +702,7 @@ int rgn_rot2verts(rgn_body_handle h, const float* x, const uint8_t* mask, int32_
         hipLaunchKernelGGL(k_lbs_shape, dim3((3 * h->Vp + 255) / 256), dim3(256), 0, s, h->vt, h->sd, wf + w.vsh, h->V, h->Vp, h->nb, be);
         LBS_HIP(h, hipGetLastError());
         hipLaunchKernelGGL(k_lbs_chain<false>, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, x, mask, rotmat, wf + w.hdr, wf + w.A, wf + w.pf, B, T,
-                           num_person, J, C, pose_rep, flags, h->identity, sk, rest, FkShape{}, 0);
+                           num_person, J, C, pose_rep, flags, h->identity, sk, rest, FkShape{}, 0, nullptr);
         LBS_HIP(h, hipGetLastError());
         const int vtiles = h->Vp / 32;
         // vertex tiles per workgroup (one pf image in LDS serves them all): 8 where that still leaves a few workgroups per CU, else one per wave
@@ -530,7 +764,7 @@ int rgn_rot2verts_shaped(rgn_body_handle h, const float* x, const uint8_t* mask,
         const int C = pose_rep == RGN_POSE_ROT6D ? 6 : pose_rep == RGN_POSE_ROTVEC ? 3 : pose_rep == RGN_POSE_ROTQUAT ? 4 : 9;
         const unsigned ntiles = (unsigned)((NF + FK_FRAMES - 1) / FK_FRAMES);
         hipLaunchKernelGGL(k_lbs_chain<true>, dim3(ntiles), dim3(FK_THREADS), (size_t)J * FK_JSTRIDE * sizeof(float), s, x, mask, rotmat, wf + w.hdr, wf + w.A,
-                           wf + w.pf, B, T, num_person, J, C, pose_rep, flags, h->identity, sk, rest, sh, h->nbp);
+                           wf + w.pf, B, T, num_person, J, C, pose_rep, flags, h->identity, sk, rest, sh, h->nbp, nullptr);
         LBS_HIP(h, hipGetLastError());
         const int vtiles = h->Vp / 32;
         const int tpw = (long long)ntiles * ((vtiles + 7) / 8) >= 2048 ? 8 : LBS_WAVES;         // (as rgn_rot2verts)
@@ -541,6 +775,84 @@ int rgn_rot2verts_shaped(rgn_body_handle h, const float* x, const uint8_t* mask,
                            h->nbp + h->K);
         LBS_HIP(h, hipGetLastError());
         return RGN_OK;
+    });
+}
+
+int rgn_body_set_joint_regressors(rgn_body_handle b, int32_t Np, const int32_t* vertex_joints, int32_t Jr, const float* regressor) {
+    return body_guard(b, "rgn_body_set_joint_regressors", [&]() -> int {
+        auto bad = [&](const std::string& m) -> int {
+            if (b) return b->fail(RGN_ERR_INVALID_ARG, "rgn_body_set_joint_regressors: " + m);
+            g_body_create_error = "rgn_body_set_joint_regressors: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        const std::string args = lbs_regressor_args(Np, vertex_joints, Jr, regressor);
+        if (!args.empty()) return bad(args);
+        if (!b) return bad("null handle");
+        LbsCompact c;
+        const LbsDims d{b->V, b->J, b->Jp, b->nb, b->nbp, b->K, b->Kp, b->pose};
+        const std::string why = lbs_compact(d, b->h_vt.data(), b->h_sd.data(), b->h_pd.data(), b->h_wt.data(), Np, vertex_joints, Jr, regressor, c);
+        if (!why.empty()) return bad(why);
+        LBS_HIP(b, hipSetDevice(b->device));
+        void* dev = nullptr;
+        LBS_HIP(b, hipMalloc(&dev, c.blob.size() * sizeof(float)));
+        if (hipError_t e = hipMemcpy(dev, c.blob.data(), c.blob.size() * sizeof(float), hipMemcpyHostToDevice); e != hipSuccess) {
+            (void)hipFree(dev);
+            return b->fail(RGN_ERR_HIP, std::string("rgn_body_set_joint_regressors: hipMemcpy: ") + hipGetErrorString(e));
+        }
+        // (here, not in the call, which may run under a stream capture) the feature image as k_lbs_skin<true>'s, never less than the partial sums
+        const int lds = (LBS_MAX_BETAS + round_up(9 * (FK_MAX_JOINTS - 1), LBS_KGROUP)) * FK_FRAMES * (int)sizeof(float);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_joints<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lbs_joints<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            return b->fail(RGN_ERR_HIP, std::string("rgn_body_set_joint_regressors: hipFuncSetAttribute: ") + hipGetErrorString(e));
+        }
+        static_assert(LBS_JOINTS_SUMS <= (LBS_MAX_BETAS + 9 * (FK_MAX_JOINTS - 1)) * FK_FRAMES * (int)sizeof(float), "the partial sums fit the LDS limit set above");
+        if (b->jblob) {                             // a second call replaces the data, once nothing enqueued can still read it
+            (void)hipDeviceSynchronize();
+            (void)hipFree(b->jblob);
+        }
+        b->jblob = reinterpret_cast<float*>(dev);
+        b->jvt = b->jblob + c.o_vt;
+        b->jsd = b->jblob + c.o_sd;
+        b->jvtp = b->jblob + c.o_vtp;
+        b->jsdp = b->jblob + c.o_sdp;
+        b->jpd = b->jblob + c.o_pd;
+        b->jwt = b->jblob + c.o_wt;
+        b->jwj = b->jblob + c.o_wj;
+        b->Np = Np;
+        b->Jr = Jr;
+        b->nS = c.nS;
+        b->Sp = c.Sp;
+        return RGN_OK;
+    });
+}
+
+int rgn_rot2joints_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes) {
+    return body_guard(b, "rgn_rot2joints_workspace", [&]() -> int { return joints_workspace(b, "rgn_rot2joints_workspace", B, T, num_person, nbytes, false); });
+}
+
+int rgn_rot2joints_shaped_workspace(rgn_body_handle b, int32_t B, int32_t T, int32_t num_person, uint64_t* nbytes) {
+    return body_guard(b, "rgn_rot2joints_shaped_workspace",
+                      [&]() -> int { return joints_workspace(b, "rgn_rot2joints_shaped_workspace", B, T, num_person, nbytes, true); });
+}
+
+int rgn_rot2joints(rgn_body_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t T, const float* rest_joints, const int32_t* parents,
+                   int32_t pose_rep, int32_t num_person, int32_t flags, const float* glob_rot, const float* betas, int32_t n_map, const int32_t* map,
+                   int32_t root, float* joints, float* rotmat, void* work, uint64_t work_bytes, void* stream) {
+    return body_guard(h, "rgn_rot2joints", [&]() -> int {
+        const JointsArgs a{x, mask, B, T, rest_joints, parents, pose_rep, num_person, flags, glob_rot, n_map, map, root, joints, rotmat, work, work_bytes, stream};
+        return rot2joints<false>(h, "rgn_rot2joints", a, betas, FkShape{});
+    });
+}
+
+int rgn_rot2joints_shaped(rgn_body_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t T, const float* rest_joints, const int32_t* parents,
+                          const float* shape_joints, int32_t nb, const float* betas, int64_t beta_stride_b, int64_t beta_stride_p, int64_t beta_stride_t,
+                          int32_t pose_rep, int32_t num_person, int32_t flags, const float* glob_rot, int32_t n_map, const int32_t* map, int32_t root,
+                          float* joints, float* rotmat, void* work, uint64_t work_bytes, void* stream) {
+    return body_guard(h, "rgn_rot2joints_shaped", [&]() -> int {
+        const JointsArgs a{x, mask, B, T, rest_joints, parents, pose_rep, num_person, flags, glob_rot, n_map, map, root, joints, rotmat, work, work_bytes, stream};
+        return rot2joints<true>(h, "rgn_rot2joints_shaped", a, nullptr, FkShape{shape_joints, betas, beta_stride_b, beta_stride_p, beta_stride_t, nb});
     });
 }
 

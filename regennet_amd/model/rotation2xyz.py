@@ -22,7 +22,18 @@ jointstype='vertices' needs the body model's surface: a BODY FILE is a skeleton 
     faces            [F, 3] int32       optional, for writing meshes
     identity_joints  [n]                joints whose rotation the reference's wrapper does not hand to the layer (SMPL-X: 22, 23, 24)
 
-and linear blend skinning runs on the device too (rgn_rot2verts, csrc/rgn_lbs.hip)."""
+and linear blend skinning runs on the device too (rgn_rot2verts, csrc/rgn_lbs.hip).
+
+The joint types the reference's SMPL layer regresses from the mesh - 'vibe', 'a2m', 'a2mpl' (model/smpl.py:76-98) - are index maps into
+[J skeleton joints | Np vertex joints | Jr regressed joints]. A body file may hold what they need (`make_skeleton.py --mesh --vertex_joints
+--joint_regressor_extra --joint_maps`; `synth.make_joint_regressors` gives synthetic ones),
+
+    vertex_joints      [Np] int32      vertex ids in [0, V): vertices[:, ids] are joints
+    J_regressor_extra  [Jr, V]         finite; Np + Jr <= 32, not both 0
+    map_vibe, map_a2m, map_a2mpl       int32, 1 - 64 entries in [0, J + Np + Jr); any subset; DATA of the file, not constants of this package
+    map_roots          [3]             optional: the output row that is subtracted, default 8, 0, 0
+
+and those joints come from the device as well, skinned over the touched vertices only (rgn_rot2joints)."""
 import numpy as np
 import torch
 
@@ -61,6 +72,9 @@ def load_skeleton(path):
 
 
 MESH_KEYS = ("v_template", "posedirs", "lbs_weights", "shapedirs", "faces", "identity_joints")
+REGRESSED_JOINTSTYPES = ("vibe", "a2m", "a2mpl")                         # index maps into [chain joints | vertex joints | regressed joints] (model/smpl.py:76-98)
+DEFAULT_MAP_ROOTS = {"vibe": 8, "a2m": 0, "a2mpl": 0}                     # the output row that is subtracted (JOINTSTYPE_ROOT, model/smpl.py)
+REGRESSOR_KEYS = ("vertex_joints", "J_regressor_extra", "map_vibe", "map_a2m", "map_a2mpl", "map_roots")
 
 
 def check_body(d):
@@ -104,7 +118,71 @@ def check_body(d):
     if len(idj) and (idj.min() < 1 or idj.max() >= J):
         raise ValueError(f"body: identity_joints {idj.tolist()} outside [1, J) = [1, {J})")
     out["mesh"] = {"v_template": vt, "posedirs": pd, "lbs_weights": w, "shapedirs": sd, "faces": faces, "identity_joints": idj}
+    out["mesh"].update(check_joint_regressors(m, V, J))
     return out
+
+
+def check_joint_regressors(m, V, J):
+    """The regressed joint types' part of a body dict -> dict(vertex_joints int32 [Np] | None, J_regressor_extra fp32 [Jr, V] | None, joint_maps
+    {type: int32 [n]}, map_roots {type: int}), validated (the checks rgn_body_set_joint_regressors and rgn_rot2joints make, and those only a file
+    can fail). Maps come as `joint_maps` (a dict) or as the file's keys map_vibe / map_a2m / map_a2mpl; all four values are None / empty where the
+    body holds no regressors."""
+    vj, reg = m.get("vertex_joints", None), m.get("J_regressor_extra", None)
+    maps = dict(m["joint_maps"]) if isinstance(m.get("joint_maps", None), dict) else {t: m["map_" + t] for t in REGRESSED_JOINTSTYPES if m.get("map_" + t, None) is not None}
+    roots = m.get("map_roots", None)
+    if vj is None and reg is None:
+        if maps or roots is not None:
+            raise ValueError("body: joint_maps / map_roots without vertex_joints or J_regressor_extra")
+        return {"vertex_joints": None, "J_regressor_extra": None, "joint_maps": {}, "map_roots": {}}
+    vj = np.zeros(0, np.int32) if vj is None else np.asarray(vj)
+    if vj.ndim != 1 or (vj.size and (not np.issubdtype(vj.dtype, np.integer) or vj.min() < 0 or vj.max() >= V)):
+        raise ValueError(f"body: vertex_joints {vj.shape} is not [Np] integer vertex ids in [0, V) = [0, {V})")
+    vj = np.ascontiguousarray(vj, dtype=np.int32)
+    reg = np.zeros((0, V), np.float32) if reg is None else np.ascontiguousarray(reg, dtype=np.float32)
+    if reg.ndim != 2 or reg.shape[1] != V:
+        raise ValueError(f"body: J_regressor_extra {reg.shape} is not [Jr, V] = [Jr, {V}]")
+    if not np.isfinite(reg).all():
+        raise ValueError("body: J_regressor_extra holds a value that is not finite")
+    Np, Jr = len(vj), len(reg)
+    if Np + Jr == 0:
+        raise ValueError("body: vertex_joints and J_regressor_extra are both empty (Np or Jr may be 0, not both)")
+    if Np + Jr > 32:
+        raise ValueError(f"body: Np + Jr = {Np} + {Jr} > 32 vertex and regressed joints")
+    nall, good = J + Np + Jr, {}
+    for t, a in maps.items():
+        if t not in REGRESSED_JOINTSTYPES:
+            raise ValueError(f"body: joint_maps has {t!r}; the joint types are {REGRESSED_JOINTSTYPES}")
+        a = np.asarray(a)
+        if a.ndim != 1 or not 1 <= a.size <= 64 or not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= nall:
+            raise ValueError(f"body: map_{t} {a.shape} is not 1 to 64 integer entries in [0, J + Np + Jr) = [0, {nall})")
+        good[t] = np.ascontiguousarray(a, dtype=np.int32)
+    if roots is None:
+        roots = DEFAULT_MAP_ROOTS
+    elif not isinstance(roots, dict):
+        r = np.asarray(roots).reshape(-1)
+        if r.shape != (3,) or not np.issubdtype(r.dtype, np.integer):
+            raise ValueError(f"body: map_roots {r.shape} is not [3] integers (the root rows of {REGRESSED_JOINTSTYPES})")
+        roots = dict(zip(REGRESSED_JOINTSTYPES, (int(v) for v in r)))
+    for t, a in good.items():
+        if not 0 <= int(roots.get(t, 0)) < len(a):
+            raise ValueError(f"body: map_roots[{t!r}] = {roots.get(t, 0)} is no row of map_{t} ({len(a)} rows)")
+    return {"vertex_joints": vj, "J_regressor_extra": reg, "joint_maps": good, "map_roots": {t: int(roots.get(t, 0)) for t in REGRESSED_JOINTSTYPES}}
+
+
+def body_file_arrays(body):
+    """check_body's dict -> the flat {key: array} a body npz holds (np.savez(path, **body_file_arrays(body)); load_body reads it back)."""
+    d = {"rest_joints": body["rest_joints"], "parents": body["parents"], "body_model": np.array(body.get("body_model", ""))}
+    if body.get("shape_joints", None) is not None:
+        d["shape_joints"] = body["shape_joints"]
+    m = body["mesh"]
+    for k in MESH_KEYS + ("vertex_joints", "J_regressor_extra"):
+        if m.get(k, None) is not None:
+            d[k] = m[k]
+    for t, a in (m.get("joint_maps", None) or {}).items():
+        d["map_" + t] = a
+    if m.get("joint_maps", None):
+        d["map_roots"] = np.array([m["map_roots"][t] for t in REGRESSED_JOINTSTYPES], np.int32)
+    return d
 
 
 def load_body(path):
@@ -113,7 +191,7 @@ def load_body(path):
         d = {k: z[k] for k in ("rest_joints", "parents")}
         d["shape_joints"] = z["shape_joints"] if "shape_joints" in z.files else None
         d["body_model"] = str(z["body_model"]) if "body_model" in z.files else ""
-        for k in MESH_KEYS:
+        for k in MESH_KEYS + REGRESSOR_KEYS:
             d[k] = z[k] if k in z.files else None
     return check_body(d)
 
@@ -226,6 +304,8 @@ class Rotation2xyz:
             if self._body is not None:
                 self._body[0].close()
             self._body, self._work = (_lib.BodyEngine(self.mesh, len(self.skeleton["parents"]), dev.index or 0), dev), None
+            if self.mesh["vertex_joints"] is not None:      # the regressed joint types: the body cut to their vertices, once
+                self._body[0].set_joint_regressors(self.mesh["vertex_joints"], self.mesh["J_regressor_extra"])
         return self._body[0]
 
     def __call__(self, x, mask, pose_rep, translation, glob, jointstype, vertstrans, betas=None, beta=0, glob_rot=None, num_person=1,
@@ -237,6 +317,12 @@ class Rotation2xyz:
         if jointstype not in JOINTSTYPES:
             raise NotImplementedError("This jointstype is not implemented.")
         vertices = jointstype == "vertices" and self.mesh is not None
+        jmap = None                                     # (map, root row) of a regressed joint type the body file serves
+        if jointstype in REGRESSED_JOINTSTYPES and self.mesh is not None and self.mesh["vertex_joints"] is not None:
+            if jointstype not in self.mesh["joint_maps"]:
+                raise NotImplementedError(f"jointstype={jointstype!r}: the body file holds joint regressors but no `map_{jointstype}` "
+                                          f"(tools/make_skeleton.py --mesh --joint_maps)")
+            jmap, vertices = (self.mesh["joint_maps"][jointstype], self.mesh["map_roots"][jointstype]), True
         if jointstype not in SKELETON_JOINTSTYPES and not vertices:
             raise NotImplementedError(
                 f"jointstype={jointstype!r} is computed from the body model's vertices, which a skeleton file does not hold: "
@@ -255,7 +341,7 @@ class Rotation2xyz:
         model = self.model
         plan = self.shape_plan(betas, beta, betas_per_motion, mask, B, T, P, vertices)      # not None: a shape per frame, read on the device
         if vertices:
-            return self._vertices(x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan)
+            return self._vertices(x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan, jmap)
         eng = model._engine if (model._engine is not None and not model._engine_stale) else model._get_engine(B, T)[0]
         dev = next(model.parameters()).device
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
@@ -278,9 +364,10 @@ class Rotation2xyz:
             return out, r[:, 1:], r[:, 0]
         return out
 
-    def _vertices(self, x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan=None):
+    def _vertices(self, x, mask, pose_rep, translation, glob, vertstrans, betas, beta, glob_rot, P, get_rotations_back, plan=None, jmap=None):
         """jointstype='vertices' (:236-249 / :303-321): [B, V, 3 P, T] by linear blend skinning on the device (rgn_rot2verts; with a shape per
-        frame rgn_rot2verts_shaped)."""
+        frame rgn_rot2verts_shaped). jmap = (map, root row): a regressed joint type (:17-155 over model/smpl.py:76-98) instead, [B, len(map), 3 P, T]
+        from the same skinning restricted to the vertices its joints touch (rgn_rot2joints / rgn_rot2joints_shaped); no vertex array exists."""
         J, V = len(self.skeleton["parents"]), self.mesh["v_template"].shape[0]
         B, T = x.shape[0], x.shape[-1]
         dev = next(self.model.parameters()).device
@@ -297,15 +384,24 @@ class Rotation2xyz:
             bv = np.zeros(body.nb, np.float32)
             bv[:len(b)] = b
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
-        out = torch.empty((B, V, 3 * P, T), device=dev, dtype=torch.float32)
+        out = torch.empty((B, V if jmap is None else len(jmap[0]), 3 * P, T), device=dev, dtype=torch.float32)
         rot = torch.empty((B, P, T, J, 3, 3), device=dev, dtype=torch.float32) if get_rotations_back else None
-        need = body.workspace_bytes(B, T, P) if shape is None else body.workspace_bytes_shaped(B, T, P)
+        if jmap is None:
+            need = body.workspace_bytes(B, T, P) if shape is None else body.workspace_bytes_shaped(B, T, P)
+        else:
+            need = body.joints_workspace_bytes(B, T, P) if shape is None else body.joints_workspace_bytes_shaped(B, T, P)
         if self._work is None or self._work.numel() < need:
             self._work = torch.empty(need, device=dev, dtype=torch.uint8)
         flags = (_lib.R2X_TRANSLATION if translation else 0) | (_lib.R2X_GLOB if glob else 0) | (_lib.R2X_VERTSTRANS if vertstrans else 0)
         gr = None if glob else np.asarray(glob_rot, dtype=np.float32).reshape(3)
         with torch.cuda.device(dev):
-            if shape is not None:
+            if jmap is not None and shape is not None:
+                body.rot2joints_shaped(xc, mc, self.skeleton["rest_joints"], self.skeleton["parents"], shape[2], shape[0], shape[1],
+                                       _lib.POSE_REP[pose_rep], P, flags, gr, jmap[0], jmap[1], out, rot, self._work, dist_util.stream_handle(dev))
+            elif jmap is not None:
+                body.rot2joints(xc, mc, self.rest_joints(betas, beta), self.skeleton["parents"], _lib.POSE_REP[pose_rep], P, flags, gr, bv, jmap[0],
+                                jmap[1], out, rot, self._work, dist_util.stream_handle(dev))
+            elif shape is not None:
                 body.rot2verts_shaped(xc, mc, self.skeleton["rest_joints"], self.skeleton["parents"], shape[2], shape[0], shape[1],
                                       _lib.POSE_REP[pose_rep], P, flags, gr, out, rot, self._work, dist_util.stream_handle(dev))
             else:

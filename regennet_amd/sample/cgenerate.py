@@ -12,7 +12,10 @@ kinematics on the device, no body model needed. With `--vertices` and a `--skele
 renders from (visualize/vis_utils.py:35-41), and `--obj_dir DIR` writes them as DIR/sample{i:02d}/frame{t:03d}.obj. `--render_dir DIR` draws them on the
 device (utils/render.py; `--render_size N`, default 1024 as render/crendermotion.py:109-110) and writes DIR/sample{i:02d}/frame{t:03d}.png.
 `--betas_npz FILE` ('betas' [N, nb]; `synthetic`: seeded N(0, 1)) gives every generated sample its own body shape - joints and meshes alike, read
-per frame on the device (`betas_per_motion`) - cycled over repetitions like the actor clips, and stores 'betas' beside them."""
+per frame on the device (`betas_per_motion`) - cycled over repetitions like the actor clips, and stores 'betas' beside them.
+`--jointstype vibe | a2m | a2mpl` makes 'motion' that joint type of the reference's SMPL layer (regressed from the mesh; [N, len(map), 3, T]) in
+place of the skeleton's joints: it needs a `--skeleton` body file that holds the regressors and the type's map (`synthetic`:
+synth.make_joint_regressors)."""
 import os
 import time
 import types
@@ -45,19 +48,28 @@ def set_skeleton(model, args):
         raise SystemExit("--obj_dir writes the meshes of --vertices")
     if getattr(args, "render_dir", "") and not vertices:
         raise SystemExit("--render_dir renders the meshes of --vertices")
+    jointstype = getattr(args, "jointstype", "")
     if not args.skeleton:
         if vertices:
             raise SystemExit("--vertices needs --skeleton BODY.npz (tools/make_skeleton.py --mesh) or --skeleton synthetic")
+        if jointstype:
+            raise SystemExit("--jointstype needs --skeleton BODY.npz (tools/make_skeleton.py --mesh with the joint regressors) or --skeleton synthetic")
         return False
     from ..model.rotation2xyz import load_skeleton_or_body
     if args.skeleton == "synthetic":
-        sk = synth.make_body(model.njoints - 1) if vertices else synth.make_skeleton(model.njoints - 1)
+        sk = synth.make_body(model.njoints - 1) if vertices or jointstype else synth.make_skeleton(model.njoints - 1)
+        if jointstype:
+            sk["mesh"].update(synth.make_joint_regressors(sk))
         print(f"--skeleton synthetic: a synthetic {model.njoints - 1}-joint tree (synth.make_skeleton), not a body model's skeleton"
-              + (f", under a synthetic {sk['mesh']['v_template'].shape[0]}-vertex surface (synth.make_body)" if vertices else ""))
+              + (f", under a synthetic {sk['mesh']['v_template'].shape[0]}-vertex surface (synth.make_body)" if vertices or jointstype else "")
+              + (", with synthetic vertex joints, regressor and joint maps (synth.make_joint_regressors)" if jointstype else ""))
     else:
         sk = load_skeleton_or_body(args.skeleton)
     if vertices and sk.get("mesh", None) is None:
         raise SystemExit(f"--vertices: {args.skeleton} is a skeleton file without mesh arrays (write a body file with tools/make_skeleton.py --mesh)")
+    if jointstype and (sk.get("mesh", None) is None or sk["mesh"].get("vertex_joints", None) is None or jointstype not in sk["mesh"]["joint_maps"]):
+        raise SystemExit(f"--jointstype {jointstype}: {args.skeleton} holds no joint regressors (vertex_joints / J_regressor_extra) or no map_{jointstype} "
+                         f"(write a body file with tools/make_skeleton.py --mesh --vertex_joints ... --joint_regressor_extra ... --joint_maps ...)")
     model.set_skeleton(sk)
     return True
 
@@ -86,8 +98,15 @@ def joint_positions(model, args, sample, y, jointstype=None, betas=None):
     pose_rep = "xyz" if model.data_rep in ("xyz", "hml_vec") else model.data_rep
     mask = None if pose_rep == "xyz" else y["mask"].reshape(sample.shape[0], sample.shape[-1]).bool()
     shapes = {} if betas is None or pose_rep == "xyz" else {"betas_per_motion": torch.from_numpy(np.ascontiguousarray(betas))}
-    return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=jointstype or args.body_model, vertstrans=True,
+    jointstype = jointstype or getattr(args, "jointstype", "") or args.body_model
+    return model.rot2xyz(x=sample, mask=mask, pose_rep=pose_rep, glob=True, translation=True, jointstype=jointstype, vertstrans=True,
                          num_person=1, betas=None, beta=0, glob_rot=None, get_rotations_back=False, **shapes)
+
+
+def motion_rows(model, args):
+    """Rows of 'motion': the skeleton's joints, or with --jointstype the entries of that type's map."""
+    jointstype = getattr(args, "jointstype", "")
+    return len(model.rot2xyz.mesh["joint_maps"][jointstype]) if jointstype else model.njoints - 1
 
 
 def vertex_positions(model, args, sample, y, betas=None):
@@ -206,7 +225,7 @@ def main(argv=None):
             all_betas.append(shapes[(np.arange(B) + rep_i * B) % len(shapes)])
             betas = all_betas[-1][lo:hi]
         if with_motion:                            # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
-            motion = joint_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
+            motion = joint_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, motion_rows(inner, args), 3, n_frames), device=dev)
             all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if with_vertices:
             verts = vertex_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)

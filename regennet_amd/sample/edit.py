@@ -75,7 +75,7 @@ def main(argv=None):
     from ..utils.fixseed import fixseed
     from ..utils.model_util import create_model_and_diffusion, load_model_wo_clip
     from ..utils.parser_util import edit_args
-    from .cgenerate import joint_positions, mesh_results, set_skeleton, vertex_positions
+    from .cgenerate import joint_positions, mesh_results, motion_rows, set_skeleton, vertex_positions
 
     args = edit_args(argv)
     fixseed(args.seed)
@@ -166,7 +166,7 @@ def main(argv=None):
         cms.append(dist_util.all_gather_samples(y["cmotion"], B).cpu().numpy())
         ins.append(dist_util.all_gather_samples(y["inpainted_motion"], B).cpu().numpy())
         if with_motion:
-            motion = joint_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, inner.njoints - 1, 3, n_frames), device=dev)
+            motion = joint_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, motion_rows(inner, args), 3, n_frames), device=dev)
             motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if with_vertices:
             verts = vertex_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, nverts, 3, n_frames), device=dev)

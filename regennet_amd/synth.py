@@ -389,3 +389,33 @@ def make_body(njoints=55, nverts=130, nbetas=10, seed=0, identity_joints=None):
         mesh["shapedirs"] = sd.astype(np.float32)
     sk["mesh"] = mesh
     return sk
+
+
+def make_joint_regressors(body, npicks=21, nreg=9, support=6, seed=0):
+    """Deterministic SYNTHETIC vertex joints, extra-joint regressor and joint-type maps for a body of make_body (or any body dict), as a body file
+    holds them beside the mesh (model/rotation2xyz.py check_joint_regressors): body['mesh'].update(make_joint_regressors(body)) attaches them.
+      vertex_joints      `npicks` distinct vertices (fewer where the body has fewer)
+      J_regressor_extra  [nreg, V]: `support` non-zero weights of mixed sign per row, on random vertices
+      joint_maps         index maps into [J chain joints | picked | regressed] with the reference's lengths - vibe 49, a2m 18 of vibe's entries,
+                         a2mpl the sorted union of a2m with the first 24 chain joints - drawn to reach all three blocks and to repeat indices
+      map_roots          the subtracted output row: vibe 8, a2m 0, a2mpl 0; in all three that row is chain joint 0
+    They have the shapes of a body model's tables and nothing else of them: the licensed ones come from tools/make_skeleton.py."""
+    rng = np.random.Generator(np.random.PCG64([seed, 0x6a726567]))
+    V, J = int(body["mesh"]["v_template"].shape[0]), len(body["parents"])
+    Np, Jr, sup = min(int(npicks), V), int(nreg), min(int(support), V)
+    picks = np.sort(rng.choice(V, Np, replace=False)).astype(np.int32) if Np else np.zeros(0, np.int32)
+    picks = picks[rng.permutation(Np)] if Np else picks
+    reg = np.zeros((Jr, V), np.float32)
+    for r in range(Jr):
+        cols = rng.choice(V, sup, replace=False)
+        sign = np.where((np.arange(sup) + rng.integers(0, 2)) % 2 == 0, 1.0, -1.0)
+        reg[r, cols] = (sign * rng.uniform(0.2, 1.0, sup)).astype(np.float32)
+    nall = J + Np + Jr
+    vibe = rng.integers(0, nall, 49)
+    vibe[[0, 1, 2]] = [J - 1, min(J, nall - 1), nall - 1]            # the last chain joint, the first and the last joint behind the chain
+    vibe[8], vibe[48] = 0, vibe[3]                                  # the root row is chain joint 0; one repeat for certain
+    a2m = vibe[np.r_[8, 0, 1, 2, np.sort(rng.choice(np.arange(9, 49), 14, replace=False))]]
+    a2mpl = np.unique(np.r_[np.arange(min(24, J)), a2m])
+    return {"vertex_joints": picks, "J_regressor_extra": reg,
+            "joint_maps": {"vibe": vibe.astype(np.int32), "a2m": a2m.astype(np.int32), "a2mpl": a2mpl.astype(np.int32)},
+            "map_roots": {"vibe": 8, "a2m": 0, "a2mpl": 0}}

@@ -72,6 +72,10 @@ def add_generate_options(p):
                    help="skeleton npz (tools/make_skeleton.py) or 'synthetic': also store 'motion', the joint positions model.rot2xyz gives")
     g.add_argument("--vertices", action="store_true",
                    help="also store 'vertices' [N,V,3,T] and 'faces': needs a --skeleton with mesh arrays (tools/make_skeleton.py --mesh; 'synthetic': synth.make_body)")
+    g.add_argument("--jointstype", default="", choices=["", "vibe", "a2m", "a2mpl"], type=str,
+                   help="'motion' holds this joint type (regressed from the mesh) instead of the skeleton's joints: needs a --skeleton body file with "
+                        "vertex_joints / J_regressor_extra and the type's map (tools/make_skeleton.py --mesh --joint_maps ...; 'synthetic': "
+                        "synth.make_joint_regressors)")
     g.add_argument("--betas_npz", default="", type=str,
                    help="with --skeleton: npz with 'betas' [N,nb], the reactor's body shape per generated sample (cycled over repetitions like the actor "
                         "clips), for 'motion' and 'vertices'; 'synthetic': seeded N(0,1) shapes; results.npy stores 'betas'")

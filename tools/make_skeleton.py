@@ -18,7 +18,15 @@ With `--mesh` the file becomes a BODY FILE, which also serves jointstype='vertic
     lbs_weights     [V, J]            `weights` of the model file
     shapedirs       [V, 3, nb]
     faces           [F, 3] int32      where the model file has `f`
-    identity_joints [22, 23, 24] for --body_model smplx (the jaw and eye rotations the reference's wrapper does not hand over), else empty"""
+    identity_joints [22, 23, 24] for --body_model smplx (the jaw and eye rotations the reference's wrapper does not hand over), else empty
+
+and, for the joint types the reference regresses from the mesh (jointstype 'vibe' / 'a2m' / 'a2mpl'; `--jointstype` of the CLIs), from three more
+inputs (INTEGRATION.md says where each comes from):
+
+    vertex_joints      [Np] int32      --vertex_joints FILE          .npy, or a text list of vertex ids
+    J_regressor_extra  [Jr, V]         --joint_regressor_extra FILE.npy
+    map_vibe / map_a2m / map_a2mpl     --joint_maps FILE.npz         int arrays `vibe`, `a2m`, `a2mpl` (any subset): indices into
+    map_roots          [3] int32                                     [J joints | Np vertex joints | Jr regressed joints]; `roots` [3] optional (8, 0, 0)"""
 import argparse
 
 import numpy as np
@@ -56,6 +64,23 @@ def make_mesh(model, num_betas=10, body_model=""):
     return out
 
 
+def make_joint_regressors(vertex_joints="", joint_regressor_extra="", joint_maps=""):
+    """dict of the regressed joint types' arrays from the three option files ('' : not given)."""
+    out = {}
+    if vertex_joints:
+        ids = np.load(vertex_joints, allow_pickle=False) if vertex_joints.endswith(".npy") else np.array(open(vertex_joints).read().replace(",", " ").split(), dtype=np.int64)
+        out["vertex_joints"] = np.asarray(ids).reshape(-1).astype(np.int32)
+    if joint_regressor_extra:
+        out["J_regressor_extra"] = np.asarray(np.load(joint_regressor_extra, allow_pickle=False), dtype=np.float32)
+    if joint_maps:
+        with np.load(joint_maps, allow_pickle=False) as z:
+            for t in ("vibe", "a2m", "a2mpl"):
+                if t in z.files:
+                    out["map_" + t] = np.asarray(z[t]).reshape(-1).astype(np.int32)
+            out["map_roots"] = np.asarray(z["roots"]).reshape(-1).astype(np.int32) if "roots" in z.files else np.array([8, 0, 0], np.int32)
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("model", help="body-model npz (J_regressor, v_template, shapedirs, kintree_table)")
@@ -63,11 +88,24 @@ def main(argv=None):
     p.add_argument("--body_model", default="", help="label stored in the file, e.g. smplx")
     p.add_argument("--num_betas", default=10, type=int)
     p.add_argument("--mesh", action="store_true", help="write a body file: also v_template, posedirs, lbs_weights, shapedirs, faces, identity_joints")
+    p.add_argument("--vertex_joints", default="", help="with --mesh: .npy or text list of the vertex ids that are joints")
+    p.add_argument("--joint_regressor_extra", default="", help="with --mesh: .npy [Jr, V], the extra joints' regressor")
+    p.add_argument("--joint_maps", default="", help="with --mesh: .npz with int arrays vibe / a2m / a2mpl (and roots [3])")
     args = p.parse_args(argv)
+    extras = make_joint_regressors(args.vertex_joints, args.joint_regressor_extra, args.joint_maps)
+    if extras and not args.mesh:
+        p.error("--vertex_joints / --joint_regressor_extra / --joint_maps belong to a body file: give --mesh")
     with np.load(args.model, allow_pickle=False) as z:
         sk = make_skeleton({k: z[k] for k in z.files if k in ("J_regressor", "v_template", "shapedirs", "kintree_table")}, args.num_betas, args.body_model)
         if args.mesh:
             sk.update(make_mesh({k: z[k] for k in z.files if k in ("v_template", "weights", "posedirs", "shapedirs", "f")}, args.num_betas, args.body_model))
+    if extras:                                          # validated as the loader will validate them
+        import os
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from regennet_amd.model.rotation2xyz import check_joint_regressors
+        check_joint_regressors(extras, sk["v_template"].shape[0], len(sk["parents"]))
+        sk.update(extras)
     np.savez(args.out, **sk)
     print(f"{args.out}: {len(sk['parents'])} joints, {sk.get('shape_joints', np.zeros((0, 0, 0))).shape[2]} shape directions"
           + (f", {sk['v_template'].shape[0]} vertices" if args.mesh else ""))
