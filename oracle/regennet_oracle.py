@@ -213,6 +213,38 @@ def cfg_forward(sd, cfg, x, timesteps, y):
 # --------------------------------------------------------------------------------------
 # a5-a10: sampling loops                      gaussian_diffusion.py:289-400,508-560,610-794,891-1005
 # --------------------------------------------------------------------------------------
+def _sqrt(x):
+    """torch.sqrt in float32, CORRECTLY ROUNDED - what IEEE 754 asks of a square root and what sqrtf and the reference's device kernels give.
+    torch's CPU sqrt goes through a vector math library that is allowed a last-place error (measured: every fifth result one ulp off on one
+    host, 0.6 % on another, at any tensor size), and ddim_sample's sqrt(1 - abp - sigma^2) cancels: one ulp in sigma moves that coefficient by
+    1e-4 of itself at the first step of the cosine schedule with eta = 1, or makes its argument negative. numpy's float32 sqrt is the hardware
+    instruction."""
+    with np.errstate(invalid="ignore"):                                     # (a negative argument is nan, as in torch)
+        return torch.from_numpy(np.sqrt(x.contiguous().numpy()))
+
+
+def sampler_step(tb, i, x, x0, noise, mode="ddpm", eta=0.0, clip=False):
+    """One step of p_sample (mode='ddpm') or ddim_sample (mode='ddim') at loop index i from the state x and the model's prediction x0:
+    the clamp, then the update in the reference's fp32 operation order. Returns (next state, pred_xstart as the step used it)."""
+    t = torch.tensor([i] * x.shape[0])                                       # gaussian_diffusion.py:724
+    if clip:
+        x0 = x0.clamp(-1, 1)                                                 # process_xstart :366-372
+    nz = (t != 0).float().view(-1, 1, 1, 1)
+    if mode == "ddpm":                                                       # p_sample :508-560; FIXED_SMALL :344-364
+        mean = _extract(tb["posterior_mean_coef1"], t, x.shape) * x0 + \
+               _extract(tb["posterior_mean_coef2"], t, x.shape) * x
+        logvar = _extract(tb.get("model_log_variance", tb["posterior_log_variance_clipped"]), t, x.shape)
+        return mean + nz * torch.exp(0.5 * logvar) * noise, x0
+    # ddim_sample :744-794
+    eps = (_extract(tb["sqrt_recip_alphas_cumprod"], t, x.shape) * x - x0) / \
+          _extract(tb["sqrt_recipm1_alphas_cumprod"], t, x.shape)
+    ab = _extract(tb["alphas_cumprod"], t, x.shape)
+    abp = _extract(tb["alphas_cumprod_prev"], t, x.shape)
+    sigma = eta * _sqrt((1 - abp) / (1 - ab)) * _sqrt(1 - ab / abp)
+    mean = x0 * _sqrt(abp) + _sqrt(1 - abp - sigma ** 2) * eps
+    return mean + nz * sigma * noise, x0
+
+
 def sample_loop(sd, cfg, schedule, tape, y, mode="ddpm", guided=False, eta=0.0, trace=None, clip_denoised=False,
                 skip_timesteps=0, init_image=None):
     """Run p_sample_loop (mode='ddpm') or ddim_sample_loop (mode='ddim') with an injected noise tape.
@@ -238,23 +270,8 @@ def sample_loop(sd, cfg, schedule, tape, y, mode="ddpm", guided=False, eta=0.0, 
         for i in range(first, -1, -1):
             t = torch.tensor([i] * B)                                        # gaussian_diffusion.py:724
             x0 = fwd(sd, cfg, img, tmap_t[t], y)                             # respace.py:124-129; START_X :381
-            if clip_denoised:
-                x0 = x0.clamp(-1, 1)                                         # process_xstart :366-372
             noise = torch.as_tensor(tape[k]); k += 1
-            nz = (t != 0).float().view(-1, 1, 1, 1)
-            if mode == "ddpm":                                               # p_sample :508-560; FIXED_SMALL :344-364
-                mean = _extract(tb["posterior_mean_coef1"], t, img.shape) * x0 + \
-                       _extract(tb["posterior_mean_coef2"], t, img.shape) * img
-                logvar = _extract(tb.get("model_log_variance", tb["posterior_log_variance_clipped"]), t, img.shape)
-                img = mean + nz * torch.exp(0.5 * logvar) * noise
-            else:                                                            # ddim_sample :744-794
-                eps = (_extract(tb["sqrt_recip_alphas_cumprod"], t, img.shape) * img - x0) / \
-                      _extract(tb["sqrt_recipm1_alphas_cumprod"], t, img.shape)
-                ab = _extract(tb["alphas_cumprod"], t, img.shape)
-                abp = _extract(tb["alphas_cumprod_prev"], t, img.shape)
-                sigma = eta * torch.sqrt((1 - abp) / (1 - ab)) * torch.sqrt(1 - ab / abp)
-                mean = x0 * torch.sqrt(abp) + torch.sqrt(1 - abp - sigma ** 2) * eps
-                img = mean + nz * sigma * noise
+            img, x0 = sampler_step(tb, i, img, x0, noise, mode, eta, clip_denoised)
             if trace is not None:
                 trace.setdefault("x0", []).append(x0.clone())
                 trace.setdefault("x", []).append(img.clone())
