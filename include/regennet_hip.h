@@ -297,6 +297,53 @@ RGN_API int rgn_loss_terms(rgn_handle h, const float* target_dev, const float* o
                            const int32_t* foot_joints_host /*[4]*/, int32_t transl_row, float vel_threshold, int32_t flags /*RGN_LOSS_FC*/,
                            float* terms_dev /*[B,7]*/, void* stream);
 
+/* ---- The variational bound of held-out motions: GaussianDiffusion.calc_bpd_loop (diffusion/gaussian_diffusion.py:1546-1601) ----
+ * The reference walks the S timesteps of a batch one after the other (one randn_like, one q_sample, one forward and ~25 elementwise ops each).
+ * The timesteps of a motion do not depend on one another; here they are ROWS: N = n_t x B rows in (timestep, motion) order, row r belongs to
+ * motion b = r % B and carries its own loop index t_dev[r] and its own schedule coefficients. Both calls are stateless, allocate nothing, enqueue
+ * on `stream` and can be captured into a graph. `features` = R F (njoints x nfeats), so a row has n = features x T elements; n need be no
+ * multiple of anything.
+ *
+ * rgn_q_sample_rows: q_sample (:245-263) per row,
+ *   x_t_dev[r] = coef_dev[r, 0] * x_start_dev[r % B] + coef_dev[r, 1] * noise_r
+ * in fp32 with two separately rounded products and one add (no fma): bit-equal to the torch expression on the same noise.
+ *   x_start_dev fp32 [B, R, F, T]; coef_dev fp32 [N, 2] = (sqrt_alphas_cumprod[t_r], sqrt_one_minus_alphas_cumprod[t_r]), the fp64 table entries
+ *           rounded to fp32 (what _extract_into_tensor(...).float() hands the reference's arithmetic, :1604-1617); t_dev int32 [N]
+ *   noise_dev fp32 [N, R, F, T], or NULL: the noise is drawn in the kernel, element (feature, frame) of row r being exactly the value
+ *           rgn_randn_step(seed, sample_offset + r % B, loop_index = t_dev[r]) yields - Philox(seed; sample_offset + b, t_r, feature * 4096 + frame).
+ *           A motion's x_t at a timestep therefore depends neither on how timesteps are grouped into calls nor on the batch it sits in.
+ *   x_t_dev fp32 [N, R, F, T]; noise_out_dev (nullable) fp32 [N, R, F, T] receives the noise that was used.
+ *
+ * rgn_vb_terms: the terms of _vb_terms_bpd (:1204-1237) and of the loop body (:1584-1587) for a model output that is already on the device,
+ *   terms_dev fp32 [N, 3] = (vb, xstart_mse, mse), each a mean over the row's n elements, with p = output (clamped to [-1, 1] under RGN_VB_CLIP,
+ *   :366-372), mean_q = c1 x0 + c2 x_t (:265-276) and mean_m = c1 p + c2 x_t (:386):
+ *     vb, t != 0   mean(0.5 (-1 + lv_m - lv_q + exp(lv_q - lv_m) + (mean_q - mean_m)^2 exp(-lv_m))) / ln 2      diffusion/losses.py:12-39, :1223-1226
+ *     vb, t == 0   mean(-log p_disc) / ln 2: the discretised Gaussian log-likelihood of x0 under (mean_m, 0.5 lv_m) as diffusion/losses.py:42-77
+ *                  writes it - the tanh approximation of the normal CDF, the +-1/255 bin, the x < -0.999 / x > 0.999 branches and the clamp at 1e-12
+ *                  before each log (:1228-1232). Only rows with t_dev[r] == 0 evaluate it; t_dev is looked at for nothing else.
+ *     xstart_mse   mean((p - x0)^2)                                                                             :1585
+ *     mse          mean((eps - noise)^2), eps = (sr x_t - p) / srm1                                             :419-423, :1586-1587
+ *                  noise_dev == NULL: the column is 0 and no noise is read; the other two columns are unchanged bit for bit.
+ *   x_start_dev fp32 [B, R, F, T]; x_t_dev, output_dev, noise_dev (nullable) fp32 [N, R, F, T]; t_dev int32 [N]
+ *   coef_dev fp32 [N, 6] = posterior_mean_coef1 (c1), posterior_mean_coef2 (c2), posterior_log_variance_clipped (lv_q), the model's log variance
+ *           (lv_m: FIXED_SMALL or FIXED_LARGE, :344-364), sqrt_recip_alphas_cumprod (sr), sqrt_recipm1_alphas_cumprod (srm1) at t_r, each the fp64 table
+ *           entry rounded to fp32.
+ * Arithmetic: fp64 from the fp32 inputs and the fp32 coefficients, every output rounded to fp32 once (rgn_loss_terms' convention). One workgroup per
+ * row, sums in a fixed order, no atomics: a row's three numbers depend neither on N nor on the other rows and are the same on every run.
+ *
+ * Both check their arguments before the handle or the device is touched - RGN_ERR_INVALID_ARG for a null pointer, B, N, features or T < 1,
+ * N % B != 0, a row of more than 2^31 - 1 elements, an unknown flag; rgn_q_sample_rows also for a call of more than 2^31 - 1 workgroups (N times
+ * ceil(n / 256)) and, when it draws, for T > 4096 or features > 2^19 (the Philox element counter feature * 4096 + frame) - with text in rgn_last_error(h), or rgn_last_error(NULL) when h is NULL (which is itself
+ * RGN_ERR_INVALID_ARG once the other arguments have passed). */
+enum { RGN_VB_CLIP = 1 };
+enum { RGN_VB_VB = 0, RGN_VB_XSTART_MSE, RGN_VB_MSE, RGN_VB_NTERMS };
+RGN_API int rgn_q_sample_rows(rgn_handle h, const float* x_start_dev, const float* noise_dev /*nullable*/, const float* coef_dev /*[N,2]*/,
+                              const int32_t* t_dev /*[N]*/, int32_t B, int32_t N, int32_t features, int32_t T, uint64_t seed, uint64_t sample_offset,
+                              float* x_t_dev, float* noise_out_dev /*nullable*/, void* stream);
+RGN_API int rgn_vb_terms(rgn_handle h, const float* x_start_dev, const float* x_t_dev, const float* output_dev, const float* noise_dev /*nullable*/,
+                         const int32_t* t_dev /*[N]*/, const float* coef_dev /*[N,6]*/, int32_t B, int32_t N, int32_t features, int32_t T,
+                         int32_t flags /*RGN_VB_CLIP*/, float* terms_dev /*[N,3]*/, void* stream);
+
 /* ---- Mesh vertices: jointstype='vertices' ----
  * Replaces the body layer the reference keeps in Rotation2xyz.smpl_model / Rotation2xyz_x.smpl_model (model/rotation2xyz.py:14-15 / :161-162, a CPU
  * smplx layer over a licensed model file): the mesh data of a BODY FILE (tools/make_skeleton.py --mesh), resident on `device`.

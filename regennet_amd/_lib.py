@@ -26,6 +26,8 @@ POSE_REP_CHANNELS = {"rot6d": 6, "rotvec": 3, "rotquat": 4, "rotmat": 9}
 R2X_TRANSLATION, R2X_GLOB, R2X_VERTSTRANS = 1, 2, 4
 LOSS_FC = 1                                                          # RGN_LOSS_FC
 LOSS_TERMS = ("rot_mse", "rcxyz_mse", "vel_mse", "fc", "orient", "body", "transl")      # the columns of rgn_loss_terms (RGN_LOSS_*)
+VB_CLIP = 1                                                          # RGN_VB_CLIP
+VB_TERMS = ("vb", "xstart_mse", "mse")                               # the columns of rgn_vb_terms (RGN_VB_*)
 
 
 class RgnError(RuntimeError):
@@ -77,6 +79,8 @@ SYMBOLS = {
     "rgn_rot2xyz": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rgn_rot2xyz_shaped": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "rgn_loss_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp]),
+    "rgn_q_sample_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp]),
+    "rgn_vb_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "rgn_profile_enable": (C.c_int, [_vp, _i32]),
     "rgn_profile_query": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "rgn_profile_bracket_overhead": (C.c_int, [_vp, C.POINTER(C.c_double)]),
@@ -366,6 +370,28 @@ class Engine:
         self._ck(self.lib.rgn_loss_terms(self.h, _ptr(target), _ptr(output), _ptr(cmotion), _ptr(mask), int(B), int(T), int(R), len(pa),
                                          rj.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p), fj.ctypes.data_as(C.c_void_p), int(transl_row),
                                          float(vel_threshold), int(flags), _ptr(terms), C.c_void_p(stream)))
+
+    def q_sample_rows(self, x_start, noise, coef, t, seed, sample_offset, x_t, noise_out, stream):
+        """rgn_q_sample_rows: x_start fp32 [B, R, F, T], coef fp32 [N, 2], t int32 [N] -> x_t fp32 [N, R, F, T], row r of motion r % B; noise fp32
+        [N, R, F, T], or None: drawn as rgn_randn_step(seed, sample_offset + b, t[r]) and, when noise_out is given, written there."""
+        B, R, F, T = x_start.shape
+        N = int(x_t.shape[0])
+        assert tuple(x_t.shape) == (N, R, F, T) and tuple(coef.shape) == (N, 2) and tuple(t.shape) == (N,) and t.element_size() == 4
+        assert all(a is None or (tuple(a.shape) == (N, R, F, T) and a.is_contiguous() and a.element_size() == 4) for a in (noise, noise_out))
+        assert all(a.is_contiguous() and a.element_size() == 4 for a in (x_start, coef, t, x_t))
+        self._ck(self.lib.rgn_q_sample_rows(self.h, _ptr(x_start), _ptr(noise), _ptr(coef), _ptr(t), int(B), N, int(R * F), int(T),
+                                            int(seed) & (2 ** 64 - 1), int(sample_offset), _ptr(x_t), _ptr(noise_out), C.c_void_p(stream)))
+
+    def vb_terms(self, x_start, x_t, output, noise, t, coef, flags, terms, stream):
+        """rgn_vb_terms: x_start fp32 [B, R, F, T]; x_t, output and noise (or None) fp32 [N, R, F, T]; t int32 [N]; coef fp32 [N, 6] -> terms fp32
+        [N, 3] (columns: VB_TERMS), row r of motion r % B."""
+        B, R, F, T = x_start.shape
+        N = int(x_t.shape[0])
+        assert tuple(x_t.shape) == tuple(output.shape) == (N, R, F, T) and tuple(coef.shape) == (N, 6) and tuple(t.shape) == (N,) and t.element_size() == 4
+        assert noise is None or (tuple(noise.shape) == (N, R, F, T) and noise.is_contiguous() and noise.element_size() == 4)
+        assert tuple(terms.shape) == (N, len(VB_TERMS)) and all(a.is_contiguous() and a.element_size() == 4 for a in (x_start, x_t, output, coef, t, terms))
+        self._ck(self.lib.rgn_vb_terms(self.h, _ptr(x_start), _ptr(x_t), _ptr(output), _ptr(noise), _ptr(t), _ptr(coef), int(B), N, int(R * F), int(T),
+                                       int(flags), _ptr(terms), C.c_void_p(stream)))
 
     def profile_enable(self, on):
         self._ck(self.lib.rgn_profile_enable(self.h, int(bool(on))))

@@ -611,6 +611,66 @@ int rgn_loss_terms(rgn_handle h, const float* target, const float* output, const
     });
 }
 
+// The checks rgn_q_sample_rows and rgn_vb_terms share: the complaint's text, or empty. n receives the elements of a row.
+static std::string vb_check_rows(int32_t B, int32_t N, int32_t features, int32_t T, int& n) {
+    if (B < 1 || N < 1 || features < 1 || T < 1) return "B < 1, N < 1, features < 1 or T < 1";
+    if (N % B != 0) return "N = " + std::to_string(N) + " rows are no multiple of B = " + std::to_string(B) + " motions";
+    const long long ne = (long long)features * T;
+    if (ne > 0x7fffffffLL) return "a row of " + std::to_string(ne) + " elements (more than 2^31 - 1)";
+    n = (int)ne;
+    return std::string();
+}
+
+int rgn_q_sample_rows(rgn_handle h, const float* x_start, const float* noise, const float* coef, const int32_t* t_idx, int32_t B, int32_t N,
+                      int32_t features, int32_t T, uint64_t seed, uint64_t sample_offset, float* x_t, float* noise_out, void* stream) {
+    return rgn_guard(h, "rgn_q_sample_rows", [&]() -> int {
+        // the arguments first, the handle after them (text: rgn_last_error(NULL) while there is no handle)
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_q_sample_rows: " + m);
+            g_create_error = "rgn_q_sample_rows: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        if (!x_start || !coef || !t_idx || !x_t) return bad("null x_start, coef, t or x_t");
+        int n = 0;
+        const std::string why = vb_check_rows(B, N, features, T, n);
+        if (!why.empty()) return bad(why);
+        if ((long long)N * q_sample_chunks(n) > 0x7fffffffLL) return bad("N = " + std::to_string(N) + " rows of " + std::to_string(n) + " elements (more than 2^31 - 1 workgroups)");
+        if (!noise && (T > 4096 || features > (1 << 19))) return bad("drawn noise needs T <= 4096 and features <= 2^19 (Philox element counter)");
+        if (!h) return bad("null handle");
+        RGN_HIP(h, hipSetDevice(h->cfg.device));
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_q_sample_rows: weights not finalized");
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = h->stream;
+        int rc = stream_enter(h, us);
+        if (rc) return rc;
+        RGN_LAUNCH(h, KC_MISC, s, launch_q_sample_rows(x_start, noise, coef, t_idx, x_t, noise_out, B, N, n, T, seed, sample_offset, s));
+        return stream_exit(h, us);
+    });
+}
+
+int rgn_vb_terms(rgn_handle h, const float* x_start, const float* x_t, const float* output, const float* noise, const int32_t* t_idx, const float* coef,
+                 int32_t B, int32_t N, int32_t features, int32_t T, int32_t flags, float* terms, void* stream) {
+    return rgn_guard(h, "rgn_vb_terms", [&]() -> int {
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_vb_terms: " + m);
+            g_create_error = "rgn_vb_terms: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        if (!x_start || !x_t || !output || !t_idx || !coef || !terms) return bad("null x_start, x_t, output, t, coef or terms");
+        int n = 0;
+        const std::string why = vb_check_rows(B, N, features, T, n);
+        if (!why.empty()) return bad(why);
+        if (flags & ~RGN_VB_CLIP) return bad("unknown flag");
+        if (!h) return bad("null handle");
+        RGN_HIP(h, hipSetDevice(h->cfg.device));
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_vb_terms: weights not finalized");
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = h->stream;
+        int rc = stream_enter(h, us);
+        if (rc) return rc;
+        RGN_LAUNCH(h, KC_MISC, s, launch_vb_terms(x_start, x_t, output, noise, t_idx, coef, terms, B, N, n, flags, s));
+        return stream_exit(h, us);
+    });
+}
+
 int rgn_profile_enable(rgn_handle h, int32_t on) {
     return rgn_guard(h, "rgn_profile_enable", [&]() -> int {
         if (!h) return RGN_ERR_INVALID_ARG;

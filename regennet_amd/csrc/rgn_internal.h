@@ -395,6 +395,13 @@ inline const char* fk_check_shape(const float* shape_joints, int nb, const float
 size_t loss_lds_bytes(int J);
 hipError_t launch_loss_terms(const float* target, const float* output, const float* cmotion, const uint8_t* mask, float* terms, int B, int T, int J,
                              const int* foot, int transl_row, float vel_threshold, int flags, const FkSkel& sk, hipStream_t s);
+// ---- rgn_vb.hip: calc_bpd_loop's rows (rgn_q_sample_rows, rgn_vb_terms). N rows of n = R F T elements, row r of motion r % B; x_start [B, n],
+// every other tensor [N, n]; coef [N, 2] / [N, 6] fp32, t_idx [N] int32 on the device
+int q_sample_chunks(int n);     // workgroups per row of n elements: the call's grid is N times that
+hipError_t launch_q_sample_rows(const float* x_start, const float* noise_in, const float* coef, const int* t_idx, float* x_t, float* noise_out, int B,
+                                int N, int n, int T, unsigned long long seed, unsigned long long sample_offset, hipStream_t s);
+hipError_t launch_vb_terms(const float* x_start, const float* x_t, const float* output, const float* noise, const int* t_idx, const float* coef,
+                           float* terms, int B, int N, int n, int flags, hipStream_t s);
 // The skeleton argument checks of rgn_rot2xyz / rgn_rot2verts and the table their kernels take by value. nullptr when `sk` was filled, else the text of
 // the complaint (without the entry point's name); `at` receives the offending joint for the parent-table complaint, else -1. Host only.
 inline const char* fk_build_skel(int J, const float* rest_joints, const int32_t* parents, FkSkel& sk, int& at) {

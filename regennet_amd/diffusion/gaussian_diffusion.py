@@ -1,6 +1,6 @@
 """Host side of the diffusion sampler — mirror of the reference's `diffusion/gaussian_diffusion.py`
-(the sampling half, and `training_losses` as an EVALUATION of the objective: its terms for given motions, no backward; PLMS and classifier
-guidance are out of scope).
+(the sampling half, and `training_losses` and `calc_bpd_loop` as EVALUATIONS: the objective's terms and the variational bound for given motions,
+no backward; PLMS and classifier guidance are out of scope).
 
 The schedule tables are fp64 NumPy exactly as the reference builds them (gaussian_diffusion.py:172-209);
 the step loop itself runs inside libregennet_hip.so (rgn_sample_range): per step one denoiser evaluation
@@ -73,6 +73,21 @@ def _engine_of(model):
             "regennet_amd diffusion drives the HIP denoiser only: pass a regennet_amd CMDM or "
             "ClassifierFreeSampleModel (got %r). There is no generic eager fallback." % type(model).__name__)
     return eng
+
+
+def _denoiser_of(model):
+    """The CMDM behind the wrappers a caller may hand in - ClassifierFreeSampleModel and SpacedDiffusion's wrapper (`.model`), a
+    DistributedDataParallel stand-in (`.module`) - whose engine runs the stand-alone kernels."""
+    m = model
+    for _ in range(8):
+        if hasattr(m, "_get_engine"):
+            return m
+        m = getattr(m, "model", None) or getattr(m, "module", None)
+        if m is None:
+            break
+    raise TypeError(
+        "regennet_amd diffusion drives the HIP denoiser only: pass a regennet_amd CMDM or "
+        "ClassifierFreeSampleModel (got %r). There is no generic eager fallback." % type(model).__name__)
 
 
 class GaussianDiffusion:
@@ -230,6 +245,135 @@ class GaussianDiffusion:
         eng.loss_terms(f32(target), f32(model_output), f32(cmotion), mk, r2x.rest_joints(), r2x.skeleton["parents"], self.LOSS_FOOT_JOINTS, self.LOSS_TRANSL_ROW,
                        float(getattr(self, "vel_threshold", 0.01)), _lib.LOSS_FC, terms, dist_util.stream_handle(dev))
         return self._loss_dict(terms.to(x_start.device), dataset)
+
+    # ---- the variational bound, evaluated (gaussian_diffusion.py:228-243, :265-287, :419-423, :1204-1237, :1528-1601) ------
+    def q_mean_variance(self, x_start, t):
+        """q(x_t | x_0) = N(sqrt(abar_t) x_0, (1 - abar_t) I) -> (mean, variance, log variance), each of x_start's shape, fp32 (what
+        gaussian_diffusion.py:228-243 returns)."""
+        at = lambda table: _extract_into_tensor(table, t, x_start.shape)      # noqa: E731
+        return at(self.sqrt_alphas_cumprod) * x_start, at(1.0 - self.alphas_cumprod), at(self.log_one_minus_alphas_cumprod)
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """q(x_{t-1} | x_t, x_0): mean c1_t x_0 + c2_t x_t, the posterior variance and its clipped logarithm, each of x_t's shape, fp32 (what
+        gaussian_diffusion.py:265-287 returns)."""
+        if x_start.shape != x_t.shape or t.shape[0] != x_t.shape[0]:
+            raise AssertionError(f"x_start {tuple(x_start.shape)}, x_t {tuple(x_t.shape)} and t {tuple(t.shape)} do not belong together")
+        at = lambda table: _extract_into_tensor(table, t, x_t.shape)          # noqa: E731
+        mean = at(self.posterior_mean_coef1) * x_start + at(self.posterior_mean_coef2) * x_t
+        return mean, at(self.posterior_variance), at(self.posterior_log_variance_clipped)
+
+    def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
+        """The noise that takes pred_xstart to x_t: (sqrt(1 / abar_t) x_t - x_0) / sqrt(1 / abar_t - 1) (gaussian_diffusion.py:419-423)."""
+        at = lambda table: _extract_into_tensor(table, t, x_t.shape)          # noqa: E731
+        return (at(self.sqrt_recip_alphas_cumprod) * x_t - pred_xstart) / at(self.sqrt_recipm1_alphas_cumprod)
+
+    def _prior_bpd(self, x_start):
+        """gaussian_diffusion.py:1528-1544: KL(q(x_{S-1} | x_0) || N(0, I)) per motion in bits per dimension. One torch expression; CPU tensors work too."""
+        from .losses import mean_flat, normal_kl
+        last = th.full((x_start.shape[0],), self.num_timesteps - 1, device=x_start.device, dtype=th.long)
+        mean, _, log_variance = self.q_mean_variance(x_start, last)
+        return mean_flat(normal_kl(mean, log_variance, 0.0, 0.0)) / math.log(2.0)
+
+    def _vb_tables(self):
+        """The six tables behind the columns of rgn_vb_terms' coef_dev, in its order."""
+        return (self.posterior_mean_coef1, self.posterior_mean_coef2, self.posterior_log_variance_clipped, self._model_variance_tables()[1],
+                self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod)
+
+    def _vb_checks(self, model_kwargs):
+        if self.model_mean_type != ModelMeanType.START_X:
+            raise NotImplementedError("CMDM predicts x_start (model_util.py:77)")
+        self._model_variance_tables()                              # raises for learned variances
+        if model_kwargs is None or "y" not in model_kwargs:
+            raise KeyError("model_kwargs['y'] with 'cmotion' is required (gaussian_diffusion.py:319, cmdm.py:189)")
+
+    @staticmethod
+    def _inpainting_blend(model_output, y):
+        """gaussian_diffusion.py:319-323."""
+        if "inpainting_mask" in y and "inpainted_motion" in y:
+            m, im = y["inpainting_mask"], y["inpainted_motion"]
+            assert model_output.shape == m.shape == im.shape
+            model_output = ((model_output * ~m) + (im * m)).contiguous()
+        return model_output
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """gaussian_diffusion.py:1204-1237: {'output': [B] the decoder NLL (t == 0) or KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)) in bits per
+        dimension, 'pred_xstart'}. ONE ordinary forward of the model and one rgn_vb_terms call of B rows."""
+        from .. import _lib
+        from ..utils import dist_util
+        self._vb_checks(model_kwargs)
+        enc = _denoiser_of(model)
+        B = x_t.shape[0]
+        assert x_start.shape == x_t.shape and t.shape == (B,)
+        with th.no_grad():
+            model_output = self._inpainting_blend(model(x_t, self._model_timesteps(t), **model_kwargs), model_kwargs["y"])
+        dev = model_output.device
+        f32 = lambda a: a.detach().to(device=dev, dtype=th.float32).contiguous()      # noqa: E731
+        td = t.to(dev)
+        coef = th.stack([th.from_numpy(tab).to(dev)[td].float() for tab in self._vb_tables()], 1).contiguous()
+        terms = th.empty((B, len(_lib.VB_TERMS)), device=dev, dtype=th.float32)
+        enc._engine.vb_terms(f32(x_start), f32(x_t), f32(model_output), None, td.to(th.int32).contiguous(), coef,
+                             _lib.VB_CLIP if clip_denoised else 0, terms, dist_util.stream_handle(dev))
+        return {"output": terms[:, 0].to(x_start.device), "pred_xstart": model_output.clamp(-1, 1) if clip_denoised else model_output}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, noise_tape=None, seed=None, sample_offset=0,
+                      max_rows_per_call=256):
+        """gaussian_diffusion.py:1546-1601: the variational bound of x_start [B, njoints, nfeats, T] in bits per dimension ->
+        {'total_bpd' [B], 'prior_bpd' [B], 'vb', 'xstart_mse', 'mse' [B, S]}, column k holding timestep S - 1 - k as the reference stacks them.
+        The reference runs the S timesteps one after the other; they do not depend on one another, so here they are rows of larger evaluations:
+        as many whole timesteps as fit into `max_rows_per_call` rows (at least one) go through rgn_q_sample_rows, ONE forward and rgn_vb_terms,
+        in (t, b) order with the per-sample entries of y repeated (eval/auto_regressive.repeat_y).
+        Extra keyword-only arguments (not in the reference): noise_tape [S, B, njoints, nfeats, T], entry k being the reference's k-th randn_like
+        (timestep S - 1 - k); otherwise the noise of (motion b, timestep t) is the Philox draw rgn_randn_step(seed, sample_offset + b, t) -
+        `seed` None: derived from torch's generator - so a motion's x_t depends neither on max_rows_per_call nor on the batch it sits in."""
+        from .. import _lib
+        from ..eval.auto_regressive import repeat_y
+        from ..utils import dist_util
+        self._vb_checks(model_kwargs)
+        enc = _denoiser_of(model)
+        y = model_kwargs["y"]
+        B, R, F, T = (int(v) for v in x_start.shape)
+        S = self.num_timesteps
+        per = min(S, max(1, int(max_rows_per_call) // B))          # timesteps per evaluation
+        # the two kernels need ANY live finalized handle on the device: the first q_sample takes the engine sized for the largest evaluation
+        # (the forward asks for the same (rows, T), so nothing is rebuilt), every later call the engine the last forward ran on
+        eng, dev = enc._get_engine(per * B, T)
+        stream = dist_util.stream_handle(dev)
+        x0 = x_start.detach().to(device=dev, dtype=th.float32).contiguous()
+        tape = None
+        if noise_tape is not None:
+            tape = noise_tape.to(device=dev, dtype=th.float32)
+            assert tuple(tape.shape[1:]) == (B, R, F, T) and tape.shape[0] >= S, "noise tape [S, B, njoints, nfeats, T] expected"
+        elif seed is None:   # derived from torch's default generator so fixseed() makes runs reproducible
+            seed = int(th.randint(0, 2 ** 62, (1,), dtype=th.int64).item())
+        tables, flags = self._vb_tables(), (_lib.VB_CLIP if clip_denoised else 0)
+        blocks = []
+        for hi in range(S - 1, -1, -per):
+            ts = np.arange(hi, max(hi - per, -1), -1)              # descending, like the reference's loop
+            n = len(ts)
+            t_rows = np.repeat(ts, B)                               # row r = (k, b): timestep ts[k] of motion b = r % B
+            t32 = th.from_numpy(t_rows.astype(np.int32)).to(dev)
+            qc = th.from_numpy(np.stack([self.sqrt_alphas_cumprod[t_rows], self.sqrt_one_minus_alphas_cumprod[t_rows]], 1).astype(np.float32)).to(dev)
+            coef = th.from_numpy(np.stack([tab[t_rows] for tab in tables], 1).astype(np.float32)).to(dev)
+            x_t = th.empty((n * B, R, F, T), device=dev, dtype=th.float32)
+            if tape is not None:
+                noise = tape[S - 1 - hi: S - 1 - hi + n].reshape(n * B, R, F, T).contiguous()
+                eng.q_sample_rows(x0, noise, qc, t32, 0, 0, x_t, None, stream)
+            else:
+                noise = th.empty_like(x_t)
+                eng.q_sample_rows(x0, None, qc, t32, seed, sample_offset, x_t, noise, stream)
+            kw = dict(model_kwargs, y=repeat_y(y, B, n, T, skip=()))
+            with th.no_grad():
+                out = model(x_t, self._model_timesteps(th.from_numpy(t_rows.astype(np.int64)).to(dev)), **kw)
+                out = self._inpainting_blend(out, kw["y"]).to(dtype=th.float32).contiguous()
+            eng = enc._engine                                       # the forward's engine, for rgn_vb_terms here and the next rgn_q_sample_rows
+            terms = th.empty((n * B, len(_lib.VB_TERMS)), device=dev, dtype=th.float32)
+            eng.vb_terms(x0, x_t, out, noise, t32, coef, flags, terms, stream)
+            blocks.append(terms.view(n, B, len(_lib.VB_TERMS)))
+        terms = th.cat(blocks, 0).permute(2, 1, 0).contiguous()    # [3, B, S], column k = timestep S - 1 - k
+        vb, xstart_mse, mse = terms[0], terms[1], terms[2]
+        prior_bpd = self._prior_bpd(x0)
+        total_bpd = vb.sum(dim=1) + prior_bpd
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
 
     # ---- per-call API (one denoiser evaluation on the HIP path + torch elementwise glue) ----------
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):

@@ -25,14 +25,13 @@ import torch as th
 _PER_SAMPLE = ("cmotion", "action", "action_cond", "text_features", "scale", "lengths", "mask", "trans_mask")
 
 
-def _expand_y(y, B, f0, f1, cm_full, T_call=None):
-    """model_kwargs['y'] for the samples (f, b), f in [f0, f1): index (f - f0) * B + b; sequences cut to T_call frames."""
-    n = f1 - f0
-    T = cm_full.shape[-1]
+def repeat_y(y, B, n, T, T_call=None, skip=("cmotion",)):
+    """The per-sample entries of y (leading dimension B) repeated n times, copy i at rows i * B .. i * B + B - 1; sequences cut to T_call of T
+    frames. Entries named in `skip` are left out; everything else is passed on as it is."""
     T_call = T if T_call is None else T_call
     out = {}
     for k, v in y.items():
-        if k == "cmotion":
+        if k in skip:
             continue
         if th.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B:
             if k in ("mask", "trans_mask") and v.shape[-1] == T:
@@ -44,6 +43,15 @@ def _expand_y(y, B, f0, f1, cm_full, T_call=None):
             out[k] = list(v) * n
         else:
             out[k] = v
+    return out
+
+
+def _expand_y(y, B, f0, f1, cm_full, T_call=None):
+    """model_kwargs['y'] for the samples (f, b), f in [f0, f1): index (f - f0) * B + b; sequences cut to T_call frames."""
+    n = f1 - f0
+    T = cm_full.shape[-1]
+    T_call = T if T_call is None else T_call
+    out = repeat_y(y, B, n, T, T_call)
     # frame f sees the actor's frames 0..f; everything after is zero (stgcn_eval.py:52,58)
     frames = th.arange(T, device=cm_full.device)
     keep = (frames[None, :] <= th.arange(f0, f1, device=cm_full.device)[:, None]).to(cm_full.dtype)   # [n, T]

@@ -9,7 +9,14 @@ timestep, and the per-motion values in `scores.npy`. Far cheaper than the FID ev
 and 'lengths' [N] (+ 'action' [N] for an action-conditioned model); without one, --num_samples synthetic motions. --skeleton FILE.npz |
 synthetic supplies the rest joints of the joint terms (tools/make_skeleton.py). Every motion is scored at --t_grid evenly spaced timesteps of the
 (respaced) schedule with Philox noise keyed by (--seed, motion, timestep), so a motion's noise depends neither on the batch size nor on
-the other motions. The weights: parser_util.score_args."""
+the other motions. The weights: parser_util.score_args.
+
+    python -m regennet_amd.eval.score --bpd --model_path save/cmdm_ntu/model000300000.pt --data_path heldout.npy --t_grid 10
+
+--bpd scores with the variational bound instead (`diffusion.calc_bpd_loop`, rgn_q_sample_rows + rgn_vb_terms): every timestep of the (respaced)
+schedule in bits per dimension, the number that compares checkpoints and noise schedules without sampling. The table shows vb, xstart_mse and
+mse at --t_grid timesteps and the mean prior_bpd / total_bpd; scores.npy holds total_bpd, prior_bpd [N] and vb, xstart_mse, mse [S, N] in
+ascending t. The noise is keyed as above; no skeleton is needed."""
 import os
 import types
 
@@ -55,6 +62,51 @@ def format_table(grid, scores):
     return "\n".join(lines)
 
 
+BPD_COLUMNS = ("vb", "xstart_mse", "mse")
+
+
+def format_bpd_table(grid, scores):
+    lines = ["%6s " % "t" + " ".join("%12s" % k for k in BPD_COLUMNS)]
+    for t in grid:
+        lines.append("%6d " % t + " ".join("%12.5e" % float(np.nanmean(scores[k][t])) for k in BPD_COLUMNS))
+    return "\n".join(lines)
+
+
+def score_bpd(args, model, diffusion, cfg, dev):
+    """--bpd: diffusion.calc_bpd_loop over the whole (respaced) schedule, batch by batch. The noise of (motion i, timestep t) is the Philox draw
+    keyed by (--seed, i, t): a motion's numbers depend neither on --batch_size nor on the other motions."""
+    motion, cmotion, lengths, action = load_motions(args, cfg)
+    if motion.shape[1:3] != (model.njoints, model.nfeats):
+        raise SystemExit(f"motions {motion.shape} do not fit the model's [N, {model.njoints}, {model.nfeats}, T]")
+    N, T = len(motion), motion.shape[-1]
+    S = diffusion.num_timesteps
+    bs = max(1, min(args.batch_size, N))
+    parts = {}
+    for lo in range(0, N, bs):
+        hi = min(N, lo + bs)
+        y = {"cmotion": torch.from_numpy(cmotion[lo:hi]).to(dev), "lengths": torch.from_numpy(lengths[lo:hi]),
+             "mask": (torch.arange(T)[None, :] < torch.from_numpy(lengths[lo:hi])[:, None]).reshape(hi - lo, 1, 1, T)}
+        if model.cond_mode == "action":
+            y["action"] = torch.from_numpy(action[lo:hi]).to(dev)
+        out = diffusion.calc_bpd_loop(model, torch.from_numpy(motion[lo:hi]).to(dev), clip_denoised=True, model_kwargs={"y": y}, seed=args.seed,
+                                      sample_offset=lo)
+        for k, v in out.items():
+            parts.setdefault(k, []).append(v.cpu().numpy())
+    scores = {k: np.concatenate(v) for k, v in parts.items()}
+    for k in BPD_COLUMNS:
+        scores[k] = np.ascontiguousarray(scores[k][:, ::-1].T)              # [N, S] in the loop's descending order -> [S, N], ascending t
+    grid = timestep_grid(S, args.t_grid)
+    print(f"{N} motions of {T} frames, variational bound over {S} timesteps in bits per dimension; mean per timestep at {len(grid)} of them:")
+    print(format_bpd_table(grid, scores))
+    print("prior_bpd %.5e  total_bpd %.5e" % (float(np.nanmean(scores["prior_bpd"])), float(np.nanmean(scores["total_bpd"]))))
+    out_dir = args.output_dir or os.path.dirname(args.model_path) or "."
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "scores.npy")
+    np.save(path, dict(scores, timesteps=np.arange(S), lengths=lengths))
+    print(f"saved the per-motion values to [{os.path.abspath(path)}]")
+    return path
+
+
 def main(argv=None):
     args = score_args(argv)
     fixseed(args.seed)
@@ -71,6 +123,8 @@ def main(argv=None):
     load_model_wo_clip(model, sd)
     model.to(dev)
     model.eval()
+    if args.bpd:
+        return score_bpd(args, model, diffusion, cfg, dev)
     if not set_skeleton(model, args):
         raise SystemExit("the joint terms need rest joints: --skeleton FILE.npz (tools/make_skeleton.py) or --skeleton synthetic")
     motion, cmotion, lengths, action = load_motions(args, cfg)

@@ -101,6 +101,9 @@ def add_score_options(p):
     """regennet_amd.eval.score: the grid of timesteps and where the table goes (the weights are the model group's lambda_* / --vel_threshold)."""
     g = p.add_argument_group("score")
     g.add_argument("--t_grid", default=10, type=int, help="score every motion at this many evenly spaced timesteps of the (respaced) schedule")
+    g.add_argument("--bpd", action="store_true",
+                   help="score with the variational bound in bits per dimension over the WHOLE (respaced) schedule (diffusion.calc_bpd_loop) instead of "
+                        "the training terms; the table shows --t_grid of its timesteps, scores.npy holds all of them. Needs no skeleton.")
 
 
 def _group_keys(parser, args, title):
