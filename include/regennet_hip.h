@@ -55,7 +55,9 @@ enum { RGN_PREC_F32 = 0,      /* fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact
                                  loop (rgn_set_x3_tail) and for every rgn_denoise call; the residual stream and
                                  LayerNorm/softmax stay hi+lo / fp32 throughout. Inside the 1e-3 parity bound. */
 enum { RGN_ARCH_ONLINE = 0,   /* causal nn.TransformerDecoder (model/cmdm.py:205-227)                 */
-       RGN_ARCH_OFFLINE = 1 };/* non-causal nn.TransformerEncoder, embedding as token 0 (cmdm.py:228-238) */
+       RGN_ARCH_OFFLINE = 1,  /* non-causal nn.TransformerEncoder, embedding as token 0 (cmdm.py:228-238) */
+       RGN_ARCH_MLP = 3 };    /* (2 stays unassigned and refused) DiffMLP time / feature mixer (cmdm.py:239-242, model/mlp.py); num_heads, ff_size, emb_trans_dec and
+                                 wo_pos_emb are not read; at most 160 frames; no k_layers, no fp16 sub-phase, no small-batch engine */
 enum { RGN_SAMPLER_DDPM = 0,  /* GaussianDiffusion.p_sample   diffusion/gaussian_diffusion.py:508  */
        RGN_SAMPLER_DDIM = 1 };/* GaussianDiffusion.ddim_sample diffusion/gaussian_diffusion.py:744 */
 enum { RGN_FLAG_UNCOND = 1,   /* y['uncond']=True  (model/cmdm.py:181, mask_cond :129-137)         */

@@ -15,7 +15,7 @@ RGN_OK = 0
 RGN_ERR_UNSUPPORTED = -7
 ERR_NAMES = {-1: "INVALID_ARG", -2: "BAD_KEY", -3: "BAD_SHAPE", -4: "MISSING_KEY", -5: "STATE", -6: "HIP", -7: "UNSUPPORTED", -8: "INTERNAL"}
 CM = {"add": 0, "concat": 1}
-ARCH = {"online": 0, "offline": 1}     # RGN_ARCH_* (include/regennet_hip.h)
+ARCH = {"online": 0, "offline": 1, "mlp": 3}     # RGN_ARCH_* (include/regennet_hip.h)
 COND = {"no_cond": 0, "action": 1, "text": 2}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16_x3tail": 3}
 DEFAULT_PRECISION = "bf16_x3tail"

@@ -41,6 +41,7 @@ struct Lin {  // one packed nn.Linear: offsets (bytes) into the weight blob
 struct LayerW {
     Lin qkv, out, ff1, ff2;
     size_t ln[6];  // g1,b1,g2,b2,g3,b3 (encoder layers: norm1 in [0..1], norm2 in [4..5], [2..3] unused)
+    // arch='mlp' blocks (model/mlp.py): fc0 [T, T] (row-major hi / lo, K padded to 32) in `out`, fc1 [d, d] in `ff1`, norm0 in ln[0..1], norm1 in ln[2..3]
 };
 
 struct ProfEv {
@@ -79,6 +80,7 @@ struct rgn_ctx {
     std::map<std::string, int> opts;   // rgn_set_option: per-handle kernel-selection switches (they take precedence over REGENNET_<KEY> in the environment)
     bool finalized = false, have_sched = false, have_cond = false;
     int F = 0, d = 0, Tq = 0, etd = 0, L = 0, H = 0, ff = 0, pe_len = 0;
+    int mix = 0;                       // arch='mlp': the time / feature mixer stack (rgn_mixer.hip): fp32 residual stream, no attention, no token, no positional encoding
     int enc = 0;                       // arch='offline': encoder layers (non-causal self-attention, norm1 / norm2, no cross-attention); implies etd
 
     // packed weights
@@ -232,6 +234,7 @@ struct EvalPlan {
     bool layers = false;      // k_layers: the whole decoder stack in one kernel, one sample per workgroup
     bool steps = false;       // k_layers<true>: whole runs of sampler steps in one launch (sampling only)
     bool step_fused = false;  // k_step: output projection + sampler update + next input embedding (sampling only)
+    bool mix = false;         // arch='mlp': k_mix_time + the feature-mix GEMM per layer (attn / tail are not read)
     AttnForm attn = AF_PLAIN;
     TailForm tail = TF_GEMM_LN;
 };

@@ -22,6 +22,7 @@ enum KClass : int {
     KC_STEP,          // fused step boundary: output projection + sampler update + next input embedding (k_step)
     KC_LAYERS,        // the whole decoder stack of an evaluation, one sample per workgroup (k_layers)
     KC_STEPS,         // a run of complete sampler steps (stack + step boundary per sample) in one launch (k_layers<true>)
+    KC_MIX,           // arch='mlp': time mix of a layer, one sample per workgroup (k_mix_time), + the stack's elementwise ends (k_mix_emb, k_mix_fin)
     KC_COUNT
 };
 
@@ -358,6 +359,31 @@ hipError_t launch_randn(float* x, int B, int FT, int T, unsigned long long seed,
                         uint32_t noise_stream, hipStream_t s);
 hipError_t launch_rot6d(const float* d6, float* mat, long long n, hipStream_t s);
 hipError_t launch_gauss1d(const float* x, float* out, long long rows, int T, float sigma, hipStream_t s);
+
+// ---- rgn_mixer.hip: the time / feature mixer stack of arch='mlp' (model/mlp.py:9-86). The residual stream of such a handle is fp32 (h) in every
+// precision mode; the feature mix is the handle's ordinary GEMM (k_gemm_x3 / k_gemm_f32, SiLU epilogue) on the LayerNorm1 image k_mix_time leaves,
+// and its result s is added by whoever reads the stream next (sadd below; k_mix_fin behind the last layer).
+//   k_mix_time, one workgroup per sample:  x = h + sadd + e ; h <- x + SiLU(W0 . LN0(x) + b0[:, None]) (W0 [T, T] contracts over FRAMES) ; w <- LN1(h)
+enum MixFmt { MXF_F32 = 0, MXF_BF16 = 1, MXF_X3 = 2 };   // operand format of the frame contraction: fp32 FMA | bf16 MFMA | split-bf16, three MFMAs per product
+constexpr int MIX_MAX_T = 160;
+struct MixTimeArgs {
+    float* h;                              // residual stream [ns T, d] fp32 (advanced to the first sample), updated in place
+    const float* sadd;                     // the previous layer's feature-mix result [ns T, d], not yet added to h (layer 0: null)
+    const float* e; int lde;               // per-sample vector emb_fc_l(SiLU(emb)) + bias: e[b lde + j] (advanced to the first sample and to layer l)
+    const float *g0, *be0, *g1, *be1;      // norm0 / norm1 weight and bias [d]
+    const float* W0;                       // fc0 weight fp32 [T][Tp] (MXF_F32)
+    const __bf16 *W0hi, *W0lo;             // ... and its bf16 hi / lo parts, row-major [T][Tp], k-padding columns zero (W0lo: MXF_X3 only)
+    const float* b0;                       // fc0 bias [T]: per OUTPUT frame
+    float* w32;                            // LN1 image fp32 [ns T, d] (MXF_F32), else null
+    Planes wp;                             // ... as K32-blocked planes (advanced to the first row; lo: MXF_X3 only)
+    int T, Tp, d, ns;                      // Tp = T rounded up to 32
+};
+inline bool mix_supported(int T, int d) { return T >= 1 && T <= MIX_MAX_T && d % 64 == 0; }
+hipError_t launch_mix_time(const MixTimeArgs& g, int fmt, hipStream_t s);
+// out[b, :] = SiLU(rows[b, :] + stepemb[*d_step, :]) (either addend may be null): the operand of the emb_fc GEMM of all layers
+hipError_t launch_mix_emb(const float* rows, const float* stepemb, const int* d_step, float* out, int Bm, int d, hipStream_t s);
+// behind the last layer: h + sadd -> hp planes (lo nullable) where hp.hi is given, else -> h in place
+hipError_t launch_mix_fin(float* h, const float* sadd, Planes hp, int M, int d, hipStream_t s);
 
 // ---- rgn_fk.hip: forward kinematics of a skeleton (rgn_rot2xyz). Passed to the kernel by value: the call keeps no state.
 constexpr int FK_MAX_JOINTS = 64;

@@ -14,7 +14,7 @@ void build_expected(rgn_ctx* c) {
     e["input_process.poseEmbedding.bias"] = {d};
     e["cmo_process.poseEmbedding.weight"] = {d, F};
     e["cmo_process.poseEmbedding.bias"] = {d};
-    if (c->cfg.cm_mode == RGN_CM_CONCAT) {
+    if (c->cfg.cm_mode == RGN_CM_CONCAT) {   // (arch='mlp' never calls it - block 0's conct fuses - but a concat checkpoint carries the keys)
         e["fuse_process.weight"] = {d, 2 * d};
         e["fuse_process.bias"] = {d};
     }
@@ -24,7 +24,26 @@ void build_expected(rgn_ctx* c) {
     e["embed_timestep.time_embed.0.bias"] = {d};
     e["embed_timestep.time_embed.2.weight"] = {d, d};
     e["embed_timestep.time_embed.2.bias"] = {d};
-    for (int l = 0; l < c->L; ++l) {
+    for (int l = 0; c->mix && l < c->L; ++l) {
+        // arch='mlp': DiffMLP's blocks (model/mlp.py:30-86). fc0 is Conv1d(num_frames, num_frames, 1): [T, T, 1]
+        const int64_t T = c->cfg.num_frames;
+        const std::string p = "mlp.motion_mlp.mlps." + std::to_string(l) + ".";
+        if (l == 0) {
+            e[p + "conct.weight"] = {d, 2 * d};
+            e[p + "conct.bias"] = {d};
+        }
+        e[p + "fc0.weight"] = {T, T, 1};
+        e[p + "fc0.bias"] = {T};
+        e[p + "fc1.weight"] = {d, d};
+        e[p + "fc1.bias"] = {d};
+        e[p + "emb_fc.weight"] = {d, d};
+        e[p + "emb_fc.bias"] = {d};
+        for (const char* n : {"norm0", "norm1"}) {
+            e[p + n + ".weight"] = {d};
+            e[p + n + ".bias"] = {d};
+        }
+    }
+    for (int l = 0; !c->mix && l < c->L; ++l) {
         // arch='offline': nn.TransformerEncoderLayer keys (self_attn, linear1/2, norm1/2); 'online': nn.TransformerDecoderLayer's
         const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         for (const char* a : {"self_attn.", "multihead_attn."}) {
@@ -152,7 +171,7 @@ bool opt_flag(const rgn_ctx* c, const char* key) {
 int finalize_weights(rgn_ctx* c) {
     std::string missing;
     for (auto& kv : c->expected)
-        if (!c->sd.count(kv.first)) missing += (missing.empty() ? "" : ", ") + kv.first;
+        if (!c->sd.count(kv.first) && !(c->mix && kv.first.rfind("fuse_process.", 0) == 0)) missing += (missing.empty() ? "" : ", ") + kv.first;
     if (!missing.empty()) return c->fail(RGN_ERR_MISSING_KEY, "missing keys in state_dict: " + missing);
     RGN_HIP(c, hipSetDevice(c->cfg.device));
     auto W = [&](const std::string& k) -> const float* { return c->sd[k].v.data(); };
@@ -160,7 +179,7 @@ int finalize_weights(rgn_ctx* c) {
     // fp16 operands for the plain phase of the precision schedule (k_layers<.., F16>): same MFMA rate and bytes as bf16, 2^-12 instead of
     // 2^-9 operand rounding - but a 5-bit exponent: a weight at or beyond fp16's range would become inf, so such a checkpoint is refused
     // here, with the key named (activations are LayerNorm outputs, probabilities and GELU values: O(1) by construction)
-    { int v = 1; (void)opt_get(c, "BULK_F16", &v); c->bulk_f16 = c->cfg.precision == RGN_PREC_BF16_X3TAIL && v != 0; }
+    { int v = 1; (void)opt_get(c, "BULK_F16", &v); c->bulk_f16 = c->cfg.precision == RGN_PREC_BF16_X3TAIL && v != 0 && !c->mix; }   // (arch='mlp': no fp16 sub-phase)
     { int v; if (opt_get(c, "F16_STEPS", &v)) c->f16_steps = c->f16_steps_default = v < 0 ? -1 : v; }
     auto f16_range = [&](const std::string& key, const float* w, size_t n) -> bool {
         for (size_t i = 0; i < n; ++i)
@@ -186,14 +205,16 @@ int finalize_weights(rgn_ctx* c) {
         const float* wcm = W("cmo_process.poseEmbedding.weight");
         const float* bin = W("input_process.poseEmbedding.bias");
         const float* bcm = W("cmo_process.poseEmbedding.bias");
-        if (c->cfg.cm_mode == RGN_CM_CONCAT) {
-            const float* wf = W("fuse_process.weight");  // [d, 2d] = [Wf_x | Wf_c]
-            const float* bf = W("fuse_process.bias");
+        if (c->cfg.cm_mode == RGN_CM_CONCAT || c->mix) {
+            // [d, 2d] = [Wf_x | Wf_c]; arch='mlp': block 0's conct takes cat(c_in, x_in) - the ACTOR half first - whatever cm_mode says
+            const float* wf = c->mix ? W("mlp.motion_mlp.mlps.0.conct.weight") : W("fuse_process.weight");
+            const float* bf = c->mix ? W("mlp.motion_mlp.mlps.0.conct.bias") : W("fuse_process.bias");
+            const int xo = c->mix ? d : 0, co = c->mix ? 0 : d;
             std::vector<float> wfx((size_t)d * d), wfc((size_t)d * d);
             for (int n = 0; n < d; ++n)
                 for (int j = 0; j < d; ++j) {
-                    wfx[(size_t)n * d + j] = wf[(size_t)n * 2 * d + j];
-                    wfc[(size_t)n * d + j] = wf[(size_t)n * 2 * d + d + j];
+                    wfx[(size_t)n * d + j] = wf[(size_t)n * 2 * d + xo + j];
+                    wfc[(size_t)n * d + j] = wf[(size_t)n * 2 * d + co + j];
                 }
             matmul64(wfx.data(), win, d, d, F, wx);
             matmul64(wfc.data(), wcm, d, d, F, wc);
@@ -221,7 +242,21 @@ int finalize_weights(rgn_ctx* c) {
     // --- layers; cross-attention folded: G_l = Wo_c * Wv_c, g_l = Wo_c * bv_c + bo_c (1-token memory)
     std::vector<float> gall((size_t)c->L * d * d), gb((size_t)c->L * d);
     c->layers.resize(c->L);
-    for (int l = 0; l < c->L; ++l) {
+    for (int l = 0; c->mix && l < c->L; ++l) {
+        // arch='mlp': fc0 row-major [T][Tp] (fp32 + bf16 hi / lo, k-padding columns zero: k_mix_time's operand), fc1 as a k_gemm_x3 / k_gemm_f32
+        // operand, the norms, and emb_fc of all layers stacked into ONE [L d, d] linear (lin_g: e = SiLU(emb) . W^T + b for every layer at once)
+        const std::string p = "mlp.motion_mlp.mlps." + std::to_string(l) + ".";
+        LayerW& lw = c->layers[l];
+        const int T = c->cfg.num_frames;
+        lw.out = pack_linear(c, W(p + "fc0.weight"), W(p + "fc0.bias"), T, T);
+        lw.ff1 = pack_linear(c, W(p + "fc1.weight"), W(p + "fc1.bias"), d, d, true);
+        const char* names[4] = {"norm0.weight", "norm0.bias", "norm1.weight", "norm1.bias"};
+        for (int i = 0; i < 4; ++i) lw.ln[i] = blob_put(c, W(p + names[i]), (size_t)d * 4);
+        lw.ln[4] = lw.ln[5] = 0;
+        memcpy(&gall[(size_t)l * d * d], W(p + "emb_fc.weight"), (size_t)d * d * 4);
+        memcpy(&gb[(size_t)l * d], W(p + "emb_fc.bias"), (size_t)d * 4);
+    }
+    for (int l = 0; !c->mix && l < c->L; ++l) {
         const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         LayerW& lw = c->layers[l];
         if (c->bulk_f16)
@@ -289,9 +324,9 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->c0, M * d))) return rc;
     if ((rc = ws_alloc(c, &c->h, M * d))) return rc;
     if ((rc = ws_alloc(c, &c->tmp, M * d))) return rc;
-    if ((rc = ws_alloc(c, &c->qkv, M * 3 * d))) return rc;
+    if (!c->mix && (rc = ws_alloc(c, &c->qkv, M * 3 * d))) return rc;   // (arch='mlp': no attention, no feed-forward hidden tensor, no cross-attention fold)
     if ((rc = ws_alloc(c, &c->att, M * d))) return rc;
-    if ((rc = ws_alloc(c, &c->ffn, M * ff))) return rc;
+    if (!c->mix && (rc = ws_alloc(c, &c->ffn, M * ff))) return rc;
     if ((rc = ws_alloc(c, &c->x0tok, M * F))) return rc;
     if ((rc = ws_alloc(c, &c->pe_rows, Bm * d))) return rc;
     if ((rc = ws_alloc(c, &c->emb1, Bm * d))) return rc;
@@ -301,9 +336,24 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->scale, B))) return rc;
     if ((rc = ws_alloc(c, &c->te_all, (size_t)1024 * d))) return rc;
     if ((rc = ws_alloc(c, &c->sched_tmp, (size_t)2 * 1024 * d))) return rc;
-    if ((rc = ws_alloc(c, &c->call_time, (size_t)1024 * c->L * d))) return rc;
-    if ((rc = ws_alloc(c, &c->call_cond, Bm * c->L * d))) return rc;
-    if (c->cfg.precision != RGN_PREC_F32) {
+    if (!c->mix && (rc = ws_alloc(c, &c->call_time, (size_t)1024 * c->L * d))) return rc;
+    if (!c->mix && (rc = ws_alloc(c, &c->call_cond, Bm * c->L * d))) return rc;
+    if (c->mix) c->sb_rows = c->sb_rows_default = 0;   // no small-batch engine for these handles, in any mode (rgn_set_small_batch_rows refuses to turn it on)
+    if (c->cfg.precision != RGN_PREC_F32 && c->mix) {
+        // arch='mlp': the stream is fp32 (h, tmp); planes only for the sampler state, the LN1 image (att) and the output projection's operand (h)
+        const size_t Fp = align_up((size_t)F, 32);
+        if ((rc = ws_alloc(c, &c->xin_hi, M * Fp))) return rc;
+        if ((rc = ws_alloc(c, &c->xin_lo, M * Fp))) return rc;
+        if ((rc = ws_alloc(c, &c->h_hi, M * d))) return rc;
+        if ((rc = ws_alloc(c, &c->h_lo, M * d))) return rc;
+        if ((rc = ws_alloc(c, &c->att_hi, M * d))) return rc;
+        if ((rc = ws_alloc(c, &c->att_lo, M * d))) return rc;
+        RGN_HIP(c, hipMemset(c->xin_hi, 0, M * Fp * 2));   // K padding columns must read as 0
+        RGN_HIP(c, hipMemset(c->xin_lo, 0, M * Fp * 2));
+        RGN_HIP(c, configure_gemm_x3());
+        { int v; if (opt_get(c, "BIG_TILE_ROWS", &v)) c->big_tile_rows = v; }
+        c->bulk_f16 = false;
+    } else if (c->cfg.precision != RGN_PREC_F32) {
         const size_t Fp = align_up((size_t)F, 32), ffp = align_up((size_t)ff, 32);
         if ((rc = ws_alloc(c, &c->xin_hi, M * Fp))) return rc;
         if ((rc = ws_alloc(c, &c->xin_lo, M * Fp))) return rc;
@@ -378,7 +428,7 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->d_tab, (size_t)1024))) return rc;
     if ((rc = ws_alloc(c, &c->d_step, (size_t)4 + 1 + B))) return rc;   // [0] loop index, [3] scratch, [4 ..] k_update's ticket counters
     if ((rc = ws_alloc(c, &c->d_sp, (size_t)1))) return rc;
-    RGN_HIP(c, configure_attention(c->Tq, c->d / c->H));
+    if (!c->mix) RGN_HIP(c, configure_attention(c->Tq, c->d / c->H));
     RGN_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     RGN_HIP(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     RGN_HIP(c, hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));

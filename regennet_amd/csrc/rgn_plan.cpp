@@ -112,6 +112,10 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     const int prec = c->cfg.precision, rows = dm.Bm * dm.Tq;
     const bool fast = prec != RGN_PREC_F32;
     const bool lo_planes = prec == RGN_PREC_BF16X3 || prec == RGN_PREC_BF16_X3TAIL;     // has_lo()
+    // arch='mlp' handles: the mixer stack (rgn_mixer.hip) in every mode and phase - never k_layers, k_step, the small-batch engine or an attention
+    // form (all of them are off for such a handle: rgn_pack.cpp)
+    p.mix = c->mix != 0;
+    if (p.mix) return p;
     p.sb = use_sb(c, rows);
     if (p.sb) {
         p.attn = AF_GEMM_ATTN;
@@ -165,7 +169,7 @@ PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided) {
     pp.n16 = !f16_ok ? 0 : (c->f16_steps >= 0 ? c->f16_steps : F16_STEPS_DEFAULT);
     if (c->x3_tail >= 0) pp.tail = c->x3_tail;
     else if (pp.n16 > 0 && c->L >= 8 && !c->etd) pp.tail = F16_TAIL < c->S ? F16_TAIL : c->S;
-    else pp.tail = default_tail(c->S, c->L, c->etd != 0);
+    else pp.tail = default_tail(c->S, c->L, c->etd != 0 || c->mix != 0);   // (arch='mlp': split-bf16 on every step, like encoder handles - no plain-phase error has been measured)
     if (pp.tail > c->S) pp.tail = c->S;
     if (pp.n16 > c->S - pp.tail) pp.n16 = c->S - pp.tail;
     return pp;
@@ -195,7 +199,7 @@ struct LayerVecs { const float* pervec; int ldper; const float* stepvec; int lds
 LayerVecs layer_vecs(const rgn_ctx* c, int l, int s0, bool sampling, const float* ccond_rows) {
     const size_t d = c->d, Ld = (size_t)c->L * d, off = (size_t)s0 * Ld + (size_t)l * d;
     LayerVecs v{};
-    if (!c->enc) {
+    if (!c->enc && !c->mix) {
         v.pervec = sampling ? (ccond_rows ? ccond_rows + off : nullptr) : c->call + off;
         v.stepvec = sampling ? c->call_time + (size_t)l * d : nullptr;
     }
@@ -356,9 +360,9 @@ int run_layers(rgn_ctx* c, const Eval& ev, int s0, int ns, hipStream_t s) {
                  ffn_p = pln(c->ffn_hi, c->ffn_lo, x3);
     float* h = c->h + (size_t)row0 * d;
     float* tmp = c->tmp + (size_t)row0 * d;
-    float* qkv = c->qkv + (size_t)row0 * 3 * d;
+    float* qkv = c->qkv ? c->qkv + (size_t)row0 * 3 * d : nullptr;   // (not allocated for arch='mlp' handles)
     float* att = c->att + (size_t)row0 * d;
-    float* ffn = c->ffn + (size_t)row0 * c->ff;
+    float* ffn = c->ffn ? c->ffn + (size_t)row0 * c->ff : nullptr;
     // The residual stream: fp32 `h` in F32 mode (and for the fused-LN variant, whose kernel reads it), added in the GEMM
     // epilogue. In the bf16 modes only its split planes exist: k_layernorm adds hi + lo to the GEMM output it normalises
     // and writes planes only, so neither kernel touches an fp32 copy (31 MB less HBM traffic per LayerNorm at B=256).
@@ -393,13 +397,36 @@ int run_layers(rgn_ctx* c, const Eval& ev, int s0, int ns, hipStream_t s) {
     if (pl.step_fused) {
         // fused step boundary (k_step): the residual-stream planes already hold this evaluation's input embedding
     } else if (fast) {   // xin planes and c0 already hold both guidance halves
-        if ((rc = big(c->lin_x, nullptr, 0, xin_p, h32 ? h : nullptr, d, h_p, c->c0 + (size_t)row0 * d, 0, M))) return rc;
+        if ((rc = big(c->lin_x, nullptr, 0, xin_p, (h32 || pl.mix) ? h : nullptr, d, pl.mix ? none : h_p, c->c0 + (size_t)row0 * d, 0, M))) return rc;
     } else {
         if ((rc = big(c->lin_x, c->xin, c->F, none, c->h, d, none, c->c0, 0, Mb))) return rc;
         if (ev.guided)
             RGN_HIP(c, hipMemcpyAsync(c->h + (size_t)Mb * d, c->h, (size_t)Mb * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (c->etd && (rc = embed_token(c, ev, dm, s0, h, h_p, s))) return rc;
+    if (pl.mix) {
+        // arch='mlp': per layer k_mix_time (a sample per workgroup: + e_l, LayerNorm0, the [T, T] frame contraction, SiLU, residual, LayerNorm1 image) and
+        // the feature mix as this handle's GEMM with the SiLU epilogue, s = SiLU(LN1(h) . W1^T + b1) -> tmp. The stream h is fp32 in every mode; s is
+        // added by the next reader: the next k_mix_time, or k_mix_fin, which also leaves the output projection's operand
+        const int fmt = !fast ? MXF_F32 : (x3 ? MXF_X3 : MXF_BF16);
+        const int T = dm.Tq, Ld = c->L * d;
+        const float* e0 = c->call + (size_t)s0 * Ld;
+        for (int l = 0; l < c->L; ++l) {
+            const LayerW& w = c->layers[l];
+            MixTimeArgs g{};
+            g.h = h; g.sadd = l ? tmp : nullptr;
+            g.e = e0 + (size_t)l * d; g.lde = Ld;
+            g.g0 = c->dp<float>(w.ln[0]); g.be0 = c->dp<float>(w.ln[1]); g.g1 = c->dp<float>(w.ln[2]); g.be1 = c->dp<float>(w.ln[3]);
+            g.W0 = c->dp<float>(w.out.w); g.W0hi = c->dp<__bf16>(w.out.hi); g.W0lo = c->dp<__bf16>(w.out.lo); g.b0 = c->dp<float>(w.out.b);
+            g.w32 = fast ? nullptr : att;
+            g.wp = att_p;
+            g.T = T; g.Tp = w.out.Kp; g.d = d; g.ns = ns;
+            RGN_LAUNCH(c, KC_MIX, s, launch_mix_time(g, fmt, s));
+            if ((rc = big(w.ff1, att, d, att_p, tmp, d, none, nullptr, 2, M))) return rc;
+        }
+        RGN_LAUNCH(c, KC_MIX, s, launch_mix_fin(h, tmp, h_p, M, d, s));
+        return big(c->lin_out, h, d, h_p, c->x0tok + (size_t)row0 * c->F, c->F, none, nullptr, 0, M);
+    }
     const size_t slab0 = (size_t)s0 * c->H * c->Tqp * dm.dh;      // attention-ready planes: first slab of this range
     if (pl.layers) {
         // plain-bf16 phase, <= 64 tokens, d = 512 / ff = 1024 / 4 heads: ALL layers in one kernel, one sample per workgroup - the residual
@@ -537,7 +564,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
     // timesteps and evaluates them here.
     const bool has_cond = c->cfg.cond_mode != RGN_COND_NONE;
     const float* cond_rows = !has_cond ? nullptr : ((uncond && !guided) ? c->condemb + (size_t)B * d : c->condemb);
-    const float* ccond_rows = !has_cond ? nullptr : ((uncond && !guided) ? c->call_cond + (size_t)B * Ld : c->call_cond);
+    const float* ccond_rows = (!has_cond || c->mix) ? nullptr : ((uncond && !guided) ? c->call_cond + (size_t)B * Ld : c->call_cond);
     const Eval ev{dm, pl, ph, guided, sampling, cond_rows, ccond_rows};
     if (!sampling) {
         RGN_LAUNCH(c, KC_EMBED, s, launch_gather_pe(c->dp<float>(c->off_pe), c->d_tab, c->d_step, c->d_sp, c->pe_rows, dm.Bm, B, d, c->pe_len, s));
@@ -549,10 +576,17 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
         g.ldadd = d;
         RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
         // cross-attention onto the 1-token memory, all layers at once: call[b, l*d:(l+1)*d] (encoder layers have none)
-        if (!c->enc) {
+        if (!c->enc && !c->mix) {
             g = gemm_args(c, c->lin_g, c->emb, d, c->call, Ld, dm.Bm);
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
         }
+    }
+    if (c->mix) {
+        // arch='mlp': e_l[b] = emb_fc_l(SiLU(emb_b)) + bias of all layers from ONE [Bm, d] x [d, L d] GEMM. SiLU is not linear, so nothing of it is
+        // per schedule or per condition alone: a sampling step makes emb = TE[*d_step] + condition row on the device (capturable), rgn_denoise has it in c->emb
+        RGN_LAUNCH(c, KC_MIX, s, launch_mix_emb(sampling ? cond_rows : c->emb, sampling ? c->te_all : nullptr, c->d_step, c->emb1, dm.Bm, d, s));
+        GemmArgs g = gemm_args(c, c->lin_g, c->emb1, d, c->call, Ld, dm.Bm);
+        RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
     }
     // ---- layers. In the bf16 modes the samples of the evaluation are split into contiguous groups that run as
     //      independent kernel chains on separate streams (fork/join with events, also inside graph capture): the
@@ -826,7 +860,15 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     const char* kn[KC_COUNT] = {nullptr};
     for (int i = 0; i < KC_COUNT; ++i) kn[i] = "";
     const double Fp = (double)align_up((size_t)c->F, 32), wl = L * (4 * d * d + 2 * d * ff);
-    if (pl.sb) {
+    if (pl.mix) {
+        const bool f32 = c->cfg.precision == RGN_PREC_F32;
+        kn[KC_GEMM] = f32 ? "k_gemm_f32" : "k_gemm_x3";
+        mac[KC_GEMM] = embed + M * d * d * L + (double)dm.Bm * d * d * L; n[KC_GEMM] = 2 + L + 1;   // embedding, projection, the feature mixes, emb_fc of all layers
+        mac[KC_MIX] = M * T * d * L; n[KC_MIX] = L + 2;
+        kn[KC_MIX] = f32 ? "k_mix_time<f32>" : (x3 ? "k_mix_time<bf16x3>" : "k_mix_time<bf16>");
+        l2[KC_MIX] = (double)dm.Bm * L * T * (double)align_up((size_t)dm.T, 32) * (f32 ? 4.0 : (x3 ? 4.0 : 2.0));
+        n[KC_UPDATE] = 1; kn[KC_UPDATE] = "k_update";
+    } else if (pl.sb) {
         mac[KC_SB] = embed + tail + qkv; n[KC_SB] = 2 + L * 4; kn[KC_SB] = "k_sb_gemm";
         mac[KC_ATTN] = attn; n[KC_ATTN] = L; kn[KC_ATTN] = enc ? "k_attn_x3<full>" : "k_attn_x3";
         n[KC_UPDATE] = 1; kn[KC_UPDATE] = "k_update";

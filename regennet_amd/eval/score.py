@@ -113,7 +113,7 @@ def main(argv=None):
     dev = dist_util.setup_dist()
     cfg = synth.get_config("chi3d" if args.dataset == "chi3d" else ("ntu" if args.unconstrained else "ntu_action"))
     data = types.SimpleNamespace(dataset=types.SimpleNamespace(num_actions=cfg["num_actions"], num_person=2))
-    model, diffusion = create_model_and_diffusion(args, data)
+    model, diffusion = create_model_and_diffusion(args, data, allow_mlp=True)
     model.precision = args.precision
     if args.synthetic or not args.model_path:
         sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(model.engine_config() | {"layers": model.num_layers}, seed=0).items()}

@@ -62,6 +62,29 @@ class _Encoder(nn.Module):       # nn.TransformerEncoder without a final norm (t
         self.layers = nn.ModuleList([_EncoderLayer(d, ff) for _ in range(n)])
 
 
+class _MixBlock(nn.Module):     # one block of the reference's DiffMLP (arch='mlp', model/mlp.py:9-26): parameter containers only
+    def __init__(self, d, seq, first):
+        super().__init__()
+        self.fc0 = nn.Conv1d(seq, seq, 1)            # mixes along TIME: weight [seq, seq, 1]
+        if first:
+            self.conct = nn.Linear(2 * d, d)         # block 0 fuses cat(actor, reactor)
+        self.emb_fc = nn.Linear(d, d)
+        self.fc1 = nn.Linear(d, d)
+        self.norm0, self.norm1 = nn.LayerNorm(d), nn.LayerNorm(d)
+
+
+class _MixStack(nn.Module):
+    def __init__(self, d, seq, n):
+        super().__init__()
+        self.mlps = nn.ModuleList([_MixBlock(d, seq, i == 0) for i in range(n)])
+
+
+class _DiffMLP(nn.Module):      # keys mlp.motion_mlp.mlps.<l>.* (cmdm.py:85-87)
+    def __init__(self, d, seq, n):
+        super().__init__()
+        self.motion_mlp = _MixStack(d, seq, n)
+
+
 class PositionalEncoding(nn.Module):
     """Sinusoid table buffer `pe` [max_len,1,d] (cmdm.py:265-276)."""
 
@@ -105,10 +128,11 @@ class CMDM(nn.Module):
                  arch="trans_enc", cm_mode="add", body_model="smpl", wo_pos_emb=False, emb_trans_dec=False,
                  clip_version=None, **kargs):
         super().__init__()
-        if arch not in ("online", "offline"):
+        if arch not in ("online", "offline", "mlp"):
             raise NotImplementedError(
-                f"arch={arch!r}: the HIP hot path runs the 'online' decoder (cmdm.py:205-227) and the 'offline' encoder "
-                "(cmdm.py:228-238); trans_enc has no forward branch in the reference, mlp/gru are ablations (SURVEY.md §2 row 3)")
+                f"arch={arch!r}: the HIP hot path runs the 'online' decoder (cmdm.py:205-227), the 'offline' encoder "
+                "(cmdm.py:228-238) and the 'mlp' time / feature mixer (cmdm.py:239-242); trans_enc has no forward branch in the "
+                "reference, gru is an ablation without a HIP form (SURVEY.md §2 row 3)")
         if activation != "gelu":
             raise NotImplementedError("activation is hard-coded to gelu by the reference factory (model_util.py:70)")
         if data_rep not in ("rot6d", "xyz", "hml_vec"):
@@ -140,6 +164,8 @@ class CMDM(nn.Module):
             self.fuse_process = nn.Linear(2 * d, d)
         if arch == "offline":   # (emb_trans_dec / wo_pos_emb do not apply: the embedding is always token 0, positions always encoded)
             self.seqTransEncoder = _Encoder(d, ff_size, num_layers)
+        elif arch == "mlp":     # (no attention: num_heads / ff_size, emb_trans_dec / wo_pos_emb and cm_mode are not read; fc0 fixes the frame count)
+            self.mlp = _DiffMLP(d, num_frames, num_layers)
         else:
             self.seqTransDecoder = _Decoder(d, ff_size, num_layers)
         self.embed_timestep = TimestepEmbedder(d, self.sequence_pos_encoder)
@@ -233,6 +259,8 @@ class CMDM(nn.Module):
         reference's module the model itself is length-agnostic (the sequence length comes from x.shape, cmdm.py:176); an
         engine's workspace is sized per (max batch, T), so engines are cached per T (least recently used evicted) and one is
         rebuilt when a larger batch arrives."""
+        if self.arch == "mlp" and T is not None and int(T) != self.num_frames:
+            raise ValueError(f"arch='mlp': fc0 is Conv1d(num_frames, num_frames, 1) with num_frames = {self.num_frames} - it cannot mix {int(T)} frames")
         dev = next(self.parameters()).device
         if dev.type != "cuda" and getattr(_lib.Engine, "requires_gpu", True):
             raise RuntimeError("regennet_amd CMDM runs on an AMD GPU only: call model.to(dist_util.dev()) first "
@@ -280,7 +308,8 @@ class CMDM(nn.Module):
         eng.set_f16_steps(-1 if self.f16_steps is None else int(self.f16_steps))
         eng.set_small_batch_rows(-1 if self.small_batch_rows is None else int(self.small_batch_rows))
         eng.set_layers_min_b(-1 if self.layers_min_b is None else int(self.layers_min_b))
-        eng.set_option("LAYERS_GUIDED", -1 if self.layers_guided is None else int(self.layers_guided))
+        if self.arch != "mlp":                                # (an arch='mlp' engine has no k_layers and refuses its switches)
+            eng.set_option("LAYERS_GUIDED", -1 if self.layers_guided is None else int(self.layers_guided))
         return eng, dev
 
     def _rgn_bind(self, B, y, device=None, guided=False, T=None, cache=False):

@@ -40,6 +40,9 @@ CONFIGS = {
 # arch='offline' (model/cmdm.py:228-238): the same shapes with the non-causal encoder denoiser
 for _name in ("tiny", "tiny_add", "ntu", "ntu_action", "chi3d"):
     CONFIGS[_name + "_offline"] = dict(CONFIGS[_name], arch="offline")
+# arch='mlp' (model/cmdm.py:239-242, model/mlp.py): the same shapes with the DiffMLP time / feature mixer (num_heads / ff_size are not read)
+for _name in ("tiny", "tiny_add", "tiny_text", "ntu", "ntu_action", "chi3d"):
+    CONFIGS[_name + "_mlp"] = dict(CONFIGS[_name], arch="mlp")
 del _name
 
 
@@ -69,6 +72,9 @@ def make_state_dict(cfg, seed=0):
     far from uniform; LayerNorm gamma ~ 1+0.1N, beta ~ 0.1N; biases ~ 0.02..0.1 N.
     cfg["arch"] == "offline": nn.TransformerEncoderLayer keys (seqTransEncoder.layers.<l>: self_attn, linear1/2, norm1/2) drawn
     in the decoder's order without the cross-attention and norm3 draws, q/k at gain 1; every other config draws exactly what it always did.
+    cfg["arch"] == "mlp": DiffMLP keys (mlp.motion_mlp.mlps.<l>: conct in block 0, fc0 [T, T, 1], fc1, emb_fc, norm0/1). The stack adds 2 L
+    un-normalised SiLU branches to the stream and ends in no LayerNorm, so the branch weights are drawn at a gain (MLP_GAIN) and the output
+    projection at one (MLP_OUT_GAIN) that keep the denoiser's outputs O(1): an absolute parity bound means nothing on a stream that has blown up.
     """
     rng = np.random.Generator(np.random.PCG64(seed))
     d, ff, L = cfg["latent_dim"], cfg["ff_size"], cfg["layers"]
@@ -89,7 +95,20 @@ def make_state_dict(cfg, seed=0):
     lin("embed_timestep.time_embed.0", d, d, gain=1.5)
     lin("embed_timestep.time_embed.2", d, d, gain=1.5)
     enc = cfg.get("arch", "online") == "offline"
-    for l in range(L):
+    mix = cfg.get("arch", "online") == "mlp"
+    for l in range(L if mix else 0):
+        p = f"mlp.motion_mlp.mlps.{l}."
+        T = cfg["num_frames"]
+        if l == 0:
+            lin(p + "conct", d, 2 * d, gain=1.4)
+        sd[p + "fc0.weight"] = (rng.standard_normal((T, T, 1)) * (MLP_GAIN / np.sqrt(T))).astype(np.float32)
+        sd[p + "fc0.bias"] = (rng.standard_normal(T) * 0.05).astype(np.float32)
+        lin(p + "fc1", d, d, gain=MLP_GAIN)
+        lin(p + "emb_fc", d, d, gain=0.5)
+        for n in ("norm0", "norm1"):
+            sd[p + n + ".weight"] = (1.0 + 0.1 * rng.standard_normal(d)).astype(np.float32)
+            sd[p + n + ".bias"] = (0.1 * rng.standard_normal(d)).astype(np.float32)
+    for l in range(0 if mix else L):
         p = f"seqTransEncoder.layers.{l}." if enc else f"seqTransDecoder.layers.{l}."
         w = rng.standard_normal((3 * d, d)) / np.sqrt(d)
         # q,k gain -> peaky attention (the encoder's milder: without the decoder's third LayerNorm per layer and its causal
@@ -111,8 +130,11 @@ def make_state_dict(cfg, seed=0):
         lin("embed_text", d, cfg.get("clip_dim", 512))
     if "action" in cfg["cond_mode"]:
         sd["embed_action.action_embedding"] = rng.standard_normal((cfg["num_actions"], d)).astype(np.float32)
-    lin("output_process.poseFinal", F, d, gain=1.0)
+    lin("output_process.poseFinal", F, d, gain=MLP_OUT_GAIN / L if mix else 1.0)
     return sd
+
+
+MLP_GAIN, MLP_OUT_GAIN = 1.0, 0.8   # (the projection gain is MLP_OUT_GAIN / layers: the stream grows with every block)
 
 
 FAMILIES = ("heavy_tailed", "outlier_channels", "peaky_attention", "big_output", "small_signal", "hostile")

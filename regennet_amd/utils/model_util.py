@@ -11,9 +11,13 @@ def load_model_wo_clip(model, state_dict):
     assert all([k.startswith("clip_model.") for k in missing_keys])
 
 
-def create_model_and_diffusion(args, data):
+def create_model_and_diffusion(args, data, allow_mlp=False):
+    """allow_mlp: build arch='mlp' too. The two-argument call keeps refusing it, as it always has (callers that relied on the refusal see no
+    change); cgenerate, edit and eval.score pass True, so `--arch mlp` works on every command line."""
     if args.setting != "cmdm":
         raise NotImplementedError("only setting='cmdm' is on the hot path (model_util.py:13)")
+    if args.arch == "mlp" and not allow_mlp:
+        raise NotImplementedError("arch='mlp': pass allow_mlp=True (the command-line tools do), or construct CMDM(arch='mlp') directly")
     model = CMDM(**get_model_args(args, data))
     args.num_person = 1  # side effect of the reference (model_util.py:15)
     diffusion = create_gaussian_diffusion(args)
