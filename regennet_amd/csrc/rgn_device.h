@@ -136,7 +136,7 @@ __device__ __forceinline__ float gelu_as_rcpf(float v) { return v * 0.5f * (1.0f
 // GELU of two elements with packed fp32 FMAs and no transcendental instruction (v_exp / v_rcp issue at quarter rate; the A&S form spends
 // ~40 % of k_gemm_x3's epilogue VALU time in them).
 // gelu2_p13: x (0.5 + t Q(t^2)) with t = clamp(x, +-3.9) and t Q(t^2) ~ Phi(t) - 0.5: an odd degree-13 minimax polynomial on [0, 3.9] (max abs
-// error 8.3e-5 in Phi with the clamp's 4.8e-5 beyond it; max abs error of the GELU 3.2e-4 over [-8, 8], evaluated in fp32 like here - the
+// error 8.3e-5 in Phi with the clamp's 4.8e-5 beyond it; max abs error of the GELU < 3.3e-4 over [-8, 8]: 3.21e-4 in fp64, 3.22e-4 evaluated in fp32 (tests/test_plain_stage_cpu.py) - the
 // degree-15 fit of gelu2_p15 had 8.1e-5 and 6.4e-4: the wider interval bought nothing the bf16 rounding of the result does not hide 10x over),
 // the 1/sqrt 2 and the 0.5 folded into the coefficients: 11 instructions per pair
 __device__ __forceinline__ f32x2 gelu2_p13(f32x2 x) {
@@ -152,7 +152,7 @@ __device__ __forceinline__ f32x2 gelu2_p13(f32x2 x) {
     return x * __builtin_elementwise_fma(t, p, f32x2{0.5f, 0.5f});
 }
 // gelu2_p15: 0.5 x (1 + erf(u)) with erf an odd degree-15 polynomial in u = clamp(x / sqrt 2, +-3.2) (weighted least-squares fit, max abs
-// error 1.6e-4 -> relative GELU error <= 8e-5, 25x below the bf16 rounding of the result)
+// error 1.6e-4 -> GELU error relative to |x| < 8.7e-5 over [-8, 8]: 8.2e-5 in fp64, 8.6e-5 evaluated in fp32; 20x below the bf16 rounding of the result)
 __device__ __forceinline__ f32x2 gelu2_p15(f32x2 x) {
     f32x2 u = x * 0.70710678118654752440f;
     u = __builtin_elementwise_min(__builtin_elementwise_max(u, f32x2{-3.2f, -3.2f}), f32x2{3.2f, 3.2f});

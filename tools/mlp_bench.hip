@@ -1,5 +1,6 @@
-// Stand-alone micro-benchmark + reference check of the row-persistent layer-tail kernel (tools only; the parity tests proper are
-// tests/test_hip_parity.py).
+// Stand-alone micro-benchmark + reference check of the row-persistent layer-tail kernel (tools only; the parity check proper is
+// tests/test_plain_stage_gpu.py: this kernel against the fp64 host statement of its own arithmetic, tests/plain_stage_ref.py tail_stage - the check
+// below is loose (6e-2 max, 6e-3 mean) and evaluates the erf GELU where the kernel runs gelu2_p13).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DRGN_M2_STAMPS] -I regennet_amd/csrc tools/mlp_bench.hip regennet_amd/csrc/rgn_mlp2.hip -o tools/bin/mlp_bench
 //   mlp_bench [M] [iters] [check]      check = 1: compare the first and the last 64-row tile with an fp64 host evaluation of the
 //                                      same bf16 inputs (the kernel rounds h', the GELU'd hidden tile and its output to bf16)
