@@ -346,6 +346,43 @@ RGN_API int rgn_vb_terms(rgn_handle h, const float* x_start_dev, const float* x_
                          const int32_t* t_dev /*[N]*/, const float* coef_dev /*[N,6]*/, int32_t B, int32_t N, int32_t features, int32_t T,
                          int32_t flags /*RGN_VB_CLIP*/, float* terms_dev /*[N,3]*/, void* stream);
 
+/* ---- The metrics of the unconstrained evaluation: KID, and precision / recall of the generated feature manifold ----
+ * Replace eval/unconstrained/metrics/kid.py:8-126 (polynomial_mmd_averages, polynomial_mmd, _mmd2_and_variance: per subset three sklearn kernel
+ * matrices on the host) and eval/unconstrained/metrics/precision_recall.py:30-53 (manifold_estimate: a Python double loop of torch.norm calls) for
+ * features that are already on the device. The three calls take no handle: `device` is the HIP device the pointers live on. They allocate nothing,
+ * keep no state, enqueue on `stream` itself and can be captured into a graph; no floating-point atomic is used, so two calls on the same inputs agree
+ * bit for bit. The arguments are checked before the device is touched: RGN_ERR_INVALID_ARG with text "<function>: ..." in rgn_last_error(NULL); a
+ * negative `device` is refused LAST, after every other argument has passed.
+ *
+ * rgn_poly_mmd: kid.py:8-126 for S subsets in one call. x_dev fp32 [Nx, D] is the reference's codes_g, y_dev fp32 [Ny, D] its codes_r;
+ *   idx_x_dev / idx_y_dev int32 [S, m] are the rows np.random.choice drew for each subset (duplicates are legal: a draw with replacement makes them).
+ *   An index outside its set gives an unspecified result, never an access outside the buffers (the in-tree binding checks the draws on the host).
+ *   Per subset the three m x m kernel matrices K_XX, K_YY, K_XY over the gathered rows are formed tile by tile and never stored:
+ *     dot    on the fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact fp32 products, fp32 accumulation over D
+ *     k      s = fl(fl(gamma dot) + coef0), k = s^degree by degree - 1 fp32 multiplications (sklearn's polynomial_kernel on fp32 inputs); gamma is
+ *            given (kid.py's default None is 1 / D, rounded to fp32 by the caller)
+ *   and everything _mmd2_and_variance reads - the row sums of K_XX and K_YY, both marginals of K_XY, the diagonals of K_XX and K_YY, the three sums of
+ *   squares - is reduced in fp64 in a fixed order (regennet_amd/csrc/rgn_metrics.hip states it). mmds_dev fp64 [S] = mmd2 with mmd_est='unbiased',
+ *   vars_dev fp64 [S] = var_est with var_at_m = min(Nx, Ny), both evaluated in fp64 as kid.py:87-124 writes them.
+ *   Geometry: D a multiple of 4 in [4, 1024]; m in [3, 4096] (var_est divides by m - 2); S in [1, 65535]; Nx, Ny >= 2; degree in [1, 8].
+ *   x_dev, y_dev and work_dev 16-byte aligned; work_bytes at least rgn_poly_mmd_workspace(S, m): 8 S (8 + nt) 64 nt bytes, nt = ceil(m / 64).
+ *
+ * rgn_knn_radius: precision_recall.py:34-42. radii_dev fp32 [N]: r_i = the k-th order statistic (0-based, np.partition(d, k)[k]) of the multiset
+ *   { d(A_i, A_j) : j = 0..N-1 }, j = i included, equal distances counted separately. 1 <= k <= 15, k < N <= 2^24.
+ * rgn_manifold_hits: precision_recall.py:44-53. flags_dev uint8 [M]: flag_i = any_j ( d(B_i, A_j) <= r_j ), compared in fp32; count_dev int32 [1] = the
+ *   number of set flags (the reference's n; its early break changes no result). M, N in [1, 2^24].
+ * The distance of both is the DIRECT-DIFFERENCE form of torch.norm(A - A'), never the Gram form |a|^2 + |b|^2 - 2 a.b:
+ *   d2 = the fp32 chain acc = fma(t, t, acc), t = fl(a_c - b_c), over c = 0, 1, ..., D - 1 ascending; d = sqrt(d2) correctly rounded.
+ * d(A_i, A_i) = 0 and d = 0 between identical rows, exactly; the relative error of a distance is at most (D + 1) 2^-24 however small it is.
+ * D a multiple of 4 in [4, 1024]; a_dev and b_dev 16-byte aligned. */
+RGN_API int rgn_poly_mmd_workspace(int32_t S, int32_t m, uint64_t* nbytes);
+RGN_API int rgn_poly_mmd(int32_t device, const float* x_dev /*[Nx,D]*/, int32_t Nx, const float* y_dev /*[Ny,D]*/, int32_t Ny, int32_t D,
+                         const int32_t* idx_x_dev /*[S,m]*/, const int32_t* idx_y_dev /*[S,m]*/, int32_t S, int32_t m, int32_t degree, float gamma,
+                         float coef0, double* mmds_dev /*[S]*/, double* vars_dev /*[S]*/, void* work_dev, uint64_t work_bytes, void* stream);
+RGN_API int rgn_knn_radius(int32_t device, const float* a_dev /*[N,D]*/, int32_t N, int32_t D, int32_t k, float* radii_dev /*[N]*/, void* stream);
+RGN_API int rgn_manifold_hits(int32_t device, const float* b_dev /*[M,D]*/, int32_t M, const float* a_dev /*[N,D]*/, const float* radii_dev /*[N]*/,
+                              int32_t N, int32_t D, uint8_t* flags_dev /*[M]*/, int32_t* count_dev /*[1]*/, void* stream);
+
 /* ---- Mesh vertices: jointstype='vertices' ----
  * Replaces the body layer the reference keeps in Rotation2xyz.smpl_model / Rotation2xyz_x.smpl_model (model/rotation2xyz.py:14-15 / :161-162, a CPU
  * smplx layer over a licensed model file): the mesh data of a BODY FILE (tools/make_skeleton.py --mesh), resident on `device`.

@@ -132,6 +132,14 @@ SYMBOLS.update({
     "rgn_render": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(RgnRenderParams), _vp, _vp, _vp, _vp, _u64, _vp]),
 })
 
+# the metrics of the unconstrained evaluation (rgn_metrics.hip): no handle, errors through rgn_last_error(NULL)
+SYMBOLS.update({
+    "rgn_poly_mmd_workspace": (C.c_int, [_i32, _i32, C.POINTER(_u64)]),
+    "rgn_poly_mmd": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _u64, _vp]),
+    "rgn_knn_radius": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "rgn_manifold_hits": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+})
+
 _lib = None
 
 

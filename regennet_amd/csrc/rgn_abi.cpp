@@ -683,6 +683,92 @@ int rgn_vb_terms(rgn_handle h, const float* x_start, const float* x_t, const flo
     });
 }
 
+// ---- the metrics of the unconstrained evaluation (rgn_metrics.hip): no handle; text in rgn_last_error(NULL)
+static int metrics_fail(int code, const char* fn, const std::string& m) {
+    g_create_error = std::string(fn) + ": " + m;
+    return code;
+}
+static int metrics_hip(const char* fn, hipError_t e) {
+    return e == hipSuccess ? RGN_OK : metrics_fail(RGN_ERR_HIP, fn, std::string("HIP: ") + hipGetErrorString(e));
+}
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+static std::string metrics_check_dim(int32_t D) {
+    if (D < 4 || D > 1024 || D % 4) return "D = " + std::to_string(D) + " is no multiple of 4 in [4, 1024]";
+    return std::string();
+}
+static std::string poly_mmd_check_shape(int32_t S, int32_t m) {
+    if (S < 1 || S > 65535) return "S = " + std::to_string(S) + " outside [1, 65535]";
+    if (m < 3 || m > 4096) return "m = " + std::to_string(m) + " outside [3, 4096]";
+    return std::string();
+}
+
+int rgn_poly_mmd_workspace(int32_t S, int32_t m, uint64_t* nbytes) {
+    return rgn_guard(static_cast<rgn_ctx*>(nullptr), "rgn_poly_mmd_workspace", [&]() -> int {
+        if (!nbytes) return metrics_fail(RGN_ERR_INVALID_ARG, "rgn_poly_mmd_workspace", "null nbytes");
+        const std::string why = poly_mmd_check_shape(S, m);
+        if (!why.empty()) return metrics_fail(RGN_ERR_INVALID_ARG, "rgn_poly_mmd_workspace", why);
+        *nbytes = poly_mmd_workspace_bytes(S, m);
+        return RGN_OK;
+    });
+}
+
+int rgn_poly_mmd(int32_t device, const float* x, int32_t Nx, const float* y, int32_t Ny, int32_t D, const int32_t* idx_x, const int32_t* idx_y, int32_t S,
+                 int32_t m, int32_t degree, float gamma, float coef0, double* mmds, double* vars, void* work, uint64_t work_bytes, void* stream) {
+    const char* fn = "rgn_poly_mmd";
+    return rgn_guard(static_cast<rgn_ctx*>(nullptr), fn, [&]() -> int {
+        auto bad = [&](const std::string& t) { return metrics_fail(RGN_ERR_INVALID_ARG, fn, t); };
+        if (!x || !y || !idx_x || !idx_y || !mmds || !vars || !work) return bad("null x, y, idx_x, idx_y, mmds, vars or work");
+        std::string why = metrics_check_dim(D);
+        if (why.empty()) why = poly_mmd_check_shape(S, m);
+        if (!why.empty()) return bad(why);
+        if (Nx < 2 || Ny < 2) return bad("Nx < 2 or Ny < 2");
+        if (degree < 1 || degree > 8) return bad("degree = " + std::to_string(degree) + " outside [1, 8]");
+        if (!std::isfinite(gamma) || !std::isfinite(coef0)) return bad("gamma or coef0 is not finite");
+        if (misaligned16(x) || misaligned16(y)) return bad("x or y is not 16-byte aligned");
+        if (misaligned16(work)) return bad("work is not 16-byte aligned");
+        const uint64_t need = poly_mmd_workspace_bytes(S, m);
+        if (work_bytes < need) return bad("work_bytes = " + std::to_string(work_bytes) + ", " + std::to_string(need) + " needed (rgn_poly_mmd_workspace)");
+        if (device < 0) return bad("device < 0");
+        if (int rc = metrics_hip(fn, hipSetDevice(device))) return rc;
+        return metrics_hip(fn, launch_poly_mmd(x, y, idx_x, idx_y, Nx, Ny, D, S, m, degree, gamma, coef0, static_cast<double*>(work), mmds, vars,
+                                               reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int rgn_knn_radius(int32_t device, const float* a, int32_t N, int32_t D, int32_t k, float* radii, void* stream) {
+    const char* fn = "rgn_knn_radius";
+    return rgn_guard(static_cast<rgn_ctx*>(nullptr), fn, [&]() -> int {
+        auto bad = [&](const std::string& t) { return metrics_fail(RGN_ERR_INVALID_ARG, fn, t); };
+        if (!a || !radii) return bad("null a or radii");
+        const std::string why = metrics_check_dim(D);
+        if (!why.empty()) return bad(why);
+        if (N < 1 || N > (1 << 24)) return bad("N = " + std::to_string(N) + " outside [1, 2^24]");
+        if (k < 1 || k > 15) return bad("k = " + std::to_string(k) + " outside [1, 15]");
+        if (k >= N) return bad("k = " + std::to_string(k) + " is not below N = " + std::to_string(N));
+        if (misaligned16(a)) return bad("a is not 16-byte aligned");
+        if (device < 0) return bad("device < 0");
+        if (int rc = metrics_hip(fn, hipSetDevice(device))) return rc;
+        return metrics_hip(fn, launch_knn_radius(a, N, D, k, radii, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
+int rgn_manifold_hits(int32_t device, const float* b, int32_t M, const float* a, const float* radii, int32_t N, int32_t D, uint8_t* flags, int32_t* count,
+                      void* stream) {
+    const char* fn = "rgn_manifold_hits";
+    return rgn_guard(static_cast<rgn_ctx*>(nullptr), fn, [&]() -> int {
+        auto bad = [&](const std::string& t) { return metrics_fail(RGN_ERR_INVALID_ARG, fn, t); };
+        if (!b || !a || !radii || !flags || !count) return bad("null b, a, radii, flags or count");
+        const std::string why = metrics_check_dim(D);
+        if (!why.empty()) return bad(why);
+        if (M < 1 || M > (1 << 24)) return bad("M = " + std::to_string(M) + " outside [1, 2^24]");
+        if (N < 1 || N > (1 << 24)) return bad("N = " + std::to_string(N) + " outside [1, 2^24]");
+        if (misaligned16(a) || misaligned16(b)) return bad("a or b is not 16-byte aligned");
+        if (device < 0) return bad("device < 0");
+        if (int rc = metrics_hip(fn, hipSetDevice(device))) return rc;
+        return metrics_hip(fn, launch_manifold_hits(b, a, radii, M, N, D, flags, count, reinterpret_cast<hipStream_t>(stream)));
+    });
+}
+
 int rgn_profile_enable(rgn_handle h, int32_t on) {
     return rgn_guard(h, "rgn_profile_enable", [&]() -> int {
         if (!h) return RGN_ERR_INVALID_ARG;

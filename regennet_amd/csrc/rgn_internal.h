@@ -428,6 +428,13 @@ hipError_t launch_q_sample_rows(const float* x_start, const float* noise_in, con
                                 int N, int n, int T, unsigned long long seed, unsigned long long sample_offset, hipStream_t s);
 hipError_t launch_vb_terms(const float* x_start, const float* x_t, const float* output, const float* noise, const int* t_idx, const float* coef,
                            float* terms, int B, int N, int n, int flags, hipStream_t s);
+// ---- rgn_metrics.hip: KID and precision / recall of the unconstrained evaluation (rgn_poly_mmd, rgn_knn_radius, rgn_manifold_hits); every pointer on
+// the device, the arguments already checked
+unsigned long long poly_mmd_workspace_bytes(int S, int m);
+hipError_t launch_poly_mmd(const float* X, const float* Y, const int* idx_x, const int* idx_y, int Nx, int Ny, int D, int S, int m, int degree,
+                           float gamma, float coef0, double* work, double* mmds, double* vars, hipStream_t s);
+hipError_t launch_knn_radius(const float* A, int N, int D, int k, float* radii, hipStream_t s);
+hipError_t launch_manifold_hits(const float* B, const float* A, const float* radii, int M, int N, int D, uint8_t* flags, int* count, hipStream_t s);
 // The skeleton argument checks of rgn_rot2xyz / rgn_rot2verts and the table their kernels take by value. nullptr when `sk` was filled, else the text of
 // the complaint (without the entry point's name); `at` receives the offending joint for the parent-table complaint, else -1. Host only.
 inline const char* fk_build_skel(int J, const float* rest_joints, const int32_t* parents, FkSkel& sk, int& at) {

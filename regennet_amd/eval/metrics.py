@@ -19,6 +19,13 @@ def calculate_accuracy(model, motion_loader, num_labels, classifier, device):
     return (torch.trace(confusion) / torch.sum(confusion)).item(), confusion
 
 
+def pair_distance_sum(act, i, j):
+    """sum_n |act[i_n] - act[j_n]| for host index arrays i, j: one batched pass on the activations' device (a 0-dim tensor there)."""
+    dev = act.device
+    i, j = torch.as_tensor(np.asarray(i), device=dev), torch.as_tensor(np.asarray(j), device=dev)
+    return (act[i] - act[j]).norm(dim=1).sum()
+
+
 def calculate_diversity_multimodality(activations, labels, num_labels, seed=None, unconstrained=False):
     """diversity.py:6-71 (multimodality is computed for every cond_mode, as there)."""
     diversity_times, multimodality_times = 200, 20
@@ -43,14 +50,8 @@ def calculate_diversity_multimodality(activations, labels, num_labels, seed=None
         pairs_a.append(a)
         pairs_b.append(b)
     act = activations.float()
-    dev = act.device
-
-    def dist_sum(i, j):
-        i, j = torch.as_tensor(np.asarray(i), device=dev), torch.as_tensor(np.asarray(j), device=dev)
-        return (act[i] - act[j]).norm(dim=1).sum()
-
-    diversity = dist_sum(first, second) / diversity_times
-    multimodality = dist_sum(pairs_a, pairs_b) / (multimodality_times * num_labels)
+    diversity = pair_distance_sum(act, first, second) / diversity_times
+    multimodality = pair_distance_sum(act, pairs_a, pairs_b) / (multimodality_times * num_labels)
     return diversity.item(), multimodality.item()
 
 
@@ -116,6 +117,19 @@ class Evaluation:
                 metrics[f"fid_{key}"] = float(calculate_fid(gtstats, computedfeats[key]["stats"]))
             metrics_all[sets] = metrics
         return {f"{key}_{sets}": metrics_all[sets][key] for sets in ["train", "test"] for key in metrics_all[sets]}
+
+    def evaluate_unconstrained(self, loaders, fast=False, **kid_args):
+        """eval/unconstrained/evaluate.py:57-110 for a model without labels: `loaders` = {"gen": batches, "gt": batches} (batches with 'output', as for
+        `evaluate`; 'y' is not needed). The recogniser runs ONCE per loader; the features stay on the device and feed
+        `eval.unconstrained.evaluate_unconstrained_metrics` -> {'fid', 'kid', 'diversity_gen', 'diversity_gt', 'precision', 'recall'}."""
+        from .unconstrained import evaluate_unconstrained_metrics
+        feats = {}
+        for key in ("gen", "gt"):
+            batches = ({**batch, "y": batch.get("y", torch.zeros(len(batch["output"]), dtype=torch.long))} for batch in loaders[key])
+            feats[key], _ = self.compute_features(None, batches)
+        if self.seed is not None:
+            np.random.seed(self.seed)
+        return evaluate_unconstrained_metrics(feats["gen"], feats["gt"], fast=fast, **kid_args)
 
     def evaluate_acc(self, model, loaders, setting):
         """evaluate.py:127-162 (the `acc_only` runs of stgcn_eval.py:200): recognition accuracy per loader and split only."""

@@ -256,6 +256,22 @@ def make_text_features(cfg, batch, seed=3):
     return f.astype(np.float32)
 
 
+def make_stgcn_graph(V=56):
+    """A synthetic skeleton in the reference's 'spatial' partition form (stgcnutils/graph.py): a binary tree over V joints; A[0] self loops, A[1] the
+    edge from the parent, A[2] the edges from the children, column-normalised. For tools that need a recogniser without the reference's graph file."""
+    parent = [(v - 1) // 2 for v in range(V)]
+    adj = np.eye(V)
+    for v in range(1, V):
+        adj[v, parent[v]] = adj[parent[v], v] = 1.0
+    dn = adj / adj.sum(0, keepdims=True)
+    A = np.zeros((3, V, V), np.float32)
+    for v in range(V):
+        for w in range(V):
+            if adj[v, w]:
+                A[0 if v == w else (1 if parent[w] == v else 2), v, w] = dn[v, w]
+    return A
+
+
 def make_stgcn_state_dict(A, num_class=26, in_channels=12, num_person=2, seed=0):
     """Synthetic checkpoint of the ST-GCN evaluator with the reference's state_dict keys
     (eval/a2m/recognition/models/stgcn.py:44-73,183-219; stgcnutils/tgcn.py:51-59). `A` [K, V, V] is the adjacency buffer
