@@ -566,7 +566,19 @@ RGN_API int rgn_stgcn_destroy(rgn_stgcn_handle h);
 RGN_API const char* rgn_stgcn_last_error(rgn_stgcn_handle h);
 /* host fp32 copies of the checkpoint tensors (model.load_state_dict, evaluate.py:24-25) */
 RGN_API int rgn_stgcn_load_weight(rgn_stgcn_handle h, const char* ref_key, const float* host, const int64_t* shape, int32_t ndim);
-/* folds every BatchNorm (eval mode) and the edge importance into the convolutions; RGN_ERR_MISSING_KEY names what is absent */
+/* The block plan: (out_channels[i], strides[i]) of the st_gcn blocks, between rgn_stgcn_create and rgn_stgcn_finalize. Default: the ten blocks of
+ * eval/a2m/recognition/models/stgcn.py:51-62; the extractor of the unconstrained evaluation (eval/unconstrained/models/stgcn.py:52-63, built by
+ * eval/unconstrained/evaluate.py:21-32) has six: (64,1) (64,1) (64,1) (128,2) (128,1) (256,2). Accepted: 2 to 10 blocks, channels from {64, 128, 256}
+ * that never decrease and end at 256 (the features are [N, 256]), stride 1 or 2 with stride 2 only where the channel count changes. Block 0 has no
+ * residual; a later block has the convolved shortcut exactly when its channel count or stride changes (st_gcn.__init__). Anything else:
+ * RGN_ERR_INVALID_ARG with the offending entry named; after finalize: RGN_ERR_STATE. rgn_stgcn_finalize then asks for the keys of the plan's blocks
+ * and refuses (RGN_ERR_BAD_KEY, first such key named) a checkpoint that holds 'st_gcn_networks.<i>' / 'edge_importance.<i>' of a block the plan lacks. */
+RGN_API int rgn_stgcn_set_blocks(rgn_stgcn_handle h, int32_t n_blocks, const int32_t* out_channels, const int32_t* strides);
+/* the plan rules alone, without a handle or a device: RGN_OK, or RGN_ERR_INVALID_ARG with the message (NUL-terminated, cut to cap) in err (nullable) */
+RGN_API int rgn_stgcn_check_blocks(int32_t n_blocks, const int32_t* out_channels, const int32_t* strides, char* err, int32_t cap);
+/* folds every BatchNorm (eval mode) and the edge importance into the convolutions; RGN_ERR_MISSING_KEY names what is absent.
+ * Graphs of fewer than 28 nodes (the 15-node 'openpose' graph of the unconstrained evaluation, the 25-node 'smpl' layout of
+ * eval/a2m/stgcn/evaluate.py:11-12) run on a vertex count padded to 16 / 20 / 24 / 28 inside the engine; num_nodes and the input keep the real V. */
 RGN_API int rgn_stgcn_finalize(rgn_stgcn_handle h);
 /* Kernel-selection switches of ONE recogniser handle (like rgn_set_option; any time before a forward): "SG_NO_WINDOW" (row-shifted GEMMs instead of the
  * LDS-window temporal convolutions), "SG_NO_GCN_FUSE" (aggregation and 1x1 convolution as two launches), "SG_NO_TAIL_FUSE" (k_sg_post for every block), "SG_NO_POLY_TAIL" (... for the two blocks with polyphase output),

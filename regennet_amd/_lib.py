@@ -95,6 +95,8 @@ SYMBOLS.update({
     "rgn_stgcn_destroy": (C.c_int, [_vp]),
     "rgn_stgcn_last_error": (C.c_char_p, [_vp]),
     "rgn_stgcn_load_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i32]),
+    "rgn_stgcn_set_blocks": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "rgn_stgcn_check_blocks": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32]),
     "rgn_stgcn_finalize": (C.c_int, [_vp]),
     "rgn_stgcn_set_option": (C.c_int, [_vp, C.c_char_p, _i32]),
     "rgn_stgcn_forward": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
@@ -420,10 +422,27 @@ class Engine:
         return out
 
 
+def _block_arrays(blocks):
+    blocks = [(int(co), int(st)) for co, st in blocks]
+    n = max(len(blocks), 1)
+    return (C.c_int32 * n)(*[b[0] for b in blocks]), (C.c_int32 * n)(*[b[1] for b in blocks])
+
+
+def check_stgcn_blocks(blocks):
+    """rgn_stgcn_check_blocks: the block-plan rules of rgn_stgcn_set_blocks without a handle or a device. Raises RgnError (RGN_ERR_INVALID_ARG, the
+    offending entry named) for a plan the engine does not take."""
+    co, st = _block_arrays(blocks)
+    err = C.create_string_buffer(512)
+    code = load().rgn_stgcn_check_blocks(len(blocks), co, st, err, 512)
+    if code != RGN_OK:
+        raise RgnError(code, err.value.decode())
+
+
 class StgcnEngine:
     """Owns one rgn_stgcn_handle (the ST-GCN evaluator, include/regennet_hip.h)."""
 
-    def __init__(self, in_channels, num_class, num_person, num_nodes, num_frames, max_batch, device_index, options=None):
+    def __init__(self, in_channels, num_class, num_person, num_nodes, num_frames, max_batch, device_index, options=None, blocks=None):
+        """blocks: [(out_channels, stride), ...] of the st_gcn blocks (rgn_stgcn_set_blocks); None: the reference's ten."""
         self.lib = load()
         self.shape = (int(num_nodes), int(in_channels), int(num_frames))
         self.num_class, self.max_batch = int(num_class), int(max_batch)
@@ -436,6 +455,12 @@ class StgcnEngine:
         self.h = h
         for k, v in (options or {}).items():         # kernel-selection switches of this handle (rgn_stgcn_set_option)
             self.set_option(k, v)
+        if blocks is not None:
+            try:
+                self.set_blocks(blocks)
+            except Exception:
+                self.close()
+                raise
 
     def _ck(self, code):
         if code != RGN_OK:
@@ -456,6 +481,10 @@ class StgcnEngine:
         a = np.ascontiguousarray(array, dtype=np.float32)
         shape = (C.c_int64 * max(a.ndim, 1))(*a.shape)
         self._ck(self.lib.rgn_stgcn_load_weight(self.h, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
+
+    def set_blocks(self, blocks):
+        co, st = _block_arrays(blocks)
+        self._ck(self.lib.rgn_stgcn_set_blocks(self.h, len(blocks), co, st))
 
     def finalize(self):
         self._ck(self.lib.rgn_stgcn_finalize(self.h))

@@ -312,6 +312,10 @@ hipError_t configure_gemm_x3_sg();
 bool sg_tconv_supported(int N, int Kp, int V);
 hipError_t launch_sg_tconv(const GemmX3Args& g, int V, int tail, bool small_tiles, hipStream_t s);   // tail 0: C = conv + bias (fp32) | 1: planes relu(conv + bias) | 2: planes relu(conv + bias + R) | 3: as 2, polyphase
 hipError_t configure_sg_tconv();
+// ... of a small graph (16 <= V <= 28 rows per frame): the whole window of a tile resident before its taps run, two window buffers (k_sg_tconv_pre); tails as above
+bool sg_tconv_pre_supported(int N, int Kp, int V);
+hipError_t launch_sg_tconv_pre(const GemmX3Args& g, int V, int tail, hipStream_t s);
+hipError_t configure_sg_tconv_pre();
 // ... the stride-2 form on polyphase planes (region O starts o_rows rows behind region E; M = rows of one region = output rows), + the convolved shortcut;
 // output: planes relu(conv + shortcut + bias)
 bool sg_tconv_s2_supported(int N, int Kp, int V);

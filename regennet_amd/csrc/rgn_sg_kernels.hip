@@ -2,9 +2,10 @@
 // K32-blocked operand planes of rgn_gemm_x3.hip - [C/32][rows][32] bf16, hi and lo - with rows = (sequence, frame, vertex):
 //   k_sg_gcn        graph aggregation + 1 x 1 convolution: the aggregated operand is formed in registers, in MFMA fragment layout
 //   k_sg_tconv      9 x 1 temporal convolution of a stride-1 block: the activation window of a tile resident in LDS, nine taps V rows apart
+//   k_sg_tconv_pre  ... of a stride-1 block of a small graph (16 <= V <= 28): the whole window resident before its taps, the next one arriving under them
 //   k_sg_tconv_s2   ... of a stride-2 block at the output rate on polyphase planes, + the block's convolved shortcut
 //   sg_epilogue     their common epilogue: bias (per column or per vertex), identity residual, ReLU, fp32 or split-plane output
-// All three are PERSISTENT over output tiles and members of the DMA-fed GEMM family of rgn_dma_gemm.h: the product order, the weight-tile DMA, the MFMA
+// All of them are PERSISTENT over output tiles and members of the DMA-fed GEMM family of rgn_dma_gemm.h: the product order, the weight-tile DMA, the MFMA
 // groups of a k-step, the tile walk with its counted wait and the paired-column store are defined there. What stands here is each kernel's own: window
 // geometry and refill, tap order, the shortcut's register fragments, the in-register aggregation.
 #include "rgn_dma_gemm.h"
@@ -30,8 +31,9 @@ __device__ __forceinline__ float f16_bits_to_float(unsigned b) { return (float)_
 //   SGE_RELU | SGE_PLANES (output as split planes, else fp32)
 //   SGE_POLY         the planes are written POLYPHASE for a stride-2 consumer: input row (sequence, frame t < T of T + 4, vertex) -> region t & 1 (poly_region
 //                    rows each), frame t >> 1 of ceil(T / 2) + 4; the input's pad frames are not written (the consumer's pads are zeroed by the host's k_sg_zero)
+//   SGE_POLY_V16     ... for 16 <= V < 32 rows per frame (k_sg_tconv_pre): the 32 rows of a tile may step into the next frame TWICE
 // (what the callers' counted wait behind an epilogue may assume, and why a tile's operands are fetched one tile ahead: STORES_BEHIND, rgn_dma_gemm.h)
-enum { SGE_VERTEX_BIAS = 1, SGE_RELU = 2, SGE_PLANES = 4, SGE_RES_PLANES = 8, SGE_POLY = 16 };
+enum { SGE_VERTEX_BIAS = 1, SGE_RELU = 2, SGE_PLANES = 4, SGE_RES_PLANES = 8, SGE_POLY = 16, SGE_POLY_V16 = 32 };
 template <int TM, int TN, bool CHECK, int MODE, bool F16 = false>
 __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[TM][TN], int mw, int nw, int lane) {
     const int l31 = lane & 31, kh = lane >> 5;
@@ -107,7 +109,8 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 if (!CHECK || (n_ok && mb + ro < g.M)) cp[(size_t)ro * g.ldc] = r[i];
             }
         } else if constexpr ((MODE & SGE_POLY) != 0) {
-            // rows mb + ro, ro < 32 <= V: at most one step into the next frame, which may be the next sequence's first
+            // rows mb + ro, ro < 32 <= V: at most one step into the next frame, which may be the next sequence's first (SGE_POLY_V16: ro < 32 <= 2 V, two
+            // steps; T + 4 >= 5 frames per sequence, so still at most one step into the next sequence)
             const int Vv = g.poly_V, Tr = g.poly_T, Tp = Tr + 4, Tpo = ((Tr + 1) >> 1) + 4;
             const unsigned f0 = (unsigned)mb / (unsigned)Vv, nm0 = f0 / (unsigned)Tp;
             const int v0 = mb - (int)f0 * Vv, t0 = (int)(f0 - nm0 * (unsigned)Tp);
@@ -118,6 +121,9 @@ __device__ __forceinline__ void sg_epilogue(const GemmX3Args& g, f32x16 (&acc)[T
                 dg_pair_columns(r, i, odd, c0, c1);
                 const int ro = dg_pair_row(i, odd);
                 int v = v0 + ro, t = t0, nm = (int)nm0;
+                if constexpr ((MODE & SGE_POLY_V16) != 0) {
+                    if (v >= Vv) { v -= Vv; ++t; }
+                }
                 if (v >= Vv) { v -= Vv; ++t; }
                 if (t >= Tp) { t -= Tp; ++nm; }
                 if (t < Tr && (!CHECK || mb + ro < g.M))
@@ -340,6 +346,133 @@ hipError_t launch_sg_tconv(const GemmX3Args& g, int V, int tail, bool small, hip
         hipLaunchKernelGGL(kern, dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_lds_bytes(BM, BN, V), s, g, nbx, ntiles, V);
         return hipGetLastError();
     });
+}
+
+// ---- ... of a stride-1 block of a SMALL graph: 16 <= V <= 28 rows per frame (rgn_stgcn.hip pads the vertices of a graph below 28 nodes) ------------
+// k_sg_tconv refills its window strip by strip behind the taps and therefore needs 8 V >= BM: tap 0 reads window rows [0, 256) when only the first 8 V
+// are in place. Here 8 V < 256, and the window is small instead - 256 + 8 V <= 480 rows x 64 B x {hi, lo} = 61 440 B - so the WHOLE window of (tile,
+// channel block) is resident before its nine taps run, and a second buffer receives the next one (the next channel block's, or the next tile's first)
+// under them: 2 x 61 440 + two weight stages of a 128-wide tile (32 768) = 155 648 B of the 160 KiB; 64-wide tiles leave 16 KiB more. Per k-step the
+// L2 -> LDS path carries the weight tile + at most one 16-row piece per wave (60 pieces per window over taps 0-7). 256-channel blocks run as two
+// 128-wide column tiles. K order, weight planes, stage layout, DMA behind the first MFMA group, counted wait and epilogue: as k_sg_tconv
+// (rgn_dma_gemm.h). Split-bf16 only: SG_F16 is refused for small graphs (rgn_stgcn.hip).
+template <int BN, int WM, int MODE>
+__global__ __launch_bounds__(512, 1) void k_sg_tconv_pre(GemmX3Args g, int nbx, int ntiles, int V) {
+    constexpr int BM = 256, TAPS = 9;
+    constexpr int WN = 8 / WM;
+    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
+    constexpr int W_BYTES = BN * 64, W_STAGE = 2 * W_BYTES;      // one plane tile; a stage = hi | lo
+    static_assert(TM >= 1 && TN >= 1 && BN % 64 == 0 && BM % (32 * WM) == 0, "tile shape");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int l31 = lane & 31, kh = lane >> 5;
+    const int WR = BM + 8 * V, A_PLANE = WR * 64, A_WIN = 2 * A_PLANE;   // window rows (a multiple of 32: V % 4 == 0); bytes per plane, per window buffer (hi | lo)
+    char* const wst = smem + 2 * A_WIN;                          // weight stages behind the two window buffers
+    const int ncb = g.Kp / (32 * TAPS);
+    const long long row_lo = -4LL * V, row_hi = (long long)g.M + 4LL * V - 1;   // the planes' zero guard rows bound what a window may touch
+    const char* const a_pl[2] = {reinterpret_cast<const char*>(g.Ahi), reinterpret_cast<const char*>(g.Alo)};
+    const int npc = WR / 16, npieces = 2 * npc;                  // 16-row pieces (1 KiB) of a window: hi plane, then lo plane
+    // piece p of the window of (tile rows m0t, channel block cb) into window buffer buf; global rows clamped to the guard rows like k_sg_tconv's a_piece
+    auto a_piece = [&](int m0t, int cb, int p, int buf) {
+        const int pl = p >= npc ? 1 : 0, r0 = (p - pl * npc) * 16, r = r0 + (lane >> 2);
+        long long gr = (long long)m0t - 4LL * V + r;
+        gr = gr < row_lo ? row_lo : (gr > row_hi ? row_hi : gr);
+        const char* src = a_pl[pl] + ((long long)cb * g.a_rows + gr) * 64 + (img_dma_chunk(r, lane & 3) << 4);
+        __builtin_amdgcn_global_load_lds((const RGN_AS1 void*)src, (RGN_AS3 void*)(smem + buf * A_WIN + pl * A_PLANE + r0 * 64), 16, 0, 0);
+    };
+    unsigned w_lane[BN / 64];
+    dg_w_lanes<BN>(w_lane, tid);
+    auto w_tile = [&](int n0t, int kt, char* stage) {
+        dg_w_tile<BN>(reinterpret_cast<const char*>(g.Whi), reinterpret_cast<const char*>(g.Wlo), (size_t)kt * g.N + n0t, w_lane, stage, tid);
+    };
+    int w_off[TN][2];
+    dg_frag_off(w_off, wn * (BN / WN), l31, kh);
+    const int arow0 = wm * (BM / WM) + l31;
+
+    DgTile t = dg_tile<BM, BN>(xcd_affine(blockIdx.x, gridDim.x), nbx);
+    for (int p = wave; p < npieces; p += 8) a_piece(t.m0, 0, p, 0);   // prologue: the whole first window and the first weight tile
+    w_tile(t.n0, 0, wst);
+    unsigned gstep = 0, widx = 0;                                // k-steps / windows done: weight stage gstep & 1, window buffer widx & 1
+    bool stores_behind = false;
+    while (true) {
+        const DgTile tn = dg_tile<BM, BN>(t.tile + (int)gridDim.x, nbx);
+        const bool more = tn.tile < ntiles;
+        f32x16 acc[TM][TN];
+        dg_zero(acc);
+        for (int cb = 0; cb < ncb; ++cb, ++widx) {
+            const bool wlast = cb + 1 == ncb;
+            const char* const win = smem + (widx & 1) * A_WIN;
+            const bool nextw = !wlast || more;                   // a next window exists: (this tile, cb + 1) or (next tile, 0)
+            const int m0w = wlast ? tn.m0 : t.m0, cbw = wlast ? 0 : cb + 1;
+#pragma unroll 1
+            for (int dt = 0; dt < TAPS; ++dt, ++gstep) {
+                dg_step_wait<dg_tile_stores(MODE & SGE_PLANES, false) * TM * TN>(stores_behind);
+                __builtin_amdgcn_s_barrier();                    // everyone's requests have landed (at dt = 0: this window whole), and everyone is done reading
+                                                                 // the previous k-step (at dt = 0: the other window buffer, which the DMA below overwrites)
+                auto a_frag = [&](int ks, bf16x8 (&ah)[2][TM], bf16x8 (&al)[2][TM]) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        const int o = img_frag(arow0 + i * 32 + dt * V, ks, kh);      // the tap's rows start dt V further down the window
+                        ah[ks][i] = *reinterpret_cast<const bf16x8*>(win + o);
+                        al[ks][i] = *reinterpret_cast<const bf16x8*>(win + A_PLANE + o);
+                    }
+                };
+                dg_kstep<TM, TN, false>(acc, wst + (gstep & 1) * W_STAGE, W_BYTES, w_off, a_frag, [&](int grp) {
+                    if (grp == 0) {
+                        // the path's load for this k-step: the next weight tile and one piece per wave of the next window (60 pieces at most: taps 0-7)
+                        const bool klast = wlast && dt == TAPS - 1;
+                        if (!klast) w_tile(t.n0, dt + 1 < TAPS ? cb * TAPS + dt + 1 : (cb + 1) * TAPS, wst + ((gstep + 1) & 1) * W_STAGE);
+                        else if (more) w_tile(tn.n0, 0, wst + ((gstep + 1) & 1) * W_STAGE);
+                        const int p = dt * 8 + wave;
+                        if (nextw && p < npieces) a_piece(m0w, cbw, p, (widx + 1) & 1);
+                    }
+                });
+            }
+        }
+        stores_behind = dg_close<BM, BN>(g, t.m0, t.n0, [&](auto CHECK) { sg_epilogue<TM, TN, decltype(CHECK)::value, MODE>(g, acc, t.m0 + wm * (BM / WM), t.n0 + wn * (BN / WN), lane); });
+        if (!more) break;
+        t = tn;
+    }
+}
+static int tconv_pre_lds_bytes(int BN, int V) { return 2 * 2 * (256 + 8 * V) * 64 + 2 * 2 * BN * 64; }
+bool sg_tconv_pre_supported(int N, int Kp, int V) {
+    return (N == 64 || N == 128 || N == 256) && Kp == 9 * N && V % 4 == 0 && V >= 16 && V <= 28 && tconv_pre_lds_bytes(128, V) <= 160 * 1024;
+}
+// k_sg_tconv_pre's forms, named once: fn(kernel, BN) for (tile width, tail); tails as k_sg_tconv's (tail 3 with the two-step frame walk of V < 32)
+template <int BN, int WM, class Fn>
+static hipError_t tconv_pre_tail_form(int tail, Fn fn) {
+    if (tail == 0) return fn(k_sg_tconv_pre<BN, WM, 0>, BN);
+    if (tail == 1) return fn(k_sg_tconv_pre<BN, WM, SGE_RELU | SGE_PLANES>, BN);
+    if (tail == 2) return fn(k_sg_tconv_pre<BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES>, BN);
+    if constexpr (BN == 64) {
+        if (tail == 3) return fn(k_sg_tconv_pre<BN, WM, SGE_RELU | SGE_PLANES | SGE_RES_PLANES | SGE_POLY | SGE_POLY_V16>, BN);
+    }
+    return hipErrorInvalidValue;
+}
+// wide: 128-column tiles (128 and 256 channels), else 64. The polyphase tail exists 64 wide only: on a 128-wide tile (TM = TN = 2) its frame walk beside the
+// residual fragments spills two VGPRs (12 B of scratch; profiles/small_graph_resources.txt), so the one 128-channel block in front of a stride-2 block runs
+// as two 64-wide column tiles
+template <class Fn>
+static hipError_t tconv_pre_form(bool wide, int tail, Fn fn) {
+    return wide && tail != 3 ? tconv_pre_tail_form<128, 4>(tail, fn) : tconv_pre_tail_form<64, 8>(tail, fn);
+}
+hipError_t launch_sg_tconv_pre(const GemmX3Args& g, int V, int tail, hipStream_t s) {
+    if (g.f16 || !sg_tconv_pre_supported(g.N, g.Kp, V)) return hipErrorInvalidValue;
+    return tconv_pre_form(g.N != 64, tail, [&](auto kern, int BN) {
+        const int nbx = g.N / BN, ntiles = nbx * ((g.M + 255) / 256);
+        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, sg_cu_count())), dim3(512), tconv_pre_lds_bytes(BN, V), s, g, nbx, ntiles, V);
+        return hipGetLastError();
+    });
+}
+hipError_t configure_sg_tconv_pre() {
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < 8 && e == hipSuccess; ++m)               // (64, 128) x tail
+        e = tconv_pre_form(m >> 2, m & 3, [](auto kern, int BN) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, tconv_pre_lds_bytes(BN, 28));
+        });
+    return e;
 }
 
 // ---- the 9 x 1 temporal convolution of a STRIDE-2 block, at the output rate, on polyphase planes (region E: even frames, region O: odd frames, same

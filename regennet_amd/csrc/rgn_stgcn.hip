@@ -13,6 +13,8 @@
 //                                                                            next block's planes - polyphase (even | odd frames) in front of a
 //   (stride 2: taps on the even / odd frame regions, + the 1x1 shortcut)    k_sg_tconv_s2 stride-2 block, which then runs at the output rate
 //
+// The blocks follow the handle's PLAN (rgn_stgcn_set_blocks; default: the ten above; the unconstrained evaluation's extractor, eval/unconstrained/models/stgcn.py, has six),
+// and a graph of fewer than 28 nodes runs on a padded vertex count with isolated pad vertices (rgn_sg_plan.h; finalize and forward below; k_sg_tconv_pre).
 // The kernels live in rgn_sg_kernels.hip (what they share with each other and with k_gemm_x3: rgn_dma_gemm.h); this file holds the load-time folding, the plane geometry and the block loop, plus the small kernels around
 // them (input layout + data_bn, pad zeroing, pooling) and the forms the fused kernels replaced (k_sg_agg + row-shifted k_gemm_x3 + k_sg_post), which
 // still serve graphs and shapes the fused kernels do not take and can be selected per handle (rgn_stgcn_set_option; every form is tested).
@@ -25,6 +27,7 @@
 #include "../../include/regennet_hip.h"
 #include "rgn_internal.h"
 #include "rgn_device.h"
+#include "rgn_sg_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -43,8 +46,6 @@ namespace {
 
 constexpr int SG_PAD = 4;                      // temporal kernel 9 -> 4 zero frames BEHIND every sequence: they are also the pad in front of the next
                                                // one (the guard rows in front of the first), so a sequence costs T + 4 frames of rows, not T + 8
-struct SgBlockDef { int ci, co, stride; bool res_conv, res_id; };
-
 struct SgBlock {
     int ci = 0, co = 0, stride = 1, kp1 = 0, kpr = 0;
     unsigned slot_k = 0;                             // the same lists as 8 slots per vertex for k_sg_gcn (rgn_internal.h); sl_v == nullptr: they do not fit
@@ -77,6 +78,8 @@ struct rgn_stgcn_ctx {
     std::string f16_refused;                     // why SG_F16 cannot be served by this checkpoint (a folded weight beyond the fp16 range); empty: it can
     std::map<std::string, int> opts;             // rgn_stgcn_set_option: kernel-selection switches of this handle (they take precedence over REGENNET_<KEY>)
     int V = 0, K = 0, C0 = 0;
+    int Vp = 0, P = 0;                           // vertices per frame of the planes (V < 28: padded, rgn_sg_plan.h) and the period of the vertex bias table
+    std::vector<SgBlockDef> plan = sg_default_plan();   // rgn_stgcn_set_blocks
     std::vector<SgBlock> blocks;
     float *bn_s = nullptr, *bn_t = nullptr, *Wf = nullptr, *bf = nullptr;
     __bf16 *xa[2] = {nullptr, nullptr}, *xb[2] = {nullptr, nullptr}, *z[2] = {nullptr, nullptr}, *g[2] = {nullptr, nullptr};   // (hi, lo) plane buffers
@@ -129,6 +132,37 @@ __global__ void k_sg_in(const float* __restrict__ out, SgPl x, const float* __re
 #pragma unroll
     for (int c = 0; c < 32; ++c) val[c] = 0.f;
     if (tt >= 0 && tt < T) {
+        const int n = nm / M, m = nm % M;
+        for (int c = 0; c < C && c < 32; ++c) {
+            const int ch = (m * V + v) * C + c;
+            val[c] = out[(((size_t)n * V + v) * (M * C) + m * C + c) * T + tt] * s[ch] + t[ch];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float v8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v8[j] = val[8 * q + j];
+        bf16x8 h, l;
+        split_bf16(v8, h, l);
+        *reinterpret_cast<bf16x8*>(x.hi + row * 32 + 8 * q) = h;
+        *reinterpret_cast<bf16x8*>(x.lo + row * 32 + 8 * q) = l;
+    }
+}
+
+// ... for a small graph (V < 28): the input keeps its V real vertices, [N, V, M*C, T], the planes carry Vp >= V rows per frame; a pad vertex's row is
+// zero in every frame (data_bn's scale and shift are taken as zero there). Rows (n M + m, t, v < Vp).
+__global__ void k_sg_in_pad(const float* __restrict__ out, SgPl x, const float* __restrict__ s, const float* __restrict__ t, int N, int V, int Vp, int M, int C, int T) {
+    const int Tp = T + SG_PAD;
+    const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= (size_t)N * M * Tp * Vp) return;
+    const int v = (int)(row % Vp);
+    const int tt = (int)((row / Vp) % Tp);
+    const int nm = (int)(row / ((size_t)Vp * Tp));
+    float val[32];
+#pragma unroll
+    for (int c = 0; c < 32; ++c) val[c] = 0.f;
+    if (tt < T && v < V) {
         const int n = nm / M, m = nm % M;
         for (int c = 0; c < C && c < 32; ++c) {
             const int ch = (m * V + v) * C + c;
@@ -422,6 +456,34 @@ __global__ __launch_bounds__(256) void k_sg_pool(SgPl x, float* __restrict__ poo
     }
 }
 
+// ... of a small graph: the planes hold Vp rows per frame of which the first V are vertices. Behind a temporal convolution a pad row holds relu(b2' ...),
+// not zero: the pool SKIPS the pad rows (no producer zeroes them) and divides by the T V real ones.
+__global__ __launch_bounds__(256) void k_sg_pool_pad(SgPl x, float* __restrict__ pooled, int M, int T, int V, int Vp, int C) {
+    __shared__ float part[8][256];
+    const int n = blockIdx.x, Tp = T + SG_PAD, c8n = C / 8;                      // C <= 256: c8n <= 32
+    const int c8 = threadIdx.x % 32, sl = threadIdx.x / 32;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c8 < c8n)
+        for (int m = 0; m < M; ++m) {
+            const size_t o = plane_chunk(x.R, ((size_t)(n * M + m) * Tp) * Vp, c8 >> 2, c8 & 3);
+            for (int i = sl; i < T * Vp; i += 8) {
+                if (i % Vp >= V) continue;
+                const bf16x8 h = *reinterpret_cast<const bf16x8*>(x.hi + o + (size_t)i * 32), l = *reinterpret_cast<const bf16x8*>(x.lo + o + (size_t)i * 32);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += (float)h[e] + (float)l[e];
+            }
+        }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[sl][(8 * c8 + e) & 255] = acc[e];
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float a = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) a += part[q][c];
+        pooled[(size_t)n * C + c] = a / (float)(T * V) / (float)M;
+    }
+}
+
 template <typename T>
 int sg_alloc(rgn_stgcn_ctx* c, T** p, size_t count) {
     void* q = nullptr;
@@ -473,11 +535,6 @@ int sg_upload_ints(rgn_stgcn_ctx* c, int** p, const std::vector<int>& v) {
     SG_HIP(c, hipMemcpy(*p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
     return RGN_OK;
 }
-
-const SgBlockDef kBlocks[10] = {{0, 64, 1, false, false},   {64, 64, 1, false, true},   {64, 64, 1, false, true},  {64, 64, 1, false, true},
-                                {64, 128, 2, true, false},  {128, 128, 1, false, true}, {128, 128, 1, false, true}, {128, 256, 2, true, false},
-                                {256, 256, 1, false, true}, {256, 256, 1, false, true}};   // stgcn.py:51-62
-
 
 GemmArgs sg_gemm(const float* A, int lda, const float* W, int Kp, int K, const float* bias, float* C, int ldc, int M, int N) {
     GemmArgs g{};
@@ -542,6 +599,8 @@ int rgn_stgcn_create(const rgn_stgcn_config* cfg, rgn_stgcn_handle* out) {
         rgn_stgcn_ctx* c = new rgn_stgcn_ctx();
         c->cfg = *cfg;
         c->V = cfg->num_nodes;
+        c->Vp = sg_padded_nodes(c->V);
+        c->P = sg_bias_period(c->V);
         c->C0 = cfg->in_channels / cfg->num_person;
         *out = c;
         return RGN_OK;
@@ -575,6 +634,31 @@ int rgn_stgcn_load_weight(rgn_stgcn_handle h, const char* key, const float* host
     });
 }
 
+int rgn_stgcn_check_blocks(int32_t n_blocks, const int32_t* out_channels, const int32_t* strides, char* err, int32_t cap) {
+    return sg_guard(static_cast<rgn_stgcn_ctx*>(nullptr), "rgn_stgcn_check_blocks", [&]() -> int {
+        std::string m;
+        const bool ok = sg_plan_check(n_blocks, out_channels, strides, nullptr, &m);
+        if (err && cap > 0) {
+            const size_t n = std::min(m.size(), (size_t)cap - 1);
+            memcpy(err, m.data(), n);
+            err[n] = 0;
+        }
+        return ok ? RGN_OK : RGN_ERR_INVALID_ARG;
+    });
+}
+
+int rgn_stgcn_set_blocks(rgn_stgcn_handle h, int32_t n_blocks, const int32_t* out_channels, const int32_t* strides) {
+    return sg_guard(h, "rgn_stgcn_set_blocks", [&]() -> int {
+        if (!h) return RGN_ERR_INVALID_ARG;
+        if (h->finalized) return h->fail(RGN_ERR_STATE, "rgn_stgcn_set_blocks: already finalized");
+        std::string m;
+        std::vector<SgBlockDef> plan;
+        if (!sg_plan_check(n_blocks, out_channels, strides, &plan, &m)) return h->fail(RGN_ERR_INVALID_ARG, "rgn_stgcn_set_blocks: " + m);
+        h->plan.swap(plan);
+        return RGN_OK;
+    });
+}
+
 int rgn_stgcn_finalize(rgn_stgcn_handle h) {
     return sg_guard(h, "rgn_stgcn_finalize", [&]() -> int {
         if (!h) return RGN_ERR_INVALID_ARG;
@@ -599,6 +683,12 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
             return c->fail(RGN_ERR_MISSING_KEY, "rgn_stgcn_finalize: adjacency buffer 'A' [K, V, V] missing or of the wrong shape");
         c->K = (int)c->shapes["A"][0];
         const int V = c->V, K = c->K, M = c->cfg.num_person, C0 = c->C0;
+        // Small graphs: the planes run on Vp >= V vertices per frame (rgn_sg_plan.h). A pad vertex is ISOLATED - it has no entry in any aggregation list and
+        // b1' = 0, so it is zero behind every graph convolution - and the vertex bias table is replicated to P rows (add_mod). V >= 28: Vp = P = V.
+        const int Vp = c->Vp, P = c->P, nb = (int)c->plan.size();
+        for (const auto& kv : c->sd)
+            if (sg_key_block(kv.first) >= nb)
+                return c->fail(RGN_ERR_BAD_KEY, "rgn_stgcn_finalize: the checkpoint holds '" + kv.first + "' but the block plan has " + std::to_string(nb) + " blocks (rgn_stgcn_set_blocks)");
         const float* A0 = itA->second.data();
         // BatchNorm (eval): y = x * s + t with s = gamma / sqrt(var + eps), t = beta - mean * s
         auto bn_fold = [&](const std::string& p, int n, std::vector<double>& s, std::vector<double>& t) -> bool {
@@ -620,15 +710,15 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
                 if ((rc = sg_upload(c, &c->bn_s, sf)) || (rc = sg_upload(c, &c->bn_t, tf))) return rc;
             }
         }
-        c->blocks.resize(10);
-        for (int i = 0; i < 10; ++i) {
+        c->blocks.resize(nb);
+        for (int i = 0; i < nb; ++i) {
             SgBlock& b = c->blocks[i];
             const std::string p = "st_gcn_networks." + std::to_string(i) + ".";
-            b.ci = i == 0 ? C0 : kBlocks[i].ci;
-            b.co = kBlocks[i].co;
-            b.stride = kBlocks[i].stride;
-            b.res_conv = kBlocks[i].res_conv;
-            b.res_id = kBlocks[i].res_id;
+            b.ci = i == 0 ? C0 : c->plan[i].ci;
+            b.co = c->plan[i].co;
+            b.stride = c->plan[i].stride;
+            b.res_conv = c->plan[i].res_conv;
+            b.res_id = c->plan[i].res_id;
             const int ci = b.ci, co = b.co, K1 = K * ci;
             const float* imp = need("edge_importance." + std::to_string(i), (size_t)K * V * V);
             const float *wg = need(p + "gcn.conv.weight", (size_t)K * co * ci), *bg = need(p + "gcn.conv.bias", (size_t)K * co);
@@ -646,21 +736,21 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
             std::vector<float> Ak((size_t)K * V * V);
             for (size_t j = 0; j < Ak.size(); ++j) Ak[j] = A0[j] * imp[j];                       // stgcn.py:105 (fp32 product, as there)
             // nonzero lists of A'_k[:, w] (the skeleton graph is sparse; a dense A simply gives V entries per list)
-            std::vector<int> nzp((size_t)K * V + 1, 0), nzv;
+            std::vector<int> nzp((size_t)K * Vp + 1, 0), nzv;     // (lists run over the Vp plane vertices; a pad vertex's are empty)
             std::vector<float> nza;
             for (int k = 0; k < K; ++k)
-                for (int w = 0; w < V; ++w) {
-                    for (int v = 0; v < V; ++v)
+                for (int w = 0; w < Vp; ++w) {
+                    for (int v = 0; v < V && w < V; ++v)
                         if (Ak[((size_t)k * V + v) * V + w] != 0.f) {
                             nzv.push_back(v);
                             nza.push_back(Ak[((size_t)k * V + v) * V + w]);
                         }
-                    nzp[(size_t)k * V + w + 1] = (int)nzv.size();
+                    nzp[(size_t)k * Vp + w + 1] = (int)nzv.size();
                 }
             if (nzv.empty()) { nzv.push_back(0); nza.push_back(0.f); }
             // W1'[co][(k, ci)] = s1[co] * Wg[k*co_n + co][ci];  b1'[w][co] = s1 * sum_k bg[k*co_n + co] * colsum_k[w] + t1
             b.kp1 = (int)up32((size_t)K1);
-            std::vector<float> W1((size_t)co * b.kp1, 0.f), b1((size_t)V * co);
+            std::vector<float> W1((size_t)co * b.kp1, 0.f), b1((size_t)P * co, 0.f);    // b1': P rows, row r = vertex r % Vp (zero for a pad vertex)
             for (int o = 0; o < co; ++o)
                 for (int k = 0; k < K; ++k)
                     for (int q = 0; q < ci; ++q) W1[(size_t)o * b.kp1 + k * ci + q] = (float)(s1[o] * (double)wg[((size_t)k * co + o) * ci + q]);
@@ -674,6 +764,7 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
                     }
                     b1[(size_t)w * co + o] = (float)(s1[o] * acc + t1[o]);
                 }
+            for (int r = Vp; r < P; ++r) std::copy(b1.begin() + (size_t)(r % Vp) * co, b1.begin() + (size_t)(r % Vp + 1) * co, b1.begin() + (size_t)r * co);
             // W2'[co][(channel block, dt, channel in block)] = s2[co] * Wt[co][ci][dt] (K = 9 co in the order the shifted-row GEMM walks: taps innermost
             // per 32-channel block, so that consecutive k-steps re-read one channel block of the activation 56 rows further on);  b2' = s2 * bt + t2
             std::vector<float> W2((size_t)co * 9 * co, 0.f), b2(co);
@@ -686,19 +777,19 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
                 std::vector<int> cnt(K, 0);
                 int total = 0;
                 for (int k = 0; k < K; ++k) {
-                    for (int w = 0; w < V; ++w) cnt[k] = std::max(cnt[k], nzp[(size_t)k * V + w + 1] - nzp[(size_t)k * V + w]);
+                    for (int w = 0; w < Vp; ++w) cnt[k] = std::max(cnt[k], nzp[(size_t)k * Vp + w + 1] - nzp[(size_t)k * Vp + w]);
                     total += cnt[k];
                 }
                 if (total <= 8 && K <= 8) {
-                    std::vector<int> sv((size_t)V * 8);
-                    std::vector<float> sa((size_t)V * 8, 0.f);
+                    std::vector<int> sv((size_t)Vp * 8);
+                    std::vector<float> sa((size_t)Vp * 8, 0.f);
                     b.slot_k = 0xFFFFFFFFu;
-                    for (int w = 0; w < V; ++w) {
+                    for (int w = 0; w < Vp; ++w) {
                         int sidx = 0;
                         for (int k = 0; k < K; ++k)
                             for (int i = 0; i < cnt[k]; ++i, ++sidx) {
-                                const int j = nzp[(size_t)k * V + w] + i;
-                                const bool real = j < nzp[(size_t)k * V + w + 1];
+                                const int j = nzp[(size_t)k * Vp + w] + i;
+                                const bool real = j < nzp[(size_t)k * Vp + w + 1];
                                 sv[(size_t)w * 8 + sidx] = real ? nzv[j] : w;
                                 sa[(size_t)w * 8 + sidx] = real ? nza[j] : 0.f;
                                 b.slot_k = (b.slot_k & ~(15u << (4 * sidx))) | ((unsigned)k << (4 * sidx));
@@ -741,16 +832,16 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
         if (!missing.empty()) return c->fail(RGN_ERR_MISSING_KEY, "missing / mis-shaped keys in the ST-GCN state_dict: " + missing);
         c->sd.clear();
         // The plane kernels assume: channel counts of the blocks are multiples of 32 (64 / 128 / 256) behind a first block whose K C_in fits one
-        // 32-channel block, and the vertex bias row (row % V) wraps at most once inside a 32-row MFMA tile
-        if (K * C0 > 32 || C0 > 32 || V < 28) return c->fail(RGN_ERR_UNSUPPORTED, "rgn_stgcn_finalize: needs K * (in_channels / persons) <= 32 and >= 28 graph nodes");
+        // 32-channel block, and the vertex bias row (row % P) wraps at most once inside a 32-row MFMA tile (P >= 28: a small graph's table is replicated)
+        if (K * C0 > 32 || C0 > 32) return c->fail(RGN_ERR_UNSUPPORTED, "rgn_stgcn_finalize: needs K * (in_channels / persons) <= 32");
         // workspace: padded activation planes sized for the largest block (the 8 pad frames make the late, short blocks the big ones),
         // with guard rows at both ends of every plane block so that the +-4-frame row shifts of the temporal convolution never leave it
-        c->guard = (size_t)SG_PAD * V;
+        c->guard = (size_t)SG_PAD * Vp;
         size_t xmax = 0, zmax = 0, gmax = 0, cmax = 0;     // elements per plane / fp32 tensor
         {
-            auto phys = [&](int T, bool poly) { return sg_plane_rows((size_t)c->cfg.max_batch * M, T, poly, V); };
+            auto phys = [&](int T, bool poly) { return sg_plane_rows((size_t)c->cfg.max_batch * M, T, poly, Vp); };
             int T = c->cfg.num_frames;
-            for (int i = 0; i < 10; ++i) {
+            for (int i = 0; i < nb; ++i) {
                 const SgBlock& b = c->blocks[i];
                 const size_t rows = phys(T, b.stride == 2), R = rows + 2 * c->guard;
                 if (rows >= ((size_t)1 << 26)) return c->fail(RGN_ERR_UNSUPPORTED, "rgn_stgcn_finalize: max_batch x persons x frames x nodes beyond 2^26 rows");
@@ -760,7 +851,7 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
                 gmax = std::max(gmax, (size_t)b.co * R);
                 cmax = std::max(cmax, rows * b.co);
                 T = (T + b.stride - 1) / b.stride;
-                const size_t rows_o = phys(T, i + 1 < 10 && c->blocks[i + 1].stride == 2);
+                const size_t rows_o = phys(T, i + 1 < nb && c->blocks[i + 1].stride == 2);
                 xmax = std::max(xmax, (size_t)b.co * (rows_o + 2 * c->guard));
             }
         }
@@ -772,6 +863,7 @@ int rgn_stgcn_finalize(rgn_stgcn_handle h) {
         if ((rc = sg_alloc(c, &c->pooled, (size_t)c->cfg.max_batch * 256))) return rc;
         SG_HIP(c, configure_gemm_x3_sg());
         SG_HIP(c, configure_sg_tconv());
+        SG_HIP(c, configure_sg_tconv_pre());
         SG_HIP(c, configure_sg_gcn());
         SG_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         SG_HIP(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
@@ -805,14 +897,17 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
         hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = c->stream;
         SG_HIP(c, hipEventRecord(c->ev_in, us));
         SG_HIP(c, hipStreamWaitEvent(s, c->ev_in, 0));
-        const int V = c->V, K = c->K, M = c->cfg.num_person, NM = N * M;
+        // V: vertices per frame of the PLANES (a small graph's padded count; the input and the pool know the real c->V), nb: blocks of the handle's plan
+        const int V = c->Vp, K = c->K, M = c->cfg.num_person, NM = N * M, nb = (int)c->blocks.size();
+        const bool small_graph = c->V < 28;
         const int guard = (int)c->guard;
         int T = c->cfg.num_frames;
         auto planes = [&](__bf16* const (&buf)[2], size_t rows) { return SgPl{buf[0] + (size_t)guard * 32, buf[1] + (size_t)guard * 32, (long long)(rows + 2 * (size_t)guard)}; };
         auto blocks1d = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
         {
             const size_t rows = (size_t)NM * (T + SG_PAD) * V;
-            hipLaunchKernelGGL(k_sg_in, blocks1d(rows), dim3(256), 0, s, output, planes(c->xa, rows), c->bn_s, c->bn_t, N, V, M, c->C0, T);
+            if (small_graph) hipLaunchKernelGGL(k_sg_in_pad, blocks1d(rows), dim3(256), 0, s, output, planes(c->xa, rows), c->bn_s, c->bn_t, N, c->V, V, M, c->C0, T);
+            else hipLaunchKernelGGL(k_sg_in, blocks1d(rows), dim3(256), 0, s, output, planes(c->xa, rows), c->bn_s, c->bn_t, N, V, M, c->C0, T);
         }
         // kernel forms (defaults: everything fused; the switches exist for tools and for the tests that run every form against the goldens)
         const bool no_window = sg_opt(c, "SG_NO_WINDOW", 0) != 0;        // the row-shifted GEMM for every temporal convolution
@@ -832,11 +927,11 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
         };
         __bf16 *(*x)[2] = &c->xa, *(*xn)[2] = &c->xb;
         auto phys = [&](int Tf, bool poly) { return sg_plane_rows((size_t)NM, Tf, poly, V); };
-        for (int i = 0; i < 10; ++i) {
+        for (int i = 0; i < nb; ++i) {
             const SgBlock& b = c->blocks[i];
             // a stride-2 block reads POLYPHASE planes (written so by the block in front of it): region E = the even frames of every sequence, region O = the odd
             // ones, Te + 4 frames per sequence in both - its 9-tap stride-2 convolution is then five row-shifted taps on E and four on O at the OUTPUT rate
-            const bool ipoly = b.stride == 2, opoly = i + 1 < 10 && c->blocks[i + 1].stride == 2;
+            const bool ipoly = b.stride == 2, opoly = i + 1 < nb && c->blocks[i + 1].stride == 2;
             const int To = (T + b.stride - 1) / b.stride, Te = (T + 1) / 2;   // Conv2d(9x1, pad 4, stride s): ceil(T / s) frames
             const int Tpi = ipoly ? Te + SG_PAD : T + SG_PAD;                 // frames per sequence of the rows the convolution is computed on
             const size_t rows = phys(T, ipoly), rows_c = (size_t)NM * Tpi * V, rows_o = phys(To, opoly);
@@ -846,12 +941,14 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
             if (f16 && !fused && i > 0) return f16_unserved(i, "the two-launch graph convolution");
             const bool gf16 = f16 && fused;                      // (block 0, K C_in = 18 of one 32-deep k-block, keeps the split GEMM: its planes come from k_sg_in)
             GemmX3Args g1 = sg_gemm_x3(fused ? xp : zp, gf16 ? b.W1f : b.W1h, b.W1l, (int)rows, b.co, b.kp1);
-            g1.add = b.b1; g1.ldadd = b.co; g1.add_mod = V; g1.act = 3;                          // + b1'[row % V], ReLU
+            g1.add = b.b1; g1.ldadd = b.co; g1.add_mod = c->P; g1.act = 3;                       // + b1'[row % P], ReLU (P = V unless the graph is small)
             g1.Chi = gp.hi; g1.Clo = gp.lo; g1.c_rows = (int)gp.R;
             g1.f16 = gf16 ? 1 : 0;
             if (fused) SG_HIP(c, launch_sg_gcn(g1, V, K, b.slot_k, b.sl_v, b.sl_a, gcn_bn, gcn_step32, s));   // z is formed in registers, fragment by fragment
             else if (i == 0 && !no_block0 && b.ci == 6 && K == 3 && b.co == 64 && b.W1s) {
                 dispatch_bools([&](auto F) { hipLaunchKernelGGL((k_sg_block0<6, 3, 64, decltype(F)::value>), blocks1d(rows), dim3(256), 0, s, xp, gp, b.nz_ptr, b.nz_v, b.nz_a, b.W1s, b.b1, rows, V); }, f16);
+            } else if (small_graph && i == 0 && !no_block0 && !f16 && b.ci == 3 && K == 3 && b.co == 64 && b.W1s) {   // the 3-channel first block of the unconstrained evaluator
+                hipLaunchKernelGGL((k_sg_block0<3, 3, 64, false>), blocks1d(rows), dim3(256), 0, s, xp, gp, b.nz_ptr, b.nz_v, b.nz_a, b.W1s, b.b1, rows, V);
             } else {
                 if (b.ci % 32 == 0) hipLaunchKernelGGL(k_sg_agg, dim3((unsigned)((rows * 4 + 255) / 256), (unsigned)(K * (b.ci / 32))), dim3(256), 0, s, xp, zp, b.nz_ptr, b.nz_v, b.nz_a, rows, V, K, b.ci);
                 else if (b.ci == 6 && K == 3) hipLaunchKernelGGL((k_sg_agg_small_t<6, 3>), blocks1d(rows), dim3(256), 0, s, xp, zp, b.nz_ptr, b.nz_v, b.nz_a, rows, V);
@@ -878,7 +975,11 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
                 else if ((dt & 1) == 0) g2.a_tap[dt] = (long long)((dt - 4) / 2) * V * 64;                  // frame 2 t' + dt - 4 = even frame t' + (dt - 4) / 2
                 else g2.a_tap[dt] = ((long long)rows_c + (long long)((dt - 5) / 2) * V) * 64;               // ... = odd frame t' + (dt - 5) / 2
             }
-            const bool window = !ipoly && !no_window && sg_tconv_supported(b.co, 9 * b.co, V);     // activation window resident in LDS
+            // activation window resident in LDS: refilled strip by strip behind the taps (k_sg_tconv, 8 V >= 256) or, on a small graph, whole and double-buffered
+            // (k_sg_tconv_pre, 16 <= V <= 28; split bf16 only - SG_F16 falls through to f16_unserved below)
+            const bool pre = small_graph && !ipoly && !no_window && !f16 && sg_tconv_pre_supported(b.co, 9 * b.co, V);
+            const bool window = pre || (!ipoly && !no_window && sg_tconv_supported(b.co, 9 * b.co, V));
+            auto launch_window = [&](const GemmX3Args& ga, int tail) { return pre ? launch_sg_tconv_pre(ga, V, tail, s) : launch_sg_tconv(ga, V, tail, small_tiles, s); };
             if (ipoly && !opoly && b.res_conv && !no_s2 && !no_window && b.kpr == b.ci && sg_tconv_s2_supported(b.co, 9 * b.co, V)) {
                 // stride-2 block: two resident windows (even / odd frames), the convolved shortcut as extra k-steps, the tail in the epilogue
                 g2.bias = b.b2r;
@@ -894,7 +995,7 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
                 g2.Rhi = xp.hi; g2.Rlo = xp.lo; g2.r_rows = (int)xp.R;
                 const int Teo = (To + 1) / 2;
                 g2.poly_T = T; g2.poly_V = V; g2.poly_region = (int)((size_t)NM * (Teo + SG_PAD) * V);
-                SG_HIP(c, launch_sg_tconv(g2, V, 3, small_tiles, s));
+                SG_HIP(c, launch_window(g2, 3));
                 zero(xo, 0, Teo, Teo + SG_PAD, guard, 0);
                 zero(xo, (long long)g2.poly_region, To / 2, Teo + SG_PAD, 0, guard);
             } else if (window && !opoly && !b.res_conv && !no_tail) {
@@ -902,12 +1003,12 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
                 g2.bias = b.b2;
                 g2.Chi = xo.hi; g2.Clo = xo.lo; g2.c_rows = (int)xo.R;
                 g2.Rhi = xp.hi; g2.Rlo = xp.lo; g2.r_rows = (int)xp.R;
-                SG_HIP(c, launch_sg_tconv(g2, V, b.res_id ? 2 : 1, small_tiles, s));
+                SG_HIP(c, launch_window(g2, b.res_id ? 2 : 1));
                 zero(xo, 0, To, To + SG_PAD, guard, guard);
             } else {
                 if (f16) return f16_unserved(i, "the unfused temporal convolution + k_sg_post");
                 g2.C = c->conv; g2.ldc = b.co;
-                if (window) SG_HIP(c, launch_sg_tconv(g2, V, 0, small_tiles, s));
+                if (window) SG_HIP(c, launch_window(g2, 0));
                 else SG_HIP(c, launch_gemm_x3_sg(g2, s));
                 if (b.res_conv) {   // strided 1x1 convolution of the block input: the even frames = region E of the polyphase planes (all rows for a stride-1 block)
                     GemmX3Args gr = sg_gemm_x3(xp, b.Wrh, b.Wrl, (int)rows_c, b.co, b.kpr);
@@ -920,7 +1021,8 @@ int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output, float*
             std::swap(x, xn);
             T = To;
         }
-        dispatch_bools([&](auto F) { hipLaunchKernelGGL(k_sg_pool<decltype(F)::value>, dim3(N), dim3(256), 0, s, planes(*x, phys(T, false)), c->pooled, M, T, V, 256); }, f16);
+        if (small_graph) hipLaunchKernelGGL(k_sg_pool_pad, dim3(N), dim3(256), 0, s, planes(*x, phys(T, false)), c->pooled, M, T, c->V, V, 256);   // (f16: refused above)
+        else dispatch_bools([&](auto F) { hipLaunchKernelGGL(k_sg_pool<decltype(F)::value>, dim3(N), dim3(256), 0, s, planes(*x, phys(T, false)), c->pooled, M, T, V, 256); }, f16);
         if (features) SG_HIP(c, hipMemcpyAsync(features, c->pooled, (size_t)N * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (yhat) {
             GemmArgs gf = sg_gemm(c->pooled, 256, c->Wf, 256, 256, c->bf, yhat, c->cfg.num_class, N, c->cfg.num_class);

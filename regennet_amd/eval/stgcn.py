@@ -6,6 +6,10 @@ Like `regennet_amd.model.cmdm.CMDM`, the module is a checkpoint container with t
 libregennet_hip.so (`rgn_stgcn_forward`), where the whole network runs as HIP kernels with every BatchNorm folded.
 There is no eager fallback. The skeleton graph is taken from the checkpoint's `A` buffer: the reference rebuilds it from
 the licensed SMPL-X kinematic tree (stgcnutils/graph.py:81-88) and then stores it in the state_dict anyway (stgcn.py:42).
+
+`blocks=[(out_channels, stride), ...]` builds other block plans (the state_dict keys follow the plan); `UnconstrainedSTGCN` is the mirror of
+`eval/unconstrained/models/stgcn.py::STGCN`, the six-block single-person extractor of the unconstrained evaluation on its 15-node graph.
+Graphs of fewer than 28 nodes (15, the 25 of `graph_args={"layout": "smpl"}`) are padded inside the engine.
 """
 import torch
 import torch.nn as nn
@@ -14,6 +18,16 @@ from .. import _lib
 
 _BLOCKS = [(None, 64, 1), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 128, 1), (128, 256, 2),
            (256, 256, 1), (256, 256, 1)]      # stgcn.py:51-62
+TEN_BLOCKS = [(co, s) for _, co, s in _BLOCKS]                                       # the plan as rgn_stgcn_set_blocks takes it: (out_channels, stride)
+SIX_BLOCKS = [(64, 1), (64, 1), (64, 1), (128, 2), (128, 1), (256, 2)]               # eval/unconstrained/models/stgcn.py:52-63
+
+
+def _plan(blocks):
+    """[(out_channels, stride), ...] -> [(in, out, stride), ...] with in = None for the first block; checked by the engine's own rule
+    (rgn_stgcn_check_blocks, no device needed)."""
+    blocks = [(int(co), int(s)) for co, s in blocks]
+    _lib.check_stgcn_blocks(blocks)
+    return [(blocks[i - 1][0] if i else None, co, s) for i, (co, s) in enumerate(blocks)]
 
 
 class _Gcn(nn.Module):                         # ConvTemporalGraphical's parameter names (stgcnutils/tgcn.py:51-59)
@@ -34,12 +48,15 @@ class _Block(nn.Module):                       # st_gcn's parameter names (stgcn
 
 class STGCN(nn.Module):
     def __init__(self, in_channels, num_class, num_person, graph_args=None, edge_importance_weighting=True, device=None,
-                 num_nodes=None, spatial_kernel_size=3, **kwargs):
+                 num_nodes=None, spatial_kernel_size=3, blocks=None, **kwargs):
+        """blocks: [(out_channels, stride), ...] of the st_gcn blocks, None = the reference's ten (stgcn.py:51-62). The state_dict keys follow the plan."""
         super().__init__()
         if not edge_importance_weighting:
             raise NotImplementedError("the evaluator is always built with edge_importance_weighting=True (evaluate.py:19)")
         layout = (graph_args or {}).get("layout", "smplx")
-        V = num_nodes or {"smplx": 56, "smpl": 25}[layout]            # stgcnutils/graph.py:63,82
+        V = num_nodes or {"smplx": 56, "smpl": 25, "ntu-rgb+d": 25}[layout]   # stgcnutils/graph.py:56,74,83
+        self.blocks = None if blocks is None else [(int(co), int(s)) for co, s in blocks]
+        plan = _BLOCKS if blocks is None else _plan(blocks)
         K = spatial_kernel_size                                        # 'spatial' strategy with max_hop 1: 3 partitions
         self.device, self.in_channels, self.num_class, self.num_person = device, in_channels, num_class, num_person
         self.losses = ["accuracy", "cross_entropy", "mixed"]
@@ -48,8 +65,8 @@ class STGCN(nn.Module):
         self.data_bn = nn.BatchNorm1d(in_channels * V)
         c0 = in_channels // num_person
         self.st_gcn_networks = nn.ModuleList(
-            [_Block(c0 if ci is None else ci, co, K, s, residual=i > 0) for i, (ci, co, s) in enumerate(_BLOCKS)])
-        self.edge_importance = nn.ParameterList([nn.Parameter(torch.ones(K, V, V)) for _ in _BLOCKS])
+            [_Block(c0 if ci is None else ci, co, K, s, residual=i > 0) for i, (ci, co, s) in enumerate(plan)])
+        self.edge_importance = nn.ParameterList([nn.Parameter(torch.ones(K, V, V)) for _ in plan])
         self.fcn = nn.Conv2d(256, num_class, kernel_size=1)
         self._engine, self._stale, self._applied_options = None, True, {}
         self._stale_person = {}
@@ -77,7 +94,7 @@ class STGCN(nn.Module):
                 torch.cuda.synchronize(dev)
                 eng.close()
             eng = _lib.StgcnEngine(self.in_channels, self.num_class, self.num_person, V, T, max(N, eng.max_batch if eng and eng.shape == (V, self.in_channels, T) else 0),
-                                   dev.index or 0, options=self.engine_options)
+                                   dev.index or 0, options=self.engine_options, blocks=self.blocks)
             for k, v in self.state_dict().items():
                 if k.endswith("num_batches_tracked"):
                     continue
@@ -97,12 +114,14 @@ class STGCN(nn.Module):
                 return self._get_engine(N, T)
         return eng, dev
 
+    _input_key = "output"
+
     def forward(self, batch):
         """batch['output'] [N, V, C * num_person, T] -> adds batch['features'] [N, 256] (squeezed like the reference,
         stgcn.py:117) and batch['yhat'] [N, num_class]."""
-        x = batch["output"]
+        x = batch[self._input_key]
         N, V, C, T = x.shape
-        assert (V, C) == (self.A.shape[1], self.in_channels), f"batch['output'] {tuple(x.shape)} does not match the model"
+        assert (V, C) == (self.A.shape[1], self.in_channels), f"batch['{self._input_key}'] {tuple(x.shape)} does not match the model"
         eng, dev = self._get_engine(N, T)
         xc = x.to(device=dev, dtype=torch.float32).contiguous()
         feats = torch.empty(N, 256, device=dev)
@@ -140,7 +159,7 @@ class STGCN(nn.Module):
             if eng is not None:
                 torch.cuda.synchronize(dev)
                 eng.close()
-            eng = _lib.StgcnEngine(C, self.num_class, 1, V, T, max(N, eng.max_batch if eng and eng.shape == (V, C, T) else 0), dev.index or 0, options=self.engine_options)
+            eng = _lib.StgcnEngine(C, self.num_class, 1, V, T, max(N, eng.max_batch if eng and eng.shape == (V, C, T) else 0), dev.index or 0, options=self.engine_options, blocks=self.blocks)
             lo, hi = person * V * C, (person + 1) * V * C               # BatchNorm1d channel (m V + v) C + c (stgcn.py:96-101): person m's slice
             for k, v in self.state_dict().items():
                 if k.endswith("num_batches_tracked"):
@@ -174,3 +193,18 @@ class STGCN(nn.Module):
         for label, pred in zip(batch["y"], yhat):
             confusion[label][pred] += 1
         return torch.trace(confusion) / torch.sum(confusion)
+
+
+class UnconstrainedSTGCN(STGCN):
+    """Mirror of the extractor of the reference's UNCONSTRAINED evaluation, `eval/unconstrained/models/stgcn.py::STGCN` (:11-114; built by
+    eval/unconstrained/evaluate.py:21-32): one person, six st_gcn blocks (:52-63), input batch['x'] [N, V, C, T] (:83), output batch['features']
+    (squeezed, :108) and batch['yhat'] (:113). Layout 'openpose' is that project's 15-node graph (stgcnutils/graph.py:46-48); as for the other
+    recogniser the adjacency comes from the checkpoint's `A`. The same engine runs it: rgn_stgcn_set_blocks with the six-block plan on a graph the
+    engine pads to 16 vertices."""
+    _input_key = "x"
+    LAYOUT_NODES = {"openpose": 15, "smpl": 24, "smpl_noglobal": 23, "ntu-rgb+d": 25, "ntu_edge": 24}      # eval/unconstrained/models/stgcnutils/graph.py:46-92
+
+    def __init__(self, in_channels, num_class, graph_args=None, edge_importance_weighting=True, device=None, num_nodes=None, **kwargs):
+        layout = (graph_args or {}).get("layout", "openpose")
+        super().__init__(in_channels, num_class, 1, graph_args=graph_args, edge_importance_weighting=edge_importance_weighting, device=device,
+                         num_nodes=num_nodes or self.LAYOUT_NODES[layout], blocks=SIX_BLOCKS, **kwargs)

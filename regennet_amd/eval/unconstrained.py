@@ -5,6 +5,11 @@ multimodality) mean nothing; these are what the reference reports instead.
 
     python -m regennet_amd.eval.unconstrained --synthetic --num_samples 64
     python -m regennet_amd.eval.unconstrained --gen_features gen.npy --gt_features gt.npy [--fast] [--kid_subsets 100] [--kid_subset_size 1000]
+    python -m regennet_amd.eval.unconstrained --gen_motions gen.npy --gt_motions gt.npy --recogniser CKPT      # motions [N, V, 3, T] through the extractor
+    python -m regennet_amd.eval.unconstrained --synthetic_motions --num_samples 64                             # seeded motions, synthetic six-block checkpoint
+
+From motions on (`evaluate_unconstrained_motions`, evaluate.py:57-83) the features come from the reference's six-block ST-GCN on its 15-node graph
+(`regennet_amd.eval.stgcn.UnconstrainedSTGCN`), on the device like everything behind it.
 
 The features stay on the device. KID runs all subsets in ONE call of rgn_poly_mmd (no kernel matrix is ever stored; the reference pulls the
 features to the host for 300 sklearn kernel matrices), precision / recall in rgn_knn_radius + rgn_manifold_hits (the reference: a Python double
@@ -173,6 +178,74 @@ def evaluate_unconstrained_metrics(generated_features, real_features, fast=False
             "precision": precision, "recall": recall}
 
 
+def initialize_model(device, modelpath, num_classes=12):
+    """evaluate.py:21-32: the six-block extractor on the 15-node 'openpose' graph, 3 input channels, 12 classes, with the checkpoint at `modelpath`
+    (a state_dict, or an already loaded dict of tensors / arrays)."""
+    from .stgcn import UnconstrainedSTGCN
+    model = UnconstrainedSTGCN(in_channels=3, num_class=num_classes, graph_args={"layout": "openpose", "strategy": "spatial"},
+                               edge_importance_weighting=True, device=device)
+    state_dict = modelpath if isinstance(modelpath, dict) else torch.load(modelpath, map_location="cpu")
+    model.load_state_dict({k: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v for k, v in state_dict.items()})
+    model = model.to(device)
+    model.eval()
+    return model
+
+
+def compute_features(model, iterator, device):
+    """evaluate.py:41-54: (activations [N, 256], predictions [N, num_class]) of the batches [n, V, C, T] of `iterator`, on the device."""
+    activations, predictions = [], []
+    with torch.no_grad():
+        for batch in iterator:
+            batch_for_model = {"x": torch.as_tensor(batch).to(device).float()}
+            model(batch_for_model)
+            activations.append(batch_for_model["features"].reshape(-1, 256).clone())     # (a batch of one is squeezed to [256] there and would not concatenate)
+            predictions.append(batch_for_model["yhat"].clone())
+    return torch.cat(activations, dim=0), torch.cat(predictions, dim=0)
+
+
+def _batches(motions, batch_size):
+    return (motions[lo:lo + batch_size] for lo in range(0, len(motions), batch_size))
+
+
+def motion_features(motions, model, root_joint=8, batch_size=64, num_nodes=None):
+    """evaluate.py:65-70 / :76-81 for one set: motions [N, >= V, C, T] cut to the model's V vertices (the dataset carries a 16th joint, :76), centred on
+    the root joint per frame (:65, :77; not in place), through the extractor in batches. -> (features, predictions) on the model's device."""
+    dev = model.A.device
+    V = int(num_nodes or model.A.shape[1])
+    m = torch.as_tensor(np.asarray(motions) if not isinstance(motions, torch.Tensor) else motions).to(device=dev, dtype=torch.float32)
+    if m.dim() != 4 or m.shape[1] < V:
+        raise ValueError(f"motions [N, >= {V}, C, T] expected, got {tuple(m.shape)}")
+    if not 0 <= root_joint < V:
+        raise ValueError(f"root_joint {root_joint} outside the model's {V} vertices")
+    m = m[:, :V]
+    m = m - m[:, root_joint:root_joint + 1]
+    return compute_features(model, _batches(m, batch_size), dev)
+
+
+def evaluate_unconstrained_motions(generated_motions, dataset_motions, model, fast=False, root_joint=8, batch_size=64, kid_subsets=100,
+                                   kid_subset_size=1000, log=None):
+    """evaluate.py:57-110 from motions on: both sets centred on the root joint per frame (:65, :77), the dataset cut to the model's vertex count
+    (:76), features in batches of `batch_size` (:67, :78), then `evaluate_unconstrained_metrics` (unchanged) on the two feature sets."""
+    gen, _ = motion_features(generated_motions, model, root_joint, batch_size)
+    real, _ = motion_features(dataset_motions, model, root_joint, batch_size)
+    return evaluate_unconstrained_metrics(gen, real, fast=fast, kid_subsets=kid_subsets, kid_subset_size=kid_subset_size, log=log)
+
+
+def synthetic_motions(n, seed, V=15, T=60):
+    """Seeded stand-ins for joint positions [n, V, 3, T]: a smooth random walk per joint around a fixed rest pose."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    rest = np.random.Generator(np.random.PCG64(4711)).standard_normal((1, V, 3, 1))
+    return (rest + 0.1 * np.cumsum(rng.standard_normal((n, V, 3, T)), axis=3)).astype(np.float32)
+
+
+def synthetic_recogniser(dev, V=15, seed=0):
+    """A synthetic six-block checkpoint on a synthetic V-node tree, loaded as `initialize_model` loads a real one."""
+    from .. import synth
+    from .stgcn import SIX_BLOCKS
+    sd = synth.make_stgcn_state_dict(synth.make_stgcn_graph(V), num_class=12, in_channels=3, num_person=1, seed=seed, blocks=SIX_BLOCKS)
+    return initialize_model(dev, sd)
+
+
 def _synthetic_features(args, dev):
     """--synthetic: sample an unconstrained model twice (the second seed stands in for the ground truth) and pass both sets, concatenated with
     their actors as eval/a2m/stgcn_eval.py:71 does, through a synthetic recogniser."""
@@ -204,6 +277,11 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="sample a synthetic unconstrained model; a second seed is the 'ground truth'")
     ap.add_argument("--gen_features", help="FILE.npy [N, D]: features of the generated motions")
     ap.add_argument("--gt_features", help="FILE.npy [N, D]: features of the dataset's motions")
+    ap.add_argument("--gen_motions", help="FILE.npy [N, V, 3, T]: generated motions (joint positions), with --gt_motions and --recogniser")
+    ap.add_argument("--gt_motions", help="FILE.npy [N, >= V, 3, T]: the dataset's motions (cut to the recogniser's V joints)")
+    ap.add_argument("--recogniser", help="checkpoint (state_dict) of the six-block ST-GCN extractor (evaluate.py:21-32)")
+    ap.add_argument("--synthetic_motions", action="store_true", help="seeded motions (a second seed is the 'ground truth') through a synthetic six-block checkpoint")
+    ap.add_argument("--root_joint", type=int, default=8, help="the joint every frame is centred on (evaluate.py:65)")
     ap.add_argument("--num_samples", type=int, default=64)
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--timestep_respacing", default="ddim5")
@@ -213,15 +291,31 @@ def main(argv=None):
     ap.add_argument("--kid_subset_size", type=int, default=0, help="default: 1000 (kid.py), cut to the smaller feature set")
     ap.add_argument("--output_dir", default=".")
     args = ap.parse_args(argv)
+    USAGE = ("--synthetic, --synthetic_motions, --gen_features A.npy with --gt_features B.npy, or --gen_motions A.npy with --gt_motions B.npy "
+             "and --recogniser CKPT")
+    motions, features = (args.gen_motions, args.gt_motions, args.recogniser), (args.gen_features, args.gt_features)
+    modes = [bool(args.synthetic), bool(args.synthetic_motions), any(features), any(motions)]
+    if sum(modes) > 1:
+        raise SystemExit("one source at a time: " + USAGE)
+    if any(motions) and not all(motions):
+        raise SystemExit("--gen_motions, --gt_motions and --recogniser belong together: " + USAGE)
+    if any(features) and not all(features):
+        raise SystemExit("--gen_features and --gt_features belong together: " + USAGE)
+    if sum(modes) == 0:
+        raise SystemExit(USAGE)
     if not torch.cuda.is_available():
         raise SystemExit("the unconstrained metrics run on an AMD GPU only (no CPU fallback)")
     dev = torch.device("cuda:0")
     if args.synthetic:
         gen, gt = _synthetic_features(args, dev)
-    elif args.gen_features and args.gt_features:
-        gen, gt = (torch.from_numpy(np.asarray(np.load(p), dtype=np.float32)).to(dev) for p in (args.gen_features, args.gt_features))
+    elif args.synthetic_motions:
+        rec = synthetic_recogniser(dev)
+        gen, gt = (motion_features(synthetic_motions(args.num_samples, s), rec, args.root_joint, args.batch_size)[0] for s in (args.seed, args.seed + 1))
+    elif all(motions):
+        rec = initialize_model(dev, args.recogniser)
+        gen, gt = (motion_features(np.load(p, allow_pickle=True), rec, args.root_joint, args.batch_size)[0] for p in (args.gen_motions, args.gt_motions))
     else:
-        raise SystemExit("--synthetic, or --gen_features A.npy with --gt_features B.npy")
+        gen, gt = (torch.from_numpy(np.asarray(np.load(p), dtype=np.float32)).to(dev) for p in (args.gen_features, args.gt_features))
     np.random.seed(args.seed)
     size = args.kid_subset_size or min(1000, len(gen), len(gt))
     print(f"{len(gen)} generated and {len(gt)} dataset features of {gen.shape[1]} dimensions; KID over {args.kid_subsets} subsets of {size}")

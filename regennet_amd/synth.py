@@ -272,10 +272,12 @@ def make_stgcn_graph(V=56):
     return A
 
 
-def make_stgcn_state_dict(A, num_class=26, in_channels=12, num_person=2, seed=0):
+def make_stgcn_state_dict(A, num_class=26, in_channels=12, num_person=2, seed=0, blocks=None):
     """Synthetic checkpoint of the ST-GCN evaluator with the reference's state_dict keys
     (eval/a2m/recognition/models/stgcn.py:44-73,183-219; stgcnutils/tgcn.py:51-59). `A` [K, V, V] is the adjacency buffer
-    the reference registers (stgcn.py:42); BatchNorm running statistics are non-trivial so that folding them is exercised."""
+    the reference registers (stgcn.py:42); BatchNorm running statistics are non-trivial so that folding them is exercised.
+    blocks: [(out_channels, stride), ...], None = the ten blocks of stgcn.py:51-62 (the draws of the default do not change); the six of
+    eval/unconstrained/models/stgcn.py:52-63 are regennet_amd.eval.stgcn.SIX_BLOCKS."""
     rng = np.random.Generator(np.random.PCG64(seed))
     K, V = int(A.shape[0]), int(A.shape[1])
     sd = {"A": np.asarray(A, dtype=np.float32)}
@@ -294,6 +296,8 @@ def make_stgcn_state_dict(A, num_class=26, in_channels=12, num_person=2, seed=0)
     bn("data_bn", in_channels * V)
     chans = [(in_channels // num_person, 64, 1), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 128, 1),
              (128, 256, 2), (256, 256, 1), (256, 256, 1)]
+    if blocks is not None:
+        chans = [(in_channels // num_person if i == 0 else blocks[i - 1][0], co, st) for i, (co, st) in enumerate(blocks)]
     for i, (ci, co, stride) in enumerate(chans):
         p = f"st_gcn_networks.{i}."
         conv(p + "gcn.conv", co * K, ci, 1, gain=1.5)
