@@ -594,6 +594,50 @@ RGN_API int rgn_stgcn_set_option(rgn_stgcn_handle h, const char* key, int32_t va
  * features_dev fp32 [N, 256] (batch['features'], nullable) and yhat_dev fp32 [N, num_class] (batch['yhat'], nullable) */
 RGN_API int rgn_stgcn_forward(rgn_stgcn_handle h, int32_t N, const float* output_dev, float* features_dev, float* yhat_dev, void* stream);
 
+/* ---- The action2motion evaluation's recogniser: a GRU action classifier ----
+ * Replaces eval/a2m/action2motion/models.py:6-61 (MotionDiscriminator: nn.GRU(input_size, hidden_size, hidden_layer) -> Linear(hidden_size, 30) -> tanh
+ * -> Linear(30, output_size); MotionDiscriminatorForFID stops behind the tanh) as eval/a2m/action2motion/evaluate.py:18-30 and accuracy.py:4-14 use it:
+ * the features feed FID / diversity / multimodality, the logits the accuracy. Checkpoint keys are the reference's state_dict names:
+ * 'recurrent.weight_ih_l<k>' [3 H, input_size or H], 'recurrent.weight_hh_l<k>' [3 H, H], 'recurrent.bias_ih_l<k>', 'recurrent.bias_hh_l<k>' [3 H]
+ * (gate order r, z, n), 'linear1.weight' [lin1_size, H], 'linear1.bias', 'linear2.weight' [output_size, lin1_size], 'linear2.bias'.
+ * Arithmetic: fp32 throughout - every product exact (the fp32-input MFMA v_mfma_f32_16x16x4_f32 for the gates, fma chains for the head), sums in an
+ * order the geometry alone fixes, no atomics: a sequence's outputs are the same bits whatever batch it sits in and on every run. */
+typedef struct rgn_gru_ctx* rgn_gru_handle;
+typedef struct {
+    int32_t input_size;     /* njoints * nfeats of batch['output_xyz'] (72 for HumanAct12, evaluate.py:11; models.py:22-23) */
+    int32_t hidden_size;    /* 128 (models.py:69) */
+    int32_t num_layers;     /* 2 (models.py:69) */
+    int32_t lin1_size;      /* 30 (models.py:16) */
+    int32_t output_size;    /* num_classes (models.py:17) */
+    int32_t device;         /* HIP device ordinal */
+} rgn_gru_config;
+/* MotionDiscriminator.__init__ (models.py:7-17). The geometry is checked before the device is touched - RGN_ERR_UNSUPPORTED with the reason in
+ * rgn_gru_last_error(NULL) unless hidden_size is a multiple of 32 in [32, 256], 1 <= num_layers <= 4, 1 <= input_size <= 1024 (padded to the MFMA's k
+ * granule inside the engine), 1 <= lin1_size <= 64, 1 <= output_size <= 1024 - then the device: RGN_ERR_HIP, "no HIP device". */
+RGN_API int rgn_gru_create(const rgn_gru_config* cfg, rgn_gru_handle* out);
+RGN_API int rgn_gru_destroy(rgn_gru_handle h);
+RGN_API const char* rgn_gru_last_error(rgn_gru_handle h);    /* NULL: the calling thread's last failed call without a handle */
+/* classifier.load_state_dict(model["model"]) (models.py:69, :77), one host fp32 tensor per call: an unknown key, or a key given twice, is
+ * RGN_ERR_BAD_KEY; a shape other than the configuration's RGN_ERR_BAD_SHAPE (both shapes in the text). */
+RGN_API int rgn_gru_load_weight(rgn_gru_handle h, const char* ref_key, const float* host, const int64_t* shape, int32_t ndim);
+/* Every key seen once (RGN_ERR_MISSING_KEY names the absent ones); the recurrent weights are packed in MFMA operand order, b_ih + b_hh folded for the
+ * r and z gates (kept apart for n, where r multiplies W_hn h + b_hn), and everything is uploaded. */
+RGN_API int rgn_gru_finalize(rgn_gru_handle h);
+/* MotionDiscriminator.forward / MotionDiscriminatorForFID.forward (models.py:20-38 / :45-61) for N sequences of T frames in one launch:
+ *   x_dev       fp32 [N, input_size, T]: the reference's [bs, njoints, nfeats, T] as it lies, frames innermost (no permuted copy is made, :23-24)
+ *   lengths_dev int64 [N], 1 <= lengths[n] <= T: the state behind frame lengths[n] - 1 is selected (:31); frames at or behind a sequence's length
+ *               are never looked at (they may be NaN), and a workgroup stops at the longest length of its 16 sequences. Lengths are read on the device
+ *               only: one outside [1, T] is CLAMPED into it - nothing outside x is ever read - and flagged (rgn_gru_length_status)
+ *   h0_dev      fp32 [num_layers, N, hidden_size]: hidden_unit (:25-27; the caller draws it)
+ *   features_dev fp32 [N, lin1_size] = tanh(linear1(out)) (:34-35), nullable; logits_dev fp32 [N, output_size] = linear2(features) (:37), nullable
+ * The arguments are checked before the handle or the device is touched - RGN_ERR_INVALID_ARG for a null x / lengths / h0, both outputs null, N < 1,
+ * T outside [1, 4096] - with text in rgn_gru_last_error(h), or rgn_gru_last_error(NULL) when h is NULL (which is itself RGN_ERR_INVALID_ARG once the
+ * other arguments have passed). The call enqueues on `stream`, allocates nothing and can be captured into a graph. */
+RGN_API int rgn_gru_forward(rgn_gru_handle h, int32_t N, int32_t T, const float* x_dev, const int64_t* lengths_dev, const float* h0_dev,
+                            float* features_dev /*nullable*/, float* logits_dev /*nullable*/, void* stream);
+/* *clamped = 1 when a forward since the last query (or since finalize) met a length outside [1, T], else 0; synchronises the device and clears the flag. */
+RGN_API int rgn_gru_length_status(rgn_gru_handle h, int32_t* clamped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,22 @@ SYMBOLS.update({
     "rgn_manifold_hits": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
 })
 
+
+class RgnGruConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_size", "hidden_size", "num_layers", "lin1_size", "output_size", "device")]
+
+
+# the GRU action classifier of the action2motion evaluation (rgn_gru.hip)
+SYMBOLS.update({
+    "rgn_gru_create": (C.c_int, [C.POINTER(RgnGruConfig), C.POINTER(_vp)]),
+    "rgn_gru_destroy": (C.c_int, [_vp]),
+    "rgn_gru_last_error": (C.c_char_p, [_vp]),
+    "rgn_gru_load_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i32]),
+    "rgn_gru_finalize": (C.c_int, [_vp]),
+    "rgn_gru_forward": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgn_gru_length_status": (C.c_int, [_vp, C.POINTER(_i32)]),
+})
+
 _lib = None
 
 
@@ -494,6 +510,54 @@ class StgcnEngine:
 
     def forward(self, N, output, features, yhat, stream):
         self._ck(self.lib.rgn_stgcn_forward(self.h, int(N), _ptr(output), _ptr(features), _ptr(yhat), C.c_void_p(stream)))
+
+
+class GruEngine:
+    """Owns one rgn_gru_handle (the GRU action classifier of the action2motion evaluation, include/regennet_hip.h)."""
+
+    def __init__(self, input_size, hidden_size, num_layers, lin1_size, output_size, device_index):
+        self.lib = load()
+        self.input_size, self.hidden_size, self.num_layers = int(input_size), int(hidden_size), int(num_layers)
+        self.lin1_size, self.output_size = int(lin1_size), int(output_size)
+        cfg = RgnGruConfig(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers, lin1_size=lin1_size,
+                           output_size=output_size, device=int(device_index))
+        h = C.c_void_p()
+        code = self.lib.rgn_gru_create(C.byref(cfg), C.byref(h))
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_gru_last_error(None) or b"").decode())
+        self.h = h
+
+    def _ck(self, code):
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_gru_last_error(self.h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rgn_gru_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load_weight(self, key, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        shape = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+        self._ck(self.lib.rgn_gru_load_weight(self.h, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
+
+    def finalize(self):
+        self._ck(self.lib.rgn_gru_finalize(self.h))
+
+    def forward(self, N, T, x, lengths, h0, features, logits, stream):
+        self._ck(self.lib.rgn_gru_forward(self.h, int(N), int(T), _ptr(x), _ptr(lengths), _ptr(h0), _ptr(features), _ptr(logits), C.c_void_p(stream)))
+
+    def lengths_clamped(self):
+        """True when a forward since the last query met a length outside [1, T] (it was clamped). Synchronises the device."""
+        v = C.c_int32(0)
+        self._ck(self.lib.rgn_gru_length_status(self.h, C.byref(v)))
+        return bool(v.value)
 
 
 def _host(a, dtype):

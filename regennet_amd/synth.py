@@ -312,6 +312,51 @@ def make_stgcn_state_dict(A, num_class=26, in_channels=12, num_person=2, seed=0,
     return sd
 
 
+def make_gru_state_dict(input_size=72, hidden=128, layers=2, lin1=30, num_classes=12, seed=0, scale=1.0):
+    """Synthetic checkpoint of the GRU action classifier with the reference's state_dict keys (eval/a2m/action2motion/models.py:15-17: nn.GRU ->
+    Linear(hidden, 30) -> Linear(30, classes)): every tensor uniform in PyTorch's default init range (+-1/sqrt(hidden) for the GRU, +-1/sqrt(fan_in)
+    for the Linears) times `scale` (scale > 1 drives the gates into saturation)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd = {}
+
+    def uni(shape, bound):
+        return (rng.uniform(-bound, bound, shape) * scale).astype(np.float32)
+
+    kg = 1.0 / np.sqrt(hidden)
+    for l in range(layers):
+        sd[f"recurrent.weight_ih_l{l}"] = uni((3 * hidden, input_size if l == 0 else hidden), kg)
+        sd[f"recurrent.weight_hh_l{l}"] = uni((3 * hidden, hidden), kg)
+        sd[f"recurrent.bias_ih_l{l}"] = uni((3 * hidden,), kg)
+        sd[f"recurrent.bias_hh_l{l}"] = uni((3 * hidden,), kg)
+    sd["linear1.weight"] = uni((lin1, hidden), kg)
+    sd["linear1.bias"] = uni((lin1,), kg)
+    sd["linear2.weight"] = uni((num_classes, lin1), 1.0 / np.sqrt(lin1))
+    sd["linear2.bias"] = uni((num_classes,), 1.0 / np.sqrt(lin1))
+    return sd
+
+
+def make_gru_inputs(N, input_size, T, hidden=128, layers=2, seed=0, lengths="mixed", nfeats=3):
+    """Inputs of the GRU classifier: (x [N, input_size / nfeats, nfeats, T] like batch['output_xyz'] (nfeats falls back to 1 when it does not divide
+    input_size), lengths int64 [N], hidden_unit [layers, N, hidden]). lengths: "full" (all T), "mixed" (uniform in [1, T], row 0 = 1 and row 1 = T
+    where there are such rows) or an explicit list."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    if input_size % nfeats:
+        nfeats = 1
+    x = rng.standard_normal((N, input_size // nfeats, nfeats, T)).astype(np.float32)
+    h0 = rng.standard_normal((layers, N, hidden)).astype(np.float32)
+    if isinstance(lengths, str):
+        if lengths == "full":
+            ln = np.full(N, T, np.int64)
+        else:
+            ln = rng.integers(1, T + 1, N).astype(np.int64)
+            ln[0] = 1
+            if N > 1:
+                ln[1] = T
+    else:
+        ln = np.asarray(lengths, np.int64)
+    return x, ln, h0
+
+
 def build_model(cfg, sd, resp="", precision=None, device="cuda:0", noise_schedule="cosine", sigma_small=True, x3_tail=None, engine_options=None, f16_steps=None):
     """(model, diffusion) from regennet_amd for a synth config + checkpoint dict (reference key names): the same
     constructor calls the reference factory makes (utils/model_util.py:66-117), for tests, bench.py and tools.
