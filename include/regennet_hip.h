@@ -638,6 +638,74 @@ RGN_API int rgn_gru_forward(rgn_gru_handle h, int32_t N, int32_t T, const float*
 /* *clamped = 1 when a forward since the last query (or since finalize) met a length outside [1, T], else 0; synchronises the device and clears the flag. */
 RGN_API int rgn_gru_length_status(rgn_gru_handle h, int32_t* clamped);
 
+/* ---- The text-to-motion evaluation: movement encoder, bidirectional-GRU co-embedding encoders, matching ----
+ * Replaces data_loaders/humanml/networks/modules.py:79-98 (MovementConvEncoder), :311-350 (TextEncoderBiGRUCo) and :353-386 (MotionEncoderBiGRUCo) as
+ * data_loaders/humanml/networks/evaluator_wrapper.py:121-187 (EvaluatorMDMWrapper) drives them, and the distance / top-k part of
+ * data_loaders/humanml/utils/metrics.py:6-56 as eval/eval_humanml.py:20-71 uses it. Checkpoint keys are the reference's state_dict names behind the
+ * sub-model's prefix ('movement_encoder.', 'text_encoder.', 'motion_encoder.'): 'movement_encoder.main.0.weight' [Hm, dim_pose - 4, 4],
+ * 'motion_encoder.gru.weight_hh_l0_reverse' [3 H, H], 'text_encoder.hidden' [2, 1, Ht], 'motion_encoder.output_net.1.weight' [H] (the LayerNorm) ...
+ * Arithmetic: fp32 throughout, products exact (v_mfma_f32_16x16x4_f32, fma chains), sums in an order the geometry alone fixes, no atomics: a sequence's
+ * outputs are the same bits whatever batch it sits in, at whatever place, and on every run. */
+typedef struct rgn_t2m_ctx* rgn_t2m_handle;
+typedef struct {
+    int32_t device;            /* HIP device ordinal */
+    int32_t dim_pose;          /* 263 (humanml) or 251 (kit): evaluator_wrapper.py:134; the encoder reads the first dim_pose - 4 (:165) */
+    int32_t movement_hidden;   /* 512 (:135) */
+    int32_t movement_latent;   /* 512 (:136) */
+    int32_t motion_hidden;     /* 1024 (:130) */
+    int32_t dim_word;          /* 300 (:127) */
+    int32_t dim_pos_ohot;      /* 15 = len(POS_enumerator) (:129) */
+    int32_t text_hidden;       /* 512 (:132) */
+    int32_t coemb;             /* 512 (:133) */
+    int32_t unit_length;       /* 4 (:138) */
+} rgn_t2m_config;
+/* build_evaluators (evaluator_wrapper.py:95-106). The geometry is checked before the device is touched - RGN_ERR_UNSUPPORTED with the reason in
+ * rgn_t2m_last_error(NULL) unless the four hidden sizes are multiples of 64 in [64, 1024], 5 <= dim_pose <= 1024, dim_word and coemb multiples of 4 in
+ * [4, 1024], 1 <= dim_pos_ohot <= 1024, unit_length == 4 - then the device: RGN_ERR_HIP, "no HIP device". */
+RGN_API int rgn_t2m_create(const rgn_t2m_config* cfg, rgn_t2m_handle* out);
+RGN_API int rgn_t2m_destroy(rgn_t2m_handle h);
+RGN_API const char* rgn_t2m_last_error(rgn_t2m_handle h);    /* NULL: the calling thread's last failed call without a handle */
+/* load_state_dict(checkpoint['movement_encoder' | 'text_encoder' | 'motion_encoder']) (evaluator_wrapper.py:114-116), one host fp32 tensor per call:
+ * an unknown key, or a key given twice, is RGN_ERR_BAD_KEY; a shape other than the configuration's RGN_ERR_BAD_SHAPE (both shapes in the text). */
+RGN_API int rgn_t2m_load_weight(rgn_t2m_handle h, const char* ref_key, const float* host, const int64_t* shape, int32_t ndim);
+/* Every key seen once (RGN_ERR_MISSING_KEY names the absent ones); weights are packed in MFMA operand order and uploaded. */
+RGN_API int rgn_t2m_finalize(rgn_t2m_handle h);
+/* Bytes of device workspace that serve any of the calls below at up to N sequences, T frames and Lw words (monotone in each). RGN_ERR_INVALID_ARG for
+ * N outside [1, 2^19], T outside [4, 4096], Lw outside [1, 256]. SIZE: every stage's rows are kept, and the hoisted gate inputs [N, T2, 2, 3 H] fp32
+ * dominate - at the real geometry 1.9 MB per 196-frame motion, of which the gate inputs are 1.2 MB: 59 MB at N = 32, 1.9 GB at N = 1024. A caller
+ * short of memory evaluates in batches (the harness's are 32). */
+RGN_API int rgn_t2m_workspace(rgn_t2m_handle h, int32_t N, int32_t T, int32_t Lw, size_t* bytes);
+/* MovementConvEncoder.forward (modules.py:94-98; dropout is off in eval mode): x_dev fp32, frame t of motion n at x_dev + (n T + t) in_stride, the first
+ * dim_pose - 4 values read -> mov_dev fp32 [N, T2, movement_latent], T1 = (T-2)/2+1, T2 = (T1-2)/2+1. m_lens_dev int64 [N] nullable: with it only
+ * movement frames j < m_lens[n] / unit_length (clamped into [1, T2] and flagged) are computed and stored, and input frames at or behind
+ * 4 (m_lens[n] / 4) + 3 are never read (they may be NaN); without it every frame. */
+RGN_API int rgn_t2m_movements(rgn_t2m_handle h, int32_t N, int32_t T, int32_t in_stride, const float* x_dev, const int64_t* m_lens_dev /*nullable*/,
+                              float* mov_dev, void* work, size_t work_bytes, void* stream);
+/* MotionEncoderBiGRUCo.forward (modules.py:373-386): mov_dev fp32 [N, T2, movement_latent], lens_dev int64 [N] in [1, T2] (movement frames; clamped and
+ * flagged otherwise; frames at or behind a length are never read) -> emb_dev fp32 [N, coemb]. */
+RGN_API int rgn_t2m_encode_movements(rgn_t2m_handle h, int32_t N, int32_t T2, const float* mov_dev, const int64_t* lens_dev, float* emb_dev, void* work,
+                                     size_t work_bytes, void* stream);
+/* EvaluatorMDMWrapper.get_motion_embeddings (evaluator_wrapper.py:175-187) without its sort: motions_dev fp32 [N, T, dim_pose], m_lens_dev int64 [N] in
+ * frames -> emb_dev fp32 [N, coemb], row n for motion n. The two calls above in one; the movements stay in the workspace. */
+RGN_API int rgn_t2m_motion_embeddings(rgn_t2m_handle h, int32_t N, int32_t T, const float* motions_dev, const int64_t* m_lens_dev, float* emb_dev,
+                                      void* work, size_t work_bytes, void* stream);
+/* TextEncoderBiGRUCo.forward (modules.py:335-350): word_embs_dev fp32 [N, Lw, dim_word], pos_ohot_dev fp32 [N, Lw, dim_pos_ohot], cap_lens_dev int64 [N]
+ * in [1, Lw] (clamped and flagged otherwise; word rows at or behind a length are never read) -> emb_dev fp32 [N, coemb]. Rows need not be sorted by
+ * length (pack_padded_sequence demands it; the kernels are order-free).
+ * All four calls check their arguments before the handle or the device is touched (RGN_ERR_INVALID_ARG, text in rgn_t2m_last_error(h), or (NULL) when
+ * h is NULL), enqueue on `stream`, allocate nothing and can be captured into a graph. */
+RGN_API int rgn_t2m_text_embeddings(rgn_t2m_handle h, int32_t N, int32_t Lw, const float* word_embs_dev, const float* pos_ohot_dev,
+                                    const int64_t* cap_lens_dev, float* emb_dev, void* work, size_t work_bytes, void* stream);
+/* *clamped = 1 when a call since the last query (or since finalize) met a length outside its range, else 0; synchronises the device, clears the flag. */
+RGN_API int rgn_t2m_length_status(rgn_t2m_handle h, int32_t* clamped);
+/* euclidean_distance_matrix + argsort + calculate_top_k (metrics.py:6-44) and calculate_matching_score (:47-56) on consecutive groups of `group` <= 32
+ * (text, motion) pairs, as eval_humanml.py:36-45 applies them per batch: d[i, j] = || text_i - motion_j || by direct differences in fp32 (not the
+ * reference's -2ab + a^2 + b^2, which cancels); diag_dev fp32 [N] = d[i, i] (the matching-score terms); rank_dev int32 [N] = #{ j in the group :
+ * d[i, j] < d[i, i] }. Top-k hit <=> rank < k. TIES: a motion exactly as far as the true one does not count against it (the reference's argsort breaks
+ * such a tie by position). The last group may be short. D a multiple of 4 in [4, 1024]. Errors in rgn_t2m_last_error(NULL). */
+RGN_API int rgn_t2m_match(int32_t device, const float* text_dev, const float* motion_dev, int32_t N, int32_t D, int32_t group, float* diag_dev,
+                          int32_t* rank_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

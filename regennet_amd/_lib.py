@@ -158,6 +158,29 @@ SYMBOLS.update({
     "rgn_gru_length_status": (C.c_int, [_vp, C.POINTER(_i32)]),
 })
 
+
+
+class RgnT2mConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("device", "dim_pose", "movement_hidden", "movement_latent", "motion_hidden", "dim_word", "dim_pos_ohot",
+                                         "text_hidden", "coemb", "unit_length")]
+
+
+# the text-to-motion evaluation: movement encoder, bi-GRU co-embedding encoders, matching (rgn_t2m.hip)
+SYMBOLS.update({
+    "rgn_t2m_create": (C.c_int, [C.POINTER(RgnT2mConfig), C.POINTER(_vp)]),
+    "rgn_t2m_destroy": (C.c_int, [_vp]),
+    "rgn_t2m_last_error": (C.c_char_p, [_vp]),
+    "rgn_t2m_load_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i32]),
+    "rgn_t2m_finalize": (C.c_int, [_vp]),
+    "rgn_t2m_workspace": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "rgn_t2m_movements": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rgn_t2m_encode_movements": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rgn_t2m_motion_embeddings": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rgn_t2m_text_embeddings": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rgn_t2m_length_status": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "rgn_t2m_match": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+})
+
 _lib = None
 
 
@@ -558,6 +581,106 @@ class GruEngine:
         v = C.c_int32(0)
         self._ck(self.lib.rgn_gru_length_status(self.h, C.byref(v)))
         return bool(v.value)
+
+
+T2M_FIELDS = ("dim_pose", "movement_hidden", "movement_latent", "motion_hidden", "dim_word", "dim_pos_ohot", "text_hidden", "coemb", "unit_length")
+
+
+class T2mEngine:
+    """Owns one rgn_t2m_handle (the text-to-motion evaluator: movement encoder and the two bi-GRU co-embedding encoders, include/regennet_hip.h) and
+    the workspace its calls share, grown on demand."""
+
+    def __init__(self, geometry, device_index):
+        import torch
+        self.lib = load()
+        self.geometry = {k: int(geometry[k]) for k in T2M_FIELDS}
+        self.device = torch.device("cuda", int(device_index))
+        cfg = RgnT2mConfig(device=int(device_index), **self.geometry)
+        h = C.c_void_p()
+        code = self.lib.rgn_t2m_create(C.byref(cfg), C.byref(h))
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_t2m_last_error(None) or b"").decode())
+        self.h = h
+        self._work = None
+
+    def _ck(self, code):
+        if code != RGN_OK:
+            raise RgnError(code, (self.lib.rgn_t2m_last_error(self.h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.rgn_t2m_destroy(self.h)
+            self.h = None
+            self._work = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load_weight(self, key, array):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        shape = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+        self._ck(self.lib.rgn_t2m_load_weight(self.h, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
+
+    def finalize(self):
+        self._ck(self.lib.rgn_t2m_finalize(self.h))
+
+    def workspace_bytes(self, N, T, Lw):
+        v = C.c_size_t(0)
+        self._ck(self.lib.rgn_t2m_workspace(self.h, int(N), int(T), int(Lw), C.byref(v)))
+        return int(v.value)
+
+    def _workspace(self, N, T, Lw):
+        import torch
+        need = self.workspace_bytes(N, T, Lw)
+        if self._work is None or self._work.numel() < need:
+            if self._work is not None:
+                torch.cuda.synchronize(self.device)       # a kernel of an earlier call may still be using the old buffer
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._work
+
+    def movements(self, N, T, in_stride, x, m_lens, out, stream):
+        w = self._workspace(N, T, 1)
+        self._ck(self.lib.rgn_t2m_movements(self.h, int(N), int(T), int(in_stride), _ptr(x), _ptr(m_lens), _ptr(out), _ptr(w), w.numel(), C.c_void_p(stream)))
+
+    def encode_movements(self, N, T2, mov, lens, out, stream):
+        w = self._workspace(N, 4 * T2, 1)
+        self._ck(self.lib.rgn_t2m_encode_movements(self.h, int(N), int(T2), _ptr(mov), _ptr(lens), _ptr(out), _ptr(w), w.numel(), C.c_void_p(stream)))
+
+    def motion_embeddings(self, N, T, motions, m_lens, out, stream):
+        w = self._workspace(N, T, 1)
+        self._ck(self.lib.rgn_t2m_motion_embeddings(self.h, int(N), int(T), _ptr(motions), _ptr(m_lens), _ptr(out), _ptr(w), w.numel(), C.c_void_p(stream)))
+
+    def text_embeddings(self, N, Lw, word_embs, pos_ohot, cap_lens, out, stream):
+        w = self._workspace(N, 4, Lw)
+        self._ck(self.lib.rgn_t2m_text_embeddings(self.h, int(N), int(Lw), _ptr(word_embs), _ptr(pos_ohot), _ptr(cap_lens), _ptr(out), _ptr(w), w.numel(),
+                                                  C.c_void_p(stream)))
+
+    def lengths_clamped(self):
+        """True when a call since the last query met a length outside its range (it was clamped). Synchronises the device."""
+        v = C.c_int32(0)
+        self._ck(self.lib.rgn_t2m_length_status(self.h, C.byref(v)))
+        return bool(v.value)
+
+
+def t2m_match(text, motion, group=32):
+    """(diag fp32 [N], rank int32 [N]) of rgn_t2m_match for device tensors text, motion [N, D]: the distance of every true pair and the number of
+    motions of its group of `group` strictly nearer to the text. Top-k hit <=> rank < k."""
+    import torch
+    lib = load()
+    N, D = text.shape
+    if motion.shape != text.shape:
+        raise ValueError(f"text {tuple(text.shape)} and motion {tuple(motion.shape)} differ")
+    text, motion = text.float().contiguous(), motion.float().contiguous()
+    diag = torch.empty(N, dtype=torch.float32, device=text.device)
+    rank = torch.empty(N, dtype=torch.int32, device=text.device)
+    code = lib.rgn_t2m_match(text.device.index or 0, _ptr(text), _ptr(motion), int(N), int(D), int(group), _ptr(diag), _ptr(rank),
+                             C.c_void_p(torch.cuda.current_stream(text.device).cuda_stream))
+    if code != RGN_OK:
+        raise RgnError(code, (lib.rgn_t2m_last_error(None) or b"").decode())
+    return diag, rank
 
 
 def _host(a, dtype):

@@ -3,6 +3,7 @@ from .fid import calculate_activation_statistics, calculate_fid, calculate_frech
 from .metrics import Evaluation, calculate_accuracy, calculate_diversity_multimodality  # noqa: F401
 from .stgcn import STGCN, UnconstrainedSTGCN  # noqa: F401
 from .gru import MotionDiscriminator, MotionDiscriminatorForFID, load_classifier, load_classifier_for_fid  # noqa: F401
+from .t2m import EvaluatorMDMWrapper, MotionEncoderBiGRUCo, MovementConvEncoder, TextEncoderBiGRUCo  # noqa: F401
 
 _A2M = ("A2MEvaluation", "A2MLoader", "calculate_accuracy_a2m")
 

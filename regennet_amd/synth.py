@@ -357,6 +357,69 @@ def make_gru_inputs(N, input_size, T, hidden=128, layers=2, seed=0, lengths="mix
     return x, ln, h0
 
 
+def make_t2m_state_dicts(dim_pose=263, movement_hidden=512, movement_latent=512, motion_hidden=1024, dim_word=300, dim_pos_ohot=15, text_hidden=512,
+                         coemb=512, seed=0, scale=1.0, out_scale=1.0):
+    """Synthetic checkpoint of the text-to-motion evaluator, shaped like the reference's finest.tar: {'movement_encoder': {...}, 'text_encoder': {...},
+    'motion_encoder': {...}} with the state_dict keys of data_loaders/humanml/networks/modules.py (MovementConvEncoder, TextEncoderBiGRUCo,
+    MotionEncoderBiGRUCo). Tensors are uniform in PyTorch's default init range times `scale` (scale > 1 drives the gates into saturation); `hidden` is
+    normal; the LayerNorm's affine is near (1, 0); the last Linear of each head takes `out_scale` instead, so the embeddings keep their size."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+
+    def uni(shape, fan_in, sc=None):
+        b = 1.0 / np.sqrt(fan_in)
+        return (rng.uniform(-b, b, shape) * (scale if sc is None else sc)).astype(np.float32)
+
+    C = dim_pose - 4
+    mov = {"main.0.weight": uni((movement_hidden, C, 4), 4 * C), "main.0.bias": uni((movement_hidden,), 4 * C),
+           "main.3.weight": uni((movement_latent, movement_hidden, 4), 4 * movement_hidden), "main.3.bias": uni((movement_latent,), 4 * movement_hidden),
+           "out_net.weight": uni((movement_latent, movement_latent), movement_latent), "out_net.bias": uni((movement_latent,), movement_latent)}
+
+    def bigru(H, sd):
+        for sfx in ("_l0", "_l0_reverse"):
+            sd["gru.weight_ih" + sfx] = uni((3 * H, H), H)
+            sd["gru.weight_hh" + sfx] = uni((3 * H, H), H)
+            sd["gru.bias_ih" + sfx] = uni((3 * H,), H)
+            sd["gru.bias_hh" + sfx] = uni((3 * H,), H)
+        sd["output_net.0.weight"] = uni((H, 2 * H), 2 * H)
+        sd["output_net.0.bias"] = uni((H,), 2 * H)
+        sd["output_net.1.weight"] = (1.0 + 0.1 * rng.standard_normal(H)).astype(np.float32)
+        sd["output_net.1.bias"] = (0.1 * rng.standard_normal(H)).astype(np.float32)
+        sd["output_net.3.weight"] = uni((coemb, H), H, out_scale)
+        sd["output_net.3.bias"] = uni((coemb,), H, out_scale)
+        sd["hidden"] = rng.standard_normal((2, 1, H)).astype(np.float32)
+        return sd
+
+    text = bigru(text_hidden, {"pos_emb.weight": uni((dim_word, dim_pos_ohot), dim_pos_ohot), "pos_emb.bias": uni((dim_word,), dim_pos_ohot),
+                               "input_emb.weight": uni((text_hidden, dim_word), dim_word), "input_emb.bias": uni((text_hidden,), dim_word)})
+    motion = bigru(motion_hidden, {"input_emb.weight": uni((motion_hidden, movement_latent), movement_latent),
+                                   "input_emb.bias": uni((motion_hidden,), movement_latent)})
+    return {"movement_encoder": mov, "text_encoder": text, "motion_encoder": motion}
+
+
+def make_t2m_inputs(N, T, Lw, seed=0, lengths="mixed", dim_pose=263, dim_word=300, dim_pos_ohot=15):
+    """Inputs of the text-to-motion evaluator as eval_humanml's batches carry them: {'motions' [N, T, dim_pose], 'm_lens' int64 [N] in [4, T],
+    'word_embs' [N, Lw, dim_word], 'pos_ohot' [N, Lw, dim_pos_ohot] one-hot, 'cap_lens' int64 [N] in [1, Lw]}. lengths: "full", "mixed" (m_lens
+    uniform in [4, T] with T, 40, 4, 41, 42 and 43 among the first rows where they fit; cap_lens cycling 1 .. Lw) or a (m_lens, cap_lens) pair."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    motions = rng.standard_normal((N, T, dim_pose)).astype(np.float32)
+    word_embs = rng.standard_normal((N, Lw, dim_word)).astype(np.float32)
+    pos = rng.integers(0, dim_pos_ohot, (N, Lw))
+    pos_ohot = np.zeros((N, Lw, dim_pos_ohot), np.float32)
+    np.put_along_axis(pos_ohot, pos[..., None], 1.0, axis=2)
+    if isinstance(lengths, str):
+        if lengths == "full":
+            m_lens, cap_lens = np.full(N, T, np.int64), np.full(N, Lw, np.int64)
+        else:
+            m_lens = rng.integers(min(4, T), T + 1, N).astype(np.int64)
+            for i, v in enumerate(v for v in (T, 40, 4, 41, 42, 43) if 4 <= v <= T):
+                if i < N:
+                    m_lens[i] = v
+            cap_lens = (np.arange(N) % Lw + 1).astype(np.int64)
+    else:
+        m_lens, cap_lens = (np.asarray(v, np.int64) for v in lengths)
+    return {"motions": motions, "m_lens": m_lens, "word_embs": word_embs, "pos_ohot": pos_ohot, "cap_lens": cap_lens}
+
+
 def build_model(cfg, sd, resp="", precision=None, device="cuda:0", noise_schedule="cosine", sigma_small=True, x3_tail=None, engine_options=None, f16_steps=None):
     """(model, diffusion) from regennet_amd for a synth config + checkpoint dict (reference key names): the same
     constructor calls the reference factory makes (utils/model_util.py:66-117), for tests, bench.py and tools.
