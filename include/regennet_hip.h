@@ -56,8 +56,12 @@ enum { RGN_PREC_F32 = 0,      /* fp32-input MFMA (v_mfma_f32_32x32x2_f32): exact
                                  LayerNorm/softmax stay hi+lo / fp32 throughout. Inside the 1e-3 parity bound. */
 enum { RGN_ARCH_ONLINE = 0,   /* causal nn.TransformerDecoder (model/cmdm.py:205-227)                 */
        RGN_ARCH_OFFLINE = 1,  /* non-causal nn.TransformerEncoder, embedding as token 0 (cmdm.py:228-238) */
-       RGN_ARCH_MLP = 3 };    /* (2 stays unassigned and refused) DiffMLP time / feature mixer (cmdm.py:239-242, model/mlp.py); num_heads, ff_size, emb_trans_dec and
+       RGN_ARCH_MLP = 3,      /* (2 stays unassigned and refused) DiffMLP time / feature mixer (cmdm.py:239-242, model/mlp.py); num_heads, ff_size, emb_trans_dec and
                                  wo_pos_emb are not read; at most 160 frames; no k_layers, no fp16 sub-phase, no small-batch engine */
+       RGN_ARCH_GRU = 4 };    /* nn.GRU(d, d, num_layers) over [pose ; emb] embeddings (cmdm.py:191-199, 243-249; rgn_gru_stack.hip); cm_mode add only; num_heads,
+                                 ff_size, emb_trans_dec and wo_pos_emb are not read; no k_layers, no k_step, no fp16 sub-phase, no small-batch engine */
+enum { RGN_GRU_SCAN_BATCH = 0,  /* the reference's own recurrence: nn.GRU(batch_first=True) on [T, B, d] scans the B samples of a call, frames are its batch */
+       RGN_GRU_SCAN_FRAMES = 1 };/* a recurrence over the frames of every sample */
 enum { RGN_SAMPLER_DDPM = 0,  /* GaussianDiffusion.p_sample   diffusion/gaussian_diffusion.py:508  */
        RGN_SAMPLER_DDIM = 1 };/* GaussianDiffusion.ddim_sample diffusion/gaussian_diffusion.py:744 */
 enum { RGN_FLAG_UNCOND = 1,   /* y['uncond']=True  (model/cmdm.py:181, mask_cond :129-137)         */
@@ -212,6 +216,14 @@ RGN_API int rgn_set_option(rgn_handle h, const char* key, int32_t value);
  * in the plain-bf16 phase (both inside the parity bound): callers that compare a motion drawn alone with its row of a batch - the
  * precision-schedule calibration, bench.py's row check, the row-independence tests - select the batch's form with this knob. */
 RGN_API int rgn_set_layers_min_b(rgn_handle h, int32_t samples);
+
+/* arch='gru' handles only (others: RGN_ERR_UNSUPPORTED): the axis the GRU scans, RGN_GRU_SCAN_*. A property of the MODEL, not a kernel-selection
+ * switch: the two settings are different functions of the same weights. The default is the reference's (batch): sample b of a call then depends on
+ * samples 0 .. b - 1 of that call, and the two halves of a guided evaluation are two independent scans (segments). */
+RGN_API int rgn_set_gru_scan(rgn_handle h, int32_t scan);
+/* The stack's plan for an evaluation of B motions (arch='gru' handles, after rgn_finalize_weights): scan, independent segments, scan steps S,
+ * launches per evaluation (S + num_layers - 1) and the bytes of its state ring. */
+RGN_API int rgn_gru_stack_info(rgn_handle h, int32_t B, int32_t guided, int32_t* scan, int32_t* segments, int32_t* steps, int32_t* launches, uint64_t* workspace_bytes);
 
 /* Fills x_dev [B,njoints,nfeats,T] with N(0,1) from the same Philox stream (x_T, gaussian_diffusion.py:706). */
 RGN_API int rgn_randn(rgn_handle h, float* x_dev, int32_t B, uint64_t seed, uint64_t sample_offset, void* stream);

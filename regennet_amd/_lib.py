@@ -15,7 +15,8 @@ RGN_OK = 0
 RGN_ERR_UNSUPPORTED = -7
 ERR_NAMES = {-1: "INVALID_ARG", -2: "BAD_KEY", -3: "BAD_SHAPE", -4: "MISSING_KEY", -5: "STATE", -6: "HIP", -7: "UNSUPPORTED", -8: "INTERNAL"}
 CM = {"add": 0, "concat": 1}
-ARCH = {"online": 0, "offline": 1, "mlp": 3}     # RGN_ARCH_* (include/regennet_hip.h)
+ARCH = {"online": 0, "offline": 1, "mlp": 3, "gru": 4}     # RGN_ARCH_* (include/regennet_hip.h)
+GRU_SCAN = {"batch": 0, "frames": 1}              # RGN_GRU_SCAN_*: the axis an arch='gru' model scans
 COND = {"no_cond": 0, "action": 1, "text": 2}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16_x3tail": 3}
 DEFAULT_PRECISION = "bf16_x3tail"
@@ -70,6 +71,8 @@ SYMBOLS = {
     "rgn_set_inpainting": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
     "rgn_set_option": (C.c_int, [_vp, C.c_char_p, _i32]),
     "rgn_set_layers_min_b": (C.c_int, [_vp, _i32]),
+    "rgn_set_gru_scan": (C.c_int, [_vp, _i32]),
+    "rgn_gru_stack_info": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_u64)]),
     "rgn_plan_query": (C.c_int, [_vp, _i32, _i32, _i32, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rgn_randn": (C.c_int, [_vp, _vp, _i32, _u64, _u64, _vp]),
@@ -354,6 +357,17 @@ class Engine:
         """Evaluations of at least `samples` samples (<= 64 tokens) run the one-kernel decoder stack (k_layers); -1: default (64)."""
         self._ck(self.lib.rgn_set_layers_min_b(self.h, int(samples)))
 
+    def set_gru_scan(self, scan):
+        """arch='gru' engines: the axis the GRU scans, 'batch' (the reference's: sample b depends on samples 0 .. b - 1 of the call) or 'frames'."""
+        self._ck(self.lib.rgn_set_gru_scan(self.h, GRU_SCAN[scan] if isinstance(scan, str) else int(scan)))
+
+    def gru_stack_info(self, B, guided=False):
+        """arch='gru' engines: dict(scan, segments, steps, launches_per_eval, workspace_bytes) of the stack for an evaluation of B motions."""
+        scan, seg, steps, n, ws = _i32(), _i32(), _i32(), _i32(), _u64()
+        self._ck(self.lib.rgn_gru_stack_info(self.h, int(B), int(bool(guided)), C.byref(scan), C.byref(seg), C.byref(steps), C.byref(n), C.byref(ws)))
+        return {"scan": {v: k for k, v in GRU_SCAN.items()}[scan.value], "segments": seg.value, "steps": steps.value, "launches_per_eval": n.value,
+                "workspace_bytes": ws.value}
+
     def plan_query(self, B, guided=False, split_phase=False):
         """The engine's plan for one denoiser evaluation of B motions: {class: dict(kernel, launches_per_eval, flops, l2_bytes)} for the
         classes that take part (rgn_plan_query: filled by the dispatching code itself)."""
@@ -366,6 +380,10 @@ class Engine:
                 break
             if kern.value:
                 out[name.value.decode()] = {"kernel": kern.value.decode(), "launches_per_eval": n.value, "flops": fl.value, "l2_bytes": l2.value}
+        if "gru_stack" in out:                                # the stack's own key also says which scan, how many segments and how much state
+            info = self.gru_stack_info(B, guided)
+            assert info["launches_per_eval"] == out["gru_stack"]["launches_per_eval"]
+            out["gru_stack"].update(info)
         return out
 
     def randn(self, x, B, seed, sample_offset, stream):

@@ -5,7 +5,7 @@
 using namespace rgnh;
 
 namespace rgnh {
-const char* const kclass_names[KC_COUNT] = {"gemm_mfma", "attention", "layernorm", "embed", "update", "misc", "qkv_attn", "rowgemm_ln", "rowgemm_act", "mlp", "sb_gemm", "step_fused", "layers", "steps_fused", "mixer"};
+const char* const kclass_names[KC_COUNT] = {"gemm_mfma", "attention", "layernorm", "embed", "update", "misc", "qkv_attn", "rowgemm_ln", "rowgemm_act", "mlp", "sb_gemm", "step_fused", "layers", "steps_fused", "mixer", "gru_stack"};
 
 // Work is enqueued on the handle's own non-blocking stream (capturable, unlike the legacy null stream
 // torch hands over by default) and ordered after / before the caller's stream with events.
@@ -83,19 +83,26 @@ int rgn_create(const rgn_config* cfg, rgn_handle* out) {
         if (cfg->njoints <= 0 || cfg->nfeats <= 0 || cfg->num_frames <= 0 || cfg->latent_dim <= 0 || cfg->ff_size <= 0 ||
             cfg->num_heads <= 0 || cfg->num_layers <= 0 || cfg->max_batch <= 0)
             return bad(RGN_ERR_INVALID_ARG, "rgn_create: non-positive dimension");
-        const bool mix = cfg->arch == RGN_ARCH_MLP;   // (no attention, no feed-forward width: num_heads and ff_size are not read)
-        if (!mix && cfg->latent_dim % cfg->num_heads) return bad(RGN_ERR_INVALID_ARG, "rgn_create: latent_dim % num_heads != 0");
+        const bool gru = cfg->arch == RGN_ARCH_GRU;
+        const bool mix = cfg->arch == RGN_ARCH_MLP;   // (no attention, no feed-forward width: num_heads and ff_size are not read; arch='gru' likewise)
+        if (!mix && !gru && cfg->latent_dim % cfg->num_heads) return bad(RGN_ERR_INVALID_ARG, "rgn_create: latent_dim % num_heads != 0");
         if (cfg->latent_dim % 64 || cfg->latent_dim > 1024 || (cfg->latent_dim / 64 & (cfg->latent_dim / 64 - 1)))
             return bad(RGN_ERR_UNSUPPORTED, "rgn_create: latent_dim must be 64*2^k <= 1024");
         if (cfg->num_frames > 4096) return bad(RGN_ERR_UNSUPPORTED, "rgn_create: more than 4096 frames (Philox element counter)");
-        if (!mix && cfg->latent_dim / cfg->num_heads > 128)
+        if (!mix && !gru && cfg->latent_dim / cfg->num_heads > 128)
             return bad(RGN_ERR_UNSUPPORTED, "rgn_create: head dim > 128 unsupported");
         if (cfg->cm_mode != RGN_CM_ADD && cfg->cm_mode != RGN_CM_CONCAT) return bad(RGN_ERR_INVALID_ARG, "rgn_create: cm_mode");
         if (cfg->cond_mode < RGN_COND_NONE || cfg->cond_mode > RGN_COND_TEXT) return bad(RGN_ERR_INVALID_ARG, "rgn_create: cond_mode");
         if (cfg->precision < RGN_PREC_F32 || cfg->precision > RGN_PREC_BF16_X3TAIL) return bad(RGN_ERR_INVALID_ARG, "rgn_create: precision");
         if (cfg->cond_mode == RGN_COND_ACTION && cfg->num_actions <= 0) return bad(RGN_ERR_INVALID_ARG, "rgn_create: num_actions");
         if (cfg->cond_mode == RGN_COND_TEXT && cfg->clip_dim <= 0) return bad(RGN_ERR_INVALID_ARG, "rgn_create: clip_dim");
-        if (cfg->arch != RGN_ARCH_ONLINE && cfg->arch != RGN_ARCH_OFFLINE && cfg->arch != RGN_ARCH_MLP) return bad(RGN_ERR_INVALID_ARG, "rgn_create: arch");
+        if (cfg->arch != RGN_ARCH_ONLINE && cfg->arch != RGN_ARCH_OFFLINE && cfg->arch != RGN_ARCH_MLP && cfg->arch != RGN_ARCH_GRU) return bad(RGN_ERR_INVALID_ARG, "rgn_create: arch");
+        if (gru && cfg->cm_mode != RGN_CM_ADD)
+            return bad(RGN_ERR_UNSUPPORTED, "rgn_create: arch='gru' adds the two pose embeddings (cm_mode add) - the reference raises NotImplementedError for any other cm_mode (cmdm.py:244-247)");
+        if (gru && cfg->emb_trans_dec)
+            return bad(RGN_ERR_UNSUPPORTED, "rgn_create: arch='gru' has no embedding token - emb_trans_dec belongs to the 'online' decoder");
+        if (gru)
+            if (const char* why = rgn::gru_stack_geometry_error(cfg->latent_dim, cfg->num_layers)) return bad(RGN_ERR_UNSUPPORTED, std::string("rgn_create: arch='gru': ") + why);
         if (mix && cfg->num_frames > rgn::MIX_MAX_T)
             return bad(RGN_ERR_UNSUPPORTED, "rgn_create: arch='mlp' with more than " + std::to_string(rgn::MIX_MAX_T) + " frames (num_frames = " +
                                                 std::to_string(cfg->num_frames) + "): the time mix stages all frames of a column slab in LDS");
@@ -116,6 +123,9 @@ int rgn_create(const rgn_config* cfg, rgn_handle* out) {
         // ff_size are not read; the input stage is a concat one whose fuse layer is block 0's conct
         c->mix = mix ? 1 : 0;
         if (c->mix) { c->cfg.wo_pos_emb = 1; c->cfg.emb_trans_dec = 0; c->cfg.num_heads = 1; c->cfg.ff_size = cfg->latent_dim; }
+        // arch='gru' (cmdm.py:243-249): positions always encoded, no embedding token, no attention - wo_pos_emb, num_heads and ff_size are not read
+        c->gru = gru ? 1 : 0;
+        if (c->gru) { c->cfg.wo_pos_emb = 0; c->cfg.num_heads = 1; c->cfg.ff_size = cfg->latent_dim; }
         c->etd = ((cfg->emb_trans_dec && !c->mix) || c->enc) ? 1 : 0;
         c->Tq = cfg->num_frames + c->etd;
         c->L = cfg->num_layers;
@@ -238,7 +248,7 @@ int rgn_set_schedule(rgn_handle h, const rgn_schedule* s) {
         RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
         g = gemm_args(c, c->lin_t2, c->sched_tmp + (size_t)1024 * d, d, c->te_all, d, S);
         RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
-        if (!c->enc && !c->mix) {   // (encoder layers have no cross-attention to fold; arch='mlp': SiLU sits in front of emb_fc, nothing folds per step)
+        if (!c->enc && !c->mix && !c->gru) {   // (encoder layers have no cross-attention to fold; arch='mlp': SiLU sits in front of emb_fc, nothing folds per step; arch='gru': its emb GEMM is per evaluation)
             g = gemm_args(c, c->lin_g, c->te_all, d, c->call_time, c->L * d, S);
             RGN_LAUNCH(c, KC_GEMM, es, launch_gemm(g, small_prec(c), es));
         }
@@ -280,7 +290,7 @@ int rgn_set_condition(rgn_handle h, int32_t B, const float* cmotion, const int64
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(t, small_prec(c), s));
             RGN_LAUNCH(c, KC_EMBED, s, launch_fill_rows(c->condemb + (size_t)B * d, c->dp<float>(c->off_bt), B, d, s));  // embed_text(0) = bias
         }
-        if (c->cfg.cond_mode != RGN_COND_NONE && !c->enc && !c->mix) {   // folded cross-attention image of the condition rows (cond | uncond)
+        if (c->cfg.cond_mode != RGN_COND_NONE && !c->enc && !c->mix && !c->gru) {   // folded cross-attention image of the condition rows (cond | uncond)
             GemmArgs cg = gemm_args(c, c->lin_g, c->condemb, d, c->call_cond, c->L * d, 2 * B);
             cg.bias = nullptr;
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(cg, small_prec(c), s));
@@ -412,6 +422,8 @@ int rgn_set_small_batch_rows(rgn_handle h, int32_t rows) {
         if (rows < -1) return h->fail(RGN_ERR_INVALID_ARG, "rgn_set_small_batch_rows: rows < -1");
         if (h->mix && rows > 0)
             return h->fail(RGN_ERR_UNSUPPORTED, "rgn_set_small_batch_rows: the small-batch engine runs transformer layers only - it stays off for an arch='mlp' handle (0 or -1 are accepted)");
+        if (h->gru && rows > 0)
+            return h->fail(RGN_ERR_UNSUPPORTED, "rgn_set_small_batch_rows: the small-batch engine runs transformer layers only - it stays off for an arch='gru' handle (0 or -1 are accepted)");
         const int v = rows < 0 ? h->sb_rows_default : rows;
         if (v != h->sb_rows) {   // captured graphs hold the kernels of the engine that was selected when they were recorded
             if (h->stream) RGN_HIP(h, hipStreamSynchronize(h->stream));
@@ -429,6 +441,10 @@ int rgn_set_option(rgn_handle h, const char* key, int32_t value) {
         if (!key || !*key) return h->fail(RGN_ERR_INVALID_ARG, "rgn_set_option: empty key");
         if (h->mix && strncmp(key, "LAYERS", 6) == 0)
             return h->fail(RGN_ERR_UNSUPPORTED, std::string("rgn_set_option: '") + key + "' selects forms of k_layers, the one-kernel transformer decoder stack - an arch='mlp' handle has no such layers");
+        if (h->gru && strncmp(key, "LAYERS", 6) == 0)
+            return h->fail(RGN_ERR_UNSUPPORTED, std::string("rgn_set_option: '") + key + "' selects forms of k_layers, the one-kernel transformer decoder stack - an arch='gru' handle has no such layers");
+        if (h->gru && (strcmp(key, "NO_STEP_FUSION") == 0 || strcmp(key, "STEP_NO_QUADS") == 0))
+            return h->fail(RGN_ERR_UNSUPPORTED, std::string("rgn_set_option: '") + key + "' is a switch of k_step, the fused step boundary - an arch='gru' handle never runs it");
         if (h->finalized && strcmp(key, "LAYERS_GUIDED") == 0) {   // (a dispatch rule, not a packing decision: may change between calls; captured graphs hold the old form)
             const int v = value < 0 ? h->layers_guided_default : (value > 2 ? 2 : value);
             if (v != h->layers_guided) {
@@ -461,6 +477,38 @@ int rgn_set_layers_min_b(rgn_handle h, int32_t samples) {
             h->graphs.clear();
             h->layers_min_b = v;
         }
+        return RGN_OK;
+    });
+}
+
+int rgn_set_gru_scan(rgn_handle h, int32_t scan) {
+    return rgn_guard(h, "rgn_set_gru_scan", [&]() -> int {
+        if (!h) return RGN_ERR_INVALID_ARG;
+        if (!h->gru) return h->fail(RGN_ERR_UNSUPPORTED, "rgn_set_gru_scan: the scan axis belongs to the GRU stack - this handle's arch is not 'gru'");
+        if (scan != RGN_GRU_SCAN_BATCH && scan != RGN_GRU_SCAN_FRAMES) return h->fail(RGN_ERR_INVALID_ARG, "rgn_set_gru_scan: scan must be 0 (batch) or 1 (frames)");
+        if (scan != h->gru_scan) {   // captured graphs hold the strides of the scan that was set when they were recorded
+            if (h->stream) RGN_HIP(h, hipStreamSynchronize(h->stream));
+            for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
+            h->graphs.clear();
+            h->gru_scan = scan;
+        }
+        return RGN_OK;
+    });
+}
+
+int rgn_gru_stack_info(rgn_handle h, int32_t B, int32_t guided, int32_t* scan, int32_t* segments, int32_t* steps, int32_t* launches, uint64_t* workspace_bytes) {
+    return rgn_guard(h, "rgn_gru_stack_info", [&]() -> int {
+        if (!h) return RGN_ERR_INVALID_ARG;
+        if (!h->gru) return h->fail(RGN_ERR_UNSUPPORTED, "rgn_gru_stack_info: this handle's arch is not 'gru'");
+        if (!scan || !segments || !steps || !launches || !workspace_bytes) return h->fail(RGN_ERR_INVALID_ARG, "rgn_gru_stack_info: null output");
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_gru_stack_info: weights not finalized");
+        if (B <= 0 || B > h->cfg.max_batch) return h->fail(RGN_ERR_INVALID_ARG, "rgn_gru_stack_info: B outside (0, max_batch]");
+        const GruScan sc = gru_scan_of(h, make_dims(h, B, guided != 0), guided != 0);
+        *scan = h->gru_scan;
+        *segments = sc.nseg;
+        *steps = sc.S;
+        *launches = rgn::gru_stack_launches(sc.S, h->L);
+        *workspace_bytes = (uint64_t)h->gru_ring_floats * sizeof(float);
         return RGN_OK;
     });
 }

@@ -81,6 +81,11 @@ struct rgn_ctx {
     bool finalized = false, have_sched = false, have_cond = false;
     int F = 0, d = 0, Tq = 0, etd = 0, L = 0, H = 0, ff = 0, pe_len = 0;
     int mix = 0;                       // arch='mlp': the time / feature mixer stack (rgn_mixer.hip): fp32 residual stream, no attention, no token, no positional encoding
+    int gru = 0;                       // arch='gru': the layer-wavefront GRU stack (rgn_gru_stack.hip): fp32 input rows and state, positions always encoded, cm_mode add
+    int gru_scan = 0;                  // RGN_GRU_SCAN_*: rgn_set_gru_scan
+    size_t off_gru = 0;                // the L packed layers in the weight blob
+    float* gru_ring = nullptr;         // state ring of the layers below the top one
+    size_t gru_ring_floats = 0;
     int enc = 0;                       // arch='offline': encoder layers (non-causal self-attention, norm1 / norm2, no cross-attention); implies etd
 
     // packed weights
@@ -235,6 +240,7 @@ struct EvalPlan {
     bool steps = false;       // k_layers<true>: whole runs of sampler steps in one launch (sampling only)
     bool step_fused = false;  // k_step: output projection + sampler update + next input embedding (sampling only)
     bool mix = false;         // arch='mlp': k_mix_time + the feature-mix GEMM per layer (attn / tail are not read)
+    bool gru = false;         // arch='gru': k_gru_stack, one launch per anti-diagonal, on ONE chain (attn / tail are not read)
     AttnForm attn = AF_PLAIN;
     TailForm tail = TF_GEMM_LN;
 };
@@ -247,6 +253,9 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
                double* launches_per_eval, double* algo_flops_per_eval, double* l2_bytes_per_eval);                         // ... of rgn_plan_query
 struct PrecPlan { int tail = 0, n16 = 0; };
 PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided);
+// arch='gru': the scan of an evaluation of dm.Bm rows - steps, sequences per segment and segments (batch scan: the guided halves are two scans of B)
+struct GruScan { int S, N, nseg; };
+GruScan gru_scan_of(const rgn_ctx* c, const Dims& dm, bool guided);
 
 // precision of the per-schedule / per-condition / rgn_denoise-only GEMMs (k_gemm_f32 / k_gemm_bf16): the schedule mode
 // runs them split-bf16 (they are once-per-call work)

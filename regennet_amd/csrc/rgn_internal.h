@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "rgn_gru_stack_check.h"
+
 namespace rgn {
 
 // ---- kernel classes (for per-class HIP-event timing, rgn_profile_query) -------------------------
@@ -23,6 +27,7 @@ enum KClass : int {
     KC_LAYERS,        // the whole decoder stack of an evaluation, one sample per workgroup (k_layers)
     KC_STEPS,         // a run of complete sampler steps (stack + step boundary per sample) in one launch (k_layers<true>)
     KC_MIX,           // arch='mlp': time mix of a layer, one sample per workgroup (k_mix_time), + the stack's elementwise ends (k_mix_emb, k_mix_fin)
+    KC_GRU,           // arch='gru': the layer-wavefront GRU stack, one launch per anti-diagonal of (layer, step) cells (k_gru_stack), + its elementwise ends
     KC_COUNT
 };
 
@@ -388,6 +393,18 @@ hipError_t launch_mix_time(const MixTimeArgs& g, int fmt, hipStream_t s);
 hipError_t launch_mix_emb(const float* rows, const float* stepemb, const int* d_step, float* out, int Bm, int d, hipStream_t s);
 // behind the last layer: h + sadd -> hp planes (lo nullable) where hp.hi is given, else -> h in place
 hipError_t launch_mix_fin(float* h, const float* sadd, Planes hp, int M, int d, hipStream_t s);
+
+// ---- rgn_gru_stack.hip: the layer stack of arch='gru' (model/cmdm.py:243-249). launch_gru_stack runs ONE scan (rgn_gru_stack_check.h: GruStackArgs) as
+// S + L - 1 launches of k_gru_stack, one per anti-diagonal, ordered by the stream alone. Input rows and state are fp32 in every precision mode.
+hipError_t launch_gru_stack(const GruStackArgs& g, hipStream_t s);
+// one layer's weights as the kernel reads them: gru_pack(W_ih) | gru_pack(W_hh) | bias [4][d] (gru_stack_layer_floats(d) floats)
+std::vector<float> gru_stack_pack_layer(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int d);
+// out[b, :] = rows[b, :] + stepemb[*d_step, :] (either addend may be null): the operand of the emb-column GEMM
+hipError_t launch_gru_emb(const float* rows, const float* stepemb, const int* d_step, float* out, int Bm, int d, hipStream_t s);
+// h[b T + t, :] += e[b, :]
+hipError_t launch_gru_add_rows(float* h, const float* e, int Bm, int T, int d, hipStream_t s);
+// fp32 rows [M, d] -> operand planes (lo nullable)
+hipError_t launch_gru_planes(const float* src, Planes hp, int M, int d, hipStream_t s);
 
 // ---- rgn_fk.hip: forward kinematics of a skeleton (rgn_rot2xyz). Passed to the kernel by value: the call keeps no state.
 constexpr int FK_MAX_JOINTS = 64;

@@ -10,9 +10,11 @@ namespace rgnh {
 void build_expected(rgn_ctx* c) {
     const int64_t d = c->d, F = c->F, ff = c->ff;
     auto& e = c->expected;
-    e["input_process.poseEmbedding.weight"] = {d, F};
+    // arch='gru' (cmdm.py:52-54, 191-199): both pose embeddings take [pose ; emb], F + d input columns
+    const int64_t Fin = c->gru ? F + d : F;
+    e["input_process.poseEmbedding.weight"] = {d, Fin};
     e["input_process.poseEmbedding.bias"] = {d};
-    e["cmo_process.poseEmbedding.weight"] = {d, F};
+    e["cmo_process.poseEmbedding.weight"] = {d, Fin};
     e["cmo_process.poseEmbedding.bias"] = {d};
     if (c->cfg.cm_mode == RGN_CM_CONCAT) {   // (arch='mlp' never calls it - block 0's conct fuses - but a concat checkpoint carries the keys)
         e["fuse_process.weight"] = {d, 2 * d};
@@ -43,7 +45,15 @@ void build_expected(rgn_ctx* c) {
             e[p + n + ".bias"] = {d};
         }
     }
-    for (int l = 0; !c->mix && l < c->L; ++l) {
+    for (int l = 0; c->gru && l < c->L; ++l) {
+        // arch='gru': nn.GRU(d, d, num_layers) keys, gate order r, z, n
+        const std::string s = "_l" + std::to_string(l);
+        e["gru.weight_ih" + s] = {3 * d, d};
+        e["gru.weight_hh" + s] = {3 * d, d};
+        e["gru.bias_ih" + s] = {3 * d};
+        e["gru.bias_hh" + s] = {3 * d};
+    }
+    for (int l = 0; !c->mix && !c->gru && l < c->L; ++l) {
         // arch='offline': nn.TransformerEncoderLayer keys (self_attn, linear1/2, norm1/2); 'online': nn.TransformerDecoderLayer's
         const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         for (const char* a : {"self_attn.", "multihead_attn."}) {
@@ -179,7 +189,7 @@ int finalize_weights(rgn_ctx* c) {
     // fp16 operands for the plain phase of the precision schedule (k_layers<.., F16>): same MFMA rate and bytes as bf16, 2^-12 instead of
     // 2^-9 operand rounding - but a 5-bit exponent: a weight at or beyond fp16's range would become inf, so such a checkpoint is refused
     // here, with the key named (activations are LayerNorm outputs, probabilities and GELU values: O(1) by construction)
-    { int v = 1; (void)opt_get(c, "BULK_F16", &v); c->bulk_f16 = c->cfg.precision == RGN_PREC_BF16_X3TAIL && v != 0 && !c->mix; }   // (arch='mlp': no fp16 sub-phase)
+    { int v = 1; (void)opt_get(c, "BULK_F16", &v); c->bulk_f16 = c->cfg.precision == RGN_PREC_BF16_X3TAIL && v != 0 && !c->mix && !c->gru; }   // (arch='mlp' / 'gru': no fp16 sub-phase)
     { int v; if (opt_get(c, "F16_STEPS", &v)) c->f16_steps = c->f16_steps_default = v < 0 ? -1 : v; }
     auto f16_range = [&](const std::string& key, const float* w, size_t n) -> bool {
         for (size_t i = 0; i < n; ++i)
@@ -227,6 +237,17 @@ int finalize_weights(rgn_ctx* c) {
                 wxf[i] = (float)wx[i];
                 wcf[i] = (float)wc[i];
             }
+        } else if (c->gru) {
+            // arch='gru': [d, F + d] = [W_pose | W_emb] in both embeddings. The pose columns go where every handle's do; the emb columns of the two
+            // add up to ONE [d, d] linear on the per-sample embedding (lin_g, no bias): x_in + c_in = W_x x + W_c c + (W_xe + W_ce) emb + b_x + b_c
+            std::vector<float> we((size_t)d * d);
+            for (int n = 0; n < d; ++n) {
+                memcpy(&wxf[(size_t)n * F], win + (size_t)n * (F + d), (size_t)F * 4);
+                memcpy(&wcf[(size_t)n * F], wcm + (size_t)n * (F + d), (size_t)F * 4);
+                for (int j = 0; j < d; ++j) we[(size_t)n * d + j] = (float)((double)win[(size_t)n * (F + d) + F + j] + (double)wcm[(size_t)n * (F + d) + F + j]);
+                bconst[n] = (float)((double)bin[n] + (double)bcm[n]);
+            }
+            c->lin_g = pack_linear(c, we.data(), nullptr, d, d);
         } else {
             memcpy(wxf.data(), win, wxf.size() * 4);
             memcpy(wcf.data(), wcm, wcf.size() * 4);
@@ -256,7 +277,18 @@ int finalize_weights(rgn_ctx* c) {
         memcpy(&gall[(size_t)l * d * d], W(p + "emb_fc.weight"), (size_t)d * d * 4);
         memcpy(&gb[(size_t)l * d], W(p + "emb_fc.bias"), (size_t)d * 4);
     }
-    for (int l = 0; !c->mix && l < c->L; ++l) {
+    if (c->gru) {
+        // arch='gru': every layer as A fragments of the 16x16x4 fp32 MFMA + the four bias rows (gru_stack_pack_layer), one after the other
+        std::vector<float> all;
+        all.reserve((size_t)c->L * gru_stack_layer_floats(d));
+        for (int l = 0; l < c->L; ++l) {
+            const std::string s = "_l" + std::to_string(l);
+            const std::vector<float> p = gru_stack_pack_layer(W("gru.weight_ih" + s), W("gru.weight_hh" + s), W("gru.bias_ih" + s), W("gru.bias_hh" + s), d);
+            all.insert(all.end(), p.begin(), p.end());
+        }
+        c->off_gru = blob_put(c, all.data(), all.size() * 4);
+    }
+    for (int l = 0; !c->mix && !c->gru && l < c->L; ++l) {
         const std::string p = (c->enc ? "seqTransEncoder.layers." : "seqTransDecoder.layers.") + std::to_string(l) + ".";
         LayerW& lw = c->layers[l];
         if (c->bulk_f16)
@@ -296,7 +328,7 @@ int finalize_weights(rgn_ctx* c) {
             gb[(size_t)l * d + n] = (float)b;
         }
     }
-    if (!c->enc) c->lin_g = pack_linear(c, gall.data(), gb.data(), c->L * d, d);
+    if (!c->enc && !c->gru) c->lin_g = pack_linear(c, gall.data(), gb.data(), c->L * d, d);
     if (c->bulk_f16 && !f16_range("output_process.poseFinal.weight", W("output_process.poseFinal.weight"), (size_t)F * d)) return RGN_ERR_UNSUPPORTED;
     c->lin_out = pack_linear(c, W("output_process.poseFinal.weight"), W("output_process.poseFinal.bias"), F, d, true,
                              c->cfg.precision == RGN_PREC_BF16_X3TAIL, false, c->bulk_f16);   // fragment order: k_step
@@ -324,9 +356,10 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->c0, M * d))) return rc;
     if ((rc = ws_alloc(c, &c->h, M * d))) return rc;
     if ((rc = ws_alloc(c, &c->tmp, M * d))) return rc;
-    if (!c->mix && (rc = ws_alloc(c, &c->qkv, M * 3 * d))) return rc;   // (arch='mlp': no attention, no feed-forward hidden tensor, no cross-attention fold)
+    const bool notf = c->mix || c->gru;   // no transformer layers: no attention, no feed-forward hidden tensor, no cross-attention fold
+    if (!notf && (rc = ws_alloc(c, &c->qkv, M * 3 * d))) return rc;
     if ((rc = ws_alloc(c, &c->att, M * d))) return rc;
-    if (!c->mix && (rc = ws_alloc(c, &c->ffn, M * ff))) return rc;
+    if (!notf && (rc = ws_alloc(c, &c->ffn, M * ff))) return rc;
     if ((rc = ws_alloc(c, &c->x0tok, M * F))) return rc;
     if ((rc = ws_alloc(c, &c->pe_rows, Bm * d))) return rc;
     if ((rc = ws_alloc(c, &c->emb1, Bm * d))) return rc;
@@ -336,11 +369,18 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->scale, B))) return rc;
     if ((rc = ws_alloc(c, &c->te_all, (size_t)1024 * d))) return rc;
     if ((rc = ws_alloc(c, &c->sched_tmp, (size_t)2 * 1024 * d))) return rc;
-    if (!c->mix && (rc = ws_alloc(c, &c->call_time, (size_t)1024 * c->L * d))) return rc;
-    if (!c->mix && (rc = ws_alloc(c, &c->call_cond, Bm * c->L * d))) return rc;
-    if (c->mix) c->sb_rows = c->sb_rows_default = 0;   // no small-batch engine for these handles, in any mode (rgn_set_small_batch_rows refuses to turn it on)
-    if (c->cfg.precision != RGN_PREC_F32 && c->mix) {
+    if (!notf && (rc = ws_alloc(c, &c->call_time, (size_t)1024 * c->L * d))) return rc;
+    if (!notf && (rc = ws_alloc(c, &c->call_cond, Bm * c->L * d))) return rc;
+    if (notf) c->sb_rows = c->sb_rows_default = 0;   // no small-batch engine for these handles, in any mode (rgn_set_small_batch_rows refuses to turn it on)
+    if (c->gru) {
+        // the state ring of the layers below the top one, sized for either scan: frames - 2 max_batch sequences in one segment; batch - Tq sequences in two
+        const size_t seqs = std::max(Bm, (size_t)2 * c->Tq);
+        c->gru_ring_floats = gru_stack_ring_floats(d, c->L, 1, (int)seqs);
+        if (c->gru_ring_floats && (rc = ws_alloc(c, &c->gru_ring, c->gru_ring_floats))) return rc;
+    }
+    if (c->cfg.precision != RGN_PREC_F32 && notf) {
         // arch='mlp': the stream is fp32 (h, tmp); planes only for the sampler state, the LN1 image (att) and the output projection's operand (h)
+        // arch='gru': the stack's input rows (h) and output rows (att) are fp32; planes for the sampler state and the output projection's operand (att)
         const size_t Fp = align_up((size_t)F, 32);
         if ((rc = ws_alloc(c, &c->xin_hi, M * Fp))) return rc;
         if ((rc = ws_alloc(c, &c->xin_lo, M * Fp))) return rc;
@@ -428,7 +468,7 @@ int finalize_weights(rgn_ctx* c) {
     if ((rc = ws_alloc(c, &c->d_tab, (size_t)1024))) return rc;
     if ((rc = ws_alloc(c, &c->d_step, (size_t)4 + 1 + B))) return rc;   // [0] loop index, [3] scratch, [4 ..] k_update's ticket counters
     if ((rc = ws_alloc(c, &c->d_sp, (size_t)1))) return rc;
-    if (!c->mix) RGN_HIP(c, configure_attention(c->Tq, c->d / c->H));
+    if (!notf) RGN_HIP(c, configure_attention(c->Tq, c->d / c->H));
     RGN_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     RGN_HIP(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
     RGN_HIP(c, hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));

@@ -116,6 +116,9 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     // form (all of them are off for such a handle: rgn_pack.cpp)
     p.mix = c->mix != 0;
     if (p.mix) return p;
+    // arch='gru' handles: the layer-wavefront stack (rgn_gru_stack.hip) in every mode and phase, with the same things off
+    p.gru = c->gru != 0;
+    if (p.gru) return p;
     p.sb = use_sb(c, rows);
     if (p.sb) {
         p.attn = AF_GEMM_ATTN;
@@ -149,6 +152,11 @@ EvalPlan plan_eval(const rgn_ctx* c, const Dims& dm, bool guided, bool x3, bool 
     return p;
 }
 
+GruScan gru_scan_of(const rgn_ctx* c, const Dims& dm, bool guided) {
+    if (c->gru_scan == RGN_GRU_SCAN_FRAMES) return GruScan{dm.Tq, dm.Bm, 1};   // segments are further sequences
+    return GruScan{dm.B, dm.Tq, guided ? 2 : 1};                                // the reference's two forwards of B rows each: the scan restarts
+}
+
 // ---- the precision plan of a sampling loop over the bound schedule: loop indices [0, tail) run split-bf16, [tail, tail + n16) plain
 //      fp16 operands, the rest plain bf16. Why three phases: v_mfma_f32_32x32x16_f16 has the bf16 instruction's nominal rate and 8x less operand
 //      rounding, but the chip is power-managed under a matrix load and a pure f16 MFMA loop sustains 7.5 - 8 % less than the bf16 one
@@ -169,7 +177,7 @@ PrecPlan prec_plan(const rgn_ctx* c, const Dims& dm, bool guided) {
     pp.n16 = !f16_ok ? 0 : (c->f16_steps >= 0 ? c->f16_steps : F16_STEPS_DEFAULT);
     if (c->x3_tail >= 0) pp.tail = c->x3_tail;
     else if (pp.n16 > 0 && c->L >= 8 && !c->etd) pp.tail = F16_TAIL < c->S ? F16_TAIL : c->S;
-    else pp.tail = default_tail(c->S, c->L, c->etd != 0 || c->mix != 0);   // (arch='mlp': split-bf16 on every step, like encoder handles - no plain-phase error has been measured)
+    else pp.tail = default_tail(c->S, c->L, c->etd != 0 || c->mix != 0 || c->gru != 0);   // (arch='mlp': split-bf16 on every step, like encoder handles - no plain-phase error has been measured)
     if (pp.tail > c->S) pp.tail = c->S;
     if (pp.n16 > c->S - pp.tail) pp.n16 = c->S - pp.tail;
     return pp;
@@ -397,7 +405,8 @@ int run_layers(rgn_ctx* c, const Eval& ev, int s0, int ns, hipStream_t s) {
     if (pl.step_fused) {
         // fused step boundary (k_step): the residual-stream planes already hold this evaluation's input embedding
     } else if (fast) {   // xin planes and c0 already hold both guidance halves
-        if ((rc = big(c->lin_x, nullptr, 0, xin_p, (h32 || pl.mix) ? h : nullptr, d, pl.mix ? none : h_p, c->c0 + (size_t)row0 * d, 0, M))) return rc;
+        const bool rows32 = pl.mix || pl.gru;   // (these stacks read fp32 rows)
+        if ((rc = big(c->lin_x, nullptr, 0, xin_p, (h32 || rows32) ? h : nullptr, d, rows32 ? none : h_p, c->c0 + (size_t)row0 * d, 0, M))) return rc;
     } else {
         if ((rc = big(c->lin_x, c->xin, c->F, none, c->h, d, none, c->c0, 0, Mb))) return rc;
         if (ev.guided)
@@ -426,6 +435,24 @@ int run_layers(rgn_ctx* c, const Eval& ev, int s0, int ns, hipStream_t s) {
         }
         RGN_LAUNCH(c, KC_MIX, s, launch_mix_fin(h, tmp, h_p, M, d, s));
         return big(c->lin_out, h, d, h_p, c->x0tok + (size_t)row0 * c->F, c->F, none, nullptr, 0, M);
+    }
+    if (pl.gru) {
+        // arch='gru' (called with the full range, on ONE chain: in the batch scan the rows of an evaluation are coupled). h holds W_x x + W_c c + b_x + b_c
+        // + pe; the emb columns of both pose embeddings are one vector per sample (c->call, made by run_eval), added here. Then the stack: S + L - 1
+        // launches, fp32 rows in, the top layer's fp32 rows out (att), and the output projection in the handle's precision mode
+        RGN_LAUNCH(c, KC_GRU, s, launch_gru_add_rows(h, c->call + (size_t)s0 * d, ns, dm.Tq, d, s));
+        const GruScan sc = gru_scan_of(c, dmf, ev.guided);
+        const long long row = d, smp = (long long)dm.Tq * d;
+        GruStackArgs g{};
+        g.w = c->dp<float>(c->off_gru); g.x = h; g.out = att; g.ring = c->gru_ring;
+        g.d = d; g.L = c->L; g.S = sc.S; g.N = sc.N; g.nseg = sc.nseg;
+        if (c->gru_scan == RGN_GRU_SCAN_FRAMES) { g.x_step = g.o_step = row; g.x_seq = g.o_seq = smp; }
+        else { g.x_step = g.o_step = smp; g.x_seq = g.o_seq = row; g.x_seg = g.o_seg = smp * dmf.B; }
+        if (gru_stack_ring_floats(d, c->L, sc.nseg, sc.N) > c->gru_ring_floats) return c->fail(RGN_ERR_INTERNAL, "run_layers: the GRU state ring is too small for this scan");
+        if (const char* why = gru_stack_args_error(g)) return c->fail(RGN_ERR_INTERNAL, std::string("run_layers: GRU stack arguments: ") + why);
+        RGN_LAUNCH(c, KC_GRU, s, launch_gru_stack(g, s));
+        if (fast) RGN_LAUNCH(c, KC_GRU, s, launch_gru_planes(att, att_p, M, d, s));
+        return big(c->lin_out, att, d, att_p, c->x0tok + (size_t)row0 * c->F, c->F, none, nullptr, 0, M);
     }
     const size_t slab0 = (size_t)s0 * c->H * c->Tqp * dm.dh;      // attention-ready planes: first slab of this range
     if (pl.layers) {
@@ -564,7 +591,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
     // timesteps and evaluates them here.
     const bool has_cond = c->cfg.cond_mode != RGN_COND_NONE;
     const float* cond_rows = !has_cond ? nullptr : ((uncond && !guided) ? c->condemb + (size_t)B * d : c->condemb);
-    const float* ccond_rows = (!has_cond || c->mix) ? nullptr : ((uncond && !guided) ? c->call_cond + (size_t)B * Ld : c->call_cond);
+    const float* ccond_rows = (!has_cond || c->mix || c->gru) ? nullptr : ((uncond && !guided) ? c->call_cond + (size_t)B * Ld : c->call_cond);
     const Eval ev{dm, pl, ph, guided, sampling, cond_rows, ccond_rows};
     if (!sampling) {
         RGN_LAUNCH(c, KC_EMBED, s, launch_gather_pe(c->dp<float>(c->off_pe), c->d_tab, c->d_step, c->d_sp, c->pe_rows, dm.Bm, B, d, c->pe_len, s));
@@ -576,7 +603,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
         g.ldadd = d;
         RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
         // cross-attention onto the 1-token memory, all layers at once: call[b, l*d:(l+1)*d] (encoder layers have none)
-        if (!c->enc && !c->mix) {
+        if (!c->enc && !c->mix && !c->gru) {
             g = gemm_args(c, c->lin_g, c->emb, d, c->call, Ld, dm.Bm);
             RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
         }
@@ -586,6 +613,13 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
         // per schedule or per condition alone: a sampling step makes emb = TE[*d_step] + condition row on the device (capturable), rgn_denoise has it in c->emb
         RGN_LAUNCH(c, KC_MIX, s, launch_mix_emb(sampling ? cond_rows : c->emb, sampling ? c->te_all : nullptr, c->d_step, c->emb1, dm.Bm, d, s));
         GemmArgs g = gemm_args(c, c->lin_g, c->emb1, d, c->call, Ld, dm.Bm);
+        RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
+    }
+    if (c->gru) {
+        // arch='gru': the emb columns of input_process / cmo_process as ONE [Bm, d] x [d, d] GEMM, e[b] = (W_xe + W_ce) emb_b -> c->call [Bm, d]. A sampling
+        // step makes emb = TE[*d_step] + condition row on the device (capturable); the uncond rows of a guided evaluation get their own emb
+        RGN_LAUNCH(c, KC_GRU, s, launch_gru_emb(sampling ? cond_rows : c->emb, sampling ? c->te_all : nullptr, c->d_step, c->emb1, dm.Bm, d, s));
+        GemmArgs g = gemm_args(c, c->lin_g, c->emb1, d, c->call, d, dm.Bm);
         RGN_LAUNCH(c, KC_GEMM, s, launch_gemm(g, small_prec(c), s));
     }
     // ---- layers. In the bf16 modes the samples of the evaluation are split into contiguous groups that run as
@@ -609,6 +643,7 @@ int run_eval(rgn_ctx* c, int B, bool guided, bool uncond, bool sampling, Phase p
     // (B = 40 / 48: 114.3 / 113.8 vs 120.0 / 118.8 with four; B = 64, 60 tiles: the same with one, two and four)
     if (nch == 4 && !c->nchains_user && tiles64 <= 48) nch = 1;
     if (pl.sb) nch = 1;                                   // small-batch engine: one chain of column-split kernels
+    if (pl.gru) nch = 1;                                  // arch='gru': ONE chain whatever STREAMS says - the batch scan couples the rows of an evaluation
     if (nch > dm.Bm) nch = dm.Bm;
     if (nch > 1) RGN_HIP(c, hipEventRecord(c->ev_fork, s));
     const int per = dm.Bm / nch, extra = dm.Bm % nch;
@@ -860,7 +895,16 @@ int plan_query(rgn_ctx* c, int32_t B, int32_t guided, int32_t split_phase, int32
     const char* kn[KC_COUNT] = {nullptr};
     for (int i = 0; i < KC_COUNT; ++i) kn[i] = "";
     const double Fp = (double)align_up((size_t)c->F, 32), wl = L * (4 * d * d + 2 * d * ff);
-    if (pl.mix) {
+    if (pl.gru) {
+        // (launches_per_eval of the stack: its S + L - 1 diagonal launches; the three elementwise kernels around it are not counted)
+        const GruScan sc = gru_scan_of(c, dm, guided != 0);
+        kn[KC_GEMM] = c->cfg.precision == RGN_PREC_F32 ? "k_gemm_f32" : "k_gemm_x3";
+        mac[KC_GEMM] = embed + (double)dm.Bm * d * d; n[KC_GEMM] = 3;   // embedding, projection, the emb columns
+        kn[KC_GRU] = c->gru_scan == RGN_GRU_SCAN_FRAMES ? "k_gru_stack<frames>" : "k_gru_stack<batch>";
+        mac[KC_GRU] = M * 6 * d * d * L; n[KC_GRU] = gru_stack_launches(sc.S, c->L);
+        l2[KC_GRU] = (double)sc.S * L * sc.nseg * ((sc.N + GRS_TILE * GRS_WAVES - 1) / (GRS_TILE * GRS_WAVES)) * (double)gru_stack_layer_floats(c->d) * 4.0;
+        n[KC_UPDATE] = 1; kn[KC_UPDATE] = "k_update";
+    } else if (pl.mix) {
         const bool f32 = c->cfg.precision == RGN_PREC_F32;
         kn[KC_GEMM] = f32 ? "k_gemm_f32" : "k_gemm_x3";
         mac[KC_GEMM] = embed + M * d * d * L + (double)dm.Bm * d * d * L; n[KC_GEMM] = 2 + L + 1;   // embedding, projection, the feature mixes, emb_fc of all layers

@@ -109,6 +109,9 @@ def score_bpd(args, model, diffusion, cfg, dev):
 
 def main(argv=None):
     args = score_args(argv)
+    if args.arch == "gru":
+        raise NotImplementedError("eval.score does not take --arch gru: its --bpd path stacks timesteps as rows of one evaluation, and the gru model's "
+                                  "batch scan (the reference's recurrence over the samples of a call) would couple them (DESIGN.md §9)")
     fixseed(args.seed)
     dev = dist_util.setup_dist()
     cfg = synth.get_config("chi3d" if args.dataset == "chi3d" else ("ntu" if args.unconstrained else "ntu_action"))

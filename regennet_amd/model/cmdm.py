@@ -85,6 +85,16 @@ class _DiffMLP(nn.Module):      # keys mlp.motion_mlp.mlps.<l>.* (cmdm.py:85-87)
         self.motion_mlp = _MixStack(d, seq, n)
 
 
+class _GRUParams(nn.Module):    # nn.GRU(d, d, num_layers)'s parameters under its names and in its order, gate order r, z, n (arch='gru', cmdm.py:84): containers only
+    def __init__(self, d, n):
+        super().__init__()
+        for l in range(n):
+            self.register_parameter(f"weight_ih_l{l}", nn.Parameter(torch.zeros(3 * d, d)))
+            self.register_parameter(f"weight_hh_l{l}", nn.Parameter(torch.zeros(3 * d, d)))
+            self.register_parameter(f"bias_ih_l{l}", nn.Parameter(torch.zeros(3 * d)))
+            self.register_parameter(f"bias_hh_l{l}", nn.Parameter(torch.zeros(3 * d)))
+
+
 class PositionalEncoding(nn.Module):
     """Sinusoid table buffer `pe` [max_len,1,d] (cmdm.py:265-276)."""
 
@@ -128,11 +138,17 @@ class CMDM(nn.Module):
                  arch="trans_enc", cm_mode="add", body_model="smpl", wo_pos_emb=False, emb_trans_dec=False,
                  clip_version=None, **kargs):
         super().__init__()
-        if arch not in ("online", "offline", "mlp"):
+        if arch not in ("online", "offline", "mlp", "gru"):
             raise NotImplementedError(
                 f"arch={arch!r}: the HIP hot path runs the 'online' decoder (cmdm.py:205-227), the 'offline' encoder "
-                "(cmdm.py:228-238) and the 'mlp' time / feature mixer (cmdm.py:239-242); trans_enc has no forward branch in the "
-                "reference, gru is an ablation without a HIP form (SURVEY.md §2 row 3)")
+                "(cmdm.py:228-238), the 'mlp' time / feature mixer (cmdm.py:239-242) and the 'gru' stack (cmdm.py:243-249); "
+                "trans_enc has no forward branch in the reference (SURVEY.md §2 row 3)")
+        if arch == "gru" and cm_mode != "add":
+            raise NotImplementedError(f"arch='gru' with cm_mode={cm_mode!r}: the gru branch adds the two pose embeddings and the reference "
+                                      "raises NotImplementedError for anything else (cmdm.py:244-247) - pass cm_mode='add'")
+        gru_scan = kargs.get("gru_scan", None) or "batch"
+        if gru_scan not in _lib.GRU_SCAN:
+            raise ValueError(f"gru_scan={gru_scan!r}: 'batch' (the reference's recurrence over the samples of a call) or 'frames'")
         if activation != "gelu":
             raise NotImplementedError("activation is hard-coded to gelu by the reference factory (model_util.py:70)")
         if data_rep not in ("rot6d", "xyz", "hml_vec"):
@@ -153,17 +169,23 @@ class CMDM(nn.Module):
         self.arch, self.cm_mode, self.num_frames = arch, cm_mode, num_frames
         self.emb_trans_dec, self.wo_pos_emb, self.body_model = emb_trans_dec, wo_pos_emb, body_model
         self.clip_version = clip_version
+        # arch='gru': the axis nn.GRU scans. The reference hands [T, B, d] to a batch_first GRU, so its recurrence runs over the B samples of a call
+        # ('batch', the default: what a checkpoint trained with it means); 'frames' is the recurrence over each sample's frames
+        self.gru_scan = gru_scan
         if self.cond_mode not in ("no_cond", "action", "text"):
             raise NotImplementedError(f"cond_mode={self.cond_mode!r}")
 
         d = latent_dim
-        self.input_process = _Pose("poseEmbedding", self.input_feats, d)
-        self.cmo_process = _Pose("poseEmbedding", self.input_feats, d)
+        gru_emb_dim = d if arch == "gru" else 0                      # (cmdm.py:52-54: both pose embeddings read [pose ; emb])
+        self.input_process = _Pose("poseEmbedding", self.input_feats + gru_emb_dim, d)
+        self.cmo_process = _Pose("poseEmbedding", self.input_feats + gru_emb_dim, d)
         self.sequence_pos_encoder = PositionalEncoding(d, dropout)
         if cm_mode == "concat":
             self.fuse_process = nn.Linear(2 * d, d)
         if arch == "offline":   # (emb_trans_dec / wo_pos_emb do not apply: the embedding is always token 0, positions always encoded)
             self.seqTransEncoder = _Encoder(d, ff_size, num_layers)
+        elif arch == "gru":     # (parameter container: weight_ih_l{k} / weight_hh_l{k} / bias_ih_l{k} / bias_hh_l{k}; num_heads / ff_size are not read)
+            self.gru = _GRUParams(d, num_layers)
         elif arch == "mlp":     # (no attention: num_heads / ff_size, emb_trans_dec / wo_pos_emb and cm_mode are not read; fc0 fixes the frame count)
             self.mlp = _DiffMLP(d, num_frames, num_layers)
         else:
@@ -308,7 +330,9 @@ class CMDM(nn.Module):
         eng.set_f16_steps(-1 if self.f16_steps is None else int(self.f16_steps))
         eng.set_small_batch_rows(-1 if self.small_batch_rows is None else int(self.small_batch_rows))
         eng.set_layers_min_b(-1 if self.layers_min_b is None else int(self.layers_min_b))
-        if self.arch != "mlp":                                # (an arch='mlp' engine has no k_layers and refuses its switches)
+        if self.arch == "gru":
+            eng.set_gru_scan(self.gru_scan)
+        if self.arch not in ("mlp", "gru"):                   # (these engines have no k_layers and refuse its switches)
             eng.set_option("LAYERS_GUIDED", -1 if self.layers_guided is None else int(self.layers_guided))
         return eng, dev
 

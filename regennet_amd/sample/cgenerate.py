@@ -151,7 +151,10 @@ def main(argv=None):
     data = types.SimpleNamespace(dataset=types.SimpleNamespace(num_actions=cfg["num_actions"], num_person=2))
     if rank == 0:
         print("Creating model and diffusion...")
-    model, diffusion = create_model_and_diffusion(args, data, allow_mlp=True)
+    if args.arch == "gru":     # (--gru_scan reaches the model through get_model_args)
+        model, diffusion = create_model_and_diffusion(args, data, allow_gru=True)
+    else:
+        model, diffusion = create_model_and_diffusion(args, data, allow_mlp=True)
     model.precision = args.precision
     if args.synthetic or not args.model_path:
         # rank 0 owns "the checkpoint"; other ranks start from different values and receive rank 0's through the start-up broadcast

@@ -90,7 +90,10 @@ def main(argv=None):
         f"Please either increase batch_size({args.batch_size}) or reduce num_samples({args.num_samples})"
     args.batch_size = B
     data = types.SimpleNamespace(dataset=types.SimpleNamespace(num_actions=cfg["num_actions"], num_person=2))
-    model, diffusion = create_model_and_diffusion(args, data, allow_mlp=True)
+    if args.arch == "gru":     # (--gru_scan reaches the model through get_model_args)
+        model, diffusion = create_model_and_diffusion(args, data, allow_gru=True)
+    else:
+        model, diffusion = create_model_and_diffusion(args, data, allow_mlp=True)
     model.precision = args.precision
     if args.synthetic or not args.model_path:
         sd = {k: torch.from_numpy(v) for k, v in

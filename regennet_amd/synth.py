@@ -43,6 +43,9 @@ for _name in ("tiny", "tiny_add", "ntu", "ntu_action", "chi3d"):
 # arch='mlp' (model/cmdm.py:239-242, model/mlp.py): the same shapes with the DiffMLP time / feature mixer (num_heads / ff_size are not read)
 for _name in ("tiny", "tiny_add", "tiny_text", "ntu", "ntu_action", "chi3d"):
     CONFIGS[_name + "_mlp"] = dict(CONFIGS[_name], arch="mlp")
+# arch='gru' (model/cmdm.py:191-199, 243-249): the same shapes with the nn.GRU(d, d, layers) denoiser; the reference's gru branch is cm_mode='add' only
+for _name in ("tiny", "tiny_add", "tiny_text", "ntu", "ntu_action", "chi3d"):
+    CONFIGS[_name + "_gru"] = dict(CONFIGS[_name], arch="gru", cm_mode="add")
 del _name
 
 
@@ -75,6 +78,10 @@ def make_state_dict(cfg, seed=0):
     cfg["arch"] == "mlp": DiffMLP keys (mlp.motion_mlp.mlps.<l>: conct in block 0, fc0 [T, T, 1], fc1, emb_fc, norm0/1). The stack adds 2 L
     un-normalised SiLU branches to the stream and ends in no LayerNorm, so the branch weights are drawn at a gain (MLP_GAIN) and the output
     projection at one (MLP_OUT_GAIN) that keep the denoiser's outputs O(1): an absolute parity bound means nothing on a stream that has blown up.
+    cfg["arch"] == "gru": both pose embeddings read [pose ; emb] (F + d columns) and the layers are nn.GRU's keys (gru.weight_ih_l<k>, weight_hh_l<k>
+    [3d, d], bias_ih_l<k>, bias_hh_l<k> [3d], gate order r, z, n). The state lives in (-1, 1), so the recurrent and input weights are drawn at a gain
+    (GRU_GAIN) at which the state carries through the scan - the gates neither sit at 1/2 nor saturate - and the output projection at one
+    (GRU_OUT_GAIN) that puts the recorded outputs' max-abs in [1, 4].
     """
     rng = np.random.Generator(np.random.PCG64(seed))
     d, ff, L = cfg["latent_dim"], cfg["ff_size"], cfg["layers"]
@@ -85,8 +92,9 @@ def make_state_dict(cfg, seed=0):
         sd[prefix + ".weight"] = (rng.standard_normal((out_f, in_f)) * (gain / np.sqrt(in_f))).astype(np.float32)
         sd[prefix + ".bias"] = (rng.standard_normal(out_f) * bias_std).astype(np.float32)
 
-    lin("input_process.poseEmbedding", d, F)
-    lin("cmo_process.poseEmbedding", d, F)
+    gru = cfg.get("arch", "online") == "gru"
+    lin("input_process.poseEmbedding", d, F + (d if gru else 0))
+    lin("cmo_process.poseEmbedding", d, F + (d if gru else 0))
     if cfg["cm_mode"] == "concat":
         lin("fuse_process", d, 2 * d, gain=1.4)
     pe = positional_table(d)
@@ -108,7 +116,12 @@ def make_state_dict(cfg, seed=0):
         for n in ("norm0", "norm1"):
             sd[p + n + ".weight"] = (1.0 + 0.1 * rng.standard_normal(d)).astype(np.float32)
             sd[p + n + ".bias"] = (0.1 * rng.standard_normal(d)).astype(np.float32)
-    for l in range(0 if mix else L):
+    for l in range(L if gru else 0):
+        for part in ("ih", "hh"):
+            sd[f"gru.weight_{part}_l{l}"] = (rng.standard_normal((3 * d, d)) * (GRU_GAIN / np.sqrt(d))).astype(np.float32)
+        for part in ("ih", "hh"):
+            sd[f"gru.bias_{part}_l{l}"] = (rng.standard_normal(3 * d) * 0.05).astype(np.float32)
+    for l in range(0 if (mix or gru) else L):
         p = f"seqTransEncoder.layers.{l}." if enc else f"seqTransDecoder.layers.{l}."
         w = rng.standard_normal((3 * d, d)) / np.sqrt(d)
         # q,k gain -> peaky attention (the encoder's milder: without the decoder's third LayerNorm per layer and its causal
@@ -130,11 +143,12 @@ def make_state_dict(cfg, seed=0):
         lin("embed_text", d, cfg.get("clip_dim", 512))
     if "action" in cfg["cond_mode"]:
         sd["embed_action.action_embedding"] = rng.standard_normal((cfg["num_actions"], d)).astype(np.float32)
-    lin("output_process.poseFinal", F, d, gain=MLP_OUT_GAIN / L if mix else 1.0)
+    lin("output_process.poseFinal", F, d, gain=MLP_OUT_GAIN / L if mix else (GRU_OUT_GAIN if gru else 1.0))
     return sd
 
 
 MLP_GAIN, MLP_OUT_GAIN = 1.0, 0.8   # (the projection gain is MLP_OUT_GAIN / layers: the stream grows with every block)
+GRU_GAIN, GRU_OUT_GAIN = 1.5, 1.0   # (tests/golden/make_golden_gru_arch.py asserts the output range; tests/test_gru_arch_cpu.py that the recurrence matters)
 
 
 FAMILIES = ("heavy_tailed", "outlier_channels", "peaky_attention", "big_output", "small_signal", "hostile")

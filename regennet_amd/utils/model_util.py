@@ -11,13 +11,16 @@ def load_model_wo_clip(model, state_dict):
     assert all([k.startswith("clip_model.") for k in missing_keys])
 
 
-def create_model_and_diffusion(args, data, allow_mlp=False):
-    """allow_mlp: build arch='mlp' too. The two-argument call keeps refusing it, as it always has (callers that relied on the refusal see no
-    change); cgenerate, edit and eval.score pass True, so `--arch mlp` works on every command line."""
+def create_model_and_diffusion(args, data, allow_mlp=False, allow_gru=False):
+    """allow_mlp / allow_gru: build arch='mlp' / arch='gru' too. The two-argument call keeps refusing them, as it always has (callers that relied
+    on the refusal see no change); cgenerate, edit and eval.score pass allow_mlp=True, cgenerate and edit allow_gru=True (eval.score stacks
+    timesteps as rows of one evaluation, which the gru model's batch scan would couple)."""
     if args.setting != "cmdm":
         raise NotImplementedError("only setting='cmdm' is on the hot path (model_util.py:13)")
     if args.arch == "mlp" and not allow_mlp:
         raise NotImplementedError("arch='mlp': pass allow_mlp=True (the command-line tools do), or construct CMDM(arch='mlp') directly")
+    if args.arch == "gru" and not allow_gru:
+        raise NotImplementedError("arch='gru': pass allow_gru=True (cgenerate and edit do), or construct CMDM(arch='gru', cm_mode='add') directly")
     model = CMDM(**get_model_args(args, data))
     args.num_person = 1  # side effect of the reference (model_util.py:15)
     diffusion = create_gaussian_diffusion(args)
@@ -49,7 +52,7 @@ def get_model_args(args, data):
             "data_rep": data_rep, "cond_mode": cond_mode, "cond_mask_prob": args.cond_mask_prob,
             "action_emb": "tensor", "arch": args.arch, "cm_mode": args.cm_mode, "body_model": args.body_model,
             "wo_pos_emb": args.wo_pos_emb, "emb_trans_dec": args.emb_trans_dec, "clip_version": "ViT-B/32",
-            "dataset": args.dataset}
+            "dataset": args.dataset, "gru_scan": getattr(args, "gru_scan", "batch")}
 
 
 def create_gaussian_diffusion(args):

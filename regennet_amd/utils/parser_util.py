@@ -30,6 +30,9 @@ def add_model_options(p):
     g = p.add_argument_group("model")
     g.add_argument("--setting", default="cmdm", choices=["mdm", "cmdm"], type=str)
     g.add_argument("--arch", default="online", choices=["trans_enc", "trans_dec", "gru", "mlp", "online", "offline"], type=str)
+    g.add_argument("--gru_scan", default="batch", choices=["batch", "frames"], type=str,
+                   help="arch='gru' only: the axis the GRU scans. batch (default) is the reference's own recurrence over the samples of a call, so a "
+                        "motion depends on the samples before it in its batch; frames is a recurrence over each motion's frames.")
     g.add_argument("--emb_trans_dec", default=False, type=bool)
     g.add_argument("--wo_pos_emb", action="store_true")
     g.add_argument("--cm_mode", default="concat", choices=["concat", "add"], type=str)
