@@ -358,6 +358,31 @@ RGN_API int rgn_vb_terms(rgn_handle h, const float* x_start_dev, const float* x_
                          const int32_t* t_dev /*[N]*/, const float* coef_dev /*[N,6]*/, int32_t B, int32_t N, int32_t features, int32_t T,
                          int32_t flags /*RGN_VB_CLIP*/, float* terms_dev /*[N,3]*/, void* stream);
 
+/* ---- Joint positions of a HumanML3D / KIT feature vector: recover_from_ric ----
+ * Replaces what the reference does after every sampling call of a data_rep='hml_vec' model (sample/cgenerate.py:147-152, sample/edit.py:117-120,
+ * :153-155, sample/predict.py:114-117): inv_transform with the dataset's Mean / Std (data_loaders/humanml/data/dataset.py:132) and recover_from_ric
+ * (data_loaders/humanml/scripts/motion_process.py:362-381, :415-430; qrot / qinv: data_loaders/humanml/common/quaternion.py:54-73), about fifteen
+ * small launches and several [B, T, J, 3] temporaries there, one launch here.
+ *   x_dev fp32 [B, D, 1, T]: the model's own layout, the sample as the loop returns it (no permute)
+ *   D = 12 J - 1 (263 for the 22 joints of HumanML3D, 251 for the 21 of KIT): 1 rotation velocity, 2 root velocities, 1 root height, 3 (J-1) local
+ *           positions, 6 (J-1) rotations, 3 J velocities, 4 contacts. Only rows 0 .. 3 (J-1) + 3 of x_dev, mean_dev and std_dev are read.
+ *   mean_dev, std_dev fp32 [D], both given or both NULL (NULL: the features are taken as already de-normalised)
+ *   xyz_dev fp32 [B, J, 3, T]: what cgenerate.py:152 forms by view / permute. xyz_dev must NOT overlap x_dev.
+ * With f_k[t] = x[k, t] * std[k] + mean[k]:
+ *   a[t] = sum_{s < t} f_0[s] (a[0] = 0); q[t] = (cos a[t], 0, sin a[t], 0) - the angle is NOT halved, the frame turns by 2 a, as in the reference;
+ *   u[0] = 0, u[t] = qrot(qinv(q[t]), (f_1[t-1], 0, f_2[t-1])) - the velocity of frame t-1 under the angle of frame t, rotated by the INVERSE;
+ *   r[t] = sum_{s <= t} u[s] with r[t].y = f_3[t]; joint 0 = r[t]; joint j >= 1 = qrot(qinv(q[t]), (f_{4+3(j-1)}, f_{5+3(j-1)}, f_{6+3(j-1)})[t])
+ *   with r[t].x and r[t].z added to its x and z.
+ * Arithmetic (rgn_loss_terms' convention): the de-normalisation is fp32, a product and an add rounded separately (no fma) - the bits of the
+ * reference's expression on fp32 statistics; both sums, sincos and the rotations are fp64 from those fp32 values; every output is rounded to fp32
+ * once. One workgroup per motion, sums in an order fixed by T alone, no atomics: a motion's result depends neither on B nor on its neighbours and is
+ * the same on every run. The call enqueues on `stream`, allocates nothing, keeps no state and can be captured into a graph.
+ * The arguments are checked before the handle or the device is touched - RGN_ERR_INVALID_ARG for a null x_dev / xyz_dev, one statistic without the
+ * other, B < 1, T outside [1, 4096], J outside [2, 64], D != 12 J - 1 - with text in rgn_last_error(h), or rgn_last_error(NULL) when h is NULL
+ * (which is itself RGN_ERR_INVALID_ARG once the other arguments have passed). */
+RGN_API int rgn_hml_to_joints(rgn_handle h, const float* x_dev, const float* mean_dev /*nullable*/, const float* std_dev /*nullable*/, int32_t B,
+                              int32_t T, int32_t D, int32_t J, float* xyz_dev /*[B,J,3,T]*/, void* stream);
+
 /* ---- The metrics of the unconstrained evaluation: KID, and precision / recall of the generated feature manifold ----
  * Replace eval/unconstrained/metrics/kid.py:8-126 (polynomial_mmd_averages, polynomial_mmd, _mmd2_and_variance: per subset three sklearn kernel
  * matrices on the host) and eval/unconstrained/metrics/precision_recall.py:30-53 (manifold_estimate: a Python double loop of torch.norm calls) for

@@ -84,6 +84,7 @@ SYMBOLS = {
     "rgn_loss_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp]),
     "rgn_q_sample_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp]),
     "rgn_vb_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "rgn_hml_to_joints": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "rgn_profile_enable": (C.c_int, [_vp, _i32]),
     "rgn_profile_query": (C.c_int, [_vp, _i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "rgn_profile_bracket_overhead": (C.c_int, [_vp, C.POINTER(C.c_double)]),
@@ -459,6 +460,15 @@ class Engine:
         assert tuple(terms.shape) == (N, len(VB_TERMS)) and all(a.is_contiguous() and a.element_size() == 4 for a in (x_start, x_t, output, coef, t, terms))
         self._ck(self.lib.rgn_vb_terms(self.h, _ptr(x_start), _ptr(x_t), _ptr(output), _ptr(noise), _ptr(t), _ptr(coef), int(B), N, int(R * F), int(T),
                                        int(flags), _ptr(terms), C.c_void_p(stream)))
+
+    def hml_to_joints(self, x, mean, std, joints, xyz, stream):
+        """rgn_hml_to_joints: x fp32 [B, 12 J - 1, 1, T] (a HumanML3D / KIT sample in the model's layout), mean / std fp32 [12 J - 1] or both None,
+        contiguous on the engine's device -> xyz fp32 [B, J, 3, T], which must not share memory with x."""
+        B, D, F, T = x.shape
+        assert F == 1 and tuple(xyz.shape) == (B, int(joints), 3, T) and (mean is None) == (std is None)
+        assert all(a is None or (a.is_contiguous() and a.element_size() == 4) for a in (x, mean, std, xyz))
+        assert mean is None or tuple(mean.shape) == tuple(std.shape) == (D,)
+        self._ck(self.lib.rgn_hml_to_joints(self.h, _ptr(x), _ptr(mean), _ptr(std), int(B), int(T), int(D), int(joints), _ptr(xyz), C.c_void_p(stream)))
 
     def profile_enable(self, on):
         self._ck(self.lib.rgn_profile_enable(self.h, int(bool(on))))

@@ -1,6 +1,7 @@
 // The C-ABI of libregennet_hip.so (include/regennet_hip.h): argument and call-order checks, the exception guard every entry point runs in,
 // and the entry points that are a few lines of host code. Checkpoint packing is rgn_pack.cpp, planning and dispatch rgn_plan.cpp.
 #include "rgn_host.h"
+#include "rgn_hml_check.h"
 
 using namespace rgnh;
 
@@ -727,6 +728,28 @@ int rgn_vb_terms(rgn_handle h, const float* x_start, const float* x_t, const flo
         int rc = stream_enter(h, us);
         if (rc) return rc;
         RGN_LAUNCH(h, KC_MISC, s, launch_vb_terms(x_start, x_t, output, noise, t_idx, coef, terms, B, N, n, flags, s));
+        return stream_exit(h, us);
+    });
+}
+
+int rgn_hml_to_joints(rgn_handle h, const float* x, const float* mean, const float* stdv, int32_t B, int32_t T, int32_t D, int32_t J, float* xyz,
+                      void* stream) {
+    return rgn_guard(h, "rgn_hml_to_joints", [&]() -> int {
+        // the arguments first (rgn_hml_check.h), the handle after them (text: rgn_last_error(NULL) while there is no handle)
+        auto bad = [&](const std::string& m) -> int {
+            if (h) return h->fail(RGN_ERR_INVALID_ARG, "rgn_hml_to_joints: " + m);
+            g_create_error = "rgn_hml_to_joints: " + m;
+            return RGN_ERR_INVALID_ARG;
+        };
+        const std::string why = hml_check_args(x, mean, stdv, B, T, D, J, xyz);
+        if (!why.empty()) return bad(why);
+        if (!h) return bad("null handle");
+        RGN_HIP(h, hipSetDevice(h->cfg.device));
+        if (!h->finalized) return h->fail(RGN_ERR_STATE, "rgn_hml_to_joints: weights not finalized");
+        hipStream_t us = reinterpret_cast<hipStream_t>(stream), s = h->stream;
+        int rc = stream_enter(h, us);
+        if (rc) return rc;
+        RGN_LAUNCH(h, KC_MISC, s, launch_hml_joints(x, mean, stdv, xyz, B, T, D, J, s));
         return stream_exit(h, us);
     });
 }

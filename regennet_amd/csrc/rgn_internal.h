@@ -449,6 +449,9 @@ hipError_t launch_q_sample_rows(const float* x_start, const float* noise_in, con
                                 int N, int n, int T, unsigned long long seed, unsigned long long sample_offset, hipStream_t s);
 hipError_t launch_vb_terms(const float* x_start, const float* x_t, const float* output, const float* noise, const int* t_idx, const float* coef,
                            float* terms, int B, int N, int n, int flags, hipStream_t s);
+// ---- rgn_hml.hip: recover_from_ric of a HumanML3D / KIT feature vector (rgn_hml_to_joints), one workgroup per motion. x [B, D, 1, T], mean / std
+// [D] or both null -> xyz [B, J, 3, T]; every pointer on the device, the arguments already checked (rgn_hml_check.h)
+hipError_t launch_hml_joints(const float* x, const float* mean, const float* stdv, float* xyz, int B, int T, int D, int J, hipStream_t s);
 // ---- rgn_metrics.hip: KID and precision / recall of the unconstrained evaluation (rgn_poly_mmd, rgn_knn_radius, rgn_manifold_hits); every pointer on
 // the device, the arguments already checked
 unsigned long long poly_mmd_workspace_bytes(int S, int m);

@@ -15,7 +15,13 @@ device (utils/render.py; `--render_size N`, default 1024 as render/crendermotion
 per frame on the device (`betas_per_motion`) - cycled over repetitions like the actor clips, and stores 'betas' beside them.
 `--jointstype vibe | a2m | a2mpl` makes 'motion' that joint type of the reference's SMPL layer (regressed from the mesh; [N, len(map), 3, T]) in
 place of the skeleton's joints: it needs a `--skeleton` body file that holds the regressors and the type's map (`synthetic`:
-synth.make_joint_regressors)."""
+synth.make_joint_regressors).
+
+`--dataset humanml | kit` samples the HumanML3D / KIT feature vector (263 / 251 rows of one feature, up to 196 frames, text-conditioned: the CLIP
+tower is out of scope, `--text_features FILE.npy` [N, clip_dim] or `--synthetic` ones go into y['text_features']). 'motion' is then what the reference
+stores for such a model (cgenerate.py:147-152): the smoothed sample de-normalised with the dataset's Mean / Std (`--hml_stats PATH`) and turned into
+joint positions [N, 22 | 21, 3, T] by recover_from_ric - one launch on the device (utils/hml.py, rgn_hml_to_joints). It needs no skeleton; the
+options that need a body are refused."""
 import os
 import time
 import types
@@ -39,6 +45,48 @@ def _load_clips(args, cfg, n):
         return cm, act
     reps = max(1, args.num_repetitions)
     return synth.make_cmotion(cfg, n * reps, seed=1), synth.make_actions(cfg, n * reps, seed=2)
+
+
+HML_DATASETS = ("humanml", "kit")
+HML_MAX_FRAMES = 196        # max_motion_length of both datasets (data_loaders/humanml/utils/get_opt.py:63,70)
+
+
+def dataset_config(args):
+    """The synthetic configuration whose geometry the dataset's inputs (actor clips, text features) are drawn at."""
+    if args.dataset in HML_DATASETS:
+        return synth.get_config("ntu" if args.unconstrained else "text150", dataset=args.dataset, njoints={"humanml": 263, "kit": 251}[args.dataset],
+                                nfeats=1, num_frames=HML_MAX_FRAMES, num_actions=1)
+    return synth.get_config("chi3d" if args.dataset == "chi3d" else ("ntu" if args.unconstrained else "ntu_action"))
+
+
+def hml_statistics(args):
+    """--dataset humanml | kit: refuse what needs a body, then (mean, std) of --hml_stats, or (None, None) and one line that says so."""
+    for flag, given in (("--skeleton", args.skeleton), ("--vertices", getattr(args, "vertices", False)), ("--jointstype", getattr(args, "jointstype", "")),
+                        ("--betas_npz", getattr(args, "betas_npz", ""))):
+        if given:
+            raise SystemExit(f"{flag}: --dataset {args.dataset} samples a feature vector whose joint positions come from recover_from_ric, not from a "
+                             f"body model's skeleton or mesh - there is no body for {flag} to act on")
+    if not args.hml_stats:
+        print("no --hml_stats: the features are taken as already de-normalised (the dataset's Mean / Std are not applied)")
+        return None, None
+    from ..utils.hml import load_hml_stats
+    mean, std = load_hml_stats(args.hml_stats)
+    rows = {"humanml": 263, "kit": 251}[args.dataset]
+    if len(mean) != rows:
+        raise SystemExit(f"--hml_stats: {args.hml_stats} holds {len(mean)} rows, --dataset {args.dataset} has {rows}")
+    return mean, std
+
+
+def load_text_features(args, n, clip_dim):
+    """--text_features FILE.npy [N, clip_dim] (cycled over repetitions like the actor clips), or seeded synthetic ones."""
+    if args.text_features:
+        feats = np.ascontiguousarray(np.load(args.text_features, allow_pickle=False), dtype=np.float32)
+        if feats.ndim != 2 or not len(feats) or feats.shape[1] != clip_dim:
+            raise SystemExit(f"--text_features: {args.text_features} holds {feats.shape}, [N, {clip_dim}] expected")
+        return feats
+    if args.synthetic or not args.model_path:
+        return synth.make_text_features({"clip_dim": clip_dim}, n * max(1, args.num_repetitions), seed=3)
+    raise SystemExit("a text-conditioned model needs --text_features FILE.npy [N, clip_dim] (the CLIP tower is out of scope), or --synthetic")
 
 
 def set_skeleton(model, args):
@@ -140,14 +188,16 @@ def main(argv=None):
     result does not depend on N), and rank 0 gathers and saves. No collective inside the sampling loop."""
     args = cgenerate_args(argv)
     fixseed(args.seed)
-    max_frames = 150 if args.dataset == "chi3d" else 60
+    hml = args.dataset in HML_DATASETS
+    max_frames = HML_MAX_FRAMES if hml else 150 if args.dataset == "chi3d" else 60
     n_frames = min(max_frames, int(args.motion_length))
+    hml_mean, hml_std = hml_statistics(args) if hml else (None, None)
     dev = dist_util.setup_dist()
     rank, world = dist_util.world()
     assert args.num_samples <= args.batch_size, \
         f"Please either increase batch_size({args.batch_size}) or reduce num_samples({args.num_samples})"
     args.batch_size = args.num_samples
-    cfg = synth.get_config("chi3d" if args.dataset == "chi3d" else ("ntu" if args.unconstrained else "ntu_action"))
+    cfg = dataset_config(args)
     data = types.SimpleNamespace(dataset=types.SimpleNamespace(num_actions=cfg["num_actions"], num_person=2))
     if rank == 0:
         print("Creating model and diffusion...")
@@ -180,10 +230,13 @@ def main(argv=None):
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     eng, _ = inner._get_engine(max(Bl, 1), n_frames)
-    with_motion = set_skeleton(inner, args)
+    with_motion = hml or set_skeleton(inner, args)
     with_vertices = with_motion and args.vertices
+    texts = load_text_features(args, args.num_samples, inner.clip_dim) if inner.cond_mode == "text" else None
+    if hml:
+        from ..utils.hml import hml_to_joints, joints_of
     nverts = inner.rot2xyz.mesh["v_template"].shape[0] if with_vertices else 0
-    shapes = load_betas(args, args.num_samples, inner.rot2xyz.num_betas if with_motion else 0)     # [N, nb] | None: cycled like the actor clips
+    shapes = load_betas(args, args.num_samples, inner.rot2xyz.num_betas if with_motion and not hml else 0)     # [N, nb] | None: cycled like the actor clips
     all_outputs, all_cmotions, all_motions, all_vertices, all_betas, time_all = [], [], [], [], [], 0.0
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
 
@@ -193,6 +246,8 @@ def main(argv=None):
              "mask": torch.ones(Bl, 1, 1, n_frames, dtype=torch.bool)}
         if inner.cond_mode == "action":
             y["action"] = torch.from_numpy(actions[idx]).to(dev)
+        if inner.cond_mode == "text":
+            y["text_features"] = torch.from_numpy(np.ascontiguousarray(texts[(np.arange(lo, hi) + rep_i * B) % len(texts)])).to(dev)
         if args.guidance_param != 1:
             y["scale"] = torch.ones(Bl, device=dev) * args.guidance_param
         return y
@@ -227,7 +282,10 @@ def main(argv=None):
         if shapes is not None:                     # sample i of this repetition wears shape (i + rep_i B) mod N
             all_betas.append(shapes[(np.arange(B) + rep_i * B) % len(shapes)])
             betas = all_betas[-1][lo:hi]
-        if with_motion:                            # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
+        if hml:                                    # cgenerate.py:147-152: inv_transform + recover_from_ric of the smoothed sample, one launch
+            motion = hml_to_joints(smooth, hml_mean, hml_std, engine=eng) if Bl > 0 else torch.empty((0, joints_of(inner.njoints), 3, n_frames), device=dev)
+            all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
+        elif with_motion:                          # after the timed region, from the smoothed sample, like the reference (cgenerate.py:142-163)
             motion = joint_positions(inner, args, smooth, y, betas=betas) if Bl > 0 else torch.empty((0, motion_rows(inner, args), 3, n_frames), device=dev)
             all_motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if with_vertices:

@@ -9,6 +9,10 @@ loop (gaussian_diffusion.py:319-323, rgn_set_inpainting).
   --edit_mode in_between   frames [int(prefix_end * T), int(suffix_start * T)) are generated, all others kept (edit.py:76-83)
   --edit_mode rows         the pose rows of --keep_rows (e.g. 0-21,55) are kept in every frame, the others generated. This takes the place
                            of the reference's 'upper_body', a HumanML3D feature mask with no meaning for 56 SMPL-X rows.
+  --edit_mode upper_body   --dataset humanml only: the rows of humanml_utils.HML_LOWER_BODY_MASK (root, lower-body joints, foot contacts) are
+                           kept in every frame and the upper body is generated (edit.py:84-88). 'motion' and 'input_motion' then hold the joint
+                           positions of the result and of the input motions (edit.py:117-121, :153-156; utils/hml.py), de-normalised with
+                           --hml_stats when given.
 
 Input motions: --input_motions FILE.npy [N, njoints, nfeats, T], or synthetic ones with --synthetic. Like the reference's edit.py (and
 unlike cgenerate) the result is stored unsmoothed, so its kept part equals the input bit for bit; 'mask' and 'input_motions' are stored
@@ -54,13 +58,23 @@ def parse_rows(spec):
     return sorted(set(rows))
 
 
+def upper_body_mask(shape):
+    """bool [B, 263, 1, T], True = keep the input: HML_LOWER_BODY_MASK over every motion, feature and frame (edit.py:84-88), so the lower body and
+    the root are kept and the upper body is generated."""
+    from ..data_loaders.humanml_utils import HML_LOWER_BODY_MASK
+    return np.ascontiguousarray(np.broadcast_to(HML_LOWER_BODY_MASK[None, :, None, None], tuple(int(s) for s in shape)))
+
+
 def build_mask(args, shape):
     if args.edit_mode == "in_between":
         return in_between_mask(shape, args.prefix_end, args.suffix_start)
     if args.edit_mode == "rows":
         return rows_mask(shape, parse_rows(args.keep_rows))
+    if len(shape) == 4 and tuple(int(s) for s in shape[1:3]) == (263, 1):      # the HumanML3D vector, the one layout the reference's mask is written for
+        return upper_body_mask(shape)
     raise NotImplementedError(
-        "--edit_mode upper_body is the reference's HumanML3D feature mask (humanml_utils.HML_LOWER_BODY_MASK) and has no meaning for the "
+        "--edit_mode upper_body is the reference's HumanML3D feature mask (humanml_utils.HML_LOWER_BODY_MASK): it is written for the 263 x 1 rows of "
+        "--dataset humanml and has no meaning for KIT's 251 rows or the "
         "56 SMPL-X pose rows of a reaction model: name the rows to keep instead, --edit_mode rows --keep_rows 0-21,55")
 
 
@@ -75,15 +89,18 @@ def main(argv=None):
     from ..utils.fixseed import fixseed
     from ..utils.model_util import create_model_and_diffusion, load_model_wo_clip
     from ..utils.parser_util import edit_args
-    from .cgenerate import joint_positions, mesh_results, motion_rows, set_skeleton, vertex_positions
+    from .cgenerate import (HML_DATASETS, HML_MAX_FRAMES, dataset_config, hml_statistics, joint_positions, load_text_features, mesh_results, motion_rows,
+                            set_skeleton, vertex_positions)
 
     args = edit_args(argv)
     fixseed(args.seed)
-    max_frames = 150 if args.dataset == "chi3d" else 60
+    hml = args.dataset in HML_DATASETS
+    max_frames = HML_MAX_FRAMES if hml else 150 if args.dataset == "chi3d" else 60
     n_frames = min(max_frames, int(args.motion_length))
-    cfg = synth.get_config("chi3d" if args.dataset == "chi3d" else ("ntu" if args.unconstrained else "ntu_action"))
+    cfg = dataset_config(args)
     B = args.num_samples
     full_mask = build_mask(args, (B, cfg["njoints"], cfg["nfeats"], n_frames))       # (raises for upper_body before anything is built)
+    hml_mean, hml_std = hml_statistics(args) if hml else (None, None)
     dev = dist_util.setup_dist()
     rank, world = dist_util.world()
     assert args.num_samples <= args.batch_size, \
@@ -128,9 +145,16 @@ def main(argv=None):
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
     inner = model.model if isinstance(model, ClassifierFreeSampleModel) else model
     shape = (Bl, inner.njoints, inner.nfeats, n_frames)
-    with_motion = set_skeleton(inner, args)
+    with_motion = hml or set_skeleton(inner, args)
     if getattr(args, "betas_npz", ""):
         raise SystemExit("--betas_npz is served by cgenerate and render; the edit CLI draws every motion on the file's one shape")
+    texts = load_text_features(args, B, inner.clip_dim) if inner.cond_mode == "text" else None
+    if hml:
+        from ..utils.hml import hml_to_joints, joints_of
+        eng, _ = inner._get_engine(max(Bl, 1), n_frames)
+
+        def hml_joints(x):       # edit.py:117-121, :153-156: inv_transform + recover_from_ric, one launch
+            return hml_to_joints(x, hml_mean, hml_std, engine=eng) if Bl > 0 else torch.empty((0, joints_of(inner.njoints), 3, n_frames), device=dev)
 
     def make_y(rep_i):
         idx = (np.arange(lo, hi) + rep_i * B) % len(clips)
@@ -141,6 +165,8 @@ def main(argv=None):
              "inpainting_mask": torch.from_numpy(np.ascontiguousarray(full_mask[lo:hi])).to(dev)}      # True means: use the input motion
         if inner.cond_mode == "action":
             y["action"] = torch.from_numpy(actions[idx]).to(dev)
+        if inner.cond_mode == "text":
+            y["text_features"] = torch.from_numpy(np.ascontiguousarray(texts[(np.arange(lo, hi) + rep_i * B) % len(texts)])).to(dev)
         if args.guidance_param != 1:
             y["scale"] = torch.ones(Bl, device=dev) * args.guidance_param
         return y
@@ -149,7 +175,7 @@ def main(argv=None):
         diffusion.agree_x3_tail(model, shape, {"y": make_y(0)} if Bl > 0 else None, sampler="ddim" if args.use_ddim else "ddpm")
     with_vertices = with_motion and args.vertices
     nverts = inner.rot2xyz.mesh["v_template"].shape[0] if with_vertices else 0
-    outs, cms, ins, motions, vertices = [], [], [], [], []
+    outs, cms, ins, motions, vertices, in_joints = [], [], [], [], [], []
     for rep_i in range(args.num_repetitions):
         if rank == 0:
             print(f"### Start sampling [repetitions #{rep_i}]")
@@ -168,7 +194,10 @@ def main(argv=None):
         outs.append(dist_util.all_gather_samples(sample, B).cpu().numpy())
         cms.append(dist_util.all_gather_samples(y["cmotion"], B).cpu().numpy())
         ins.append(dist_util.all_gather_samples(y["inpainted_motion"], B).cpu().numpy())
-        if with_motion:
+        if hml:
+            motions.append(dist_util.all_gather_samples(hml_joints(sample), B).cpu().numpy())
+            in_joints.append(dist_util.all_gather_samples(hml_joints(y["inpainted_motion"]), B).cpu().numpy())
+        elif with_motion:
             motion = joint_positions(inner, args, sample, y) if Bl > 0 else torch.empty((0, motion_rows(inner, args), 3, n_frames), device=dev)
             motions.append(dist_util.all_gather_samples(motion, B).cpu().numpy())
         if with_vertices:
@@ -181,6 +210,7 @@ def main(argv=None):
         npy_path = os.path.join(out_path, "results.npy")
         print(f"saving results file to [{npy_path}]")
         np.save(npy_path, {**({"motion": np.concatenate(motions)} if with_motion else {}),
+                           **({"input_motion": np.concatenate(in_joints)} if hml else {}),
                            **(mesh_results(inner, args, vertices, np.full((len(outs) * B,), n_frames)) if with_vertices else {}), "output": np.concatenate(outs), "cmotion": np.concatenate(cms), "input_motions": np.concatenate(ins),
                            "mask": np.concatenate([full_mask] * len(outs)), "edit_mode": args.edit_mode,
                            "lengths": np.full((len(outs) * B,), n_frames), "num_samples": args.num_samples,

@@ -39,11 +39,16 @@ def get_model_args(args, data):
     num_actions = getattr(ds, "num_actions", 1)
     num_person = getattr(ds, "num_person", 1)
     data_rep = args.pose_rep
-    njoints = {"smpl": 25, "smplx": 56}[args.body_model]
-    nfeats = {"rot6d": 6, "xyz": 3}[data_rep]
     if args.dataset in ("humanml", "kit"):
-        raise NotImplementedError("humanml/kit are not wired in the reference either (get_data.py:6-20)")
-    num_frames = {"ntu": 60, "chi3d": 150}[args.dataset]
+        # the feature vector of model_util.py:52-59: 263 rows for HumanML3D's 22 joints, 251 for KIT's 21, one feature each. The reference's own
+        # factory leaves num_frames unbound for these two datasets (only ntu and chi3d assign it, :61-64), so it fails there; 196 is their
+        # max_motion_length (data_loaders/humanml/utils/get_opt.py:63,70), the length the reference's sampling scripts use for them.
+        data_rep, njoints, nfeats = "hml_vec", {"humanml": 263, "kit": 251}[args.dataset], 1
+        num_frames = 196
+    else:
+        njoints = {"smpl": 25, "smplx": 56}[args.body_model]
+        nfeats = {"rot6d": 6, "xyz": 3}[data_rep]
+        num_frames = {"ntu": 60, "chi3d": 150}[args.dataset]
     num_frames = getattr(args, "num_frames_override", None) or num_frames
     return {"modeltype": "", "njoints": njoints, "nfeats": nfeats, "num_actions": num_actions,
             "num_person": num_person, "num_frames": num_frames, "translation": True, "pose_rep": "rot6d",

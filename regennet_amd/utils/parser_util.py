@@ -47,7 +47,12 @@ def add_model_options(p):
 
 def add_data_options(p):
     g = p.add_argument_group("dataset")
-    g.add_argument("--dataset", default="ntu", choices=["ntu", "chi3d"], type=str)
+    g.add_argument("--dataset", default="ntu", choices=["ntu", "chi3d", "humanml", "kit"], type=str,
+                   help="humanml / kit: the 263 / 251-row feature vector (data_rep='hml_vec', text-conditioned, up to 196 frames); 'motion' is "
+                        "recover_from_ric of the sample")
+    g.add_argument("--hml_stats", default="", type=str,
+                   help="humanml / kit: the dataset's Mean / Std - an npz with 'mean' and 'std' [D], or a directory holding Mean.npy / Std.npy; "
+                        "without it the features are taken as already de-normalised")
     g.add_argument("--data_path", default="", type=str)
     g.add_argument("--num_person", default=2, type=int)
     g.add_argument("--pose_rep", default="rot6d", type=str)
@@ -70,7 +75,10 @@ def add_generate_options(p):
     g.add_argument("--action_name", default="", type=str)
     # inputs the reference takes from its (licence-restricted) h5 datasets; here an .npz or synthetic data
     g.add_argument("--cmotion_npz", default="", type=str, help="npz with 'cmotion' [N,56,6,T] (+ 'action' [N]) actor clips")
-    g.add_argument("--synthetic", action="store_true", help="synthetic checkpoint + actor motions (no assets needed)")
+    g.add_argument("--synthetic", action="store_true", help="synthetic checkpoint + actor motions (+ text features) (no assets needed)")
+    g.add_argument("--text_features", default="", type=str,
+                   help="text-conditioned models: npy [N, clip_dim] of text features for y['text_features'] (the CLIP tower is out of scope), cycled "
+                        "over repetitions like the actor clips")
     g.add_argument("--skeleton", default="", type=str,
                    help="skeleton npz (tools/make_skeleton.py) or 'synthetic': also store 'motion', the joint positions model.rot2xyz gives")
     g.add_argument("--vertices", action="store_true",
@@ -93,7 +101,8 @@ def add_edit_options(p):
     inputs this CLI takes instead of a dataset."""
     g = p.add_argument_group("edit")
     g.add_argument("--edit_mode", default="in_between", choices=["in_between", "upper_body", "rows"], type=str,
-                   help="in_between: keep the frames outside [prefix_end, suffix_start); rows: keep the pose rows of --keep_rows in every frame")
+                   help="in_between: keep the frames outside [prefix_end, suffix_start); rows: keep the pose rows of --keep_rows in every frame; "
+                        "upper_body (--dataset humanml): keep the lower-body rows of the feature vector, generate the upper body")
     g.add_argument("--prefix_end", default=0.25, type=float, help="in_between: end of the kept prefix, as a fraction of the length")
     g.add_argument("--suffix_start", default=0.75, type=float, help="in_between: start of the kept suffix, as a fraction of the length")
     g.add_argument("--keep_rows", default="", type=str, help="rows: pose rows to keep, e.g. 0-21,55")
